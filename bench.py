@@ -1,6 +1,6 @@
-"""Benchmark of the VMC hot path on MI355X (driver contract: see the task statement).
+"""Benchmark of the VMC hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[2]): 10x10 Heisenberg torus (N=100 sites, 200 bonds),
 fully-connected ansatz with 3 x 256 hidden units ("256-hidden-unit CGS"),
@@ -16,9 +16,20 @@ second, whole job.  mc_sweeps_per_sec counts batch sweeps as the reference does 
 num_sites mc_steps on the whole batch); local_energy_evals_per_sec = chains x steps / time
 spent in the local-energy kernels.
 
-Protocol: W warm-up steps, then the timed region of EXACTLY K steps (barrier +
-synchronize on both sides, max over ranks) is repeated REPS = 5 times back to back and the
-MEDIAN repetition is reported (`repetitions_ms_per_step` lists all five).
+Protocol: 10 equilibration sweeps and W warm-up steps, then the timed region of EXACTLY K steps
+(barrier + synchronize on both sides, max over ranks), once; `ms_per_step` = its time / K.  A plain
+run does nothing else: no HIP events inside the timed region, nothing after it but the result line.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller, as float32 / float64 .npy
+files: the accumulator buffer, the energy gradient derived from it, the mean local energy and the
+chains after the sweep (rank 0's shard).  The inputs are seeded, so runs with the same arguments start
+from the same weights, chains and sampler key.
+
+`--full` adds everything beyond the headline figure: the timed region repeated REPS = 5 times back
+to back with the MEDIAN repetition reported (`repetitions_ms_per_step` lists all five), per-kernel
+HIP-event timings and the roofline, the energy of the final chains, the legs after the timed region
+(extra_legs), the CPU baselines, and at N > 1 the blocking all-reduce time and the comparison of the
+two ways of taking the step.  `--no-timing` / `--no-extra` / `--no-cpu-baseline` / `--reps` trim it.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process starts N ranks of
 itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, rendezvous on 127.0.0.1) before it
@@ -44,7 +55,7 @@ if ROOT not in sys.path:
 FP32_MFMA_PEAK_TFLOPS = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md: dense f32 matrix peak
 BF16_MFMA_PEAK_TFLOPS = 2516.6  # dense bf16 matrix peak = 16 x the f32 rate (same guide)
 HBM_PEAK_GBS = 8000.0
-REPS = 5                        # repetitions of the timed region; the median is reported
+REPS = 5                        # --full: repetitions of the timed region; the median is reported
 
 WORKLOADS = {
     # name: (lx, ly, next_nearest, L, H, B per GPU[, ansatz, kernel_size])
@@ -709,6 +720,34 @@ def prove_library_transport(eng, world, rank, timeout_s=90.0):
   return dict(out), t.is_alive()
 
 
+# ----------------------------------------------------------------------------- outputs of the timed path
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(eng, out_dir):
+  """--dump-outputs: what the last timed step handed its caller, as out_dir/<name>.npy -- the accumulator
+  buffer it filled (gradient sums and energy moments, 2P + 8 floats), the EnergyGradient gradient an
+  optimizer reads from it, the mean local energy, and the chains the sweep left (this rank's shard).  When
+  the chains would take the files past DUMP_LIMIT_BYTES, a fixed sample of their rows is written instead
+  (chains.npy with the row indices in chain_rows.npy)."""
+  from cgs_vmc_amd import _hip
+  eng.synchronize()
+  outs = {'accumulators': eng.get_accumulators(),
+          'gradient': eng.get_gradient(_hip.VMC_MODE_ENERGY_GRADIENT),
+          'mean_energy': np.array([eng.mean_energy()], np.float64)}
+  chains = eng.get_configs()
+  budget = DUMP_LIMIT_BYTES - sum(a.nbytes for a in outs.values())
+  if chains.nbytes > budget:
+    n_keep = max(0, budget - 8 * chains.shape[0]) // (chains.itemsize * chains.shape[1])
+    rows = np.sort(np.random.default_rng(0).choice(chains.shape[0], n_keep, replace=False))
+    outs['chain_rows'] = rows.astype(np.float64)
+    chains = chains[rows]
+  outs['chains'] = chains
+  os.makedirs(out_dir, exist_ok=True)
+  for name, a in outs.items():
+    np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 # ----------------------------------------------------------------------------- main
 def main():
   if len(sys.argv) > 1 and sys.argv[1] == '--cpu-worker':
@@ -720,13 +759,20 @@ def main():
   ap.add_argument('--workload', default='heisenberg10x10_fc3x256_b4096', choices=sorted(WORKLOADS))
   ap.add_argument('--warm-sweeps', type=int, default=10, help='equilibration sweeps before the warm-up steps (BASELINE.md: 10; '
                   'fewer only for rocprofv3 --pmc passes of the general paths, whose sweeps are hundreds of launches)')
-  ap.add_argument('--no-cpu-baseline', action='store_true')
-  ap.add_argument('--no-timing', action='store_true', help='disable per-kernel HIP events')
+  ap.add_argument('--full', action='store_true',
+                  help='also measure and check what the headline figure does not need: {} repetitions of the timed '
+                       'region, per-kernel HIP events and the roofline, the legs after the timed region, the CPU '
+                       'baselines, at N > 1 the all-reduce time and the two step paths compared'.format(REPS))
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write what the last timed step computed to DIR/<name>.npy')
+  ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baselines')
+  ap.add_argument('--no-timing', action='store_true', help='--full: disable per-kernel HIP events')
   ap.add_argument('--no-extra', action='store_true',
-                  help='skip the legs after the timed region (soak, LogOverlapITSWO batch loop, SR CG loop, '
+                  help='--full: skip the legs after the timed region (soak, LogOverlapITSWO batch loop, SR CG loop, '
                        'default-hparams epoch); they only run at N = 1 on the headline workload anyway')
   ap.add_argument('--soak-seconds', type=float, default=10.0, help='length of the sustained-clock soak leg')
-  ap.add_argument('--reps', type=int, default=REPS, help='repetitions of the timed region (median reported)')
+  ap.add_argument('--reps', type=int, default=None,
+                  help='repetitions of the timed region, median reported (default 1; {} with --full)'.format(REPS))
   ap.add_argument('--collective', choices=['library', 'torch'], default=None,
                   help="N > 1: 'library' (default) = the step is ONE call of vmc_epoch_energy_gradient_dist, the "
                        "entry training.run_optimization_epoch uses, all-reduce issued in stream by the library "
@@ -738,6 +784,10 @@ def main():
 
   if args.gpus < 1:
     ap.error('--gpus must be >= 1')
+  if args.steps < 1:
+    ap.error('--steps must be >= 1')
+  reps = args.reps if args.reps is not None else (REPS if args.full else 1)
+  timing = args.full and not args.no_timing
   env_world = os.environ.get('WORLD_SIZE')
   if env_world is None and (args.gpus > 1 or args.spawn):
     sys.exit(spawn_ranks(args.gpus))          # no GPU call has been made in this process
@@ -835,10 +885,10 @@ def main():
   # HIP events on the library's streams: inside the timed region only around the two roofline
   # kernels (every recorded event drains the pipeline between two kernels, ~3.5 us); the small
   # kernels are timed in a few extra steps after the timed region
-  eng.timing_enable(0 if args.no_timing else 2)
+  eng.timing_enable(2 if timing else 0)
   eng.timing_reset()
   rep_s, rep_local = [], []
-  for _ in range(max(1, args.reps)):
+  for _ in range(max(1, reps)):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -858,8 +908,10 @@ def main():
     rank_ms = [None] * world
     torch.distributed.all_gather_object(rank_ms, local_ms)
   eng.timing_enable(False)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(eng, args.dump_outputs)
   main_timings = {name: eng.timing_get(name) for name in ('sweep', 'tail_eloc')}
-  if not args.no_timing:
+  if timing:
     eng.timing_enable(1)
     eng.timing_reset()
     for _ in range(min(args.steps, 20)):     # (5 samples were few for the 3 % slice they time)
@@ -869,7 +921,7 @@ def main():
 
   # the RCCL all-reduce alone (blocking), for the record
   allreduce_ms = None
-  if world > 1:
+  if world > 1 and args.full:
     barrier()
     t0 = time.perf_counter()
     for _ in range(10):
@@ -880,7 +932,7 @@ def main():
   # N > 1: the two ways of taking the step -- op by op with torch.distributed's all-reduce, and the
   # library's one-call entry with the all-reduce issued in stream -- from the same chains and step counter
   paths_agree = None
-  if world > 1:
+  if world > 1 and args.full:
     start_cfg, start_step = eng.get_configs(), eng.step_counter
     eng.set_configs(start_cfg)          # both start from chains just loaded (no sampler hand-over of activations)
     step_torch(); acc_t = eng.get_accumulators()
@@ -896,9 +948,11 @@ def main():
     except Exception as e:  # pylint: disable=broad-except
       paths_agree = {'error': repr(e)}
 
-  eng.local_energy(want_eloc=False)
-  rows = eng.last_connected_rows()
-  mean_e = eng.mean_energy()
+  rows = mean_e = None
+  if args.full:
+    eng.local_energy(want_eloc=False)
+    rows = eng.last_connected_rows()
+    mean_e = eng.mean_energy()
 
   timings = {}
   for name in ('sweep', 'tail_eloc', 'tail_amp', 'z1', 'bond_list', 'eloc_reduce', 'grad', 'adam'):
@@ -909,7 +963,7 @@ def main():
   # the legs BASELINE config 3's wording asks for beside the EnergyGradient slice (N = 1, the dense
   # headline workload only; they change theta, so they come after every headline reading)
   extra = None
-  if world == 1 and not args.no_extra and args.workload == 'heisenberg10x10_fc3x256_b4096':
+  if world == 1 and args.full and not args.no_extra and args.workload == 'heisenberg10x10_fc3x256_b4096':
     try:
       extra = extra_legs(eng, step, n, b, L, h, args.soak_seconds)
     except Exception as e:  # pylint: disable=broad-except
@@ -927,7 +981,7 @@ def main():
     # chains (sweep); one row per antiparallel bond (local energy); delta chain + the dual
     # weight-gradient GEMMs (gradient sums)
     exec_sweep = b * (n + 1) * mfma_per_row
-    exec_eloc = rows * mfma_per_row
+    exec_eloc = None if rows is None else rows * mfma_per_row      # (--full only, as the roofline)
     exec_grad = b * (n_hh * 2 * hp * hp + 4 * (n * h + n_hh * h * h + h))
     if conv:      # taped forward + transposed convolutions + the two correlation sums
       exec_sweep = b * n * mfma_per_row
@@ -955,7 +1009,7 @@ def main():
                    'parallelism': 'chains sharded x{}'.format(world)},
         'repetitions': len(rep_s), 'statistic': 'median',
         'repetitions_ms_per_step': [1e3 * t / args.steps for t in rep_s],
-        'mean_energy_per_site': mean_e / n,
+        'mean_energy_per_site': None if mean_e is None else mean_e / n,
         'connected_rows_last_eloc': rows,
         'kernels': timings,
     }
@@ -1117,7 +1171,7 @@ def main():
     if extra is not None:
       out['extra'] = extra
       out['extra_keys'] = sorted(extra)
-    if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (rank 0's host cores)
+    if args.full and not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (rank 0's host cores)
       try:
         out['cpu_baseline'] = cpu_baseline(n, h, L, bonds, jx, jz, theta, cfg, ansatz, ksz, lx, ly, args.workload)
       except Exception as e:  # pylint: disable=broad-except

@@ -249,7 +249,7 @@ def test_multi_rank_bench_path_on_one_gpu(tmp_path, gpus, collective, transport)
     env['CGS_VMC_TRANSPORT'] = transport
   p = subprocess.run(
       [sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(gpus), '--steps', '2', '--warmup',
-       '1', '--reps', '2', '--no-cpu-baseline', '--workload', 'heisenberg6x6_fc3x128_b1024']
+       '1', '--reps', '2', '--full', '--no-cpu-baseline', '--workload', 'heisenberg6x6_fc3x128_b1024']
       + (['--collective', collective] if collective else []),
       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
   assert p.returncode == 0, p.stderr.decode()[-2000:]
@@ -293,6 +293,47 @@ def test_multi_rank_bench_path_on_one_gpu(tmp_path, gpus, collective, transport)
   assert bad.returncode == 2 and b'WORLD_SIZE' in bad.stderr
 
 
+def test_plain_bench_run_times_its_steps_and_dumps_the_same_outputs_twice(tmp_path):
+  """A plain `bench.py` run (no --full) times exactly --steps steps once and runs no leg beyond them;
+  --dump-outputs writes the last timed step's results, and two runs with the same arguments write the
+  same chains and accumulators (seeded inputs, counter-based sampler)."""
+  import json
+  import subprocess
+  import sys
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  env = {k: v for k, v in os.environ.items()
+         if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
+
+  def run(d):
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--workload', 'heisenberg6x6_fc3x128_b1024', '--dump-outputs', str(d)],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    lines = [l for l in p.stdout.decode().splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    return json.loads(lines[0]), {f[:-4]: np.load(os.path.join(str(d), f)) for f in os.listdir(str(d))}
+
+  line, a = run(tmp_path / 'a')
+  assert line['steps'] == 3 and line['repetitions'] == 1 and line['value'] > 0
+  assert line['ms_per_step'] == pytest.approx(line['repetitions_ms_per_step'][0])
+  assert line['metric'] == 'mc_sweep+local_energy_evals_per_sec' and line['higher_is_better'] is True
+  assert line['unit'] == 'chain-evals/s' and line['dtype'] == 'f32'
+  for key in ('extra', 'cpu_baseline', 'roofline'):
+    assert key not in line
+  assert line['kernels'] == {}
+  n, p = 36, 36 * 128 + 128 + 2 * (128 * 128 + 128) + 128 + 1
+  assert sorted(a) == ['accumulators', 'chains', 'gradient', 'mean_energy']
+  assert a['chains'].shape == (1024, n) and a['chains'].dtype == np.float32
+  assert (a['chains'].sum(1) == 0).all() and set(np.unique(a['chains'])) == {-1.0, 1.0}
+  assert a['accumulators'].shape == (2 * p + 8,) and a['gradient'].shape == (p,)
+  assert a['mean_energy'].dtype == np.float64 and np.isfinite(a['mean_energy']).all()
+  assert sum(v.nbytes for v in a.values()) <= 64 << 20
+  _, b = run(tmp_path / 'b')
+  np.testing.assert_array_equal(a['chains'], b['chains'])
+  for k in ('accumulators', 'gradient', 'mean_energy'):
+    np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-6 * float(np.abs(a[k]).max()))
+
+
 def test_one_rank_through_the_launcher_costs_nothing():
   """`bench.py --gpus 1 --spawn` (the rank started by bench.py's own launcher, as for N > 1) against
   the direct N = 1 run: same value within 1 % (medians of 5 repetitions of 50 steps at config 3;
@@ -305,7 +346,7 @@ def test_one_rank_through_the_launcher_costs_nothing():
          if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
 
   def run(extra):
-    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '50', '--warmup', '5',
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '50', '--warmup', '5', '--full',
                         '--no-cpu-baseline', '--no-timing', '--no-extra'] + extra, env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]

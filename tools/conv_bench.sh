@@ -7,7 +7,7 @@ mkdir -p "$out"
 for w in heisenberg10x10_conv5x16k5_b4096 heisenberg10x10_conv5x32k5_b4096 heisenberg10x10_conv3x32k3_b4096 \
          heisenberg10x10_conv5x64k5_b1024 heisenberg10x10_conv3x48k3_b4096 heisenberg10x10_conv3x16k9_b4096 \
          heisenberg10x10_conv3x32k7_b4096 heisenberg10x10_resnet2x16k5_b4096; do
-  python bench.py --workload $w --steps 3 --warmup 1 --no-cpu-baseline > "$out/$w.json" 2> "$out/$w.err" || { echo "FAILED $w"; tail -5 "$out/$w.err"; }
+  python bench.py --workload $w --steps 3 --warmup 1 --full --no-cpu-baseline > "$out/$w.json" 2> "$out/$w.err" || { echo "FAILED $w"; tail -5 "$out/$w.err"; }
   python - "$out/$w.json" <<'PY'
 import json, sys
 try:

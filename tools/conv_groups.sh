@@ -6,7 +6,7 @@ wl=${1:?workload}; steps=${2:-5}; shift; shift || true
 groups=${*:-1 2 3 4}
 for g in $groups; do
   CGS_VMC_CONV_GENERAL_GROUPS=$g timeout -k 10 280 python3 bench.py --workload "$wl" --steps "$steps" --warmup 1 \
-    --warm-sweeps 1 --reps 3 --no-extra --no-cpu-baseline 2>/dev/null | python3 -c "
+    --warm-sweeps 1 --reps 3 --full --no-extra --no-cpu-baseline 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d['kernels']

@@ -13,7 +13,7 @@ for m in "$@"; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DVMC_GR_ABLATE=$m ${ABLATE_EXTRA:-} -c $C/grad.hip -o "$D/g_$m.o" 2>/dev/null || exit 1
   /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 $OBJS "$D/g_$m.o" -o "$D/lib_$m.so" || exit 1
   CGS_VMC_DIAGNOSTIC_LIBRARY="$D/lib_$m.so" CGS_VMC_ALLOW_EXTRA_BUILD=1 timeout -k 10 200 \
-    python bench.py --workload heisenberg10x10_fc3x1024_b4096 --steps 20 --warmup 3 --reps 1 --no-cpu-baseline --no-extra 2>/dev/null \
+    python bench.py --workload heisenberg10x10_fc3x1024_b4096 --steps 20 --warmup 3 --reps 1 --full --no-cpu-baseline --no-extra 2>/dev/null \
     | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('ablate mask $m ${ABLATE_EXTRA:-}: sweep %.3f ms = %.1f us per mc_step' % (d['kernels']['sweep']['ms_avg'], d['kernels']['sweep']['ms_avg'] * 10))"

@@ -9,7 +9,7 @@ if [ $# -gt 0 ]; then
   timeout -k 10 900 python -m pytest "$@" -q -m gpu -x > $OUT/tests.log 2>&1; echo rc=$? >> $OUT/tests.log
   tail -4 $OUT/tests.log
 fi
-python bench.py --steps 100 --warmup 10 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --steps 100 --warmup 10 --full --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
 python - <<PY
 import json
 d = json.loads(open("$OUT/bench.json").read().strip().splitlines()[-1])
