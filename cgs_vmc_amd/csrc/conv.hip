@@ -121,11 +121,13 @@ long long conv_num_params(int n_conv, int F, int taps) { return plan_num_params_
 
 hipError_t launch_conv_pack(hipStream_t s, const float* theta, const ConvGeom& g, float* w0,
                             float* wf, float* wb, float* bias) {
+  if (!plan_cgen_periodic(g)) return hipErrorInvalidValue;      // (a graph: the general path's table-driven gathers)
   hipLaunchKernelGGL(k_conv_pack, dim3(64), dim3(256), 0, s, theta, g, w0, wf, wb, bias);
   return hipGetLastError();
 }
 
 hipError_t launch_conv_rows(hipStream_t s, const ConvRowsArgs& a, int num_cus) {
+  if (!plan_cgen_periodic(a.g)) return hipErrorInvalidValue;      // (a graph: the general path's table-driven gathers)
   if (a.n_rows <= 0) return hipSuccess;
   const size_t lds = conv_rows_lds(a.g, a.G);
   const dim3 grid(plan_conv_grid(a.g, a.n_rows, a.G, num_cus));      // one workgroup per co-resident slot
@@ -133,18 +135,21 @@ hipError_t launch_conv_rows(hipStream_t s, const ConvRowsArgs& a, int num_cus) {
 }
 
 hipError_t launch_conv_sweep(hipStream_t s, const ConvSweepArgs& a) {
+  if (!plan_cgen_periodic(a.g)) return hipErrorInvalidValue;      // (a graph: the general path's table-driven gathers)
   const dim3 grid((a.B + a.G - 1) / a.G);
   const size_t lds = conv_rows_lds(a.g, a.G);
   CONV_BY_NCB(sweep, s, a, grid, lds);
 }
 
 hipError_t launch_conv_back(hipStream_t s, const ConvBackArgs& a, int num_cus) {
+  if (!plan_cgen_periodic(a.g)) return hipErrorInvalidValue;      // (a graph: the general path's table-driven gathers)
   const size_t lds = conv_rows_lds(a.g, a.G);
   const dim3 grid(plan_conv_grid(a.g, a.B, a.G, num_cus));
   CONV_BY_NCB(back, s, a, grid, lds);
 }
 
 hipError_t launch_conv_dw(hipStream_t s, const ConvDwArgs& a_in) {
+  if (!plan_cgen_periodic(a_in.g)) return hipErrorInvalidValue;      // (a graph: the general path's table-driven gathers)
   ConvDwArgs a = a_in;
   const dim3 grid(a.n_slices, a.g.n_conv, plan_conv_dw_grid_z(a.g));
   // the whole sample at once when it fits (two workgroups per CU at 16 filters when THAT fits), else
@@ -162,6 +167,7 @@ hipError_t launch_conv_dw(hipStream_t s, const ConvDwArgs& a_in) {
 }
 
 hipError_t launch_conv_sr_rowdot(hipStream_t s, const ConvSrRowdotArgs& a, int num_cus) {
+  if (!plan_cgen_periodic(a.g)) return hipErrorInvalidValue;      // (a graph: the general path's table-driven gathers)
   if (a.n_rows <= 0) return hipSuccess;
   const size_t lds = conv_rows_lds(a.g, a.G);
   const dim3 grid(plan_conv_grid(a.g, a.n_rows, a.G, num_cus));

@@ -135,8 +135,13 @@ struct CgenIm2colArgs {
   int rows;                  // rows of this block
   int lda;                   // floats per row of A
   float* A;                  // [rows * N][lda]
+  const int* adj;            // g.graph: the adjacency list [N][KW] (tap t of position n reads site adj[n KW + t]); else unused
 };
 hipError_t launch_cgen_im2col(hipStream_t s, const CgenIm2colArgs& a);
+// gnn: the input gradient's scatter as a gather over the inverse lists (plan_gnn_inverse: ptr [N + 1], idx [N k] = m k + t)
+//   dst[row][n][c] (+)= sum over (m, t) in inv(n), in CSR order, of dA[row N + m][t F + c]      (no atomics: the same bits every run)
+hipError_t launch_gnn_col2im(hipStream_t s, const float* dA, int lda, const int* ptr, const int* idx, int rows, int N, int k,
+                             int F, int Fp, float* dst, bool accumulate);
 // One convolution of the general path at <= 16 filters WITHOUT an im2col matrix (conv_band.hip): bands of lattice rows
 // staged through LDS with their periodic halo, 16 output channels x 16 positions per MFMA tile, weights in registers.
 struct CgenBandArgs {

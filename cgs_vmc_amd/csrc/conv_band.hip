@@ -303,7 +303,8 @@ bool cgen_band_ok(const ConvGeom& g) { return plan_cgen_band_ok(g); }
 
 // the first convolution of any filter count when the neighbour table fits LDS (epilogues 1 / 4 / 11: no residual add in front)
 bool cgen_first_direct_ok(const ConvGeom& g, int epilogue) {
-  return (epilogue == 1 || epilogue == 4 || epilogue == 11) && plan_cgen_first_direct_lds_bytes(g) <= 64 * 1024;
+  return plan_cgen_periodic(g) && (epilogue == 1 || epilogue == 4 || epilogue == 11) &&
+         plan_cgen_first_direct_lds_bytes(g) <= 64 * 1024;
 }
 hipError_t launch_cgen_first_direct(hipStream_t s, const CgenBandArgs& a, int num_cus) {
   if (a.rows <= 0) return hipSuccess;

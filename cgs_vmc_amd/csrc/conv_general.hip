@@ -38,10 +38,22 @@ __device__ __forceinline__ int cg_site(const ConvGeom& g, int n, int t, bool inv
   return s1 * g.D2 + s2;
 }
 
+// The gather policy of the im2col kernels: GRAPH = false, the periodic lattice (cg_site); GRAPH = true, the gnn ansatz's
+// adjacency list (wavefunctions.py:1083-1154: tf.gather(x, adj, axis=1)).  The table is read through the vector L1 / L2
+// caches, not staged in LDS: the items of a workgroup are consecutive (position, tap) pairs, so its table reads are one
+// contiguous slice of adj (coalesced, each entry loaded once per channel quad and then cache-resident: a whole table is
+// N k 4 bytes, 4 KB for 144 sites x 7), and staging that slice would copy the same bytes once more behind a barrier.
+// (The entries differ from lane to lane, so the scalar cache does not apply.)
+template <bool GRAPH>
+__device__ __forceinline__ int cg_tap_site(const ConvGeom& g, const int* adj, int n, int t, bool inverse) {
+  if (GRAPH) return adj[n * g.KW + t];
+  return cg_site(g, n, t, inverse);
+}
+
 // convolutions 1 ..: A[m][t F + c] = f(in[row][site(n, t)][c]); VEC = 4: F % 4 == 0 (16-byte pieces), else scalar.
 // A workgroup takes `ppb` consecutive positions (>= 512 items of VEC floats); every index is 32-bit arithmetic (a
 // 64-bit division per item made the first form of this kernel VALU-bound: 3.2 TB/s of 165 us per layer).
-template <int VEC>
+template <int VEC, bool GRAPH>
 __global__ __launch_bounds__(256) void k_cgen_im2col(CgenIm2colArgs a, int ppb) {
   const ConvGeom g = a.g;
   const int T = g.K * g.KW, C = g.F / VEC, items = T * C;
@@ -53,7 +65,7 @@ __global__ __launch_bounds__(256) void k_cgen_im2col(CgenIm2colArgs a, int ppb) 
       const int t = it / C, cq = it - t * C;
       const int m = m0 + pl;
       const int r = m / g.N, n = m - r * g.N;
-      const float* src = a.src + ((long long)r * g.N + cg_site(g, n, t, a.inverse != 0)) * a.Fp + VEC * cq;
+      const float* src = a.src + ((long long)r * g.N + cg_tap_site<GRAPH>(g, a.adj, n, t, a.inverse != 0)) * a.Fp + VEC * cq;
       float* dst = a.A + (long long)m * a.lda + t * g.F + VEC * cq;
       if (VEC == 4) {
         f32x4 v = *(const f32x4*)src;
@@ -68,6 +80,7 @@ __global__ __launch_bounds__(256) void k_cgen_im2col(CgenIm2colArgs a, int ppb) 
 }
 
 // first convolution: A[m][t] = s'(site(n, t)) with s' = the row's spins, the exchanged pair negated
+template <bool GRAPH>
 __global__ __launch_bounds__(256) void k_cgen_im2col0(CgenIm2colArgs a) {
   const ConvGeom g = a.g;
   const int T = g.K * g.KW;
@@ -85,9 +98,53 @@ __global__ __launch_bounds__(256) void k_cgen_im2col0(CgenIm2colArgs a) {
       if (ri.y != 0) { const int2 ab = a.bonds[(ri.y > 0 ? ri.y : -ri.y) - 1]; fa = ab.x; fb = ab.y; }
     }
     if (a.iup) { fa = a.iup[a.row0 + r]; fb = a.idn[a.row0 + r]; }
-    const int s = cg_site(g, n, t);
+    const int s = cg_tap_site<GRAPH>(g, a.adj, n, t, false);
     const float x = a.src[(long long)chain * g.N + s];
     a.A[(long long)m * a.lda + t] = (s == fa || s == fb) ? -x : x;
+  }
+}
+
+// gnn: d / d input of a graph convolution from dA = G W^T (dA[m][t F + c] = d logit / d A[m][t F + c], the gradient of
+// the im2col matrix): every element of the input map received dA from the (position, tap) pairs that gathered it, which
+// are the site's inverse list -- summed here by ONE thread per (row, site, channel quad) in the list's order, so that the
+// bits do not depend on the launch (no atomics).  Consecutive lanes take consecutive channel quads of one site: the dA
+// reads of an inverse-list entry are one contiguous stretch.
+template <int VEC>
+__global__ __launch_bounds__(256) void k_gnn_col2im(const float* __restrict__ dA, int lda, const int* __restrict__ ptr,
+                                                    const int* __restrict__ idx, int rows, int N, int k, int F, int Fp,
+                                                    float* __restrict__ dst, int accumulate) {
+  const int C = F / VEC;
+  const long long total = (long long)rows * N * C;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long rn = i / C;                                   // row * N + site
+    const int cq = (int)(i - rn * C);
+    const int r = (int)(rn / N), n = (int)(rn - (long long)r * N);
+    const float* base = dA + (long long)r * N * lda + VEC * cq;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const int j1 = ptr[n + 1];
+    for (int j = ptr[n]; j < j1; ++j) {
+      const int e = idx[j];
+      const int m = e / k, t = e - m * k;
+      const float* p = base + (long long)m * lda + t * F;
+      if (VEC == 4) {
+        const f32x4 v = *(const f32x4*)p;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] += v[q];
+      } else {
+        acc[0] += *p;
+      }
+    }
+    float* d = dst + rn * Fp + VEC * cq;
+    if (VEC == 4) {
+      if (accumulate) {
+        const f32x4 o = *(const f32x4*)d;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = o[q] + acc[q];
+      }
+      *(f32x4*)d = acc;
+    } else {
+      *d = accumulate ? *d + acc[0] : acc[0];
+    }
   }
 }
 
@@ -355,17 +412,37 @@ hipError_t launch_cgen_im2col(hipStream_t s, const CgenIm2colArgs& a) {
   if (a.rows <= 0) return hipSuccess;
   const ConvGeom& g = a.g;
   const long long T = (long long)g.K * g.KW;
+  const bool graph = !plan_cgen_periodic(g);
+  if (graph && (a.inverse || !a.adj)) return hipErrorInvalidValue;    // (a graph's transposed convolution: launch_gnn_col2im)
   if (a.layer == 0) {
-    hipLaunchKernelGGL(k_cgen_im2col0, dim3(cg_blocks((long long)a.rows * g.N * T)), dim3(256), 0, s, a);
+    const dim3 grid(cg_blocks((long long)a.rows * g.N * T));
+    if (graph) hipLaunchKernelGGL(k_cgen_im2col0<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_cgen_im2col0<false>, grid, dim3(256), 0, s, a);
   } else {
     const int vec = g.F % 4 == 0 ? 4 : 1;
     const long long items = T * (g.F / vec), M = (long long)a.rows * g.N;
     const int ppb = (int)(items >= 512 ? 1 : (512 + items - 1) / items);
     const long long blocks = (M + ppb - 1) / ppb;
     const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536));
-    if (vec == 4) hipLaunchKernelGGL(k_cgen_im2col<4>, grid, dim3(256), 0, s, a, ppb);
-    else hipLaunchKernelGGL(k_cgen_im2col<1>, grid, dim3(256), 0, s, a, ppb);
+    if (graph) {
+      if (vec == 4) hipLaunchKernelGGL((k_cgen_im2col<4, true>), grid, dim3(256), 0, s, a, ppb);
+      else hipLaunchKernelGGL((k_cgen_im2col<1, true>), grid, dim3(256), 0, s, a, ppb);
+    } else {
+      if (vec == 4) hipLaunchKernelGGL((k_cgen_im2col<4, false>), grid, dim3(256), 0, s, a, ppb);
+      else hipLaunchKernelGGL((k_cgen_im2col<1, false>), grid, dim3(256), 0, s, a, ppb);
+    }
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_gnn_col2im(hipStream_t s, const float* dA, int lda, const int* ptr, const int* idx, int rows, int N, int k,
+                             int F, int Fp, float* dst, bool accumulate) {
+  if (rows <= 0) return hipSuccess;
+  if (!dA || !ptr || !idx || !dst || lda < k * F || Fp < F) return hipErrorInvalidValue;
+  const int vec = F % 4 == 0 ? 4 : 1;
+  const dim3 grid(cg_blocks((long long)rows * N * (F / vec)));
+  if (vec == 4) hipLaunchKernelGGL(k_gnn_col2im<4>, grid, dim3(256), 0, s, dA, lda, ptr, idx, rows, N, k, F, Fp, dst, accumulate ? 1 : 0);
+  else hipLaunchKernelGGL(k_gnn_col2im<1>, grid, dim3(256), 0, s, dA, lda, ptr, idx, rows, N, k, F, Fp, dst, accumulate ? 1 : 0);
   return hipGetLastError();
 }
 

@@ -537,8 +537,61 @@ static void sr_schedules() {
     }
 }
 
+// gnn (plan_desc's graph geometry, plan_gnn_check_adjacency, plan_gnn_inverse): every periodic-only route refuses the
+// geometry, the inverse lists hold every (position, tap) pair exactly once under its site, in ascending order
+static void gnn_grid() {
+  char msg[256];
+  for (int n : {2, 12, 100, 1296})
+    for (int k : {1, 2, 5, 9, 64, 65})
+      for (int F : {1, 6, 16, 64, 130, 1024, 1025})
+        for (int L : {1, 3}) {
+          vmc_desc d;
+          memset(&d, 0, sizeof(d));
+          d.ansatz = VMC_ANSATZ_GNN; d.n_sites = n; d.batch_size = 64; d.num_layers = L; d.layer_size = F;
+          d.kernel_size = k; d.output_activation = VMC_ACT_EXP;
+          DescPlan p;
+          const int rc = plan_desc(&d, true, &p, msg, sizeof(msg));
+          ++g_shapes;
+          if (k < 2 || k > 64 || F > 1024) { CHECK(rc == VMC_ERR_UNSUPPORTED && msg[0]); ++g_rejected; continue; }
+          CHECK(rc == VMC_OK && p.conv && p.conv_general && !p.resnet);
+          const ConvGeom& g = p.cg;
+          CHECK(g.graph == 1 && g.K == 1 && g.KW == k && g.D1 == 1 && g.D2 == n && g.N == n && g.n_conv == L);
+          CHECK(g.lo == 0 && g.lo2 == 0 && !plan_cgen_periodic(g));
+          CHECK(!plan_cgen_band_ok(g) && !plan_cgen_patch_ok(g, 64) && !plan_cgen_patch_routes(g, 64));
+          CHECK(p.P == plan_num_params_conv(L, F, k) && p.P == (long long)k * F + F + (L - 1) * ((long long)k * F * F + F));
+          CHECK(plan_cgen_lda(g) >= k * (L > 1 ? F : 1));
+          ++g_general;
+        }
+  // the table: a random one with repeats, its inverse lists
+  for (int n : {2, 7, 144})
+    for (int k : {2, 7, 64}) {
+      std::vector<int32_t> adj((size_t)n * k), ptr((size_t)n + 1), idx((size_t)n * k);
+      unsigned x = 12345u + n * 31u + k;
+      for (auto& a : adj) { x = x * 1103515245u + 12345u; a = (int32_t)((x >> 8) % (unsigned)n); }
+      CHECK(plan_gnn_check_adjacency(n, k, n, k, adj.data(), msg, sizeof(msg)) == VMC_OK);
+      CHECK(plan_gnn_check_adjacency(n, k, n + 1, k, adj.data(), msg, sizeof(msg)) == VMC_ERR_INVALID);
+      CHECK(plan_gnn_check_adjacency(n, k, n, k - 1, adj.data(), msg, sizeof(msg)) == VMC_ERR_INVALID);
+      plan_gnn_inverse(n, k, adj.data(), ptr.data(), idx.data());
+      CHECK(ptr[0] == 0 && ptr[n] == n * k);
+      std::vector<unsigned char> seen((size_t)n * k, 0);
+      for (int s = 0; s < n; ++s)
+        for (int j = ptr[s]; j < ptr[s + 1]; ++j) {
+          CHECK(idx[j] >= 0 && idx[j] < n * k && adj[(size_t)idx[j]] == s && !seen[(size_t)idx[j]]);
+          CHECK(j == ptr[s] || idx[j - 1] < idx[j]);
+          seen[(size_t)idx[j]] = 1;
+        }
+      const int32_t keep = adj[0];
+      for (int32_t bad : {-1, n}) {
+        adj[0] = bad;
+        CHECK(plan_gnn_check_adjacency(n, k, n, k, adj.data(), msg, sizeof(msg)) == VMC_ERR_INVALID);
+      }
+      adj[0] = keep;
+    }
+}
+
 int main() {
   check_block_maps();
+  gnn_grid();
   dense_grid();
   conv_grid();
   sr_schedules();

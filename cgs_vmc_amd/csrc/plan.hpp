@@ -70,6 +70,8 @@ inline long long plan_num_params_conv(int n_conv, long long F, long long taps) {
 #define CONV_MAX_NCB 4      // num_conv_filters <= 64
 #define CONV_GENERAL_MAX_K 31   // general path (conv_general.hip): any kernel size the periodic padding allows, bounded for the index arithmetic
 #define CONV_GENERAL_MAX_F 1024
+#define PLAN_GNN_MAX_K 64       // gnn: neighbours per position
+#define PLAN_GNN_MAX_SITES (1023 * 1023)
 #define CONV_MAX_K 9        // kernel_size (one instantiation per size; weights of a block pair in register-resident chunks of <= 25 taps)
 #define CONV_LDS_PER_WG ((size_t)80 * 1024)   // two 4-wave workgroups share the 160 KiB of a CU
 
@@ -93,6 +95,8 @@ struct ConvGeom {
   int lo2, hi2; // the same padding for axis 2 (0 for the 1-D modules)
   int NCB;      // channel blocks of 16: (F + 15) / 16
   int CS;       // dwords of one sample's feature map: 4 * NCB * GS
+  int graph;    // 1: gnn -- the taps come from an adjacency list adj[N][KW] (K = D1 = 1, D2 = N, no padding), not from
+                // the periodic lattice; every route that derives a tap's site from (D1, D2, lo, lo2) must refuse it
 };
 
 // LDS of a row / sampler / backward workgroup holding G samples: buf0, buf1, xs, pinfo, row_chain,
@@ -133,6 +137,7 @@ inline int plan_cgen_band_rows_for(const ConvGeom& g, long long rows, long long 
 // against every input block fit the registers (3 x 3: 64 filters; 4 x 4: 48; 5 x 5: 32; 7 x 7: 16), 2 .. 7 taps per
 // axis (2-D: K x K; 1-D: K x 1), a band of at least one lattice row within the LDS budget
 inline bool plan_cgen_band_ok(const ConvGeom& g) {
+  if (g.graph) return false;          // (its bands are stretches of the periodic lattice)
   if (g.F < 1 || g.F > 64 || g.K < 2 || g.K > 7) return false;
   if (!(g.KW == g.K || g.KW == 1)) return false;
   if (g.K * g.KW * 4 * plan_cgen_band_ncb(g) > PLAN_CGEN_BAND_MAX_FRAGS) return false;
@@ -181,6 +186,7 @@ inline size_t plan_cgen_patch_lds_bytes(const ConvGeom& g) {
 }
 #define PLAN_CGEN_PATCH_LDS (156 * 1024)
 inline bool plan_cgen_patch_ok(const ConvGeom& g, long long B) {
+  if (g.graph) return false;          // (its boxes are rectangles of the periodic lattice)
   if (g.n_conv < 2 || g.n_conv > 9 || g.F > 16 || !plan_cgen_band_ok(g)) return false;       // (residual networks: 1 + 2 blocks convolutions)
   if (plan_cgen_patch_side(g, g.n_conv - 1, 0) > g.D1 || plan_cgen_patch_side(g, g.n_conv - 1, 1) > g.D2) return false;
   if (g.N > 16384 || B < 1) return false;
@@ -201,6 +207,11 @@ inline bool plan_cgen_patch_routes(const ConvGeom& g, long long B) {
   for (int l = 0; l < g.n_conv; ++l) boxes += 2LL * plan_cgen_patch_side(g, l, 0) * plan_cgen_patch_side(g, l, 1);
   return 5 * boxes <= (long long)g.n_conv * g.N;
 }
+// The routes of the general path whose gathers compute a tap's site from the periodic lattice -- the band kernel and
+// its first-convolution form (k_cgen_band, k_cgen_first_direct), the patch kernels, the implicit A-operand gather of
+// k_gemm_ring (GemmArgs.conv_a) -- take only these geometries; a graph (gnn) runs the table-driven im2col + GEMM form.
+// (With K = D1 = 1 a graph's shape alone would pass some of their checks and give wrong answers.)
+PLAN_HD inline bool plan_cgen_periodic(const ConvGeom& g) { return g.graph == 0; }
 // k_cgen_first_direct (conv_band.hip): spins [N], weights [taps][Fp], bias [Fp], neighbour table [N][taps]
 inline size_t plan_cgen_first_direct_lds_bytes(const ConvGeom& g) {
   const size_t fp = (size_t)((g.F + 3) & ~3), t = (size_t)g.K * g.KW;
@@ -440,8 +451,8 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
                      int conv_general_pref = 0) {
   memset(out, 0, sizeof(*out));
 #define PLAN_FAIL(code, text) do { snprintf(msg, msg_len, "%s", text); return code; } while (0)
-  if (d->ansatz < VMC_ANSATZ_FULLY_CONNECTED || d->ansatz > VMC_ANSATZ_RES_NET_1D)
-    PLAN_FAIL(VMC_ERR_UNSUPPORTED, "only the fully_connected, rbm, conv_1d/2d and res_net_1d/2d ansatz types have HIP kernels");
+  if (d->ansatz < VMC_ANSATZ_FULLY_CONNECTED || d->ansatz > VMC_ANSATZ_GNN)
+    PLAN_FAIL(VMC_ERR_UNSUPPORTED, "only the fully_connected, rbm, conv_1d/2d, res_net_1d/2d and gnn ansatz types have HIP kernels");
   const bool rbm = d->ansatz == VMC_ANSATZ_RBM;
   const bool conv = d->ansatz >= VMC_ANSATZ_CONV_2D;
   const bool resnet = d->ansatz == VMC_ANSATZ_RES_NET_2D || d->ansatz == VMC_ANSATZ_RES_NET_1D;
@@ -450,7 +461,28 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
   if (d->n_sites < 2 || d->batch_size < 1 || d->num_layers < ((rbm || resnet) ? 0 : 1) || d->layer_size < 1)
     PLAN_FAIL(VMC_ERR_INVALID, "n_sites >= 2, batch_size, layer_size >= 1, num_layers >= 1 (rbm, res_net_2d: >= 0) required");
   ConvGeom& cg = out->cg;
-  if (conv) {
+  if (d->ansatz == VMC_ANSATZ_GNN) {
+    // GraphConvNetwork (wavefunctions.py:1083-1154): a graph convolution = gather(x, adj) + snt.Conv2D with a 1 x k kernel
+    // (layers.py:415-451) = a 1 x k convolution whose taps are read off the table -- the general path's im2col + GEMM
+    // form with a table-driven gather (conv_general.hip).  Always the general path: the fused kernels, the band and patch
+    // kernels and the implicit gather are periodic (plan_cgen_periodic).
+    const int k = d->kernel_size;
+    if (k < 2 || k > PLAN_GNN_MAX_K) PLAN_FAIL(VMC_ERR_UNSUPPORTED, "gnn: kernel_size (neighbours per position) must be in 2..64");
+    if (d->layer_size > CONV_GENERAL_MAX_F)
+      PLAN_FAIL(VMC_ERR_UNSUPPORTED, "num_conv_filters > 1024 not supported by the convolution kernels");
+    if ((long long)d->num_layers > CONV_MAX_LAYERS) PLAN_FAIL(VMC_ERR_UNSUPPORTED, "too many convolutions");
+    if (d->n_sites > PLAN_GNN_MAX_SITES) PLAN_FAIL(VMC_ERR_UNSUPPORTED, "gnn: num_sites beyond the general convolution path's 1023 x 1023");
+    cg.K = 1; cg.KW = k; cg.D1 = 1; cg.D2 = d->n_sites; cg.N = d->n_sites; cg.F = d->layer_size;
+    cg.n_conv = d->num_layers; cg.resnet = 0; cg.hact = d->nonlinearity;
+    cg.GS = (4 * cg.N + 63) / 64 * 64;
+    cg.NCB = (cg.F + CONV_FP - 1) / CONV_FP;
+    cg.CS = 4 * cg.NCB * cg.GS;
+    cg.lo = cg.hi = cg.lo2 = cg.hi2 = 0;
+    cg.graph = 1;
+    if ((long long)cg.N * plan_cgen_lda(cg) >= (1LL << 28))
+      PLAN_FAIL(VMC_ERR_UNSUPPORTED, "num_sites x k x filters too large for the general convolution path (one sample's im2col rows beyond 1 GiB)");
+    out->conv_general = 1;
+  } else if (conv) {
     // Conv2DNetwork reshapes its input to [-1, size_x, size_y, 1] (wavefunctions.py:596-597);
     // Conv1DNetwork expands [B, N] to [B, N, 1] (wavefunctions.py:511): an N x 1 lattice here
     const int sx = one_d ? d->n_sites : d->size_x, sy = one_d ? 1 : d->size_y;
@@ -528,6 +560,35 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
   }
   if (msg_len) msg[0] = 0;
   return VMC_OK;
+}
+
+// ------------------------------------------------------------------------------- gnn adjacency list
+// vmc_set_adjacency's validation: the table of a ctx of n_sites sites and k taps, every entry a site
+// (wavefunctions.py:1083-1154 gathers with tf.gather, which has no wrap-around: an entry outside [0, N) is an error)
+inline int plan_gnn_check_adjacency(int n_sites, int k, int ctx_sites, int ctx_k, const int32_t* adj, char* msg, size_t msg_len) {
+  if (!adj) { snprintf(msg, msg_len, "null adjacency list"); return VMC_ERR_INVALID; }
+  if (n_sites != ctx_sites || k != ctx_k) {
+    snprintf(msg, msg_len, "adjacency list of %d x %d entries, the ctx has num_sites = %d and k = %d", n_sites, k, ctx_sites, ctx_k);
+    return VMC_ERR_INVALID;
+  }
+  for (long long i = 0; i < (long long)n_sites * k; ++i)
+    if (adj[i] < 0 || adj[i] >= n_sites) {
+      snprintf(msg, msg_len, "adjacency list entry [%lld][%lld] = %d outside [0, %d)", i / k, i % k, (int)adj[i], n_sites);
+      return VMC_ERR_INVALID;
+    }
+  if (msg_len) msg[0] = 0;
+  return VMC_OK;
+}
+// The inverse lists of a valid table, CSR: the pairs (position m, tap t) whose tap reads site n are
+// idx[ptr[n] .. ptr[n + 1]), each stored as m k + t (the column block of the im2col matrix), in ascending m k + t --
+// the fixed order in which k_gnn_col2im sums them.  ptr [n_sites + 1], idx [n_sites k]; a counting sort.
+inline void plan_gnn_inverse(int n_sites, int k, const int32_t* adj, int32_t* ptr, int32_t* idx) {
+  for (int n = 0; n <= n_sites; ++n) ptr[n] = 0;
+  for (long long i = 0; i < (long long)n_sites * k; ++i) ++ptr[adj[i] + 1];
+  for (int n = 0; n < n_sites; ++n) ptr[n + 1] += ptr[n];
+  for (long long i = 0; i < (long long)n_sites * k; ++i) idx[ptr[adj[i]]++] = (int32_t)i;   // (ptr[n] ends at ptr[n + 1])
+  for (int n = n_sites; n > 0; --n) ptr[n] = ptr[n - 1];
+  ptr[0] = 0;
 }
 
 // ------------------------------------------------------------------------------- weight-gradient GEMM

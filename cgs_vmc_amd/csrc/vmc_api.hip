@@ -11,7 +11,13 @@ namespace vmcapi { std::string g_create_error; }
 
 namespace vmcapi {
 
+int gnn_ready(vmc_ctx* c) {
+  if (c->cg.graph && !c->gnn_adj) return fail(c, VMC_ERR_INVALID, "gnn: no adjacency list (vmc_set_adjacency)");
+  return VMC_OK;
+}
+
 int ensure_packed(vmc_ctx* c, int which) {
+  PROPAGATE(gnn_ready(c));
   ParamSet& p = c->ps[which];
   if (!p.has_params) return fail(c, VMC_ERR_STATE, "parameters not set (vmc_set_params)");
   if (p.packed_valid) return VMC_OK;
@@ -310,6 +316,7 @@ int64_t vmc_num_params_ansatz(int32_t ansatz, int32_t n_sites, int32_t layer_siz
 }
 
 int64_t vmc_num_params_conv(int32_t ansatz, int32_t num_layers, int32_t num_filters, int32_t kernel_size) {
+  if (ansatz == VMC_ANSATZ_GNN) return conv_num_params(num_layers, num_filters, kernel_size);   // k taps of 1 x k
   const bool resnet = ansatz == VMC_ANSATZ_RES_NET_2D || ansatz == VMC_ANSATZ_RES_NET_1D;
   const bool one_d = ansatz == VMC_ANSATZ_CONV_1D || ansatz == VMC_ANSATZ_RES_NET_1D;
   const int n_conv = resnet ? 1 + 2 * num_layers : num_layers;
@@ -553,6 +560,7 @@ void vmc_destroy(vmc_ctx* c) {
   if (c->cg_sum) hipFree(c->cg_sum);
   if (c->cg_td) hipFree(c->cg_td);
   if (c->cg_centre) hipFree(c->cg_centre);
+  for (int* q : {c->gnn_adj, c->gnn_inv_ptr, c->gnn_inv}) if (q) hipFree(q);
   void* ptrs[] = {c->configs, c->configs_alt, c->bonds, c->half_jx, c->quarter_jz, c->cnt, c->off, c->diag, c->val,
                   c->offdiag, c->rowinfo, c->delta_all, c->d_batch[0][0], c->d_batch[0][1], c->d_batch[1][0], c->d_batch[1][1], c->ratio, c->ones, c->acc,
                   c->adam_m, c->adam_v, c->grad_tmp, c->gemm_ws, c->wg_tickets, c->d_accepted, c->d_sum,
@@ -599,6 +607,30 @@ int vmc_set_bonds(vmc_ctx* c, int32_t n_bonds, const int32_t* ij, const float* j
   HIPCHK(c, hipMemcpy(c->quarter_jz, qz.data(), n_bonds * sizeof(float), hipMemcpyHostToDevice));
   c->list_valid = false;
   c->cnt_valid = false;
+  return VMC_OK;
+}
+
+int vmc_set_adjacency(vmc_ctx* c, int32_t n_sites, int32_t k, const int32_t* adj) {
+  ENTER(c);
+  if (!c->cg.graph) return fail(c, VMC_ERR_INVALID, "vmc_set_adjacency: not a gnn ctx");
+  {
+    char msg[256];
+    const int rc = plan_gnn_check_adjacency(n_sites, k, c->N, c->cg.KW, adj, msg, sizeof(msg));
+    if (rc != VMC_OK) return fail(c, rc, msg);
+  }
+  std::vector<int32_t> ptr((size_t)n_sites + 1), inv((size_t)n_sites * k);
+  plan_gnn_inverse(n_sites, k, adj, ptr.data(), inv.data());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (!c->gnn_adj) {
+    HIPCHK(c, dalloc(&c->gnn_adj, (long long)n_sites * k));
+    HIPCHK(c, dalloc(&c->gnn_inv_ptr, (long long)n_sites + 1));
+    HIPCHK(c, dalloc(&c->gnn_inv, (long long)n_sites * k));
+  }
+  HIPCHK(c, hipMemcpy(c->gnn_adj, adj, (size_t)n_sites * k * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->gnn_inv_ptr, ptr.data(), ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->gnn_inv, inv.data(), inv.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  c->ps[0].cache_valid = c->ps[1].cache_valid = false;     // (the logits of the chains belong to the previous graph)
+  c->cg_sr_tape_rows = 0;
   return VMC_OK;
 }
 

@@ -62,8 +62,8 @@ static int cgen_conv(vmc_ctx* c, const ParamSet& p, const float* configs, const 
     else HIPCHK(c, launch_cgen_first_direct(cg_s(c), b, c->num_cus));     // more than 16 filters: the first convolution only
     return VMC_OK;
   }
-  // the gather inside the product's A operand (k_gemm_ring<., true>): no im2col matrix for this convolution
-  if (l > 0 && pre < 0 && cgen_implicit_on()) {
+  // the gather inside the product's A operand (k_gemm_ring<., true>): no im2col matrix for this convolution (periodic only)
+  if (l > 0 && pre < 0 && plan_cgen_periodic(g) && cgen_implicit_on()) {
     m.A = in; m.conv_a = 1; m.ca_N = g.N; m.ca_D1 = g.D1; m.ca_D2 = g.D2; m.ca_KW = g.KW; m.ca_lo = g.lo; m.ca_lo2 = g.lo2;
     m.ca_F = g.F; m.ca_Fp = Fp;
     if (gemm_conv_a_ok(m)) { HIPCHK(c, launch_gemm(cg_s(c), m)); return VMC_OK; }
@@ -73,6 +73,7 @@ static int cgen_conv(vmc_ctx* c, const ParamSet& p, const float* configs, const 
   CgenIm2colArgs a;
   memset(&a, 0, sizeof(a));
   a.g = g; a.layer = l; a.Fp = Fp; a.pre_act = pre; a.rows = rows; a.lda = lda; a.A = c->cg_A + c->cg_map_row0 * g.N * lda;
+  a.adj = c->gnn_adj;
   if (l == 0) {
     a.src = configs; a.rowinfo = rowinfo; a.row0 = row0; a.bonds = c->bonds ? c->bonds : c->bond_dummy;
     a.iup = iup; a.idn = idn;
@@ -139,6 +140,7 @@ int cgen_forward(vmc_ctx* c, int which, const float* configs, const int2* rowinf
   const long long moff = c->cg_map_row0 * g.N * Fp;      // (a sampler group's slice of the maps; 0 elsewhere)
   auto map = [&](int l) { return tape ? tape + (long long)l * tape_stride : c->cg_fm[g.resnet ? (l & 1 ? 1 : 0) : (l & 1)] + moff; };
   if (tape && n_rows > c->cg_rows) return fail(c, VMC_ERR_STATE, "taped forward beyond one block");
+  PROPAGATE(gnn_ready(c));
   // The rows of a row list over the ctx's chains -- the local energies' connected configurations (operators.py:162-169:
   // the chain with one antiparallel bond exchanged) -- through the patch kernel: the chains' maps once (B forwards), then
   // per row the boxes around the bond's two sites and the last map's sum with them overlaid; the sums are k_cgen_rowsum's
@@ -220,6 +222,7 @@ static int cgen_gather_input(vmc_ctx* c, int l, int rows, long long row0, const 
   CgenIm2colArgs a;
   memset(&a, 0, sizeof(a));
   a.g = g; a.layer = l; a.Fp = cgen_fp(g); a.rows = rows; a.lda = plan_cgen_lda(g); a.A = c->cg_A; a.pre_act = -1;
+  a.adj = c->gnn_adj;
   if (l == 0) { a.src = configs; a.row0 = row0; a.bonds = c->bonds ? c->bonds : c->bond_dummy; }
   else { a.src = cgen_tape(c, l - 1); a.pre_act = cgen_in_pre(c, l); }          // (residual blocks: h / the stored selu(u))
   HIPCHK(c, launch_cgen_im2col(c->stream, a));
@@ -227,9 +230,22 @@ static int cgen_gather_input(vmc_ctx* c, int l, int rows, long long row0, const 
 }
 
 // dst (+)= the transposed convolution l (>= 1) of G: the inverse gather against the transposed weight image
+// (gnn: dA = G W_l^T into cg_A -- W_l as it lies in theta, [k Cin][F], read transposed -- then the sum of dA over every
+// site's inverse list, k_gnn_col2im: a general graph has no inverse gather of the periodic kind)
 static int cgen_input_grad(vmc_ctx* c, int l, int rows, const float* G, float* dst, bool accumulate) {
   const ConvGeom& g = c->cg;
   PROPAGATE(cgen_need_A(c));
+  if (!plan_cgen_periodic(g)) {
+    const int lda = plan_cgen_lda(g), Fp = cgen_fp(g);
+    GemmArgs m; memset(&m, 0, sizeof(m));
+    m.A = G; m.sam = Fp; m.sak = 1;
+    m.B = c->ps[VMC_PSI].theta + cgen_off_w(g, l); m.sbk = 1; m.sbn = g.F;       // B(o, t F + c) = w[t][c][o]
+    m.M = rows * g.N; m.N = g.KW * g.F; m.K = g.F; m.C = c->cg_A; m.ldc = lda;
+    m.epilogue = 0; m.splitk = 1;
+    HIPCHK(c, launch_gemm(c->stream, m));
+    HIPCHK(c, launch_gnn_col2im(c->stream, c->cg_A, lda, c->gnn_inv_ptr, c->gnn_inv, rows, g.N, g.KW, g.F, Fp, dst, accumulate));
+    return VMC_OK;
+  }
   CgenIm2colArgs a;
   memset(&a, 0, sizeof(a));
   a.g = g; a.layer = l; a.Fp = cgen_fp(g); a.rows = rows; a.lda = plan_cgen_lda(g); a.A = c->cg_A; a.pre_act = -1;
@@ -295,9 +311,10 @@ int cgen_gradient_sums(vmc_ctx* c, const float* w) {
   c->cg_sr_tape_rows = 0;                  // (this path overwrites the tapes an SR solve may have left)
   const ConvGeom& g = c->cg;
   ParamSet& p = c->ps[0];
+  PROPAGATE(gnn_ready(c));
   PROPAGATE(cgen_grad_buffers(c));
   const long long map_floats = c->cg_rows * g.N * cgen_fp(g);
-  for (int l = 1; l < g.n_conv; ++l)
+  for (int l = 1; l < g.n_conv && plan_cgen_periodic(g); ++l)      // (gnn: the products read theta transposed)
     HIPCHK(c, launch_cgen_pack_t(c->stream, p.theta + cgen_off_w(g, l), g.K * g.KW, g.F, c->cg_wt + cgen_off_wt(g, l)));
   if (c->oact != VMC_ACT_EXP_) {
     PROPAGATE(ensure_cache(c, VMC_PSI));
@@ -340,10 +357,11 @@ static int cgen_sr_fwd_bwd(vmc_ctx* c, long long row0, int rows, long long n_row
 int cgen_sr_phase1(vmc_ctx* c, const float* v, int n_rows) {        // sr_t[b] = O_b . v
   const ConvGeom& g = c->cg;
   ParamSet& p = c->ps[0];
+  PROPAGATE(gnn_ready(c));
   PROPAGATE(cgen_grad_buffers(c));
   if (!c->cg_td) { HIPCHK(c, dalloc(&c->cg_td, c->cg_rows)); HIPCHK(c, dalloc(&c->cg_centre, 1)); }
   const int Fp = cgen_fp(g), lda = plan_cgen_lda(g);
-  for (int l = 1; l < g.n_conv; ++l)
+  for (int l = 1; l < g.n_conv && plan_cgen_periodic(g); ++l)      // (gnn: the products read theta transposed)
     HIPCHK(c, launch_cgen_pack_t(c->stream, p.theta + cgen_off_w(g, l), g.K * g.KW, g.F, c->cg_wt + cgen_off_wt(g, l)));
   for (long long row0 = 0; row0 < n_rows; row0 += c->cg_rows) {
     const int rows = (int)(n_rows - row0 < c->cg_rows ? n_rows - row0 : c->cg_rows);

@@ -98,6 +98,9 @@ struct vmc_ctx {
   long long cg_sr_tape_rows = 0;           // > 0: cg_tape / cg_gl hold the taped forward and the backward of the first that many STORED chains
                                            // at the parameters of the running solve (one block: kept across its CG iterations)
   float* cg_centre = nullptr;              // [1] mean of O_b . v over the stored samples (SR)
+  // gnn (cg.graph): the adjacency list [N][k] and its inverse lists (plan_gnn_inverse: [N + 1] offsets, [N k] entries m k + t),
+  // set by vmc_set_adjacency; every compute entry of a gnn ctx refuses to run without them (gnn_ready)
+  int* gnn_adj = nullptr; int* gnn_inv_ptr = nullptr; int* gnn_inv = nullptr;
   bool sr_centre = false;                  // the SR matvec may centre its weights: a single-rank solve is running
   bool sr_phase1_done = false;             // vmc_sr_matvec_phase1 has run for the current CG direction (general convolution path)
   int *wide_iup = nullptr, *wide_idn = nullptr;
@@ -380,6 +383,8 @@ int grow_tmp(vmc_ctx* c, long long rows);
 int cgen_forward(vmc_ctx* c, int which, const float* configs, const int2* rowinfo, long long n_rows,
                  const int* iup, const int* idn, bool ratio, float* out, float* tape = nullptr,
                  long long tape_stride = 0, long long first_row = 0);
+// VMC_ERR_INVALID (with the message) when `c` is a gnn ctx whose adjacency list has not been set
+int gnn_ready(vmc_ctx* c);
 int cgen_patch_mode(const vmc_ctx* c);
 int cgen_patch_maps(vmc_ctx* c, int which);
 void cgen_patch_args(const vmc_ctx* c, int which, CgenPatchArgs* a);

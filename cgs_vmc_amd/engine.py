@@ -52,12 +52,29 @@ class VmcEngine:
                nonlinearity: str = 'relu', output_activation: str = 'exp', device: int = 0,
                chain_offset: int = 0, seed: int = 2024, stream: int = 0,
                ansatz: str = 'fully_connected', kernel_size: int = 0, size_x: int = 0,
-               size_y: int = 0):
+               size_y: int = 0, adjacency=None):
     """Dense ansatz types: num_layers / layer_size = num_fc_layers / fc_layer_size.  Convolutional
     ones ('conv_2d', 'res_net_2d'): num_layers = num_conv_layers or num_resnet_blocks, layer_size =
-    num_conv_filters, plus kernel_size and the lattice size_x x size_y (= n_sites)."""
+    num_conv_filters, plus kernel_size and the lattice size_x x size_y (= n_sites).  'gnn':
+    num_layers = num_conv_layers, layer_size = num_conv_filters and `adjacency`, the [n_sites][k]
+    int table (or its int32 bytes, as GraphConvNetwork._engine_spec carries it); kernel_size may
+    be left 0 (k is read off the table)."""
     self._lib = _hip.load()
     self._ctx = C.c_void_p()
+    adj = None
+    if ansatz == 'gnn':
+      if adjacency is None:
+        raise ValueError("the 'gnn' ansatz needs an adjacency list")
+      if isinstance(adjacency, (bytes, bytearray)):
+        adj = np.frombuffer(adjacency, dtype=np.int32).reshape(n_sites, -1)
+      else:
+        adj = np.asarray(adjacency)
+        if adj.ndim != 2 or adj.shape[0] != n_sites:
+          raise ValueError('adjacency list must have shape [n_sites, k]')
+      adj = np.ascontiguousarray(adj, dtype=np.int32)
+      kernel_size = kernel_size or adj.shape[1]
+      if kernel_size != adj.shape[1]:
+        raise ValueError('kernel_size {} != the adjacency list\'s {} columns'.format(kernel_size, adj.shape[1]))
     for name, act in (('nonlinearity', nonlinearity), ('output_activation', output_activation)):
       if act not in _hip.ACT_IDS:
         raise ValueError('unknown {} {!r}'.format(name, act))
@@ -73,6 +90,12 @@ class VmcEngine:
       self._ctx = C.c_void_p()
       self._raise(rc, msg)
     _LIVE_ENGINES.add(self)
+    if adj is not None:       # the graph is part of the ansatz: set before anything can run on the ctx
+      rc = self._lib.vmc_set_adjacency(self._ctx, adj.shape[0], adj.shape[1], _iptr(adj))
+      if rc != _hip.VMC_OK:
+        msg = self._lib.vmc_last_error(self._ctx).decode()
+        self.close()
+        self._raise(rc, msg)
     self.n_sites, self.batch_size = n_sites, batch_size
     self.num_layers, self.layer_size = num_layers, layer_size
     self.chain_offset, self.seed, self.device = chain_offset, seed, device

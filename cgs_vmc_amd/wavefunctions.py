@@ -616,6 +616,83 @@ class ResNet1D(Conv1DNetwork):
     return cls(**res_net_1d_params)
 
 
+def check_adjacency(adj, num_sites=None) -> np.ndarray:
+  """The adjacency list of GraphConvNetwork as an int32 [N, k] array, or ValueError: a table that
+  loads 1-D (one column -- the reference fails there too), a row count other than num_sites, an
+  entry outside [0, N)."""
+  adj = np.asarray(adj)
+  if adj.ndim != 2:
+    raise ValueError('gnn: the adjacency list must be a 2-D table [num_sites, k], got shape %s'
+                     % (adj.shape,))
+  if adj.size and not np.issubdtype(adj.dtype, np.integer):
+    raise ValueError('gnn: the adjacency list must hold integers')
+  n = adj.shape[0] if num_sites is None else num_sites
+  if adj.shape[0] != n:
+    raise ValueError('gnn: the adjacency list has %d rows, num_sites is %d' % (adj.shape[0], n))
+  if adj.size and (adj.min() < 0 or adj.max() >= n):
+    raise ValueError('gnn: adjacency list entries must lie in [0, %d)' % n)
+  return np.ascontiguousarray(adj, dtype=np.int32)
+
+
+class GraphConvNetwork(Conv2DNetwork):
+  """[GraphConvLayer(num_filters, adj), nonlinearity] x (num_layers - 1), GraphConvLayer,
+  reduce_sum over sites and channels, (- exp_norm_shift), exp   (wavefunctions.py:1083-1154;
+  layers.GraphConvLayer, layers.py:415-451).  A layer gathers x[:, adj] -> [B, N, k, Cin] and
+  applies snt.Conv2D with a 1 x k kernel and VALID padding: a 1 x k convolution whose taps are
+  read off the table.  The kernels are the general convolution path's with table-driven gathers
+  (csrc/conv_general.hip)."""
+  _ansatz = 'gnn'
+
+  def __init__(self, num_layers: int, num_filters: int, adj: np.ndarray,
+               nonlinearity=layers.NONLINEARITIES['relu'],
+               output_activation=layers.NONLINEARITIES['exp'], name: str = 'graph_conv_network'):
+    adj = check_adjacency(adj)
+    super(GraphConvNetwork, self).__init__(
+        num_layers=num_layers, num_filters=num_filters, kernel_size=int(adj.shape[1]), size_x=0,
+        size_y=0, nonlinearity=nonlinearity, output_activation=output_activation, name=name)
+    self._adj = adj
+
+  def _conv_scopes(self):
+    return ['graph_conv_layer' if l == 0 else 'graph_conv_layer_%d' % l
+            for l in range(self._num_layers)]
+
+  def _shapes(self):
+    check_adjacency(self._adj, self._n_sites)           # tf.gather with a table of another graph fails
+    k, f, u = self._kernel_size, self._num_filters, self._unique_name
+    names, shapes, cin = [], [], 1
+    for scope in self._conv_scopes():
+      names += ['%s/%s/conv_2d/w' % (u, scope), '%s/%s/conv_2d/b' % (u, scope)]
+      shapes += [(1, k, cin, f), (f,)]
+      cin = f
+    return names, shapes
+
+  def _bind(self, configs_var):
+    check_adjacency(self._adj, configs_var.shape[1])
+    return super(GraphConvNetwork, self)._bind(configs_var)
+
+  def _engine_spec(self):
+    spec = FullyConnectedNetwork._engine_spec(self)
+    # the graph as bytes: hashable and compared by value, so psi and its dc_ copy share one ctx and
+    # two different graphs never do
+    spec.update(kernel_size=self._kernel_size, size_x=0, size_y=0, adjacency=self._adj.tobytes())
+    return spec
+
+  @classmethod
+  def from_hparams(cls, hparams, name: str = '') -> 'Wavefunction':
+    """wavefunctions.py:1138-1154; the path is read as given (relative to the working directory)."""
+    adj = np.genfromtxt(hparams.adjacency_list_path, dtype=int)
+    gnn_params = {
+        'num_layers': hparams.num_conv_layers,
+        'num_filters': hparams.num_conv_filters,
+        'adj': check_adjacency(adj, hparams.num_sites),
+        'output_activation': layers.NONLINEARITIES[hparams.output_activation],
+        'nonlinearity': layers.NONLINEARITIES[hparams.nonlinearity],
+    }
+    if name:
+      gnn_params['name'] = name
+    return cls(**gnn_params)
+
+
 class AmplitudeTensor(session_lib.Tensor):
   """psi = wavefunction(inputs); evaluates to a float32 array [rows]."""
 
@@ -640,8 +717,8 @@ class _OutOfScope(Wavefunction):
   def from_hparams(cls, hparams, name: str = ''):
     raise NotImplementedError(
         "wavefunction_type '%s' is outside the MI355X hot path (SURVEY.md 2); only "
-        "'fully_connected', 'rbm', 'conv_1d', 'conv_2d', 'res_net_1d' and 'res_net_2d' have HIP "
-        "kernels" % cls._kind)
+        "'fully_connected', 'rbm', 'conv_1d', 'conv_2d', 'res_net_1d', 'res_net_2d' and 'gnn' have "
+        "HIP kernels" % cls._kind)
 
 
 def _stub(kind):
@@ -669,5 +746,5 @@ WAVEFUNCTION_TYPES = {
     'res_net_1d': ResNet1D,
     'res_net_2d': ResNet2D,
     'ed_vector': _stub('ed_vector'),
-    'gnn': _stub('gnn'),
+    'gnn': GraphConvNetwork,
 }

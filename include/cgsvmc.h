@@ -29,6 +29,10 @@
  * Conv1DNetwork (wavefunctions.py:455-527) and ResNet1D (wavefunctions.py:618-707): the same with
  * snt.Conv1D variables w[k][in_channels][F], b[F] per layers.Conv1dPeriodic;
  * P = k*F + F + (n_conv - 1)*(k*F*F + F).
+ * GraphConvNetwork ('gnn', wavefunctions.py:1083-1154; layers.py:415-451): num_layers graph
+ * convolutions over an adjacency list adj[N][k] (vmc_set_adjacency), each one snt.Conv2D with a
+ * 1 x k kernel: w[1][k][in_channels][F] (row-major) followed by b[F];
+ * P = k*F + F + (num_layers - 1)*(k*F*F + F).
  */
 #ifndef CGSVMC_H_
 #define CGSVMC_H_
@@ -58,7 +62,8 @@ enum { VMC_MODE_ENERGY_GRADIENT = 0, VMC_MODE_LOG_OVERLAP_ITSWO = 1 };
 
 /* wavefunctions.WAVEFUNCTION_TYPES with kernels (wavefunctions.py:1157-1170) */
 enum { VMC_ANSATZ_FULLY_CONNECTED = 0, VMC_ANSATZ_RBM = 1, VMC_ANSATZ_CONV_2D = 2,
-       VMC_ANSATZ_RES_NET_2D = 3, VMC_ANSATZ_CONV_1D = 4, VMC_ANSATZ_RES_NET_1D = 5 };
+       VMC_ANSATZ_RES_NET_2D = 3, VMC_ANSATZ_CONV_1D = 4, VMC_ANSATZ_RES_NET_1D = 5,
+       VMC_ANSATZ_GNN = 6 };
 
 /* layers.NONLINEARITIES ids (layers.py:13-21).  Every id is accepted as hidden and as output
  * activation of every ansatz type with kernels. */
@@ -86,9 +91,10 @@ typedef struct {
   uint64_t seed;             /* Philox key                                           */
   void* stream;              /* hipStream_t to launch on, or NULL for the null stream*/
   /* convolutional ansatz types only (ignored otherwise) */
-  int32_t kernel_size;       /* hparams.kernel_size (utils.py:110): fused kernels 1..9, general path to 31 */
+  int32_t kernel_size;       /* hparams.kernel_size (utils.py:110): fused kernels 1..9, general path to 31;
+                                gnn: k, the neighbours per position of the adjacency list (2..64) */
   int32_t size_x, size_y;    /* hparams.size_x, size_y (utils.py:99-100); n_sites = size_x*size_y
-                                (ignored by the 1-D types: the chain has n_sites sites)          */
+                                (ignored by the 1-D types: the chain has n_sites sites; and by gnn) */
   int32_t reserved2;         /* 0                                                    */
 } vmc_desc;
 
@@ -96,7 +102,8 @@ typedef struct {
 int64_t vmc_num_params(int32_t n_sites, int32_t layer_size, int32_t num_layers);
 int64_t vmc_num_params_ansatz(int32_t ansatz, int32_t n_sites, int32_t layer_size,
                               int32_t num_layers);
-/* convolutional ansatz types: layer_size = num_conv_filters, num_layers as in vmc_desc */
+/* convolutional ansatz types: layer_size = num_conv_filters, num_layers as in vmc_desc
+ * (gnn: kernel_size = k, the neighbours per position) */
 int64_t vmc_num_params_conv(int32_t ansatz, int32_t num_layers, int32_t num_filters,
                             int32_t kernel_size);
 
@@ -111,6 +118,14 @@ const char* vmc_last_error(const vmc_ctx* ctx); /* ctx may be NULL: last create 
 int vmc_set_bonds(vmc_ctx* ctx, int32_t n_bonds, const int32_t* ij /*[n_bonds][2]*/,
                   const float* j_x, const float* j_z);
 
+/* The gnn ansatz's graph (GraphConvNetwork, wavefunctions.py:1083-1154): adj[n][t] is the site
+ * that tap t of position n reads (np.genfromtxt(adjacency_list_path, dtype=int)); repeated entries
+ * are allowed.  n_sites and k must be the ctx's num_sites and kernel_size, every entry in
+ * [0, n_sites).  Validates the table, uploads it and its inverse lists (for every site, the
+ * (position, tap) pairs that read it, CSR, position-major).  Every forward, sampler, local-energy,
+ * gradient or SR entry of a gnn ctx returns VMC_ERR_INVALID until the table is set; other ansatz
+ * types refuse the call (VMC_ERR_INVALID). */
+int vmc_set_adjacency(vmc_ctx* ctx, int32_t n_sites, int32_t k, const int32_t* adj /*[n_sites][k]*/);
 /* Variable assignment / read-back (tf.train.Saver restore/save, run_training.py:134-146;
  * module_transfer_ops, wavefunctions.py:300-325). theta has P floats. */
 int vmc_set_params(vmc_ctx* ctx, int which, const float* theta);
