@@ -464,3 +464,33 @@ struct WideStepArgs {
 hipError_t launch_wide_step(hipStream_t s, const WideStepArgs& a);
 hipError_t launch_wide_delta_last(hipStream_t s, const float* a_last, const float* wout, const float* oscale,
                                   int B, int H, int Hp, int act, float* delta, const float* dact = nullptr);
+
+// --------------------------------------------------------------------------------------
+// ProjectedBDG (pbdg.hip): projected BCS determinants, one chain / row per wave, M^-1 in LDS (plan_pbdg_*).
+// F is the parameter vector itself: the pairing matrix [N][N], row = up site, column = down site.
+// --------------------------------------------------------------------------------------
+// logit = ln|det M| (-inf singular, NaN for a row without N/2 up spins) and sign(det M) (0 singular) of n_rows
+// configurations; inv_out [n_rows][n][n] (M^-1, rows D slots, columns U slots) and pos_out [n_rows][N] (the slot of
+// every site in the sorted up / down lists) when not null
+hipError_t launch_pbdg_rows(hipStream_t s, const float* F, int N, const float* configs, int n_rows, float* logit,
+                            float* sign, float* inv_out, int* pos_out);
+struct PbdgSweepArgs {
+  const float* F; int N, B;
+  const float* configs_in; float* configs_out;    // the chains before / after the launch
+  long long n_steps; unsigned long long step0;
+  uint32_t seed_lo, seed_hi; int chain_offset;
+  const int* inj_up; const int* inj_dn; const float* inj_u;   // injected proposal (tests) or nullptr
+  unsigned char* acc_mask; unsigned long long* accepted;
+  int cpw, refresh;                               // set by the launcher (plan_pbdg_chains_per_wg / _refresh_interval)
+};
+hipError_t launch_pbdg_sweep(hipStream_t s, PbdgSweepArgs a);
+// val[row] = 0.5 jx psi(x')/psi(x) of every row of the antiparallel-bond list (launch_bond_list), from a fresh M^-1
+hipError_t launch_pbdg_eloc(hipStream_t s, const float* F, int N, const float* configs, int B, const int* off,
+                            const int2* rowinfo, const int2* bonds, const float* half_jx, float* val);
+// g1[ik] += sum_b O_ik(b), g2[ik] += sum_b w_b O_ik(b) from launch_pbdg_rows' inv_out / pos_out; ws: plan_pbdg_grad_ws_doubles
+hipError_t launch_pbdg_grad(hipStream_t s, const float* configs, const int* pos, const float* inv, const float* w,
+                            int B, int N, int slices, double* ws, float* g1, float* g2);
+hipError_t launch_pbdg_itswo_ratio(hipStream_t s, const float* logit_psi, const float* sign_psi,
+                                   const float* logit_omega, const float* sign_omega, const float* eloc_omega,
+                                   float log_factor, float beta, int B, float* ratio);
+hipError_t launch_pbdg_signed_max(hipStream_t s, const float* logit, const float* sign, int B, float* out);

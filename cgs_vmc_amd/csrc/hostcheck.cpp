@@ -227,7 +227,7 @@ static void dense_grid() {
   CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_INVALID);
   d = dense_desc(VMC_ANSATZ_FULLY_CONNECTED, 100, 4096, 3, 256, 7, VMC_ACT_EXP);
   CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_INVALID);
-  d = dense_desc(7, 100, 4096, 3, 256, 0, VMC_ACT_EXP);
+  d = dense_desc(8, 100, 4096, 3, 256, 0, VMC_ACT_EXP);
   CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_UNSUPPORTED);
   // BASELINE configs 1 - 5 (config 4 = config 3 per rank)
   const int cfg[4][4] = {{16, 64, 2, 32}, {36, 1024, 3, 128}, {100, 4096, 3, 256}, {256, 1024, 6, 256}};
@@ -589,8 +589,56 @@ static void gnn_grid() {
     }
 }
 
+// pbdg (plan_desc's shape checks, plan_pbdg_*): odd / oversized N refused, the LDS plan of every even N re-derived into
+// a real array (the carve of pbdg.hip), chains per workgroup within the budget, refresh interval and gradient slices in range
+static void pbdg_grid() {
+  char msg[256];
+  for (int n_sites = 1; n_sites <= 258; ++n_sites) {
+    vmc_desc d = dense_desc(VMC_ANSATZ_PBDG, n_sites, 64, 0, 0, VMC_ACT_RELU, VMC_ACT_EXP);
+    DescPlan p;
+    const int rc = plan_desc(&d, true, &p, msg, sizeof(msg));
+    ++g_shapes;
+    if (n_sites < 2 || (n_sites & 1)) { CHECK(rc == VMC_ERR_INVALID); ++g_rejected; continue; }
+    if (n_sites > PLAN_PBDG_MAX_SITES) { CHECK(rc == VMC_ERR_UNSUPPORTED); ++g_rejected; continue; }
+    CHECK(rc == VMC_OK && p.pbdg == 1 && p.conv == 0 && p.P == (long long)n_sites * n_sites);
+    CHECK(plan_num_params_dense(VMC_ANSATZ_PBDG, n_sites, 0, 0) == p.P);
+    const int n = n_sites / 2, ld = plan_pbdg_ld(n);
+    CHECK(ld >= n && (ld & 1) == 1);
+    const size_t bytes = plan_pbdg_chain_lds_bytes(n_sites);
+    CHECK(bytes % 4 == 0);
+    const int cpw = plan_pbdg_chains_per_wg(n_sites);
+    CHECK(cpw == 1 || cpw == 2 || cpw == 4);
+    CHECK((size_t)cpw * bytes <= PLAN_LDS_PER_CU);
+    CHECK(cpw == 1 || (size_t)cpw * bytes <= PLAN_PBDG_WG_LDS);
+    // the carve: A [n][ld], six vectors [n], spins [N] (floats), up / dn / perm [n], pos [N] (ints); the last element of
+    // every piece is touched in a real array of the planned size
+    std::vector<float> lds(bytes / 4);
+    size_t off = 0;
+    auto touch = [&](size_t len) { CHECK(off + len <= lds.size()); lds[off + len - 1] = 1.f; off += len; };
+    touch((size_t)n * ld);
+    for (int v = 0; v < 6; ++v) touch(n);
+    touch(n_sites);
+    for (int v = 0; v < 3; ++v) touch(n);
+    touch(n_sites);
+    CHECK(off == lds.size());
+    const int R = plan_pbdg_refresh_interval(n_sites);
+    CHECK(R >= 16 && R <= 128);
+    for (int cus : kCus)
+      for (long long B : {1LL, 7LL, 1024LL, 4096LL}) {
+        const int s = plan_pbdg_grad_slices(p.P, B, cus);
+        CHECK(s >= 1 && s <= 256 && s <= B);
+        CHECK(plan_pbdg_grad_ws_doubles(p.P, s) == 2 * p.P * s);
+      }
+  }
+  CHECK(plan_pbdg_chains_per_wg(256) == 1 && plan_pbdg_chains_per_wg(36) == 4);
+  CHECK(plan_pbdg_check(16, msg, sizeof(msg)) == VMC_OK);
+  CHECK(plan_pbdg_check(17, msg, sizeof(msg)) == VMC_ERR_INVALID);
+  CHECK(plan_pbdg_check(258, msg, sizeof(msg)) == VMC_ERR_UNSUPPORTED);
+}
+
 int main() {
   check_block_maps();
+  pbdg_grid();
   gnn_grid();
   dense_grid();
   conv_grid();

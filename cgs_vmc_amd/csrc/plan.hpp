@@ -56,6 +56,7 @@ inline long long plan_off_b(const ParamLayout& lay, long long H, int l) {
 }
 
 inline long long plan_num_params_dense(int ansatz, long long N, long long H, long long L) {
+  if (ansatz == VMC_ANSATZ_PBDG) return N * N;        // the pairing matrix F[N][N] (plan_pbdg_*)
   if (ansatz == VMC_ANSATZ_RBM) return N + 1 + N * H + H + L * (H * H + H);
   return N * H + H + (L - 1) * (H * H + H) + H + 1;
 }
@@ -431,9 +432,61 @@ inline bool plan_tail_lds_supported(int Hp, int n_hidden) {
   return (Hp == 384 || Hp == 512) && n_hidden >= 1 && plan_tail_lds_bytes(Hp, n_hidden) <= PLAN_LDS_PER_CU;
 }
 
+// ------------------------------------------------------------------------------- projected BCS determinant (pbdg.hip)
+// ProjectedBDG: psi(x) = det M(x), M[r][c] = F[U_r][D_c] over the n = N/2 up sites U and down sites D of x (ascending).
+// Each chain is one wave that keeps M^-1 (fp32) in LDS with an odd row stride (plan_pbdg_ld: the column walks of the
+// matrix-vector products hit distinct banks), the scratch vectors of one exchange ratio and rank-2 update, the slot lists
+// and the spins.  N <= 256 (n <= 128): the inverse stays within 64.5 KiB, so two chains still share a CU.
+#define PLAN_PBDG_MAX_SITES 256
+#define PLAN_PBDG_WG_LDS ((size_t)64 * 1024)   // chains per workgroup are packed up to this much LDS
+PLAN_HD inline int plan_pbdg_ld(int n) { return (n & 1) ? n : n + 1; }
+// floats: inverse n x ld, six vectors of n (x, y, M^-1 y, x M^-1, column r, row c), N spins; ints: up, dn, perm (n each), pos (N)
+PLAN_HD inline size_t plan_pbdg_chain_lds_bytes(int N) {
+  const size_t n = (size_t)N / 2, ld = (size_t)plan_pbdg_ld((int)n);
+  return 4 * (n * ld + 6 * n + (size_t)N) + 4 * (3 * n + (size_t)N);
+}
+// chains (waves) per workgroup: 4, 2 or 1, as many as fit PLAN_PBDG_WG_LDS (at least one; one chain at n = 128 takes 72.7 KiB)
+inline int plan_pbdg_chains_per_wg(int N) {
+  const size_t b = plan_pbdg_chain_lds_bytes(N);
+  for (int c = 4; c > 1; c >>= 1)
+    if ((size_t)c * b <= PLAN_PBDG_WG_LDS) return c;
+  return 1;
+}
+// The sampler rebuilds M^-1 by a fresh factorisation every R accepted moves of a chain (and after a move whose 2 x 2
+// determinant is below PLAN_PBDG_TINY_RATIO in magnitude: the rank-2 update divides by it).  A factorisation costs n^3,
+// an update 4 n^2 multiply-adds, so R = n keeps the refreshes at about a fifth of the update work; 16 <= R <= 128.
+#define PLAN_PBDG_TINY_RATIO 1e-2f
+inline int plan_pbdg_refresh_interval(int N) {
+  const int n = N / 2;
+  return n < 16 ? 16 : (n > 128 ? 128 : n);
+}
+// gradient sums: chain slices of the partial-sum launch (partials [slices][2][P] in double, folded in slice order):
+// enough threads to fill the chip (about 1024 per CU), at most 256 slices, never more than the chains
+inline int plan_pbdg_grad_slices(long long P, long long B, int num_cus) {
+  long long s = ((long long)num_cus * 1024 + P - 1) / (P > 0 ? P : 1);
+  if (s > 256) s = 256;
+  if (s > B) s = B;
+  return s < 1 ? 1 : (int)s;
+}
+inline long long plan_pbdg_grad_ws_doubles(long long P, int slices) { return 2LL * P * slices; }
+// vmc_create's shape checks: N even (|U| = |D| = N/2), 2 <= N <= 256
+inline int plan_pbdg_check(int N, char* msg, size_t msg_len) {
+  if (N < 2 || (N & 1)) {
+    snprintf(msg, msg_len, "pbdg: num_sites must be even and >= 2 (got %d): the projected BCS state lives at Sz = 0", N);
+    return VMC_ERR_INVALID;
+  }
+  if (N > PLAN_PBDG_MAX_SITES) {
+    snprintf(msg, msg_len, "pbdg: num_sites = %d beyond 256 (n = N/2 > 128: the inverse would exceed 64 KiB of LDS)", N);
+    return VMC_ERR_UNSUPPORTED;
+  }
+  if (msg_len) msg[0] = 0;
+  return VMC_OK;
+}
+
 // ------------------------------------------------------------------------------- vmc_create
 struct DescPlan {
   int rbm, conv, resnet, one_d;
+  int pbdg;                  // ProjectedBDG (pbdg.hip): none of the network members below apply
   int conv_general;          // conv beyond the fused kernels' limits (or forced): conv_general.hip
   int wide, wide_fast;       // > 256 units; of those, the fused 384 / 512-unit kernels
   int Hp;                    // padded units of the dense kernels (conv: 64, unused)
@@ -451,10 +504,22 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
                      int conv_general_pref = 0) {
   memset(out, 0, sizeof(*out));
 #define PLAN_FAIL(code, text) do { snprintf(msg, msg_len, "%s", text); return code; } while (0)
-  if (d->ansatz < VMC_ANSATZ_FULLY_CONNECTED || d->ansatz > VMC_ANSATZ_GNN)
-    PLAN_FAIL(VMC_ERR_UNSUPPORTED, "only the fully_connected, rbm, conv_1d/2d, res_net_1d/2d and gnn ansatz types have HIP kernels");
+  if (d->ansatz < VMC_ANSATZ_FULLY_CONNECTED || d->ansatz > VMC_ANSATZ_PBDG)
+    PLAN_FAIL(VMC_ERR_UNSUPPORTED, "only the fully_connected, rbm, conv_1d/2d, res_net_1d/2d, gnn and pbdg ansatz types have HIP kernels");
+  if (d->ansatz == VMC_ANSATZ_PBDG) {
+    // ProjectedBDG (wavefunctions.py:876-928): no layers, no activations; the dense members keep minimal shapes (unused)
+    const int rc = plan_pbdg_check(d->n_sites, msg, msg_len);
+    if (rc != VMC_OK) return rc;
+    if (d->batch_size < 1) PLAN_FAIL(VMC_ERR_INVALID, "batch_size >= 1 required");
+    out->pbdg = 1;
+    out->Hp = 64; out->n_hh = 0;
+    out->P = plan_num_params_dense(VMC_ANSATZ_PBDG, d->n_sites, 0, 0);
+    out->lay = plan_layout(false, d->n_sites, 1, 1);
+    if (msg_len) msg[0] = 0;
+    return VMC_OK;
+  }
   const bool rbm = d->ansatz == VMC_ANSATZ_RBM;
-  const bool conv = d->ansatz >= VMC_ANSATZ_CONV_2D;
+  const bool conv = d->ansatz >= VMC_ANSATZ_CONV_2D && d->ansatz <= VMC_ANSATZ_GNN;
   const bool resnet = d->ansatz == VMC_ANSATZ_RES_NET_2D || d->ansatz == VMC_ANSATZ_RES_NET_1D;
   const bool one_d = d->ansatz == VMC_ANSATZ_CONV_1D || d->ansatz == VMC_ANSATZ_RES_NET_1D;
   out->rbm = rbm; out->conv = conv; out->resnet = resnet; out->one_d = one_d;

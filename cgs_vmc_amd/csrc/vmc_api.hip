@@ -21,6 +21,7 @@ int ensure_packed(vmc_ctx* c, int which) {
   ParamSet& p = c->ps[which];
   if (!p.has_params) return fail(c, VMC_ERR_STATE, "parameters not set (vmc_set_params)");
   if (p.packed_valid) return VMC_OK;
+  if (c->pbdg) { p.packed_valid = true; return VMC_OK; }     // (the kernels read the pairing matrix in theta as it lies)
   if (c->conv) {
     // (general path: the parameter slices are the B matrices of its GEMMs as they lie in theta)
     if (!c->conv_general) HIPCHK(c, launch_conv_pack(c->stream, p.theta, c->cg, p.cw0, p.cwf, p.cwb, p.cbias));
@@ -167,6 +168,12 @@ int ensure_cache(vmc_ctx* c, int which) {
   PROPAGATE(ensure_packed(c, which));
   ParamSet& p = c->ps[which];
   if (p.cache_valid) return VMC_OK;
+  if (c->pbdg) {
+    Timer t(c, "tail_amp");
+    HIPCHK(c, launch_pbdg_rows(c->stream, p.theta, c->N, c->configs, c->B, p.logit, p.sign, nullptr, nullptr));
+    p.cache_valid = true;
+    return VMC_OK;
+  }
   if (c->conv) {
     Timer t(c, "tail_amp");
     const bool tape = which == VMC_PSI && !c->conv_general;       // (the general path keeps no gradient tape)
@@ -218,7 +225,11 @@ int local_energy_device(vmc_ctx* c, int which, bool defer_reduce, bool* deferred
   PROPAGATE(ensure_cache(c, which));
   PROPAGATE(ensure_list(c));
   ParamSet& p = c->ps[which];
-  if (c->conv) {
+  if (c->pbdg) {
+    Timer t(c, "tail_eloc");      // (a fresh M^-1 per chain: never the sampler's incrementally updated one)
+    HIPCHK(c, launch_pbdg_eloc(c->stream, p.theta, c->N, c->configs, c->B, c->off, c->rowinfo, c->bonds, c->half_jx,
+                               c->val));
+  } else if (c->conv) {
     Timer t(c, "tail_eloc");
     PROPAGATE(conv_rows(c, which, c->configs, c->rowinfo, (int)((long long)c->B * c->n_bonds), c->off + c->B,
                         true, c->val, false));
@@ -265,7 +276,7 @@ int local_energy_device(vmc_ctx* c, int which, bool defer_reduce, bool* deferred
     }
     HIPCHK(c, launch_rows(c, which, a, true));
   }
-  if (defer_reduce && deferred && !c->conv && !(c->wide && !c->wide_fast)) {
+  if (defer_reduce && deferred && !c->conv && !c->pbdg && !(c->wide && !c->wide_fast)) {
     *deferred = true;              // the fused back-propagation launch folds val into eloc
     return VMC_OK;
   }
@@ -278,14 +289,30 @@ int local_energy_device(vmc_ctx* c, int which, bool defer_reduce, bool* deferred
 
 int grow_tmp(vmc_ctx* c, long long rows) {
   if (rows <= c->tmp_rows) return VMC_OK;
-  if (c->tmp_cfg) { hipFree(c->tmp_cfg); hipFree(c->tmp_z1); hipFree(c->tmp_out); hipFree(c->tmp_rowinfo); hipFree(c->tmp_on); }
+  if (c->tmp_cfg) { hipFree(c->tmp_cfg); hipFree(c->tmp_z1); hipFree(c->tmp_out); hipFree(c->tmp_rowinfo); hipFree(c->tmp_on); hipFree(c->tmp_sign); }
   HIPCHK(c, dalloc(&c->tmp_on, rows));
+  HIPCHK(c, dalloc(&c->tmp_sign, rows));
   HIPCHK(c, dalloc(&c->tmp_rowinfo, rows));
   HIPCHK(c, launch_iota_rows(c->stream, c->tmp_rowinfo, (int)rows));
   HIPCHK(c, dalloc(&c->tmp_cfg, rows * c->N));
   HIPCHK(c, dalloc(&c->tmp_z1, rows * c->Hp));
   HIPCHK(c, dalloc(&c->tmp_out, rows));
   c->tmp_rows = rows;
+  return VMC_OK;
+}
+
+// pbdg: every row must hold as many up as down spins (the projected BCS state lives at Sz = 0); host rows
+int pbdg_check_sz(vmc_ctx* c, const float* configs, long long n_rows) {
+  if (!c->pbdg) return VMC_OK;
+  for (long long r = 0; r < n_rows; ++r) {
+    double m = 0.0;
+    for (int i = 0; i < c->N; ++i) m += configs[r * c->N + i];
+    if (m != 0.0) {
+      char msg[160];
+      snprintf(msg, sizeof(msg), "pbdg: configuration %lld has magnetisation %g; the ansatz needs as many up as down spins", r, m);
+      return fail(c, VMC_ERR_INVALID, msg);
+    }
+  }
   return VMC_OK;
 }
 
@@ -340,6 +367,7 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
     if (rc != VMC_OK) return fail(nullptr, rc, msg);
   }
   const bool rbm = dp.rbm != 0, conv = dp.conv != 0, wide = dp.wide != 0, wide_fast_ok = dp.wide_fast != 0;
+  const bool pbdg = dp.pbdg != 0;
   const ConvGeom cg = dp.cg;
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
@@ -355,9 +383,11 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
   c->rbm = rbm;
   c->conv = conv; c->cg = cg; c->conv_general = conv && dp.conv_general != 0;
   if (conv) { c->L = 1; c->overlap = false; }   // minimal dense-side shapes (unused)
+  c->pbdg = pbdg;
+  if (pbdg) { c->L = 1; c->H = 1; c->overlap = false; c->hact = VMC_ACT_RELU_; }
   c->wide = wide;
   if (wide) c->overlap = false;
-  c->hact = d->nonlinearity; c->oact = d->output_activation;
+  c->hact = pbdg ? VMC_ACT_RELU_ : d->nonlinearity; c->oact = pbdg ? VMC_ACT_EXP_ : d->output_activation;
   c->lay = dp.lay;
   // 257 .. 512 units (wide_fast): the fused sampler padded to 384 / 512 units (k_sweep16<24|32>), rows on
   // the LDS-operand kernel (k_tail_lds; without an H x H layer: k_tail0) and the fused back-propagation
@@ -372,14 +402,14 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
     c->split = (atoi(e) == 1 || atoi(e) == 2) && !conv && !wide && !rbm && c->Hp == 256 && c->n_hh >= 1 && c->hact == VMC_ACT_RELU_;
     c->split_sweep = c->split && atoi(e) == 2 && sweep16_split_supported(c->N, c->Hp, c->n_hh);
   }
-  if (const char* e = getenv("CGS_VMC_OVERLAP")) { c->overlap = !conv && !wide && atoi(e) != 0; c->overlap_full = atoi(e) == 2; }
+  if (const char* e = getenv("CGS_VMC_OVERLAP")) { c->overlap = !conv && !wide && !pbdg && atoi(e) != 0; c->overlap_full = atoi(e) == 2; }
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, d->device) == hipSuccess && prop.multiProcessorCount > 0)
       c->num_cus = prop.multiProcessorCount;
   }
   // eight-chain sampler tiles where sixteen-chain tiles would leave half of the chip idle (sweep8.hip)
-  c->sweep8_ok = !conv && !wide && !rbm && c->hact == VMC_ACT_RELU_ && !c->split_sweep &&
+  c->sweep8_ok = !conv && !wide && !rbm && !pbdg && c->hact == VMC_ACT_RELU_ && !c->split_sweep &&
                  plan_sweep8(c->N, c->Hp, c->n_hh, c->sweep_no_w1l != 0).ok;
   {
     int forced = 0;
@@ -433,7 +463,7 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
     // fully_connected on the kernels that run k_backprop16: the N = 1 output layer leaves the MFMA tile grid
     // (CGS_VMC_WGRAD_OUT_TILES=1 keeps it there: A/B measurements)
     const char* e_out = getenv("CGS_VMC_WGRAD_OUT_TILES");
-    c->wg_out_partials = !rbm && !conv && !(wide && !c->wide_fast) && !(e_out && atoi(e_out) == 1);
+    c->wg_out_partials = !rbm && !conv && !pbdg && !(wide && !c->wide_fast) && !(e_out && atoi(e_out) == 1);
     c->wg_tiles = plan_wgrad_total_tiles((int)N, c->H, (int)NH, rbm, !c->wg_out_partials);
     if (c->wg_out_partials) CA(dalloc(&c->wg_outpart, ((B + 15) / 16) * 2 * (Hp + 4)));
     CA(dalloc(&c->wg_tickets, c->wg_tiles > 0 ? c->wg_tiles : 1));
@@ -468,6 +498,18 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
     CA(dalloc(&c->wide_dot, (long long)gemm_rowdot_tiles(c->H) * c->wrows));
     CA(dalloc(&c->wide_iup, B)); CA(dalloc(&c->wide_idn, B)); CA(dalloc(&c->wide_zero, Hp));
     CA(hipMemsetAsync(c->wide_zero, 0, Hp * sizeof(float), c->stream));
+  }
+  if (pbdg) {
+    const long long n = N / 2;
+    for (int w = 0; w < 2; ++w) {
+      CA(dalloc(&c->ps[w].sign, B));
+      CA(hipMemsetAsync(c->ps[w].sign, 0, B * sizeof(float), c->stream));
+    }
+    CA(dalloc(&c->ps[0].sign_alt, B));
+    CA(hipMemsetAsync(c->ps[0].sign_alt, 0, B * sizeof(float), c->stream));
+    CA(dalloc(&c->pbdg_inv, B * n * n)); CA(dalloc(&c->pbdg_pos, B * N));
+    c->pbdg_slices = plan_pbdg_grad_slices(P, B, c->num_cus);
+    CA(dalloc(&c->pbdg_ws, plan_pbdg_grad_ws_doubles(P, c->pbdg_slices)));
   }
   if (conv && c->conv_general) {
     // blocks of at most ~768 MB of im2col rows (one row configuration at least), at least B rows when that fits
@@ -560,7 +602,9 @@ void vmc_destroy(vmc_ctx* c) {
   if (c->cg_sum) hipFree(c->cg_sum);
   if (c->cg_td) hipFree(c->cg_td);
   if (c->cg_centre) hipFree(c->cg_centre);
-  for (int* q : {c->gnn_adj, c->gnn_inv_ptr, c->gnn_inv}) if (q) hipFree(q);
+  for (int* q : {c->gnn_adj, c->gnn_inv_ptr, c->gnn_inv, c->pbdg_pos}) if (q) hipFree(q);
+  for (float* q : {c->ps[0].sign, c->ps[1].sign, c->ps[0].sign_alt, c->pbdg_inv, c->tmp_sign}) if (q) hipFree(q);
+  if (c->pbdg_ws) hipFree(c->pbdg_ws);
   void* ptrs[] = {c->configs, c->configs_alt, c->bonds, c->half_jx, c->quarter_jz, c->cnt, c->off, c->diag, c->val,
                   c->offdiag, c->rowinfo, c->delta_all, c->d_batch[0][0], c->d_batch[0][1], c->d_batch[1][0], c->d_batch[1][1], c->ratio, c->ones, c->acc,
                   c->adam_m, c->adam_v, c->grad_tmp, c->gemm_ws, c->wg_tickets, c->d_accepted, c->d_sum,
@@ -666,6 +710,7 @@ int vmc_transfer_params(vmc_ctx* c) {
 int vmc_set_configs(vmc_ctx* c, const float* configs) {
   ENTER(c);
   if (!configs) return fail(c, VMC_ERR_INVALID, "null configs");
+  PROPAGATE(pbdg_check_sz(c, configs, c->B));
   const long long n = (long long)c->B * c->N;
   // staged in the alternate chain buffer (free between sampler launches), validated on the
   // device, and only then made current: a rejected batch leaves the chains untouched
@@ -707,11 +752,22 @@ int vmc_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, f
   ENTER(c);
   if (which != 0 && which != 1) return fail(c, VMC_ERR_INVALID, "bad which");
   if (n_rows < 0) return fail(c, VMC_ERR_INVALID, "n_rows < 0");
-  std::vector<float> host((size_t)n_rows);
+  std::vector<float> host((size_t)n_rows), hsign(c->pbdg ? (size_t)n_rows : 0);
   if (!configs) {
     if (n_rows != c->B) return fail(c, VMC_ERR_INVALID, "n_rows must equal batch_size when configs == NULL");
     PROPAGATE(ensure_cache(c, which));
     HIPCHK(c, hipMemcpyAsync(host.data(), c->ps[which].logit, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (c->pbdg)
+      HIPCHK(c, hipMemcpyAsync(hsign.data(), c->ps[which].sign, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  } else if (n_rows > 0 && c->pbdg) {
+    PROPAGATE(ensure_packed(c, which));
+    PROPAGATE(pbdg_check_sz(c, configs, n_rows));
+    PROPAGATE(grow_tmp(c, n_rows));
+    HIPCHK(c, hipMemcpyAsync(c->tmp_cfg, configs, n_rows * c->N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_pbdg_rows(c->stream, c->ps[which].theta, c->N, c->tmp_cfg, (int)n_rows, c->tmp_out, c->tmp_sign,
+                               nullptr, nullptr));
+    HIPCHK(c, hipMemcpyAsync(host.data(), c->tmp_out, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hsign.data(), c->tmp_sign, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   } else if (n_rows > 0) {
     PROPAGATE(ensure_packed(c, which));
     PROPAGATE(grow_tmp(c, n_rows));
@@ -737,7 +793,8 @@ int vmc_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, f
   for (int64_t i = 0; i < n_rows; ++i) {
     if (logit) logit[i] = host[i];
     // wavefunctions.py:350-353: exp(x - shift) (232), or the output activation itself, no shift
-    if (psi) psi[i] = c->oact == VMC_ACT_EXP_ ? expf(host[i] - shift) : host_activation(c->oact, host[i]);
+    if (psi) psi[i] = c->pbdg ? hsign[i] * expf(host[i] - shift)      // signed: sign(det M) exp(logit - shift)
+                              : c->oact == VMC_ACT_EXP_ ? expf(host[i] - shift) : host_activation(c->oact, host[i]);
   }
   return VMC_OK;
 }
@@ -771,7 +828,7 @@ int vmc_local_energy_terms(vmc_ctx* c, int which, float* diag, float* offdiag_ov
 int vmc_debug_kernel_path(vmc_ctx* c, int32_t* path) {
   CHECK_CTX(c);
   if (!path) return fail(c, VMC_ERR_INVALID, "null");
-  *path = c->conv ? (c->conv_general ? 6 : 3) : (c->wide ? (c->wide_fast ? 1 : 2) : (c->split ? (c->split_sweep ? 5 : 4) : 0));
+  *path = c->pbdg ? 7 : c->conv ? (c->conv_general ? 6 : 3) : (c->wide ? (c->wide_fast ? 1 : 2) : (c->split ? (c->split_sweep ? 5 : 4) : 0));
   return VMC_OK;
 }
 

@@ -81,7 +81,7 @@ static int run_sweep_wide(vmc_ctx* c, long long n_steps, bool injected, bool dbg
 // goes to the buffer the next sampler launch overwrites anyway); nothing is swapped.
 bool sampler_refresh_ok(const vmc_ctx* c) {
   static const bool on = !(getenv("CGS_VMC_SAMPLER_REFRESH") && atoi(getenv("CGS_VMC_SAMPLER_REFRESH")) == 0);
-  return on && !c->conv && !(c->wide && !c->wide_fast);
+  return on && !c->conv && !c->pbdg && !(c->wide && !c->wide_fast);
 }
 int refresh_cache_by_sampler(vmc_ctx* c, int which) {
   PROPAGATE(ensure_packed(c, which));
@@ -236,6 +236,38 @@ static int run_sweep_cgen(vmc_ctx* c, long long n_steps, bool injected, bool dbg
   return VMC_OK;
 }
 
+// The pbdg sampler (pbdg.hip): one persistent launch of n_steps steps reads the current chains and writes the alternate
+// set, then the rows kernel writes the logits and signs of the final chains from a fresh factorisation (no drift from the
+// sampler's rank-2 updates: the cache equals vmc_amplitude's bit for bit).  Proposal dumps: k_wide_propose, the rule the
+// sampler follows.
+static int run_sweep_pbdg(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn,
+                          float* dbg_u, unsigned long long step0, bool count_accepted) {
+  ParamSet& p = c->ps[0];
+  const uint32_t seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull), seed_hi = (uint32_t)(c->d.seed >> 32);
+  if (dbg) {
+    HIPCHK(c, launch_wide_propose(c->stream, c->configs, c->B, c->N, seed_lo, seed_hi, c->d.chain_offset, step0, nullptr,
+                                  nullptr, nullptr, dbg_up, dbg_dn, dbg_u));
+    return VMC_OK;
+  }
+  if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), c->stream));
+  PbdgSweepArgs a;
+  memset(&a, 0, sizeof(a));
+  a.F = p.theta; a.N = c->N; a.B = c->B;
+  a.configs_in = c->configs; a.configs_out = c->configs_alt;
+  a.n_steps = n_steps; a.step0 = step0; a.seed_lo = seed_lo; a.seed_hi = seed_hi; a.chain_offset = c->d.chain_offset;
+  if (injected) { a.inj_up = c->inj_up; a.inj_dn = c->inj_dn; a.inj_u = c->inj_u; a.acc_mask = c->acc_mask; }
+  a.accepted = c->d_accepted;
+  {
+    Timer t(c, "sweep");
+    HIPCHK(c, launch_pbdg_sweep(c->stream, a));
+    HIPCHK(c, launch_pbdg_rows(c->stream, p.theta, c->N, c->configs_alt, c->B, p.logit_alt, p.sign_alt, nullptr, nullptr));
+  }
+  swap_chain_buffers(c);
+  c->acts_valid = false;
+  c->acc_since_sweep = false;
+  return VMC_OK;
+}
+
 static int run_sweep(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn,
                      float* dbg_u, unsigned long long step0, bool count_accepted = false,
                      bool overtake = false, hipEvent_t dep = nullptr) {
@@ -243,6 +275,8 @@ static int run_sweep(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int
   if (!dbg) c->cnt_valid = false;   // the chains change (set again below when this launch leaves their census)
   if (c->wide && !c->wide_fast)
     return run_sweep_wide(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
+  if (c->pbdg)
+    return run_sweep_pbdg(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
   if (c->conv_general)
     return run_sweep_cgen(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
   ParamSet& p = c->ps[0];
@@ -397,7 +431,7 @@ int vmc_debug_proposals(vmc_ctx* c, uint64_t step, int32_t* i_up, int32_t* i_dn,
 int vmc_debug_sweep_profile(vmc_ctx* c, int64_t n_steps, double* phase_cycles) {
   ENTER(c);
   if (n_steps < 1 || !phase_cycles) return fail(c, VMC_ERR_INVALID, "bad arguments");
-  if (c->rbm || c->conv || c->wide) return fail(c, VMC_ERR_UNSUPPORTED, "the diagnostic sweep build exists for fully_connected (<= 256 units) only");
+  if (c->rbm || c->conv || c->wide || c->pbdg) return fail(c, VMC_ERR_UNSUPPORTED, "the diagnostic sweep build exists for fully_connected (<= 256 units) only");
   PROPAGATE(ensure_packed(c, 0));
   const bool tile8 = c->sweep_tile == 8;      // k_sweep8's stamped instantiation (phases: sweep8.hip)
   const int wpg = tile8 ? c->Hp / 32 : c->sweep_waves;

@@ -17,6 +17,14 @@ static int gradient_sums(vmc_ctx* c, const float* w, bool fresh, const float* e,
   float* g1 = c->acc;
   float* g2 = c->acc + c->P;
   Timer t(c, "grad");
+  if (c->pbdg) {
+    // O_ik = M^-1[pos k][pos i] of psi on the chains, from a fresh factorisation (pbdg.hip)
+    // (the logits / signs land in the rows' scratch buffers, which the cache of `p` does not share)
+    PROPAGATE(grow_tmp(c, B));
+    HIPCHK(c, launch_pbdg_rows(c->stream, p.theta, N, c->configs, B, c->tmp_out, c->tmp_sign, c->pbdg_inv, c->pbdg_pos));
+    HIPCHK(c, launch_pbdg_grad(c->stream, c->configs, c->pbdg_pos, c->pbdg_inv, w, B, N, c->pbdg_slices, c->pbdg_ws, g1, g2));
+    return VMC_OK;
+  }
   if (c->conv_general) return cgen_gradient_sums(c, w);
   if (c->conv) {
     // forward tapes (the inputs of every convolution), d logit / d (output of every convolution)
@@ -184,7 +192,10 @@ int vmc_accumulate(vmc_ctx* c, int mode, float beta) {
     }
     PROPAGATE(local_energy_device(c, VMC_OMEGA, true, &fold_eloc));   // training.py:664, 667
     PROPAGATE(ensure_cache(c, VMC_PSI));
-    if (!fold_eloc)   // (otherwise the back-propagation launch folds E_loc^w and forms the ratio: two launches less)
+    if (c->pbdg)      // signed amplitudes: sign_w sign_psi exp(...)
+      HIPCHK(c, launch_pbdg_itswo_ratio(c->stream, c->ps[0].logit, c->ps[0].sign, c->ps[1].logit, c->ps[1].sign,
+                                        c->ps[1].eloc, c->ps[0].shift - c->ps[1].shift, beta, c->B, c->ratio));
+    else if (!fold_eloc)   // (otherwise the back-propagation launch folds E_loc^w and forms the ratio: two launches less)
       HIPCHK(c, launch_itswo_ratio(c->stream, c->ps[0].logit, c->ps[1].logit, c->ps[1].eloc,
                                    c->ps[0].shift - c->ps[1].shift, beta, c->B, c->ratio, c->oact));
     w = c->ratio; e = c->ps[1].eloc;
@@ -192,7 +203,7 @@ int vmc_accumulate(vmc_ctx* c, int mode, float beta) {
   PROPAGATE(ensure_cache(c, VMC_PSI));
   // the batched weight-gradient GEMMs of the dense ansatz types cover every parameter, so a pending
   // reset is absorbed: their reduction stores instead of adding (conv: zero first)
-  if (c->conv) PROPAGATE(acc_zeros(c));
+  if (c->conv || c->pbdg) PROPAGATE(acc_zeros(c));
   const bool fresh = c->acc_fresh;
   bool scalars_done = false;
   PROPAGATE(gradient_sums(c, w, fresh, e, mode, &scalars_done, fold_eloc, beta));
@@ -291,11 +302,15 @@ int vmc_set_adam_state(vmc_ctx* c, const float* m, const float* v, int64_t t) {
 static int update_norm_impl(vmc_ctx* c, void* comm, int world, float max_value) {
   if (c->oact != VMC_ACT_EXP_) return VMC_OK;   // wavefunctions.py:276-277: no exp_norm_shift, nothing to do
   PROPAGATE(ensure_cache(c, VMC_PSI));
-  HIPCHK(c, launch_max(c->stream, c->ps[0].logit, c->B, c->d_max));
+  // pbdg: max_b psi_b of the SIGNED amplitudes (wavefunctions.py:283): the largest logit among the chains with psi > 0
+  if (c->pbdg) HIPCHK(c, launch_pbdg_signed_max(c->stream, c->ps[0].logit, c->ps[0].sign, c->B, c->d_max));
+  else HIPCHK(c, launch_max(c->stream, c->ps[0].logit, c->B, c->d_max));
   PROPAGATE(reduce_buffer(c, comm, world, c->d_max, 1, VMC_REDUCE_MAX));
   float mx = 0.f;
   HIPCHK(c, hipMemcpyAsync(&mx, c->d_max, sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  // no chain with psi > 0: the reference writes log(max psi) = NaN into the shift; the shift is kept
+  if (c->pbdg && !(mx > -INFINITY)) return VMC_OK;
   // wavefunctions.py:280-288: log_max = log(reduce_max(psi)); where psi overflows float32 the
   // reference yields inf; the logit-domain value is used there instead.
   const float shift = c->ps[0].shift;

@@ -28,8 +28,9 @@ struct ParamSet {
   float* z1 = nullptr;     // [B][Hp] cache for the ctx's chains
   float* onsite = nullptr; // [B] cached x . w_on (RBM)
   float* logit = nullptr;  // [B]
+  float* sign = nullptr;   // [B] pbdg: sign(det M) of the chains (+-1, 0 singular); psi = sign exp(logit - shift)
   // psi only: the buffers the NEXT sampler launch writes (see vmc_ctx::configs_alt)
-  float *z1_alt = nullptr, *onsite_alt = nullptr, *logit_alt = nullptr;
+  float *z1_alt = nullptr, *onsite_alt = nullptr, *logit_alt = nullptr, *sign_alt = nullptr;
   float* eloc = nullptr;   // [B]
   // convolutional ansatz types: fragment images of conv.hpp ConvParams
   float *cw0 = nullptr, *cwf = nullptr, *cwb = nullptr, *cbias = nullptr;
@@ -52,6 +53,12 @@ struct vmc_ctx {
   vmc_desc d;
   int N = 0, B = 0, L = 0, H = 0, Hp = 0;
   bool rbm = false;        // RestrictedBoltzmannNetwork instead of FullyConnectedNetwork
+  // ProjectedBDG (pbdg.hip): theta is the pairing matrix; the network members keep minimal shapes (unused).  The
+  // gradient path factorises psi on the chains into pbdg_inv [B][n][n] / pbdg_pos [B][N] and folds the partial sums
+  // of pbdg_slices chain slices (pbdg_ws, double) in slice order
+  bool pbdg = false;
+  float* pbdg_inv = nullptr; int* pbdg_pos = nullptr; double* pbdg_ws = nullptr; int pbdg_slices = 1;
+  float* tmp_sign = nullptr;   // [tmp_rows] signs of vmc_amplitude's rows
   // Conv2DNetwork / ResNet2D (conv.hip).  The dense-ansatz members below keep harmless minimal
   // shapes (H = filters, Hp = 64, no H x H layer); acts_valid tells whether the forward tapes
   // hold the inputs of every convolution for psi on the current chains.
@@ -294,6 +301,7 @@ inline void swap_chain_buffers(vmc_ctx* c) {
   ParamSet& p = c->ps[0];
   std::swap(c->configs, c->configs_alt);
   std::swap(p.z1, p.z1_alt); std::swap(p.logit, p.logit_alt); std::swap(p.onsite, p.onsite_alt);
+  std::swap(p.sign, p.sign_alt);
   std::swap(c->act_all, c->act_alt);
   std::swap(c->dact_all, c->dact_alt);
   std::swap(c->cnt, c->cnt_alt); std::swap(c->diag, c->diag_alt);
@@ -379,6 +387,7 @@ void invalidate_configs(vmc_ctx* c);
 int ensure_list(vmc_ctx* c);
 int local_energy_device(vmc_ctx* c, int which, bool defer_reduce = false, bool* deferred = nullptr);
 int grow_tmp(vmc_ctx* c, long long rows);
+int pbdg_check_sz(vmc_ctx* c, const float* configs, long long n_rows);
 // vmc_api_cgen.hip (the general convolution path)
 int cgen_forward(vmc_ctx* c, int which, const float* configs, const int2* rowinfo, long long n_rows,
                  const int* iup, const int* idn, bool ratio, float* out, float* tape = nullptr,

@@ -99,6 +99,8 @@ class Wavefunction:
 
     def run():
       log_max = self._global_log_max(batch_of_amplitudes)
+      if log_max is None:        # no psi > 0 anywhere (signed amplitudes): the shift is kept
+        return
       self._set_shift(np.float32(self._get_shift() + (log_max - np.log(np.float32(max_value)))))
     return session_lib.Op(run, 'normalize_batch')
 
@@ -326,7 +328,7 @@ class FullyConnectedNetwork(Wavefunction):
       return
     log_max = self._global_log_max(batch_of_amplitudes)
     max_log = np.log(np.float32(max_value))
-    if log_max > max_log:
+    if log_max is not None and log_max > max_log:
       self._set_shift(np.float32(self._get_shift() + (log_max - max_log)))
 
   @classmethod
@@ -693,6 +695,77 @@ class GraphConvNetwork(Conv2DNetwork):
     return cls(**gnn_params)
 
 
+class ProjectedBDG(FullyConnectedNetwork):
+  """Gutzwiller-projected BCS (RVB) state (wavefunctions.py:876-928): psi(x) = det M(x), M[r][c] = F[U_r][D_c] over
+  the up sites U and the down sites D of x in ascending order, F the pairing matrix (the only variable,
+  projected_bdg/pairing_matrix [1, N, N]); psi = sign(det M) exp(ln|det M| - exp_norm_shift).  Signed amplitudes
+  without any lattice geometry.  The kernels (csrc/pbdg.hip) keep M^-1 of every chain in LDS: determinant ratios
+  and rank-2 updates per Monte Carlo move, a fresh factorisation for amplitudes and local energies."""
+  _ansatz = 'pbdg'
+
+  def __init__(self, num_sites: int, name: str = 'projected_bdg'):
+    num_sites = int(num_sites)
+    if num_sites < 2 or num_sites % 2:
+      raise ValueError('pbdg: num_sites must be even (as many up as down spins), got %d' % num_sites)
+    if num_sites > 256:
+      raise NotImplementedError('pbdg: num_sites > 256 is not supported by the HIP kernels')
+    super(ProjectedBDG, self).__init__(num_layers=1, layer_size=1, name=name)
+    self._num_sites = num_sites
+
+  def _shapes(self):
+    if self._n_sites is not None and self._n_sites != self._num_sites:
+      raise ValueError('Input tensor has wrong shape.')
+    n = self._num_sites
+    return ['%s/pairing_matrix' % self._unique_name], [(1, n, n)]
+
+  def initialize(self, seed=None):
+    """tf.get_variable's default glorot_uniform on [1, N, N]: fan_in = fan_out = N, U(-sqrt(3/N), sqrt(3/N))."""
+    n = self._num_sites
+    limit = np.sqrt(6.0 / (n + n))
+    rng = np.random.default_rng(seed)
+    self._set_theta(rng.uniform(-limit, limit, size=n * n).astype(np.float32))
+
+  def _maybe_initialize(self):
+    if self._n_sites is not None and self._get_theta(allow_none=True) is None:
+      seed = os.environ.get('CGS_VMC_INIT_SEED')
+      self.initialize(None if seed is None else int(seed) + _init_count())
+
+  def _engine_spec(self):
+    return dict(ansatz=self._ansatz, num_layers=1, layer_size=1, nonlinearity='relu', output_activation='exp')
+
+  def _global_log_max(self, batch_of_amplitudes):
+    """log(max_b psi_b) of the SIGNED amplitudes over all ranks, as the reference takes it (wavefunctions.py:250, 283):
+    the largest logit among the chains with psi > 0 (a sign bit clear -- psi may underflow to +0 -- and a finite
+    logit), or None where there is none (the reference writes NaN into the shift there: SURVEY.md B10)."""
+    from . import parallel
+    if isinstance(batch_of_amplitudes, AmplitudeTensor) and batch_of_amplitudes.wavefunction is self:
+      logit, psi = self._engine.amplitude(batch_of_amplitudes.configs, self._which)
+      pos = ~np.signbit(psi) & np.isfinite(logit)
+      top = float(np.max(logit[pos])) if pos.any() else -np.inf
+      top = np.float32(parallel.allreduce_max(top))
+      if not np.isfinite(top):
+        return None
+      gap = np.float32(top - np.float32(self._get_shift()))
+      with np.errstate(over='ignore'):
+        psi_max = np.exp(gap, dtype=np.float32)
+      if np.isfinite(psi_max) and psi_max > 0:
+        return np.float32(np.log(psi_max))
+      return gap
+    psi = np.asarray(batch_of_amplitudes._run())
+    top = parallel.allreduce_max(float(np.max(psi)))
+    if not top > 0:
+      return None
+    return np.float32(np.log(np.float32(top)))
+
+  @classmethod
+  def from_hparams(cls, hparams, name: str = '') -> 'Wavefunction':
+    """wavefunctions.py:915-928."""
+    params = {'num_sites': hparams.num_sites}
+    if name:
+      params['name'] = name
+    return cls(**params)
+
+
 class AmplitudeTensor(session_lib.Tensor):
   """psi = wavefunction(inputs); evaluates to a float32 array [rows]."""
 
@@ -717,7 +790,7 @@ class _OutOfScope(Wavefunction):
   def from_hparams(cls, hparams, name: str = ''):
     raise NotImplementedError(
         "wavefunction_type '%s' is outside the MI355X hot path (SURVEY.md 2); only "
-        "'fully_connected', 'rbm', 'conv_1d', 'conv_2d', 'res_net_1d', 'res_net_2d' and 'gnn' have "
+        "'fully_connected', 'rbm', 'conv_1d', 'conv_2d', 'res_net_1d', 'res_net_2d', 'gnn' and 'pbdg' have "
         "HIP kernels" % cls._kind)
 
 
@@ -741,7 +814,7 @@ WAVEFUNCTION_TYPES = {
     'conv_1d': Conv1DNetwork,
     'conv_2d': Conv2DNetwork,
     'mps': _stub('mps'),
-    'pbdg': _stub('pbdg'),
+    'pbdg': ProjectedBDG,
     'fully_connected_nnb': _stub('fully_connected_nnb'),
     'res_net_1d': ResNet1D,
     'res_net_2d': ResNet2D,

@@ -33,6 +33,14 @@
  * convolutions over an adjacency list adj[N][k] (vmc_set_adjacency), each one snt.Conv2D with a
  * 1 x k kernel: w[1][k][in_channels][F] (row-major) followed by b[F];
  * P = k*F + F + (num_layers - 1)*(k*F*F + F).
+ * ProjectedBDG ('pbdg', wavefunctions.py:876-928): the pairing matrix projected_bdg/pairing_matrix
+ * [1][N][N], F[i][k] = theta[i*N + k] (i an up site, k a down site); P = N*N.  psi(x) = det M(x),
+ * M[r][c] = F[U_r][D_c] over the up sites U and down sites D of x in ascending order: logit =
+ * ln|det M|, psi = sign(det M) exp(logit - shift) (psi = 0, logit = -inf where M is singular).
+ * n_sites must be even (VMC_ERR_INVALID otherwise) and at most 256 (VMC_ERR_UNSUPPORTED: M^-1 of
+ * a chain stays in LDS); every configuration the ctx takes (vmc_set_configs, vmc_amplitude) must
+ * have as many up as down spins (VMC_ERR_INVALID).  num_layers, layer_size and the activations are
+ * ignored.  Stochastic reconfiguration is not available (vmc_sr_reserve: VMC_ERR_UNSUPPORTED).
  */
 #ifndef CGSVMC_H_
 #define CGSVMC_H_
@@ -63,7 +71,7 @@ enum { VMC_MODE_ENERGY_GRADIENT = 0, VMC_MODE_LOG_OVERLAP_ITSWO = 1 };
 /* wavefunctions.WAVEFUNCTION_TYPES with kernels (wavefunctions.py:1157-1170) */
 enum { VMC_ANSATZ_FULLY_CONNECTED = 0, VMC_ANSATZ_RBM = 1, VMC_ANSATZ_CONV_2D = 2,
        VMC_ANSATZ_RES_NET_2D = 3, VMC_ANSATZ_CONV_1D = 4, VMC_ANSATZ_RES_NET_1D = 5,
-       VMC_ANSATZ_GNN = 6 };
+       VMC_ANSATZ_GNN = 6, VMC_ANSATZ_PBDG = 7 };
 
 /* layers.NONLINEARITIES ids (layers.py:13-21).  Every id is accepted as hidden and as output
  * activation of every ansatz type with kernels. */
@@ -360,7 +368,8 @@ int vmc_last_connected_rows(vmc_ctx* ctx, int64_t* rows);
  * units); 1: fused, LDS-operand rows (257 .. 512 units); 2: general multi-launch path (> 512 units,
  * or CGS_VMC_WIDE_FAST=0); 3: convolutional kernels; 4: the 3 x bf16 split experiment of the row kernel
  * (CGS_VMC_SPLIT_BF16=1: fully_connected, relu, 193 .. 256 units; fp32 results from the bf16 matrix cores,
- * cgs_vmc_amd/csrc/tail_split.hip -- never the headline configuration). */
+ * cgs_vmc_amd/csrc/tail_split.hip -- never the headline configuration); 5: the split sampler as well; 6: the
+ * general convolution path; 7: the projected BCS determinant kernels of pbdg (cgs_vmc_amd/csrc/pbdg.hip). */
 int vmc_debug_kernel_path(vmc_ctx* ctx, int32_t* path);
 /* Chains per workgroup of the fused dense sampler: 16 (k_sweep16, sweep16.hpp) or 8 (k_sweep8, sweep8.hip: chosen by
  * vmc_create when sixteen-chain tiles would occupy at most half of the CUs -- BASELINE configs 2 and 5 -- or by
