@@ -494,3 +494,25 @@ hipError_t launch_pbdg_itswo_ratio(hipStream_t s, const float* logit_psi, const 
                                    const float* logit_omega, const float* sign_omega, const float* eloc_omega,
                                    float log_factor, float beta, int B, float* ratio);
 hipError_t launch_pbdg_signed_max(hipStream_t s, const float* logit, const float* sign, int B, float* out);
+
+// --------------------------------------------------------------------------------------
+// FullyConnectedNNB (nnb.hip): neural-network backflow, psi(x) = det F(x)[up sites, down sites] with the pairing
+// matrix F(x) = reshape(trunk(x), [N, N]) written by the general dense path as a dense block [rows][N^2]
+// --------------------------------------------------------------------------------------
+struct NnbRowsArgs {
+  float* out; long long ldo;            // the block's pairing layer [n_rows][ldo >= N^2] (write_delta: overwritten)
+  int N, cpw;                           // cpw: set by the launcher (plan_pbdg_chains_per_wg)
+  const float* configs;                 // base configurations, indexed by rowinfo[].x
+  const int2* rowinfo; const int2* bonds;   // row r = configs[rowinfo[r].x], the sites of bond |y| - 1 exchanged when y != 0
+  long long n_rows;
+  float* logit; float* sign;            // [n_rows] ln|det M| (-inf singular, NaN without N/2 up spins), sign(det M)
+  // local-energy rows (val != nullptr): val[r] = half_jx[bond] psi(row) / psi(chain) from the chains' cached logits / signs
+  const float* half_jx; const float* logit_base; const float* sign_base; float* val;
+  int write_delta;                      // gradient path: out[r] <- d ln|psi| / d out (M^-1 scattered, zero elsewhere)
+};
+hipError_t launch_nnb_rows(hipStream_t s, NnbRowsArgs a);
+hipError_t launch_nnb_candidates(hipStream_t s, const float* configs, const int* iup, const int* idn, int B, int N,
+                                 float* cand);
+hipError_t launch_nnb_accept(hipStream_t s, float* configs, const float* cand, const int* iup, const int* idn,
+                             const float* u, float* logit, float* sign, const float* lcand, const float* scand, int B,
+                             int N, unsigned char* acc_mask, unsigned long long* accepted);

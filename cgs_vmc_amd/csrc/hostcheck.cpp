@@ -636,8 +636,72 @@ static void pbdg_grid() {
   CHECK(plan_pbdg_check(258, msg, sizeof(msg)) == VMC_ERR_UNSUPPORTED);
 }
 
+// fully_connected_nnb (plan_nnb_*, the NNB branch of plan_desc / plan_num_params_dense): every even N from 4 to 100 (and the
+// edges up to 258) with L, H and batch sizes; the parameter layout ends exactly at P; the block of rows stays within the
+// planned workspace for every block size; the rows kernel's grid covers the block; the weight-gradient tiles and the
+// slices' workspace are in range
+static void nnb_grid() {
+  char msg[256];
+  const int Ns[] = {1, 2, 3, 4, 6, 8, 10, 12, 14, 16, 18, 20, 22, 24, 26, 28, 30, 32, 34, 36, 38, 40, 42, 44, 46, 48, 50, 52, 54,
+                    56, 58, 60, 62, 64, 66, 68, 70, 72, 74, 76, 78, 80, 82, 84, 86, 88, 90, 92, 94, 96, 98, 99, 100, 128, 200,
+                    255, 256, 257, 258};
+  for (int n_sites : Ns)
+    for (int L : {0, 1, 2, 3, 16, 17})
+      for (int H : {1, 7, 32, 64, 100, 256, 300, 512, 513})
+        for (long long B : {1LL, 7LL, 64LL, 1024LL, 4096LL, 65536LL}) {
+          vmc_desc d = dense_desc(VMC_ANSATZ_NNB, n_sites, (int)B, L, H, VMC_ACT_TANH, VMC_ACT_IDENTITY);   // activations ignored
+          DescPlan p;
+          const int rc = plan_desc(&d, true, &p, msg, sizeof(msg));
+          ++g_shapes;
+          CHECK(rc == plan_nnb_check(n_sites, L, H, B, msg, sizeof(msg)));
+          if (n_sites < 2 || (n_sites & 1)) { CHECK(rc == VMC_ERR_INVALID); ++g_rejected; continue; }
+          const long long NN = (long long)n_sites * n_sites;
+          if (n_sites > PLAN_NNB_MAX_SITES || L < 1 || L > PLAN_NNB_MAX_LAYERS || H > PLAN_NNB_MAX_UNITS ||
+              B * NN > PLAN_NNB_MAX_DELTA) {
+            CHECK(rc == VMC_ERR_UNSUPPORTED); ++g_rejected; continue;
+          }
+          CHECK(rc == VMC_OK && p.nnb == 1 && p.wide == 1 && p.wide_fast == 0 && p.pbdg == 0 && p.conv == 0);
+          CHECK(p.Hp >= H && p.Hp % 64 == 0 && p.Hp < H + 64 && p.n_hh == L - 1);
+          const long long P = (long long)n_sites * H + H + (long long)(L - 1) * ((long long)H * H + H) + H * NN + NN;
+          CHECK(p.P == P && plan_num_params_dense(VMC_ANSATZ_NNB, n_sites, H, L) == P);
+          // the layout: layers in order, the pairing layer's weights then its biases, ending at P
+          CHECK(plan_off_w(p.lay, H, 0) == 0 && plan_off_b(p.lay, H, 0) == (long long)n_sites * H);
+          for (int l = 1; l < L; ++l) CHECK(plan_off_b(p.lay, H, l) == plan_off_w(p.lay, H, l) + (long long)H * H);
+          CHECK(p.lay.off_wout == (long long)n_sites * H + H + (long long)(L - 1) * ((long long)H * H + H));
+          CHECK(p.lay.off_bout == p.lay.off_wout + H * NN && p.lay.off_bout + NN == P);
+          // row blocks: bounded by the block size for every knob value, never empty
+          for (long long mb : {-5LL, 0LL, 1LL, 16LL, 256LL, 4096LL, 1LL << 40}) {
+            const long long rows = plan_nnb_block_rows(n_sites, mb);
+            const long long eff = mb < 1 ? 1 : (mb > PLAN_NNB_BLOCK_MB_MAX ? PLAN_NNB_BLOCK_MB_MAX : mb);
+            CHECK(rows >= 1 && rows <= (1LL << 20));
+            CHECK(rows == 1 || rows * NN * 4 <= (eff << 20));
+            CHECK(rows * NN < (1LL << 31) * 4);
+            CHECK(plan_nnb_block_floats(n_sites, p.Hp, rows) == rows * (NN + 2 * p.Hp));
+            const long long grid = plan_nnb_rows_grid(rows, n_sites);
+            CHECK(grid >= 1 && grid * plan_pbdg_chains_per_wg(n_sites) >= rows && grid < (1LL << 31));
+          }
+          // the default block on the headline lattice: 4 x 10^5 connected rows walk in blocks of a bounded workspace
+          if (n_sites == 100) CHECK(plan_nnb_block_rows(100, PLAN_NNB_BLOCK_MB_DEFAULT) == 6710);
+          CHECK((size_t)plan_pbdg_chains_per_wg(n_sites) * plan_pbdg_chain_lds_bytes(n_sites) <= PLAN_LDS_PER_CU);
+          const int tiles = plan_nnb_wgrad_total_tiles(n_sites, H, L - 1);
+          CHECK(tiles == plan_wgrad_tiles(H, (int)NN) + (L - 1) * plan_wgrad_tiles(H, H) + plan_wgrad_tiles(n_sites, H));
+          for (int cus : kCus) {
+            const int s = plan_wgrad_slices(tiles, B, cus, 1, 0);
+            CHECK(s >= 1 && s <= WG_MAX_SPLIT && (long long)plan_wgrad_kchunk((int)B, s) * s >= B);
+            CHECK(plan_wgrad_grid(tiles, s) >= tiles * s);
+            CHECK(plan_wgrad_ws_floats(tiles, s) < (1LL << 33));
+          }
+        }
+  vmc_desc d = dense_desc(8, 16, 64, 2, 32, VMC_ACT_RELU, VMC_ACT_EXP);        // id 8 stays unassigned
+  DescPlan p;
+  CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_UNSUPPORTED);
+  d = dense_desc(10, 16, 64, 2, 32, VMC_ACT_RELU, VMC_ACT_EXP);
+  CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_UNSUPPORTED);
+}
+
 int main() {
   check_block_maps();
+  nnb_grid();
   pbdg_grid();
   gnn_grid();
   dense_grid();

@@ -57,6 +57,7 @@ inline long long plan_off_b(const ParamLayout& lay, long long H, int l) {
 
 inline long long plan_num_params_dense(int ansatz, long long N, long long H, long long L) {
   if (ansatz == VMC_ANSATZ_PBDG) return N * N;        // the pairing matrix F[N][N] (plan_pbdg_*)
+  if (ansatz == VMC_ANSATZ_NNB) return N * H + H + (L - 1) * (H * H + H) + H * N * N + N * N;   // trunk + pairing layer
   if (ansatz == VMC_ANSATZ_RBM) return N + 1 + N * H + H + L * (H * H + H);
   return N * H + H + (L - 1) * (H * H + H) + H + 1;
 }
@@ -483,10 +484,66 @@ inline int plan_pbdg_check(int N, char* msg, size_t msg_len) {
   return VMC_OK;
 }
 
+// ------------------------------------------------------------------------------- neural-network backflow (nnb.hip)
+// FullyConnectedNNB: the fully_connected trunk (L relu layers of H units) with a pairing layer of N^2 outputs,
+// psi(x) = det F(x)[U, D].  The trunk and the pairing layer run on the general dense path in blocks of rows whose dense
+// pairing layer [rows][N^2] is the only large buffer; the determinant rows reuse pbdg's LDS plan (plan_pbdg_*), hence
+// N <= 256.  H <= 512 and L <= 16 are what hostcheck walks; the gradient path holds d ln|psi| / d out of all B chains
+// densely ([B][N^2], the A operand of the weight-gradient launch), bounded by PLAN_NNB_MAX_DELTA floats (4 GiB).
+#define PLAN_NNB_MAX_SITES PLAN_PBDG_MAX_SITES
+#define PLAN_NNB_MAX_UNITS 512
+#define PLAN_NNB_MAX_LAYERS 16
+#define PLAN_NNB_MAX_DELTA (1LL << 30)
+#define PLAN_NNB_BLOCK_MB_DEFAULT 256      // CGS_VMC_NNB_BLOCK_MB
+#define PLAN_NNB_BLOCK_MB_MAX 4096
+inline int plan_nnb_check(int N, int L, int H, long long B, char* msg, size_t msg_len) {
+  if (N < 2 || (N & 1)) {
+    snprintf(msg, msg_len, "fully_connected_nnb: num_sites must be even and >= 2 (got %d): psi = det F[up, down] lives at Sz = 0", N);
+    return VMC_ERR_INVALID;
+  }
+  if (B < 1 || H < 1) { snprintf(msg, msg_len, "batch_size, layer_size >= 1 required"); return VMC_ERR_INVALID; }
+  if (N > PLAN_NNB_MAX_SITES) {
+    snprintf(msg, msg_len, "fully_connected_nnb: num_sites = %d beyond 256 (n = N/2 > 128: the inverse would exceed 64 KiB of LDS)", N);
+    return VMC_ERR_UNSUPPORTED;
+  }
+  if (L < 1 || L > PLAN_NNB_MAX_LAYERS) {
+    snprintf(msg, msg_len, "fully_connected_nnb: num_layers = %d outside 1..16", L);
+    return VMC_ERR_UNSUPPORTED;
+  }
+  if (H > PLAN_NNB_MAX_UNITS) {
+    snprintf(msg, msg_len, "fully_connected_nnb: layer_size = %d beyond 512", H);
+    return VMC_ERR_UNSUPPORTED;
+  }
+  if (B * (long long)N * N > PLAN_NNB_MAX_DELTA) {
+    snprintf(msg, msg_len, "fully_connected_nnb: batch_size x num_sites^2 = %lld beyond 2^30 (the gradient path's dense pairing-layer delta)",
+             B * (long long)N * N);
+    return VMC_ERR_UNSUPPORTED;
+  }
+  if (msg_len) msg[0] = 0;
+  return VMC_OK;
+}
+// rows per block of the forward passes: block_mb MiB of dense pairing layer (clamped to 1 .. 4096), at least one row, at
+// most 2^20 rows (the trunk's buffers follow) -- the whole workspace of a block is rows x (N^2 + 2 Hp) floats
+inline long long plan_nnb_block_rows(int N, long long block_mb) {
+  if (block_mb < 1) block_mb = 1;
+  if (block_mb > PLAN_NNB_BLOCK_MB_MAX) block_mb = PLAN_NNB_BLOCK_MB_MAX;
+  long long rows = (block_mb << 20) / ((long long)N * N * (long long)sizeof(float));
+  if (rows < 1) rows = 1;
+  if (rows > (1LL << 20)) rows = 1LL << 20;
+  return rows;
+}
+inline long long plan_nnb_block_floats(int N, int Hp, long long rows) { return rows * ((long long)N * N + 2LL * Hp); }
+// launches of the determinant rows kernel: cpw rows (waves) per workgroup
+inline long long plan_nnb_rows_grid(long long rows, int N) {
+  const int cpw = plan_pbdg_chains_per_wg(N);
+  return (rows + cpw - 1) / cpw;
+}
+
 // ------------------------------------------------------------------------------- vmc_create
 struct DescPlan {
   int rbm, conv, resnet, one_d;
   int pbdg;                  // ProjectedBDG (pbdg.hip): none of the network members below apply
+  int nnb;                   // FullyConnectedNNB (nnb.hip): the general dense path (wide, never wide_fast) into determinant rows
   int conv_general;          // conv beyond the fused kernels' limits (or forced): conv_general.hip
   int wide, wide_fast;       // > 256 units; of those, the fused 384 / 512-unit kernels
   int Hp;                    // padded units of the dense kernels (conv: 64, unused)
@@ -504,8 +561,20 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
                      int conv_general_pref = 0) {
   memset(out, 0, sizeof(*out));
 #define PLAN_FAIL(code, text) do { snprintf(msg, msg_len, "%s", text); return code; } while (0)
-  if (d->ansatz < VMC_ANSATZ_FULLY_CONNECTED || d->ansatz > VMC_ANSATZ_PBDG)
-    PLAN_FAIL(VMC_ERR_UNSUPPORTED, "only the fully_connected, rbm, conv_1d/2d, res_net_1d/2d, gnn and pbdg ansatz types have HIP kernels");
+  if (d->ansatz < VMC_ANSATZ_FULLY_CONNECTED || (d->ansatz > VMC_ANSATZ_PBDG && d->ansatz != VMC_ANSATZ_NNB))
+    PLAN_FAIL(VMC_ERR_UNSUPPORTED, "only the fully_connected, rbm, conv_1d/2d, res_net_1d/2d, gnn, pbdg and fully_connected_nnb ansatz types have HIP kernels");
+  if (d->ansatz == VMC_ANSATZ_NNB) {
+    // FullyConnectedNNB (wavefunctions.py:931-998): the fully_connected layout with an output layer N^2 wide; always relu
+    const int rc = plan_nnb_check(d->n_sites, d->num_layers, d->layer_size, d->batch_size, msg, msg_len);
+    if (rc != VMC_OK) return rc;
+    out->nnb = 1; out->wide = 1; out->wide_fast = 0;
+    out->Hp = (d->layer_size + 63) / 64 * 64; out->n_hh = d->num_layers - 1;
+    out->P = plan_num_params_dense(VMC_ANSATZ_NNB, d->n_sites, d->layer_size, d->num_layers);
+    out->lay = plan_layout(false, d->n_sites, d->layer_size, d->num_layers);
+    out->lay.off_bout = out->lay.off_wout + (long long)d->layer_size * d->n_sites * d->n_sites;
+    if (msg_len) msg[0] = 0;
+    return VMC_OK;
+  }
   if (d->ansatz == VMC_ANSATZ_PBDG) {
     // ProjectedBDG (wavefunctions.py:876-928): no layers, no activations; the dense members keep minimal shapes (unused)
     const int rc = plan_pbdg_check(d->n_sites, msg, msg_len);
@@ -718,6 +787,10 @@ inline int plan_wgrad_grid(int tiles, int slices) { return tiles <= 0 ? 0 : 8 * 
 // out_in_tiles: the N = 1 layer (w_out, b_out / w_on, b_on) is one of the tile problems; false: its sums come
 // from the back-propagation kernel's per-workgroup partials and are folded by plan_wgrad_fold_blocks(H)
 // workgroups of the same launch (fully_connected on the fused kernels)
+// (neural-network backflow: the output problem is the pairing layer [H][N^2])
+inline int plan_nnb_wgrad_total_tiles(int N, int H, int n_hh) {
+  return plan_wgrad_tiles(H, N * N) + n_hh * plan_wgrad_tiles(H, H) + plan_wgrad_tiles(N, H);
+}
 inline int plan_wgrad_total_tiles(int N, int H, int n_hh, bool rbm, bool out_in_tiles = true) {
   return (out_in_tiles ? plan_wgrad_tiles(rbm ? N : H, 1) : 0) + n_hh * plan_wgrad_tiles(H, H) + plan_wgrad_tiles(N, H);
 }

@@ -163,6 +163,41 @@ int wide_forward(vmc_ctx* c, int which, const float* z1, const int2* rowinfo, lo
   return VMC_OK;
 }
 
+int nnb_forward(vmc_ctx* c, int which, const float* z1, const float* configs, const int2* rowinfo, long long n_rows,
+                bool ratio, float* out, float* out_sign) {
+  ParamSet& p = c->ps[which];
+  const int H = c->H, Hp = c->Hp, NH = c->n_hh;
+  const long long NN = (long long)c->N * c->N;
+  const int2* bonds = c->bonds ? c->bonds : c->bond_dummy;
+  for (long long row0 = 0; row0 < n_rows; row0 += c->nnb_rows) {
+    const int rows = (int)(n_rows - row0 < c->nnb_rows ? n_rows - row0 : c->nnb_rows);
+    HIPCHK(c, launch_wide_rows_act(c->stream, z1, p.w1p, rowinfo, bonds, row0, rows, Hp, VMC_ACT_RELU_, c->wbuf[0]));
+    for (int l = 1; l <= NH; ++l) {
+      GemmArgs g; memset(&g, 0, sizeof(g));
+      g.A = c->wbuf[(l - 1) & 1]; g.sam = Hp; g.sak = 1;
+      g.B = p.theta + off_w(c, l); g.sbk = H; g.sbn = 1;
+      g.M = rows; g.N = H; g.K = H; g.C = c->wbuf[l & 1]; g.ldc = Hp;
+      g.bias = p.theta + off_b(c, l); g.epilogue = 1; g.splitk = 1; g.act = VMC_ACT_RELU_;
+      HIPCHK(c, launch_gemm(c->stream, g));
+    }
+    {   // the pairing layer of the block: out[rows][N^2] = a_L W_out + b_out
+      GemmArgs g; memset(&g, 0, sizeof(g));
+      g.A = c->wbuf[NH & 1]; g.sam = Hp; g.sak = 1;
+      g.B = p.theta + off_wout(c); g.sbk = NN; g.sbn = 1;
+      g.M = rows; g.N = (int)NN; g.K = H; g.C = c->nnb_out; g.ldc = NN;
+      g.bias = p.theta + off_bout(c); g.epilogue = 4; g.splitk = 1;
+      HIPCHK(c, launch_gemm(c->stream, g));
+    }
+    NnbRowsArgs a; memset((void*)&a, 0, sizeof(a));
+    a.out = c->nnb_out; a.ldo = NN; a.N = c->N; a.configs = configs; a.rowinfo = rowinfo + row0; a.bonds = bonds;
+    a.n_rows = rows;
+    if (ratio) { a.half_jx = c->half_jx; a.logit_base = p.logit; a.sign_base = p.sign; a.val = out + row0; }
+    else { a.logit = out + row0; a.sign = out_sign + row0; }
+    HIPCHK(c, launch_nnb_rows(c->stream, a));
+  }
+  return VMC_OK;
+}
+
 // z1 / logit cache of parameter set `which` for the ctx's chains
 int ensure_cache(vmc_ctx* c, int which) {
   PROPAGATE(ensure_packed(c, which));
@@ -187,7 +222,10 @@ int ensure_cache(vmc_ctx* c, int which) {
     PROPAGATE(first_layer(c, p, c->configs, p.z1, c->B));
     if (c->rbm) HIPCHK(c, launch_onsite(c->stream, c->configs, p.won, c->B, c->N, p.onsite));
   }
-  if (c->wide) {
+  if (c->nnb) {
+    Timer t(c, "tail_amp");
+    PROPAGATE(nnb_forward(c, which, p.z1, c->configs, c->rowinfo_id, c->B, false, p.logit, p.sign));
+  } else if (c->wide) {
     Timer t(c, "tail_amp");
     PROPAGATE(wide_forward(c, which, p.z1, c->rowinfo_id, c->B, false, p.logit, p.onsite));
   } else {
@@ -247,6 +285,8 @@ int local_energy_device(vmc_ctx* c, int which, bool defer_reduce, bool* deferred
     int n_rows = 0;      // the GEMM grids need the row count on the host
     HIPCHK(c, hipMemcpyAsync(&n_rows, c->off + c->B, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->nnb) PROPAGATE(nnb_forward(c, which, p.z1, c->configs, c->rowinfo, n_rows, true, c->val, nullptr));
+    else
     PROPAGATE(wide_forward(c, which, p.z1, c->rowinfo, n_rows, true, c->val, p.onsite));
   } else {
     Timer t(c, "tail_eloc");
@@ -303,13 +343,13 @@ int grow_tmp(vmc_ctx* c, long long rows) {
 
 // pbdg: every row must hold as many up as down spins (the projected BCS state lives at Sz = 0); host rows
 int pbdg_check_sz(vmc_ctx* c, const float* configs, long long n_rows) {
-  if (!c->pbdg) return VMC_OK;
+  if (!c->sgn) return VMC_OK;
   for (long long r = 0; r < n_rows; ++r) {
     double m = 0.0;
     for (int i = 0; i < c->N; ++i) m += configs[r * c->N + i];
     if (m != 0.0) {
       char msg[160];
-      snprintf(msg, sizeof(msg), "pbdg: configuration %lld has magnetisation %g; the ansatz needs as many up as down spins", r, m);
+      snprintf(msg, sizeof(msg), "%s: configuration %lld has magnetisation %g; the ansatz needs as many up as down spins", c->nnb ? "fully_connected_nnb" : "pbdg", r, m);
       return fail(c, VMC_ERR_INVALID, msg);
     }
   }
@@ -367,7 +407,7 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
     if (rc != VMC_OK) return fail(nullptr, rc, msg);
   }
   const bool rbm = dp.rbm != 0, conv = dp.conv != 0, wide = dp.wide != 0, wide_fast_ok = dp.wide_fast != 0;
-  const bool pbdg = dp.pbdg != 0;
+  const bool pbdg = dp.pbdg != 0, nnb = dp.nnb != 0;
   const ConvGeom cg = dp.cg;
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
@@ -385,9 +425,12 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
   if (conv) { c->L = 1; c->overlap = false; }   // minimal dense-side shapes (unused)
   c->pbdg = pbdg;
   if (pbdg) { c->L = 1; c->H = 1; c->overlap = false; c->hact = VMC_ACT_RELU_; }
+  c->nnb = nnb; c->sgn = pbdg || nnb;
+  if (nnb) c->ps[0].shift = c->ps[1].shift = 0.f;     // no exponent shift: psi = det M itself
   c->wide = wide;
   if (wide) c->overlap = false;
-  c->hact = pbdg ? VMC_ACT_RELU_ : d->nonlinearity; c->oact = pbdg ? VMC_ACT_EXP_ : d->output_activation;
+  // (pbdg, nnb: the activations of the desc are ignored -- relu trunk, amplitudes kept as (logit, sign))
+  c->hact = c->sgn ? VMC_ACT_RELU_ : d->nonlinearity; c->oact = c->sgn ? VMC_ACT_EXP_ : d->output_activation;
   c->lay = dp.lay;
   // 257 .. 512 units (wide_fast): the fused sampler padded to 384 / 512 units (k_sweep16<24|32>), rows on
   // the LDS-operand kernel (k_tail_lds; without an H x H layer: k_tail0) and the fused back-propagation
@@ -464,7 +507,10 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
     // (CGS_VMC_WGRAD_OUT_TILES=1 keeps it there: A/B measurements)
     const char* e_out = getenv("CGS_VMC_WGRAD_OUT_TILES");
     c->wg_out_partials = !rbm && !conv && !pbdg && !(wide && !c->wide_fast) && !(e_out && atoi(e_out) == 1);
-    c->wg_tiles = plan_wgrad_total_tiles((int)N, c->H, (int)NH, rbm, !c->wg_out_partials);
+    c->wg_tiles = nnb ? plan_nnb_wgrad_total_tiles((int)N, c->H, (int)NH)
+                      : plan_wgrad_total_tiles((int)N, c->H, (int)NH, rbm, !c->wg_out_partials);
+    // (nnb: hundreds of tiles and more -- the workspace follows the planned slices, not the bound)
+    if (nnb) c->nnb_wg_slices = plan_wgrad_slices(c->wg_tiles, B, c->num_cus, 1, 0);
     if (c->wg_out_partials) CA(dalloc(&c->wg_outpart, ((B + 15) / 16) * 2 * (Hp + 4)));
     CA(dalloc(&c->wg_tickets, c->wg_tiles > 0 ? c->wg_tiles : 1));
     CA(hipMemsetAsync(c->wg_tickets, 0, (size_t)(c->wg_tiles > 0 ? c->wg_tiles : 1) * sizeof(int), c->stream));
@@ -482,7 +528,7 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
   CA(hipMemsetAsync(c->acc, 0, (2 * P + 8) * sizeof(float), c->stream));
   CA(hipMemsetAsync(c->adam_m, 0, P * sizeof(float), c->stream));
   CA(hipMemsetAsync(c->adam_v, 0, P * sizeof(float), c->stream));
-  CA(dalloc(&c->gemm_ws, plan_wgrad_ws_floats(c->wg_tiles, WG_MAX_SPLIT)));
+  CA(dalloc(&c->gemm_ws, plan_wgrad_ws_floats(c->wg_tiles, nnb ? c->nnb_wg_slices : WG_MAX_SPLIT)));
   CA(dalloc(&c->d_accepted, 1)); CA(dalloc(&c->d_sum, 1)); CA(dalloc(&c->d_max, 1));
   CA(dalloc(&c->inj_up, B)); CA(dalloc(&c->inj_dn, B)); CA(dalloc(&c->inj_u, B));
   CA(dalloc(&c->acc_mask, B));
@@ -493,18 +539,29 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
   CA(dalloc(&c->offdiag, B));
   if (wide) {
     c->wrows = B > 131072 ? B : 131072;
+    if (nnb) {   // blocks of rows whose dense pairing layer takes CGS_VMC_NNB_BLOCK_MB (default 256) MiB
+      long long mb = PLAN_NNB_BLOCK_MB_DEFAULT;
+      if (const char* e = getenv("CGS_VMC_NNB_BLOCK_MB")) mb = atoll(e);
+      c->nnb_rows = plan_nnb_block_rows((int)N, mb);
+      if (const char* e = getenv("CGS_VMC_NNB_BLOCK_ROWS")) { const long long r = atoll(e); if (r >= 1 && r < c->nnb_rows) c->nnb_rows = r; }   // tests: several blocks at small shapes
+      c->wrows = c->nnb_rows;
+      CA(dalloc(&c->nnb_out, c->nnb_rows * N * N));
+      CA(dalloc(&c->nnb_delta, B * N * N));
+      CA(dalloc(&c->nnb_cl, B)); CA(dalloc(&c->nnb_cs, B));
+    }
     CA(dalloc(&c->wbuf[0], c->wrows * Hp)); CA(dalloc(&c->wbuf[1], c->wrows * Hp));
     CA(dalloc(&c->wide_u, B));
     CA(dalloc(&c->wide_dot, (long long)gemm_rowdot_tiles(c->H) * c->wrows));
     CA(dalloc(&c->wide_iup, B)); CA(dalloc(&c->wide_idn, B)); CA(dalloc(&c->wide_zero, Hp));
     CA(hipMemsetAsync(c->wide_zero, 0, Hp * sizeof(float), c->stream));
   }
-  if (pbdg) {
-    const long long n = N / 2;
+  if (c->sgn)
     for (int w = 0; w < 2; ++w) {
       CA(dalloc(&c->ps[w].sign, B));
       CA(hipMemsetAsync(c->ps[w].sign, 0, B * sizeof(float), c->stream));
     }
+  if (pbdg) {
+    const long long n = N / 2;
     CA(dalloc(&c->ps[0].sign_alt, B));
     CA(hipMemsetAsync(c->ps[0].sign_alt, 0, B * sizeof(float), c->stream));
     CA(dalloc(&c->pbdg_inv, B * n * n)); CA(dalloc(&c->pbdg_pos, B * N));
@@ -603,7 +660,7 @@ void vmc_destroy(vmc_ctx* c) {
   if (c->cg_td) hipFree(c->cg_td);
   if (c->cg_centre) hipFree(c->cg_centre);
   for (int* q : {c->gnn_adj, c->gnn_inv_ptr, c->gnn_inv, c->pbdg_pos}) if (q) hipFree(q);
-  for (float* q : {c->ps[0].sign, c->ps[1].sign, c->ps[0].sign_alt, c->pbdg_inv, c->tmp_sign}) if (q) hipFree(q);
+  for (float* q : {c->ps[0].sign, c->ps[1].sign, c->ps[0].sign_alt, c->pbdg_inv, c->tmp_sign, c->nnb_out, c->nnb_delta, c->nnb_cl, c->nnb_cs}) if (q) hipFree(q);
   if (c->pbdg_ws) hipFree(c->pbdg_ws);
   void* ptrs[] = {c->configs, c->configs_alt, c->bonds, c->half_jx, c->quarter_jz, c->cnt, c->off, c->diag, c->val,
                   c->offdiag, c->rowinfo, c->delta_all, c->d_batch[0][0], c->d_batch[0][1], c->d_batch[1][0], c->d_batch[1][1], c->ratio, c->ones, c->acc,
@@ -737,7 +794,7 @@ int vmc_get_configs(vmc_ctx* c, float* configs) {
 int vmc_set_shift(vmc_ctx* c, int which, float shift) {
   CHECK_CTX(c);
   if (which != 0 && which != 1) return fail(c, VMC_ERR_INVALID, "bad which");
-  c->ps[which].shift = shift;
+  if (!c->nnb) c->ps[which].shift = shift;     // (neural-network backflow has no exponent shift: it stays 0)
   return VMC_OK;
 }
 
@@ -752,12 +809,12 @@ int vmc_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, f
   ENTER(c);
   if (which != 0 && which != 1) return fail(c, VMC_ERR_INVALID, "bad which");
   if (n_rows < 0) return fail(c, VMC_ERR_INVALID, "n_rows < 0");
-  std::vector<float> host((size_t)n_rows), hsign(c->pbdg ? (size_t)n_rows : 0);
+  std::vector<float> host((size_t)n_rows), hsign(c->sgn ? (size_t)n_rows : 0);
   if (!configs) {
     if (n_rows != c->B) return fail(c, VMC_ERR_INVALID, "n_rows must equal batch_size when configs == NULL");
     PROPAGATE(ensure_cache(c, which));
     HIPCHK(c, hipMemcpyAsync(host.data(), c->ps[which].logit, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (c->pbdg)
+    if (c->sgn)
       HIPCHK(c, hipMemcpyAsync(hsign.data(), c->ps[which].sign, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   } else if (n_rows > 0 && c->pbdg) {
     PROPAGATE(ensure_packed(c, which));
@@ -766,6 +823,15 @@ int vmc_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, f
     HIPCHK(c, hipMemcpyAsync(c->tmp_cfg, configs, n_rows * c->N * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, launch_pbdg_rows(c->stream, c->ps[which].theta, c->N, c->tmp_cfg, (int)n_rows, c->tmp_out, c->tmp_sign,
                                nullptr, nullptr));
+    HIPCHK(c, hipMemcpyAsync(host.data(), c->tmp_out, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hsign.data(), c->tmp_sign, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  } else if (n_rows > 0 && c->nnb) {
+    PROPAGATE(ensure_packed(c, which));
+    PROPAGATE(pbdg_check_sz(c, configs, n_rows));
+    PROPAGATE(grow_tmp(c, n_rows));
+    HIPCHK(c, hipMemcpyAsync(c->tmp_cfg, configs, n_rows * c->N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    PROPAGATE(first_layer(c, c->ps[which], c->tmp_cfg, c->tmp_z1, (int)n_rows));
+    PROPAGATE(nnb_forward(c, which, c->tmp_z1, c->tmp_cfg, c->tmp_rowinfo, n_rows, false, c->tmp_out, c->tmp_sign));
     HIPCHK(c, hipMemcpyAsync(host.data(), c->tmp_out, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(hsign.data(), c->tmp_sign, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   } else if (n_rows > 0) {
@@ -793,7 +859,7 @@ int vmc_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, f
   for (int64_t i = 0; i < n_rows; ++i) {
     if (logit) logit[i] = host[i];
     // wavefunctions.py:350-353: exp(x - shift) (232), or the output activation itself, no shift
-    if (psi) psi[i] = c->pbdg ? hsign[i] * expf(host[i] - shift)      // signed: sign(det M) exp(logit - shift)
+    if (psi) psi[i] = c->sgn ? hsign[i] * expf(host[i] - shift)      // signed: sign(det M) exp(logit - shift)
                               : c->oact == VMC_ACT_EXP_ ? expf(host[i] - shift) : host_activation(c->oact, host[i]);
   }
   return VMC_OK;
@@ -828,7 +894,7 @@ int vmc_local_energy_terms(vmc_ctx* c, int which, float* diag, float* offdiag_ov
 int vmc_debug_kernel_path(vmc_ctx* c, int32_t* path) {
   CHECK_CTX(c);
   if (!path) return fail(c, VMC_ERR_INVALID, "null");
-  *path = c->pbdg ? 7 : c->conv ? (c->conv_general ? 6 : 3) : (c->wide ? (c->wide_fast ? 1 : 2) : (c->split ? (c->split_sweep ? 5 : 4) : 0));
+  *path = c->nnb ? 8 : c->pbdg ? 7 : c->conv ? (c->conv_general ? 6 : 3) : (c->wide ? (c->wide_fast ? 1 : 2) : (c->split ? (c->split_sweep ? 5 : 4) : 0));
   return VMC_OK;
 }
 

@@ -268,11 +268,46 @@ static int run_sweep_pbdg(vmc_ctx* c, long long n_steps, bool injected, bool dbg
   return VMC_OK;
 }
 
+// The neural-network-backflow sampler (nnb.hip): per mc_step the proposals (k_wide_propose: the Philox streams of every
+// sampler), the candidates as configurations in the alternate chain buffer, their amplitudes by the route vmc_amplitude
+// takes (first-layer GEMM off the spins, trunk, pairing layer, determinant rows: no incrementally updated state, nothing
+// to refresh), and the accept launch, which updates chains, logits and signs in place.
+static int run_sweep_nnb(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn,
+                         float* dbg_u, unsigned long long step0, bool count_accepted) {
+  ParamSet& p = c->ps[0];
+  const int B = c->B, N = c->N;
+  const uint32_t seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull), seed_hi = (uint32_t)(c->d.seed >> 32);
+  if (dbg) {
+    HIPCHK(c, launch_wide_propose(c->stream, c->configs, B, N, seed_lo, seed_hi, c->d.chain_offset, step0, nullptr,
+                                  nullptr, nullptr, dbg_up, dbg_dn, dbg_u));
+    return VMC_OK;
+  }
+  PROPAGATE(ensure_cache(c, VMC_PSI));
+  if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), c->stream));
+  Timer t(c, "sweep");
+  for (long long st = 0; st < n_steps; ++st) {
+    HIPCHK(c, launch_wide_propose(c->stream, c->configs, B, N, seed_lo, seed_hi, c->d.chain_offset,
+                                  step0 + (unsigned long long)st, injected ? c->inj_up : nullptr,
+                                  injected ? c->inj_dn : nullptr, injected ? c->inj_u : nullptr, c->wide_iup,
+                                  c->wide_idn, c->wide_u));
+    HIPCHK(c, launch_nnb_candidates(c->stream, c->configs, c->wide_iup, c->wide_idn, B, N, c->configs_alt));
+    PROPAGATE(first_layer(c, p, c->configs_alt, p.z1_alt, B));
+    PROPAGATE(nnb_forward(c, VMC_PSI, p.z1_alt, c->configs_alt, c->rowinfo_id, B, false, c->nnb_cl, c->nnb_cs));
+    HIPCHK(c, launch_nnb_accept(c->stream, c->configs, c->configs_alt, c->wide_iup, c->wide_idn, c->wide_u, p.logit,
+                                p.sign, c->nnb_cl, c->nnb_cs, B, N, injected ? c->acc_mask : nullptr, c->d_accepted));
+  }
+  c->acts_valid = false;
+  c->acc_since_sweep = false;
+  return VMC_OK;
+}
+
 static int run_sweep(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn,
                      float* dbg_u, unsigned long long step0, bool count_accepted = false,
                      bool overtake = false, hipEvent_t dep = nullptr) {
   PROPAGATE(ensure_packed(c, 0));
   if (!dbg) c->cnt_valid = false;   // the chains change (set again below when this launch leaves their census)
+  if (c->nnb)
+    return run_sweep_nnb(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
   if (c->wide && !c->wide_fast)
     return run_sweep_wide(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
   if (c->pbdg)

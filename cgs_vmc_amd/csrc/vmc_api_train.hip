@@ -71,6 +71,29 @@ static int gradient_sums(vmc_ctx* c, const float* w, bool fresh, const float* e,
   // workgroup, transposed weight fragments on 16x16x4 MFMA (k_backprop16)
   if (c->wide && !c->wide_fast) {
     // delta_NH = w_out (.) f'(z_NH); delta_{l-1} = f'(z_{l-1}) (.) (delta_l W_l^T) on the generic GEMM
+    if (c->nnb) {
+      // the pairing layer of psi on the chains, dense [B][N^2]; the rows kernel factorises every M and overwrites the row
+      // by d ln|psi| / d out = (M^-1)^T at the (up, down) entries; delta_NH = relu' (.) (d_out W_out^T)
+      const long long NN = (long long)N * N;
+      PROPAGATE(grow_tmp(c, B));
+      GemmArgs g; memset(&g, 0, sizeof(g));
+      g.A = c->act[NH]; g.sam = Hp; g.sak = 1;
+      g.B = p.theta + off_wout(c); g.sbk = NN; g.sbn = 1;
+      g.M = B; g.N = (int)NN; g.K = H; g.C = c->nnb_delta; g.ldc = NN;
+      g.bias = p.theta + off_bout(c); g.epilogue = 4; g.splitk = 1;
+      HIPCHK(c, launch_gemm(c->stream, g));
+      NnbRowsArgs a; memset((void*)&a, 0, sizeof(a));
+      a.out = c->nnb_delta; a.ldo = NN; a.N = N; a.configs = c->configs; a.rowinfo = c->rowinfo_id;
+      a.bonds = c->bonds ? c->bonds : c->bond_dummy; a.n_rows = B;
+      a.logit = c->tmp_out; a.sign = c->tmp_sign; a.write_delta = 1;
+      HIPCHK(c, launch_nnb_rows(c->stream, a));
+      memset(&g, 0, sizeof(g));
+      g.A = c->nnb_delta; g.sam = NN; g.sak = 1;
+      g.B = p.theta + off_wout(c); g.sbk = 1; g.sbn = NN;           // B(k = out, n = in) = W_out[in][out]
+      g.M = B; g.N = H; g.K = (int)NN; g.C = c->delta[NH]; g.ldc = Hp;
+      g.bias = c->wide_zero; g.mask = c->act[NH]; g.ldmask = Hp; g.epilogue = 5; g.splitk = 1; g.act = c->hact;
+      HIPCHK(c, launch_gemm(c->stream, g));
+    } else
     if (c->rbm)   // d sum log cosh(z) / d z = tanh(z), which the forward left in act[NH]
       HIPCHK(c, hipMemcpyAsync(c->delta[NH], c->act[NH], (size_t)B * Hp * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     else
@@ -109,7 +132,9 @@ static int gradient_sums(vmc_ctx* c, const float* w, bool fresh, const float* e,
       wgrad_fill_problem(tab.data(), n++, a, a_ld, delta, ldd, off, k_in, n_out, tile0);
       tile0 += plan_wgrad_tiles(k_in, n_out);
     };
-    if (c->rbm)   // onsite layer: d logit / d w_on = x, d logit / d b_on = 1
+    if (c->nnb)   // pairing layer: d ln|psi| / d w_out = a_L^T d_out, d ln|psi| / d b_out = d_out
+      add(c->act[NH], Hp, H, c->nnb_delta, (long long)N * N, N * N, off_wout(c));
+    else if (c->rbm)   // onsite layer: d logit / d w_on = x, d logit / d b_on = 1
       add(c->configs, N, N, c->ones, 1, 1, c->lay.off_won);
     else if (!c->wg_out_partials)   // output layer: d logit / d w_out = a_L, d logit / d b_out = 1
       add(c->act[NH], Hp, H, c->oscale, 1, 1, off_wout(c));   // oscale == 1 for the exp output
@@ -129,7 +154,8 @@ static int gradient_sums(vmc_ctx* c, const float* w, bool fresh, const float* e,
       L.out_part = c->wg_outpart; L.out_nwg = (B + 15) / 16; L.out_H = H; L.out_ld = Hp + 4; L.out_off = off_wout(c);
     }
     L.tiles = c->wg_tiles;
-    L.slices = plan_wgrad_slices(c->wg_tiles, B, c->num_cus, 1 + (c->wg_out_partials ? plan_wgrad_fold_blocks(H) : 0), forced);
+    L.slices = c->nnb ? c->nnb_wg_slices
+                      : plan_wgrad_slices(c->wg_tiles, B, c->num_cus, 1 + (c->wg_out_partials ? plan_wgrad_fold_blocks(H) : 0), forced);
     L.K = B; L.w = w; L.g1 = g1; L.g2 = g2; L.ws = c->gemm_ws; L.tickets = c->wg_tickets; L.fresh = fresh;
     L.sc_eloc = e; L.sc_ratio = mode == 1 ? c->ratio : nullptr; L.sc_out = c->acc + 2 * c->P; L.sc_B = B; L.sc_mode = mode;
     HIPCHK(c, launch_wgrad(c->stream, L));
@@ -192,7 +218,7 @@ int vmc_accumulate(vmc_ctx* c, int mode, float beta) {
     }
     PROPAGATE(local_energy_device(c, VMC_OMEGA, true, &fold_eloc));   // training.py:664, 667
     PROPAGATE(ensure_cache(c, VMC_PSI));
-    if (c->pbdg)      // signed amplitudes: sign_w sign_psi exp(...)
+    if (c->sgn)       // signed amplitudes: sign_w sign_psi exp(...)
       HIPCHK(c, launch_pbdg_itswo_ratio(c->stream, c->ps[0].logit, c->ps[0].sign, c->ps[1].logit, c->ps[1].sign,
                                         c->ps[1].eloc, c->ps[0].shift - c->ps[1].shift, beta, c->B, c->ratio));
     else if (!fold_eloc)   // (otherwise the back-propagation launch folds E_loc^w and forms the ratio: two launches less)
@@ -300,7 +326,7 @@ int vmc_set_adam_state(vmc_ctx* c, const float* m, const float* v, int64_t t) {
 
 // Wavefunction.update_norm (wavefunctions.py:261-288); max_b psi over the chains of all ranks
 static int update_norm_impl(vmc_ctx* c, void* comm, int world, float max_value) {
-  if (c->oact != VMC_ACT_EXP_) return VMC_OK;   // wavefunctions.py:276-277: no exp_norm_shift, nothing to do
+  if (c->oact != VMC_ACT_EXP_ || c->nnb) return VMC_OK;   // wavefunctions.py:276-277: no exp_norm_shift, nothing to do
   PROPAGATE(ensure_cache(c, VMC_PSI));
   // pbdg: max_b psi_b of the SIGNED amplitudes (wavefunctions.py:283): the largest logit among the chains with psi > 0
   if (c->pbdg) HIPCHK(c, launch_pbdg_signed_max(c->stream, c->ps[0].logit, c->ps[0].sign, c->B, c->d_max));

@@ -59,6 +59,15 @@ struct vmc_ctx {
   bool pbdg = false;
   float* pbdg_inv = nullptr; int* pbdg_pos = nullptr; double* pbdg_ws = nullptr; int pbdg_slices = 1;
   float* tmp_sign = nullptr;   // [tmp_rows] signs of vmc_amplitude's rows
+  // FullyConnectedNNB (nnb.hip): the general dense path (wide && !wide_fast) whose output stage is the pairing layer of a
+  // block of nnb_rows rows (nnb_out [nnb_rows][N^2], wbuf[] [nnb_rows][Hp]) and the determinant rows kernel.  sgn: signed
+  // amplitudes (pbdg || nnb: sign buffers, the signed ITSWO ratio, Sz = 0 configurations only).  nnb_delta [B][N^2]: the
+  // pairing layer of psi on the chains, overwritten by d ln|psi| / d out (gradient path); nnb_cl / nnb_cs [B]: logits and
+  // signs of the sampler's candidates; nnb_wg_slices: K slices of the weight-gradient launch
+  bool nnb = false, sgn = false;
+  long long nnb_rows = 0;
+  float *nnb_out = nullptr, *nnb_delta = nullptr, *nnb_cl = nullptr, *nnb_cs = nullptr;
+  int nnb_wg_slices = 1;
   // Conv2DNetwork / ResNet2D (conv.hip).  The dense-ansatz members below keep harmless minimal
   // shapes (H = filters, Hp = 64, no H x H layer); acts_valid tells whether the forward tapes
   // hold the inputs of every convolution for psi on the current chains.
@@ -388,6 +397,10 @@ int ensure_list(vmc_ctx* c);
 int local_energy_device(vmc_ctx* c, int which, bool defer_reduce = false, bool* deferred = nullptr);
 int grow_tmp(vmc_ctx* c, long long rows);
 int pbdg_check_sz(vmc_ctx* c, const float* configs, long long n_rows);
+// neural-network backflow: rows {chain, bond} of a row list over `configs` and the chains' first-layer cache z1 -> logits
+// and signs (ratio == false) or the local-energy terms (ratio: out = val, out_sign unused), in blocks of c->nnb_rows
+int nnb_forward(vmc_ctx* c, int which, const float* z1, const float* configs, const int2* rowinfo, long long n_rows,
+                bool ratio, float* out, float* out_sign);
 // vmc_api_cgen.hip (the general convolution path)
 int cgen_forward(vmc_ctx* c, int which, const float* configs, const int2* rowinfo, long long n_rows,
                  const int* iup, const int* idn, bool ratio, float* out, float* tape = nullptr,

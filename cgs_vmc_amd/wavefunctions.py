@@ -766,6 +766,71 @@ class ProjectedBDG(FullyConnectedNetwork):
     return cls(**params)
 
 
+class FullyConnectedNNB(FullyConnectedNetwork):
+  """Neural-network backflow (wavefunctions.py:931-998): a relu trunk of num_layers snt.Linear(layer_size) layers and a
+  pairing layer snt.Linear(N^2); psi(x) = det M(x), M[r][c] = F(x)[U_r][D_c] with F(x) = out.reshape(N, N) over the up
+  sites U and the down sites D of x in ascending order.  Signed amplitudes and no exponent shift (the reference returns
+  tf.linalg.det as it is): normalize_batch / update_norm return None.  The kernels (csrc/nnb.hip) run the trunk and the
+  pairing layer on the general dense path and factorise every M in LDS; they keep (ln|det M|, sign) throughout."""
+  _ansatz = 'fully_connected_nnb'
+  MAX_SITES, MAX_UNITS, MAX_LAYERS = 256, 512, 16     # plan.hpp PLAN_NNB_*
+
+  def __init__(self, num_sites: int, num_layers: int, layer_sizes, name: str = 'fully_connected_nnb'):
+    num_sites, num_layers = int(num_sites), int(num_layers)
+    sizes = [int(s) for s in layer_sizes]
+    if num_sites < 2 or num_sites % 2:
+      raise ValueError('fully_connected_nnb: num_sites must be even (as many up as down spins), got %d' % num_sites)
+    if len(sizes) != num_layers:
+      raise ValueError('fully_connected_nnb: layer_sizes must hold num_layers entries')
+    if num_layers < 1:
+      raise NotImplementedError('fully_connected_nnb: num_layers = 0 is not supported by the HIP kernels')
+    if len(set(sizes)) != 1:
+      raise NotImplementedError('fully_connected_nnb: hidden layers of unequal width are not supported')
+    if num_sites > self.MAX_SITES or sizes[0] > self.MAX_UNITS or num_layers > self.MAX_LAYERS or sizes[0] < 1:
+      raise NotImplementedError('fully_connected_nnb: the HIP kernels cover num_sites <= %d, layer size <= %d and '
+                                'num_layers <= %d' % (self.MAX_SITES, self.MAX_UNITS, self.MAX_LAYERS))
+    super(FullyConnectedNNB, self).__init__(num_layers=num_layers, layer_size=sizes[0], name=name)
+    self._exp_norm_shift = None          # no add_exp_normalization: psi is the determinant itself
+    self._num_sites = num_sites
+    self._layer_sizes = sizes
+
+  def _shapes(self):
+    if self._n_sites is not None and self._n_sites != self._num_sites:
+      raise ValueError('Input tensor has wrong shape.')
+    n, h, u = self._num_sites, self._layer_size, self._unique_name
+    names, shapes, fan_in = [], [], n
+    for l in range(self._num_layers + 1):
+      out = h if l < self._num_layers else n * n
+      lin = 'linear' if l == 0 else 'linear_%d' % l
+      names += ['%s/%s/w' % (u, lin), '%s/%s/b' % (u, lin)]
+      shapes += [(fan_in, out), (out,)]
+      fan_in = out
+    return names, shapes
+
+  def initialize(self, seed=None):
+    if self._n_sites is None:
+      self._n_sites = self._num_sites
+    super(FullyConnectedNNB, self).initialize(seed)
+
+  def _engine_spec(self):
+    return dict(ansatz=self._ansatz, num_layers=self._num_layers, layer_size=self._layer_size,
+                nonlinearity='relu', output_activation='exp')
+
+  def _bind(self, configs_var):
+    if configs_var.shape[1] != self._num_sites:
+      raise ValueError('Input tensor has wrong shape.')
+    return super(FullyConnectedNNB, self)._bind(configs_var)
+
+  @classmethod
+  def from_hparams(cls, hparams, name: str = '') -> 'Wavefunction':
+    """wavefunctions.py:982-998."""
+    params = {'num_sites': hparams.num_sites, 'num_layers': hparams.num_fc_layers,
+              'layer_sizes': [hparams.fc_layer_size] * hparams.num_fc_layers}
+    if name:
+      params['name'] = name
+    return cls(**params)
+
+
 class AmplitudeTensor(session_lib.Tensor):
   """psi = wavefunction(inputs); evaluates to a float32 array [rows]."""
 
@@ -790,7 +855,7 @@ class _OutOfScope(Wavefunction):
   def from_hparams(cls, hparams, name: str = ''):
     raise NotImplementedError(
         "wavefunction_type '%s' is outside the MI355X hot path (SURVEY.md 2); only "
-        "'fully_connected', 'rbm', 'conv_1d', 'conv_2d', 'res_net_1d', 'res_net_2d', 'gnn' and 'pbdg' have "
+        "'fully_connected', 'rbm', 'conv_1d', 'conv_2d', 'res_net_1d', 'res_net_2d', 'gnn', 'pbdg' and 'fully_connected_nnb' have "
         "HIP kernels" % cls._kind)
 
 
@@ -815,7 +880,7 @@ WAVEFUNCTION_TYPES = {
     'conv_2d': Conv2DNetwork,
     'mps': _stub('mps'),
     'pbdg': ProjectedBDG,
-    'fully_connected_nnb': _stub('fully_connected_nnb'),
+    'fully_connected_nnb': FullyConnectedNNB,
     'res_net_1d': ResNet1D,
     'res_net_2d': ResNet2D,
     'ed_vector': _stub('ed_vector'),

@@ -41,6 +41,17 @@
  * a chain stays in LDS); every configuration the ctx takes (vmc_set_configs, vmc_amplitude) must
  * have as many up as down spins (VMC_ERR_INVALID).  num_layers, layer_size and the activations are
  * ignored.  Stochastic reconfiguration is not available (vmc_sr_reserve: VMC_ERR_UNSUPPORTED).
+ * FullyConnectedNNB ('fully_connected_nnb', VMC_ANSATZ_NNB, wavefunctions.py:931-998): neural-network
+ * backflow.  The fully_connected trunk (num_layers = L >= 1 hidden layers of layer_size = H units,
+ * always relu) followed by a pairing layer of N*N outputs: w_1 [N][H], b_1 [H], (w_l [H][H], b_l [H])
+ * x (L - 1), w_out [H][N*N], b_out [N*N]; P = N*H + H + (L-1)*(H*H + H) + H*N*N + N*N.
+ * F(x)[i][k] = out[i*N + k], psi(x) = det M(x), M[r][c] = F(x)[U_r][D_c] (the convention of pbdg):
+ * logit = ln|det M|, psi = sign(det M) exp(logit); psi = 0, logit = -inf where M is singular.  There
+ * is no exponent shift: vmc_set_shift and vmc_update_norm leave it at 0 and return VMC_OK.  The
+ * activations of vmc_desc are ignored.  n_sites must be even (VMC_ERR_INVALID) and at most 256,
+ * layer_size at most 512, num_layers at most 16 and batch_size * N*N at most 2^30
+ * (VMC_ERR_UNSUPPORTED); configurations must have as many up as down spins (VMC_ERR_INVALID).
+ * Stochastic reconfiguration is not available (vmc_sr_reserve: VMC_ERR_UNSUPPORTED).
  */
 #ifndef CGSVMC_H_
 #define CGSVMC_H_
@@ -71,7 +82,7 @@ enum { VMC_MODE_ENERGY_GRADIENT = 0, VMC_MODE_LOG_OVERLAP_ITSWO = 1 };
 /* wavefunctions.WAVEFUNCTION_TYPES with kernels (wavefunctions.py:1157-1170) */
 enum { VMC_ANSATZ_FULLY_CONNECTED = 0, VMC_ANSATZ_RBM = 1, VMC_ANSATZ_CONV_2D = 2,
        VMC_ANSATZ_RES_NET_2D = 3, VMC_ANSATZ_CONV_1D = 4, VMC_ANSATZ_RES_NET_1D = 5,
-       VMC_ANSATZ_GNN = 6, VMC_ANSATZ_PBDG = 7 };
+       VMC_ANSATZ_GNN = 6, VMC_ANSATZ_PBDG = 7, VMC_ANSATZ_NNB = 9 /* 8 is unassigned */ };
 
 /* layers.NONLINEARITIES ids (layers.py:13-21).  Every id is accepted as hidden and as output
  * activation of every ansatz type with kernels. */
@@ -369,7 +380,8 @@ int vmc_last_connected_rows(vmc_ctx* ctx, int64_t* rows);
  * or CGS_VMC_WIDE_FAST=0); 3: convolutional kernels; 4: the 3 x bf16 split experiment of the row kernel
  * (CGS_VMC_SPLIT_BF16=1: fully_connected, relu, 193 .. 256 units; fp32 results from the bf16 matrix cores,
  * cgs_vmc_amd/csrc/tail_split.hip -- never the headline configuration); 5: the split sampler as well; 6: the
- * general convolution path; 7: the projected BCS determinant kernels of pbdg (cgs_vmc_amd/csrc/pbdg.hip). */
+ * general convolution path; 7: the projected BCS determinant kernels of pbdg (cgs_vmc_amd/csrc/pbdg.hip); 8: neural-network backflow -- the
+ * general dense path into the determinant rows of cgs_vmc_amd/csrc/nnb.hip. */
 int vmc_debug_kernel_path(vmc_ctx* ctx, int32_t* path);
 /* Chains per workgroup of the fused dense sampler: 16 (k_sweep16, sweep16.hpp) or 8 (k_sweep8, sweep8.hip: chosen by
  * vmc_create when sixteen-chain tiles would occupy at most half of the CUs -- BASELINE configs 2 and 5 -- or by
