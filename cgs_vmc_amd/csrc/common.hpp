@@ -516,3 +516,34 @@ hipError_t launch_nnb_candidates(hipStream_t s, const float* configs, const int*
 hipError_t launch_nnb_accept(hipStream_t s, float* configs, const float* cand, const int* iup, const int* idn,
                              const float* u, float* logit, float* sign, const float* lcand, const float* scand, int B,
                              int N, unsigned char* acc_mask, unsigned long long* accepted);
+
+// --------------------------------------------------------------------------------------
+// FullVector / 'ed_vector' (edvec.hip): psi(x) = vec[top[top(x)] + bot[bot(x)]], the parameter vector itself addressed
+// through Lin's two tables [2^(N/2)] (plan_edvec_*).  psi buffers hold the gathered entries themselves (signed, 0 allowed).
+// --------------------------------------------------------------------------------------
+hipError_t launch_edvec_rows(hipStream_t s, const float* vec, int len, const int* top, const int* bot, int N,
+                             const float* configs, int n_rows, float* logit, float* psi);
+struct EdvecSweepArgs {
+  const float* vec; int len; const int* top; const int* bot; int N, B;
+  int tables_lds;                                  // the tables are staged in LDS (plan_edvec_tables_in_lds)
+  const float* configs_in; float* configs_out;    // the chains before / after the launch
+  float* psi_out; float* logit_out;               // the amplitudes of the final chains: the last accepted gathers
+  long long n_steps; unsigned long long step0;
+  uint32_t seed_lo, seed_hi; int chain_offset;
+  const int* inj_up; const int* inj_dn; const float* inj_u;   // injected proposal (tests) or nullptr
+  unsigned char* acc_mask; unsigned long long* accepted;
+};
+hipError_t launch_edvec_sweep(hipStream_t s, EdvecSweepArgs a, int num_cus);
+hipError_t edvec_sweep_reserve_lds(int N);          // before the first launch with tables_lds set
+// val[row] = 0.5 jx psi(x')/psi(x) of every row of the antiparallel-bond list (launch_bond_list); psi [B]: the chains' amplitudes
+hipError_t launch_edvec_eloc(hipStream_t s, const float* vec, int len, const int* top, const int* bot, int N,
+                             const float* configs, const float* psi, int B, const int* off, const int2* rowinfo,
+                             const int2* bonds, const float* half_jx, float* val);
+hipError_t launch_edvec_itswo_ratio(hipStream_t s, const float* psi, const float* psi_omega, const float* eloc_omega,
+                                    float beta, int B, float* ratio);
+// g1[idx_b] += 1 / psi_b, g2[idx_b] += w_b / psi_b, every entry summed over its chains in chain order (no atomics);
+// keys / keys_sorted [B], sort_tmp: edvec_sort_bytes(B, len) bytes
+hipError_t edvec_sort_bytes(int B, int len, size_t* bytes);
+hipError_t launch_edvec_grad(hipStream_t s, const int* top, const int* bot, int N, int len, const float* configs,
+                             const float* psi, const float* w, int B, unsigned long long* keys,
+                             unsigned long long* keys_sorted, void* sort_tmp, size_t sort_bytes, float* g1, float* g2);

@@ -695,12 +695,72 @@ static void nnb_grid() {
   vmc_desc d = dense_desc(8, 16, 64, 2, 32, VMC_ACT_RELU, VMC_ACT_EXP);        // id 8 stays unassigned
   DescPlan p;
   CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_UNSUPPORTED);
-  d = dense_desc(10, 16, 64, 2, 32, VMC_ACT_RELU, VMC_ACT_EXP);
+  d = dense_desc(11, 16, 64, 2, 32, VMC_ACT_RELU, VMC_ACT_EXP);                 // the first id past ed_vector
   CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_UNSUPPORTED);
+}
+
+// ed_vector (plan_desc's shape checks, plan_edvec_*): odd / oversized N and bad lengths refused, the sampler's grid covers
+// every chain in whole waves within a workgroup, the LDS decision keeps the staged tables within a CU, and the table
+// check accepts Lin's tables of the Sz = 0 sector (built here) and refuses a short vector, a shifted entry, a wrong size
+static void edvec_grid() {
+  char msg[256];
+  for (int n_sites = 1; n_sites <= 34; ++n_sites) {
+    long long len = 1;                                   // C(N, N/2)
+    for (int k = 1; k <= n_sites / 2; ++k) len = len * (n_sites / 2 + k) / k;
+    vmc_desc d = dense_desc(VMC_ANSATZ_ED_VECTOR, n_sites, 64, 0, (int)len, VMC_ACT_RELU, VMC_ACT_EXP);
+    DescPlan p;
+    const int rc = plan_desc(&d, true, &p, msg, sizeof(msg));
+    ++g_shapes;
+    if (n_sites < 2 || (n_sites & 1)) { CHECK(rc == VMC_ERR_INVALID); ++g_rejected; continue; }
+    if (n_sites > PLAN_EDVEC_MAX_SITES) { CHECK(rc == VMC_ERR_UNSUPPORTED); ++g_rejected; continue; }
+    CHECK(rc == VMC_OK && p.edvec == 1 && p.pbdg == 0 && p.conv == 0 && p.P == len);
+    CHECK(plan_num_params_dense(VMC_ANSATZ_ED_VECTOR, n_sites, len, 0) == len);
+    CHECK(2 * p.P + 8 < 0x7fffffffLL);                    // the accumulator offsets Adam indexes with int
+    const size_t tb = plan_edvec_tables_bytes(n_sites);
+    CHECK(tb == (size_t)8 << (n_sites / 2));
+    CHECK(!plan_edvec_tables_in_lds(n_sites) || tb <= PLAN_LDS_PER_CU);
+    CHECK(plan_edvec_tables_in_lds(n_sites));             // (every size under the cap)
+    for (int cus : kCus)
+      for (long long B : {1LL, 63LL, 64LL, 65LL, 1000LL, 4096LL, 65536LL, 1000000LL}) {
+        const int t = plan_edvec_sweep_threads(B, cus);
+        CHECK(t >= 64 && t <= 1024 && t % 64 == 0);
+        const unsigned g = plan_edvec_sweep_grid(B, t);
+        CHECK((long long)g * t >= B && (long long)(g - 1) * t < B);
+        CHECK(t == 1024 || g <= (unsigned)cus);           // below the workgroup limit no CU holds two workgroups
+      }
+    d.layer_size = 0;
+    CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_INVALID);
+    if (n_sites > 16) continue;
+    // Lin's tables: the configurations in ascending order of (top, bot) with popcount(top) + popcount(bot) = N/2
+    const int h = n_sites / 2, n_half = 1 << h;
+    std::vector<int32_t> top(n_half), bot(n_half), seen(h + 1, 0);
+    std::vector<long long> cls(h + 1, 1);               // C(h, k)
+    for (int k = 1; k <= h; ++k) cls[k] = cls[k - 1] * (h - k + 1) / k;
+    long long base = 0;
+    for (int t = 0; t < n_half; ++t) {
+      const int k = __builtin_popcount(t);
+      top[t] = (int32_t)base; base += cls[h - k];
+      bot[t] = seen[k]++;
+    }
+    CHECK(base == len);
+    CHECK(plan_edvec_check_tables(n_sites, n_half, top.data(), bot.data(), len, msg, sizeof(msg)) == VMC_OK);
+    CHECK(plan_edvec_check_tables(n_sites, n_half, top.data(), bot.data(), len - 1, msg, sizeof(msg)) == VMC_ERR_INVALID);
+    CHECK(plan_edvec_check_tables(n_sites, n_half / 2, top.data(), bot.data(), len, msg, sizeof(msg)) == VMC_ERR_INVALID);
+    CHECK(plan_edvec_check_tables(n_sites, n_half, nullptr, bot.data(), len, msg, sizeof(msg)) == VMC_ERR_INVALID);
+    bot[0] = -1;                                          // top = all ones, bot = 0: index top[n_half - 1] - 1 = len - 2, still inside
+    top[n_half - 1] = 0;                                  // ... now -1
+    CHECK(plan_edvec_check_tables(n_sites, n_half, top.data(), bot.data(), len, msg, sizeof(msg)) == VMC_ERR_INVALID);
+  }
+  CHECK(plan_edvec_check(16, 12870, msg, sizeof(msg)) == VMC_OK);
+  CHECK(plan_edvec_check(15, 100, msg, sizeof(msg)) == VMC_ERR_INVALID);
+  CHECK(plan_edvec_check(30, 100, msg, sizeof(msg)) == VMC_ERR_UNSUPPORTED);
+  CHECK(plan_edvec_check(16, 0x80000000LL, msg, sizeof(msg)) == VMC_ERR_UNSUPPORTED);
+  CHECK(plan_edvec_sweep_threads(4096, 256) == 64 && plan_edvec_sweep_threads(65536, 256) == 256);
 }
 
 int main() {
   check_block_maps();
+  edvec_grid();
   nnb_grid();
   pbdg_grid();
   gnn_grid();

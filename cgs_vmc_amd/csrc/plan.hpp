@@ -57,6 +57,7 @@ inline long long plan_off_b(const ParamLayout& lay, long long H, int l) {
 
 inline long long plan_num_params_dense(int ansatz, long long N, long long H, long long L) {
   if (ansatz == VMC_ANSATZ_PBDG) return N * N;        // the pairing matrix F[N][N] (plan_pbdg_*)
+  if (ansatz == VMC_ANSATZ_ED_VECTOR) return H;       // the state vector; layer_size carries its length (plan_edvec_*)
   if (ansatz == VMC_ANSATZ_NNB) return N * H + H + (L - 1) * (H * H + H) + H * N * N + N * N;   // trunk + pairing layer
   if (ansatz == VMC_ANSATZ_RBM) return N + 1 + N * H + H + L * (H * H + H);
   return N * H + H + (L - 1) * (H * H + H) + H + 1;
@@ -539,9 +540,81 @@ inline long long plan_nnb_rows_grid(long long rows, int N) {
   return (rows + cpw - 1) / cpw;
 }
 
+// ------------------------------------------------------------------------------- Lin-table state vector (edvec.hip)
+// FullVector: psi(x) = v[top_t[top(x)] + bot_t[bot(x)]] at Sz = 0; a configuration is one 32-bit word, bot(x) its low
+// N/2 bits.  N even and at most 28: the largest size the tests run (C(28,14) = 40,116,600 entries, 160 MB); the index
+// arithmetic itself is 32-bit up to N = 32 (C(32,16) < 2^31).  The two tables hold 2^(N/2) int32 each; the persistent
+// sampler stages them in LDS (at most 128 KiB at N = 28, one workgroup per CU), every other kernel reads them through L2.
+#define PLAN_EDVEC_MAX_SITES 28
+#define PLAN_EDVEC_TABLES_LDS_MAX ((size_t)128 * 1024)
+PLAN_HD inline size_t plan_edvec_tables_bytes(int N) { return (size_t)2 * sizeof(int32_t) << (N / 2); }
+inline bool plan_edvec_tables_in_lds(int N) { return plan_edvec_tables_bytes(N) <= PLAN_EDVEC_TABLES_LDS_MAX; }
+// sampler: one thread per chain and a step is one dependent gather, so the time is latency over chains in flight.
+// The chains are spread over all CUs in whole waves (a CU's waves interleave their gathers), at most 1024 per workgroup
+inline int plan_edvec_sweep_threads(long long B, int num_cus) {
+  const long long cus = num_cus > 0 ? num_cus : 1;
+  long long waves = (B + 64 * cus - 1) / (64 * cus);
+  if (waves < 1) waves = 1;
+  if (waves > 16) waves = 16;
+  return (int)(64 * waves);
+}
+inline unsigned plan_edvec_sweep_grid(long long B, int threads) { return (unsigned)((B + threads - 1) / threads); }
+// vmc_create's shape checks: N even, 2 <= N <= 28, 1 <= len < 2^31
+inline int plan_edvec_check(int N, long long len, char* msg, size_t msg_len) {
+  if (N < 2 || (N & 1)) {
+    snprintf(msg, msg_len, "ed_vector: num_sites must be even and >= 2 (got %d): the Lin tables address the Sz = 0 sector", N);
+    return VMC_ERR_INVALID;
+  }
+  if (N > PLAN_EDVEC_MAX_SITES) {
+    snprintf(msg, msg_len, "ed_vector: num_sites = %d beyond %d (the largest size the kernels are tested at)", N, PLAN_EDVEC_MAX_SITES);
+    return VMC_ERR_UNSUPPORTED;
+  }
+  if (len < 1) {
+    snprintf(msg, msg_len, "ed_vector: the vector length (layer_size) must be >= 1 (got %lld)", len);
+    return VMC_ERR_INVALID;
+  }
+  if (len > 0x7fffffffLL) {
+    snprintf(msg, msg_len, "ed_vector: a vector of %lld entries is beyond the 32-bit index", len);
+    return VMC_ERR_UNSUPPORTED;
+  }
+  if (msg_len) msg[0] = 0;
+  return VMC_OK;
+}
+// vmc_set_lin_tables: n_half = 2^(N/2), and every Sz = 0 configuration -- a top half-word with N/2 - k set bits and a bot
+// half-word with k -- lands in [0, len).  Per popcount class the smallest and the largest entry decide.
+inline int plan_edvec_check_tables(int N, int n_half, const int32_t* top, const int32_t* bot, long long len, char* msg,
+                                   size_t msg_len) {
+  const int h = N / 2;
+  if (n_half != (1 << h)) {
+    snprintf(msg, msg_len, "ed_vector: the Lin tables must hold 2^(N/2) = %d entries each (got %d)", 1 << h, n_half);
+    return VMC_ERR_INVALID;
+  }
+  if (!top || !bot) { snprintf(msg, msg_len, "ed_vector: null Lin table"); return VMC_ERR_INVALID; }
+  long long lo_t[17], hi_t[17], lo_b[17], hi_b[17];
+  for (int k = 0; k <= h; ++k) { lo_t[k] = lo_b[k] = 0x7fffffffffffLL; hi_t[k] = hi_b[k] = -0x7fffffffffffLL; }
+  for (int wd = 0; wd < n_half; ++wd) {
+    int k = 0;
+    for (int i = 0; i < h; ++i) k += (wd >> i) & 1;
+    if (top[wd] < lo_t[k]) lo_t[k] = top[wd];
+    if (top[wd] > hi_t[k]) hi_t[k] = top[wd];
+    if (bot[wd] < lo_b[k]) lo_b[k] = bot[wd];
+    if (bot[wd] > hi_b[k]) hi_b[k] = bot[wd];
+  }
+  for (int k = 0; k <= h; ++k)
+    if (lo_t[h - k] + lo_b[k] < 0 || hi_t[h - k] + hi_b[k] >= len) {
+      const long long bad = lo_t[h - k] + lo_b[k] < 0 ? lo_t[h - k] + lo_b[k] : hi_t[h - k] + hi_b[k];
+      snprintf(msg, msg_len, "ed_vector: an Sz = 0 configuration with %d up spins in its lower half has index %lld outside [0, %lld)",
+               k, bad, len);
+      return VMC_ERR_INVALID;
+    }
+  if (msg_len) msg[0] = 0;
+  return VMC_OK;
+}
+
 // ------------------------------------------------------------------------------- vmc_create
 struct DescPlan {
   int rbm, conv, resnet, one_d;
+  int edvec;                 // FullVector (edvec.hip): theta is the state vector; none of the network members below apply
   int pbdg;                  // ProjectedBDG (pbdg.hip): none of the network members below apply
   int nnb;                   // FullyConnectedNNB (nnb.hip): the general dense path (wide, never wide_fast) into determinant rows
   int conv_general;          // conv beyond the fused kernels' limits (or forced): conv_general.hip
@@ -561,8 +634,21 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
                      int conv_general_pref = 0) {
   memset(out, 0, sizeof(*out));
 #define PLAN_FAIL(code, text) do { snprintf(msg, msg_len, "%s", text); return code; } while (0)
-  if (d->ansatz < VMC_ANSATZ_FULLY_CONNECTED || (d->ansatz > VMC_ANSATZ_PBDG && d->ansatz != VMC_ANSATZ_NNB))
-    PLAN_FAIL(VMC_ERR_UNSUPPORTED, "only the fully_connected, rbm, conv_1d/2d, res_net_1d/2d, gnn, pbdg and fully_connected_nnb ansatz types have HIP kernels");
+  if (d->ansatz < VMC_ANSATZ_FULLY_CONNECTED ||
+      (d->ansatz > VMC_ANSATZ_PBDG && d->ansatz != VMC_ANSATZ_NNB && d->ansatz != VMC_ANSATZ_ED_VECTOR))
+    PLAN_FAIL(VMC_ERR_UNSUPPORTED, "only the fully_connected, rbm, conv_1d/2d, res_net_1d/2d, gnn, pbdg, fully_connected_nnb and ed_vector ansatz types have HIP kernels");
+  if (d->ansatz == VMC_ANSATZ_ED_VECTOR) {
+    // FullVector (wavefunctions.py:1001-1080): layer_size carries the vector length; no layers, no activations
+    const int rc = plan_edvec_check(d->n_sites, d->layer_size, msg, msg_len);
+    if (rc != VMC_OK) return rc;
+    if (d->batch_size < 1) PLAN_FAIL(VMC_ERR_INVALID, "batch_size >= 1 required");
+    out->edvec = 1;
+    out->Hp = 64; out->n_hh = 0;
+    out->P = plan_num_params_dense(VMC_ANSATZ_ED_VECTOR, d->n_sites, d->layer_size, 0);
+    out->lay = plan_layout(false, d->n_sites, 1, 1);
+    if (msg_len) msg[0] = 0;
+    return VMC_OK;
+  }
   if (d->ansatz == VMC_ANSATZ_NNB) {
     // FullyConnectedNNB (wavefunctions.py:931-998): the fully_connected layout with an output layer N^2 wide; always relu
     const int rc = plan_nnb_check(d->n_sites, d->num_layers, d->layer_size, d->batch_size, msg, msg_len);

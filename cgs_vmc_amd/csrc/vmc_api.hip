@@ -13,6 +13,7 @@ namespace vmcapi {
 
 int gnn_ready(vmc_ctx* c) {
   if (c->cg.graph && !c->gnn_adj) return fail(c, VMC_ERR_INVALID, "gnn: no adjacency list (vmc_set_adjacency)");
+  if (c->edvec && !c->ed_top) return fail(c, VMC_ERR_INVALID, "ed_vector: no Lin tables (vmc_set_lin_tables)");
   return VMC_OK;
 }
 
@@ -21,7 +22,7 @@ int ensure_packed(vmc_ctx* c, int which) {
   ParamSet& p = c->ps[which];
   if (!p.has_params) return fail(c, VMC_ERR_STATE, "parameters not set (vmc_set_params)");
   if (p.packed_valid) return VMC_OK;
-  if (c->pbdg) { p.packed_valid = true; return VMC_OK; }     // (the kernels read the pairing matrix in theta as it lies)
+  if (c->pbdg || c->edvec) { p.packed_valid = true; return VMC_OK; }     // (the kernels read theta as it lies)
   if (c->conv) {
     // (general path: the parameter slices are the B matrices of its GEMMs as they lie in theta)
     if (!c->conv_general) HIPCHK(c, launch_conv_pack(c->stream, p.theta, c->cg, p.cw0, p.cwf, p.cwb, p.cbias));
@@ -203,6 +204,12 @@ int ensure_cache(vmc_ctx* c, int which) {
   PROPAGATE(ensure_packed(c, which));
   ParamSet& p = c->ps[which];
   if (p.cache_valid) return VMC_OK;
+  if (c->edvec) {
+    Timer t(c, "tail_amp");
+    HIPCHK(c, launch_edvec_rows(c->stream, p.theta, (int)c->P, c->ed_top, c->ed_bot, c->N, c->configs, c->B, p.logit, p.sign));
+    p.cache_valid = true;
+    return VMC_OK;
+  }
   if (c->pbdg) {
     Timer t(c, "tail_amp");
     HIPCHK(c, launch_pbdg_rows(c->stream, p.theta, c->N, c->configs, c->B, p.logit, p.sign, nullptr, nullptr));
@@ -263,7 +270,11 @@ int local_energy_device(vmc_ctx* c, int which, bool defer_reduce, bool* deferred
   PROPAGATE(ensure_cache(c, which));
   PROPAGATE(ensure_list(c));
   ParamSet& p = c->ps[which];
-  if (c->pbdg) {
+  if (c->edvec) {
+    Timer t(c, "tail_eloc");
+    HIPCHK(c, launch_edvec_eloc(c->stream, p.theta, (int)c->P, c->ed_top, c->ed_bot, c->N, c->configs, p.sign, c->B, c->off,
+                                c->rowinfo, c->bonds, c->half_jx, c->val));
+  } else if (c->pbdg) {
     Timer t(c, "tail_eloc");      // (a fresh M^-1 per chain: never the sampler's incrementally updated one)
     HIPCHK(c, launch_pbdg_eloc(c->stream, p.theta, c->N, c->configs, c->B, c->off, c->rowinfo, c->bonds, c->half_jx,
                                c->val));
@@ -316,7 +327,7 @@ int local_energy_device(vmc_ctx* c, int which, bool defer_reduce, bool* deferred
     }
     HIPCHK(c, launch_rows(c, which, a, true));
   }
-  if (defer_reduce && deferred && !c->conv && !c->pbdg && !(c->wide && !c->wide_fast)) {
+  if (defer_reduce && deferred && !c->conv && !c->pbdg && !c->edvec && !(c->wide && !c->wide_fast)) {
     *deferred = true;              // the fused back-propagation launch folds val into eloc
     return VMC_OK;
   }
@@ -349,7 +360,7 @@ int pbdg_check_sz(vmc_ctx* c, const float* configs, long long n_rows) {
     for (int i = 0; i < c->N; ++i) m += configs[r * c->N + i];
     if (m != 0.0) {
       char msg[160];
-      snprintf(msg, sizeof(msg), "%s: configuration %lld has magnetisation %g; the ansatz needs as many up as down spins", c->nnb ? "fully_connected_nnb" : "pbdg", r, m);
+      snprintf(msg, sizeof(msg), "%s: configuration %lld has magnetisation %g; the ansatz needs as many up as down spins", c->edvec ? "ed_vector" : c->nnb ? "fully_connected_nnb" : "pbdg", r, m);
       return fail(c, VMC_ERR_INVALID, msg);
     }
   }
@@ -407,7 +418,9 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
     if (rc != VMC_OK) return fail(nullptr, rc, msg);
   }
   const bool rbm = dp.rbm != 0, conv = dp.conv != 0, wide = dp.wide != 0, wide_fast_ok = dp.wide_fast != 0;
-  const bool pbdg = dp.pbdg != 0, nnb = dp.nnb != 0;
+  const bool nnb = dp.nnb != 0, edvec = dp.edvec != 0;
+  const bool pbdg = dp.pbdg != 0;
+  const bool no_network = pbdg || edvec;     // theta is read as it lies: minimal dense-side shapes, no network buffers in use
   const ConvGeom cg = dp.cg;
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
@@ -423,10 +436,10 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
   c->rbm = rbm;
   c->conv = conv; c->cg = cg; c->conv_general = conv && dp.conv_general != 0;
   if (conv) { c->L = 1; c->overlap = false; }   // minimal dense-side shapes (unused)
-  c->pbdg = pbdg;
-  if (pbdg) { c->L = 1; c->H = 1; c->overlap = false; c->hact = VMC_ACT_RELU_; }
-  c->nnb = nnb; c->sgn = pbdg || nnb;
-  if (nnb) c->ps[0].shift = c->ps[1].shift = 0.f;     // no exponent shift: psi = det M itself
+  c->pbdg = pbdg; c->edvec = edvec;
+  if (no_network) { c->L = 1; c->H = 1; c->overlap = false; c->hact = VMC_ACT_RELU_; }
+  c->nnb = nnb; c->sgn = no_network || nnb;
+  if (nnb || edvec) c->ps[0].shift = c->ps[1].shift = 0.f;     // no exponent shift: psi = det M itself
   c->wide = wide;
   if (wide) c->overlap = false;
   // (pbdg, nnb: the activations of the desc are ignored -- relu trunk, amplitudes kept as (logit, sign))
@@ -445,14 +458,14 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
     c->split = (atoi(e) == 1 || atoi(e) == 2) && !conv && !wide && !rbm && c->Hp == 256 && c->n_hh >= 1 && c->hact == VMC_ACT_RELU_;
     c->split_sweep = c->split && atoi(e) == 2 && sweep16_split_supported(c->N, c->Hp, c->n_hh);
   }
-  if (const char* e = getenv("CGS_VMC_OVERLAP")) { c->overlap = !conv && !wide && !pbdg && atoi(e) != 0; c->overlap_full = atoi(e) == 2; }
+  if (const char* e = getenv("CGS_VMC_OVERLAP")) { c->overlap = !conv && !wide && !no_network && atoi(e) != 0; c->overlap_full = atoi(e) == 2; }
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, d->device) == hipSuccess && prop.multiProcessorCount > 0)
       c->num_cus = prop.multiProcessorCount;
   }
   // eight-chain sampler tiles where sixteen-chain tiles would leave half of the chip idle (sweep8.hip)
-  c->sweep8_ok = !conv && !wide && !rbm && !pbdg && c->hact == VMC_ACT_RELU_ && !c->split_sweep &&
+  c->sweep8_ok = !conv && !wide && !rbm && !no_network && c->hact == VMC_ACT_RELU_ && !c->split_sweep &&
                  plan_sweep8(c->N, c->Hp, c->n_hh, c->sweep_no_w1l != 0).ok;
   {
     int forced = 0;
@@ -506,7 +519,7 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
     // fully_connected on the kernels that run k_backprop16: the N = 1 output layer leaves the MFMA tile grid
     // (CGS_VMC_WGRAD_OUT_TILES=1 keeps it there: A/B measurements)
     const char* e_out = getenv("CGS_VMC_WGRAD_OUT_TILES");
-    c->wg_out_partials = !rbm && !conv && !pbdg && !(wide && !c->wide_fast) && !(e_out && atoi(e_out) == 1);
+    c->wg_out_partials = !rbm && !conv && !no_network && !(wide && !c->wide_fast) && !(e_out && atoi(e_out) == 1);
     c->wg_tiles = nnb ? plan_nnb_wgrad_total_tiles((int)N, c->H, (int)NH)
                       : plan_wgrad_total_tiles((int)N, c->H, (int)NH, rbm, !c->wg_out_partials);
     // (nnb: hundreds of tiles and more -- the workspace follows the planned slices, not the bound)
@@ -560,7 +573,15 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
       CA(dalloc(&c->ps[w].sign, B));
       CA(hipMemsetAsync(c->ps[w].sign, 0, B * sizeof(float), c->stream));
     }
-  if (pbdg) {
+  if (edvec) {
+    CA(dalloc(&c->ps[0].sign_alt, B));
+    CA(hipMemsetAsync(c->ps[0].sign_alt, 0, B * sizeof(float), c->stream));
+    CA(dalloc(&c->ed_keys, B)); CA(dalloc(&c->ed_keys_sorted, B));
+    CA(edvec_sort_bytes((int)B, (int)P, &c->ed_sort_bytes));
+    CA(hipMalloc(&c->ed_sort_tmp, c->ed_sort_bytes > 0 ? c->ed_sort_bytes : 1));
+    c->ed_tables_lds = plan_edvec_tables_in_lds((int)N) && !(getenv("CGS_VMC_EDVEC_TABLES_LDS") && atoi(getenv("CGS_VMC_EDVEC_TABLES_LDS")) == 0);
+    if (c->ed_tables_lds) CA(edvec_sweep_reserve_lds((int)N));
+  } else if (pbdg) {
     const long long n = N / 2;
     CA(dalloc(&c->ps[0].sign_alt, B));
     CA(hipMemsetAsync(c->ps[0].sign_alt, 0, B * sizeof(float), c->stream));
@@ -659,7 +680,8 @@ void vmc_destroy(vmc_ctx* c) {
   if (c->cg_sum) hipFree(c->cg_sum);
   if (c->cg_td) hipFree(c->cg_td);
   if (c->cg_centre) hipFree(c->cg_centre);
-  for (int* q : {c->gnn_adj, c->gnn_inv_ptr, c->gnn_inv, c->pbdg_pos}) if (q) hipFree(q);
+  for (int* q : {c->gnn_adj, c->gnn_inv_ptr, c->gnn_inv, c->pbdg_pos, c->ed_top, c->ed_bot}) if (q) hipFree(q);
+  for (void* q : {(void*)c->ed_keys, (void*)c->ed_keys_sorted, c->ed_sort_tmp}) if (q) hipFree(q);
   for (float* q : {c->ps[0].sign, c->ps[1].sign, c->ps[0].sign_alt, c->pbdg_inv, c->tmp_sign, c->nnb_out, c->nnb_delta, c->nnb_cl, c->nnb_cs}) if (q) hipFree(q);
   if (c->pbdg_ws) hipFree(c->pbdg_ws);
   void* ptrs[] = {c->configs, c->configs_alt, c->bonds, c->half_jx, c->quarter_jz, c->cnt, c->off, c->diag, c->val,
@@ -735,6 +757,23 @@ int vmc_set_adjacency(vmc_ctx* c, int32_t n_sites, int32_t k, const int32_t* adj
   return VMC_OK;
 }
 
+int vmc_set_lin_tables(vmc_ctx* c, int32_t n_half, const int32_t* top, const int32_t* bot) {
+  ENTER(c);
+  if (!c->edvec) return fail(c, VMC_ERR_INVALID, "vmc_set_lin_tables: not an ed_vector ctx");
+  {
+    char msg[256];
+    const int rc = plan_edvec_check_tables(c->N, n_half, top, bot, c->P, msg, sizeof(msg));
+    if (rc != VMC_OK) return fail(c, rc, msg);
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (!c->ed_bot) HIPCHK(c, dalloc(&c->ed_bot, n_half));
+  HIPCHK(c, hipMemcpy(c->ed_bot, bot, (size_t)n_half * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (!c->ed_top) HIPCHK(c, dalloc(&c->ed_top, n_half));      // (set last: gnn_ready takes it as "tables present")
+  HIPCHK(c, hipMemcpy(c->ed_top, top, (size_t)n_half * sizeof(int32_t), hipMemcpyHostToDevice));
+  c->ps[0].cache_valid = c->ps[1].cache_valid = false;     // (the amplitudes of the chains belong to the previous tables)
+  return VMC_OK;
+}
+
 int vmc_set_params(vmc_ctx* c, int which, const float* theta) {
   ENTER(c);
   if ((which != 0 && which != 1) || !theta) return fail(c, VMC_ERR_INVALID, "bad arguments");
@@ -794,7 +833,7 @@ int vmc_get_configs(vmc_ctx* c, float* configs) {
 int vmc_set_shift(vmc_ctx* c, int which, float shift) {
   CHECK_CTX(c);
   if (which != 0 && which != 1) return fail(c, VMC_ERR_INVALID, "bad which");
-  if (!c->nnb) c->ps[which].shift = shift;     // (neural-network backflow has no exponent shift: it stays 0)
+  if (!c->nnb && !c->edvec) c->ps[which].shift = shift;     // (neural-network backflow, ed_vector: no exponent shift, it stays 0)
   return VMC_OK;
 }
 
@@ -816,6 +855,15 @@ int vmc_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, f
     HIPCHK(c, hipMemcpyAsync(host.data(), c->ps[which].logit, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (c->sgn)
       HIPCHK(c, hipMemcpyAsync(hsign.data(), c->ps[which].sign, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  } else if (n_rows > 0 && c->edvec) {
+    PROPAGATE(ensure_packed(c, which));
+    PROPAGATE(pbdg_check_sz(c, configs, n_rows));
+    PROPAGATE(grow_tmp(c, n_rows));
+    HIPCHK(c, hipMemcpyAsync(c->tmp_cfg, configs, n_rows * c->N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_edvec_rows(c->stream, c->ps[which].theta, (int)c->P, c->ed_top, c->ed_bot, c->N, c->tmp_cfg, (int)n_rows,
+                                c->tmp_out, c->tmp_sign));
+    HIPCHK(c, hipMemcpyAsync(host.data(), c->tmp_out, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hsign.data(), c->tmp_sign, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   } else if (n_rows > 0 && c->pbdg) {
     PROPAGATE(ensure_packed(c, which));
     PROPAGATE(pbdg_check_sz(c, configs, n_rows));
@@ -859,7 +907,8 @@ int vmc_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, f
   for (int64_t i = 0; i < n_rows; ++i) {
     if (logit) logit[i] = host[i];
     // wavefunctions.py:350-353: exp(x - shift) (232), or the output activation itself, no shift
-    if (psi) psi[i] = c->sgn ? hsign[i] * expf(host[i] - shift)      // signed: sign(det M) exp(logit - shift)
+    if (psi) psi[i] = c->edvec ? hsign[i]                               // the gathered entry itself
+                              : c->sgn ? hsign[i] * expf(host[i] - shift)      // signed: sign(det M) exp(logit - shift)
                               : c->oact == VMC_ACT_EXP_ ? expf(host[i] - shift) : host_activation(c->oact, host[i]);
   }
   return VMC_OK;
@@ -894,7 +943,7 @@ int vmc_local_energy_terms(vmc_ctx* c, int which, float* diag, float* offdiag_ov
 int vmc_debug_kernel_path(vmc_ctx* c, int32_t* path) {
   CHECK_CTX(c);
   if (!path) return fail(c, VMC_ERR_INVALID, "null");
-  *path = c->nnb ? 8 : c->pbdg ? 7 : c->conv ? (c->conv_general ? 6 : 3) : (c->wide ? (c->wide_fast ? 1 : 2) : (c->split ? (c->split_sweep ? 5 : 4) : 0));
+  *path = c->edvec ? 9 : c->nnb ? 8 : c->pbdg ? 7 : c->conv ? (c->conv_general ? 6 : 3) : (c->wide ? (c->wide_fast ? 1 : 2) : (c->split ? (c->split_sweep ? 5 : 4) : 0));
   return VMC_OK;
 }
 

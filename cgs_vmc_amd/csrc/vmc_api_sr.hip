@@ -12,6 +12,8 @@ int vmc_sr_reserve(vmc_ctx* c, int32_t n_batches) {
   if (n_batches < 0) return fail(c, VMC_ERR_INVALID, "n_batches < 0");
   if (n_batches > 0 && c->nnb)
     return fail(c, VMC_ERR_UNSUPPORTED, "stochastic reconfiguration is not implemented for the fully_connected_nnb ansatz (use EnergyGradient or LogOverlapITSWO)");
+  if (n_batches > 0 && c->edvec)
+    return fail(c, VMC_ERR_UNSUPPORTED, "stochastic reconfiguration is not implemented for the ed_vector ansatz (use EnergyGradient or LogOverlapITSWO)");
   if (n_batches > 0 && c->pbdg)
     return fail(c, VMC_ERR_UNSUPPORTED, "stochastic reconfiguration is not implemented for the pbdg ansatz (use EnergyGradient or LogOverlapITSWO)");
   if (n_batches > 0 && c->oact != VMC_ACT_EXP_)

@@ -81,7 +81,7 @@ static int run_sweep_wide(vmc_ctx* c, long long n_steps, bool injected, bool dbg
 // goes to the buffer the next sampler launch overwrites anyway); nothing is swapped.
 bool sampler_refresh_ok(const vmc_ctx* c) {
   static const bool on = !(getenv("CGS_VMC_SAMPLER_REFRESH") && atoi(getenv("CGS_VMC_SAMPLER_REFRESH")) == 0);
-  return on && !c->conv && !c->pbdg && !(c->wide && !c->wide_fast);
+  return on && !c->conv && !c->pbdg && !c->edvec && !(c->wide && !c->wide_fast);
 }
 int refresh_cache_by_sampler(vmc_ctx* c, int which) {
   PROPAGATE(ensure_packed(c, which));
@@ -268,6 +268,36 @@ static int run_sweep_pbdg(vmc_ctx* c, long long n_steps, bool injected, bool dbg
   return VMC_OK;
 }
 
+// The ed_vector sampler (edvec.hip): one persistent launch of n_steps steps, one thread per chain; it leaves the final
+// chains in the alternate set together with their amplitudes -- the last accepted gathers, hence vmc_amplitude's bits.
+static int run_sweep_edvec(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn,
+                           float* dbg_u, unsigned long long step0, bool count_accepted) {
+  ParamSet& p = c->ps[0];
+  const uint32_t seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull), seed_hi = (uint32_t)(c->d.seed >> 32);
+  if (dbg) {
+    HIPCHK(c, launch_wide_propose(c->stream, c->configs, c->B, c->N, seed_lo, seed_hi, c->d.chain_offset, step0, nullptr,
+                                  nullptr, nullptr, dbg_up, dbg_dn, dbg_u));
+    return VMC_OK;
+  }
+  if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), c->stream));
+  EdvecSweepArgs a;
+  memset(&a, 0, sizeof(a));
+  a.vec = p.theta; a.len = (int)c->P; a.top = c->ed_top; a.bot = c->ed_bot; a.N = c->N; a.B = c->B;
+  a.tables_lds = c->ed_tables_lds ? 1 : 0;
+  a.configs_in = c->configs; a.configs_out = c->configs_alt; a.psi_out = p.sign_alt; a.logit_out = p.logit_alt;
+  a.n_steps = n_steps; a.step0 = step0; a.seed_lo = seed_lo; a.seed_hi = seed_hi; a.chain_offset = c->d.chain_offset;
+  if (injected) { a.inj_up = c->inj_up; a.inj_dn = c->inj_dn; a.inj_u = c->inj_u; a.acc_mask = c->acc_mask; }
+  a.accepted = c->d_accepted;
+  {
+    Timer t(c, "sweep");
+    HIPCHK(c, launch_edvec_sweep(c->stream, a, c->num_cus));
+  }
+  swap_chain_buffers(c);
+  c->acts_valid = false;
+  c->acc_since_sweep = false;
+  return VMC_OK;
+}
+
 // The neural-network-backflow sampler (nnb.hip): per mc_step the proposals (k_wide_propose: the Philox streams of every
 // sampler), the candidates as configurations in the alternate chain buffer, their amplitudes by the route vmc_amplitude
 // takes (first-layer GEMM off the spins, trunk, pairing layer, determinant rows: no incrementally updated state, nothing
@@ -306,6 +336,8 @@ static int run_sweep(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int
                      bool overtake = false, hipEvent_t dep = nullptr) {
   PROPAGATE(ensure_packed(c, 0));
   if (!dbg) c->cnt_valid = false;   // the chains change (set again below when this launch leaves their census)
+  if (c->edvec)
+    return run_sweep_edvec(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
   if (c->nnb)
     return run_sweep_nnb(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
   if (c->wide && !c->wide_fast)
@@ -466,7 +498,7 @@ int vmc_debug_proposals(vmc_ctx* c, uint64_t step, int32_t* i_up, int32_t* i_dn,
 int vmc_debug_sweep_profile(vmc_ctx* c, int64_t n_steps, double* phase_cycles) {
   ENTER(c);
   if (n_steps < 1 || !phase_cycles) return fail(c, VMC_ERR_INVALID, "bad arguments");
-  if (c->rbm || c->conv || c->wide || c->pbdg) return fail(c, VMC_ERR_UNSUPPORTED, "the diagnostic sweep build exists for fully_connected (<= 256 units) only");
+  if (c->rbm || c->conv || c->wide || c->pbdg || c->edvec) return fail(c, VMC_ERR_UNSUPPORTED, "the diagnostic sweep build exists for fully_connected (<= 256 units) only");
   PROPAGATE(ensure_packed(c, 0));
   const bool tile8 = c->sweep_tile == 8;      // k_sweep8's stamped instantiation (phases: sweep8.hip)
   const int wpg = tile8 ? c->Hp / 32 : c->sweep_waves;

@@ -17,6 +17,12 @@ static int gradient_sums(vmc_ctx* c, const float* w, bool fresh, const float* e,
   float* g1 = c->acc;
   float* g2 = c->acc + c->P;
   Timer t(c, "grad");
+  if (c->edvec) {
+    // O_k(b) = delta(k, idx_b) / psi_b: a scatter of 1 / psi_b and w_b / psi_b, every entry summed in chain order (edvec.hip)
+    HIPCHK(c, launch_edvec_grad(c->stream, c->ed_top, c->ed_bot, N, (int)c->P, c->configs, p.sign, w, B, c->ed_keys,
+                                c->ed_keys_sorted, c->ed_sort_tmp, c->ed_sort_bytes, g1, g2));
+    return VMC_OK;
+  }
   if (c->pbdg) {
     // O_ik = M^-1[pos k][pos i] of psi on the chains, from a fresh factorisation (pbdg.hip)
     // (the logits / signs land in the rows' scratch buffers, which the cache of `p` does not share)
@@ -218,7 +224,9 @@ int vmc_accumulate(vmc_ctx* c, int mode, float beta) {
     }
     PROPAGATE(local_energy_device(c, VMC_OMEGA, true, &fold_eloc));   // training.py:664, 667
     PROPAGATE(ensure_cache(c, VMC_PSI));
-    if (c->sgn)       // signed amplitudes: sign_w sign_psi exp(...)
+    if (c->edvec)     // the amplitudes themselves: psi_w / psi (1 - beta E_loc^w)
+      HIPCHK(c, launch_edvec_itswo_ratio(c->stream, c->ps[0].sign, c->ps[1].sign, c->ps[1].eloc, beta, c->B, c->ratio));
+    else if (c->sgn)       // signed amplitudes: sign_w sign_psi exp(...)
       HIPCHK(c, launch_pbdg_itswo_ratio(c->stream, c->ps[0].logit, c->ps[0].sign, c->ps[1].logit, c->ps[1].sign,
                                         c->ps[1].eloc, c->ps[0].shift - c->ps[1].shift, beta, c->B, c->ratio));
     else if (!fold_eloc)   // (otherwise the back-propagation launch folds E_loc^w and forms the ratio: two launches less)
@@ -229,7 +237,7 @@ int vmc_accumulate(vmc_ctx* c, int mode, float beta) {
   PROPAGATE(ensure_cache(c, VMC_PSI));
   // the batched weight-gradient GEMMs of the dense ansatz types cover every parameter, so a pending
   // reset is absorbed: their reduction stores instead of adding (conv: zero first)
-  if (c->conv || c->pbdg) PROPAGATE(acc_zeros(c));
+  if (c->conv || c->pbdg || c->edvec) PROPAGATE(acc_zeros(c));
   const bool fresh = c->acc_fresh;
   bool scalars_done = false;
   PROPAGATE(gradient_sums(c, w, fresh, e, mode, &scalars_done, fold_eloc, beta));
@@ -326,7 +334,7 @@ int vmc_set_adam_state(vmc_ctx* c, const float* m, const float* v, int64_t t) {
 
 // Wavefunction.update_norm (wavefunctions.py:261-288); max_b psi over the chains of all ranks
 static int update_norm_impl(vmc_ctx* c, void* comm, int world, float max_value) {
-  if (c->oact != VMC_ACT_EXP_ || c->nnb) return VMC_OK;   // wavefunctions.py:276-277: no exp_norm_shift, nothing to do
+  if (c->oact != VMC_ACT_EXP_ || c->nnb || c->edvec) return VMC_OK;   // wavefunctions.py:276-277: no exp_norm_shift, nothing to do
   PROPAGATE(ensure_cache(c, VMC_PSI));
   // pbdg: max_b psi_b of the SIGNED amplitudes (wavefunctions.py:283): the largest logit among the chains with psi > 0
   if (c->pbdg) HIPCHK(c, launch_pbdg_signed_max(c->stream, c->ps[0].logit, c->ps[0].sign, c->B, c->d_max));

@@ -28,7 +28,7 @@ struct ParamSet {
   float* z1 = nullptr;     // [B][Hp] cache for the ctx's chains
   float* onsite = nullptr; // [B] cached x . w_on (RBM)
   float* logit = nullptr;  // [B]
-  float* sign = nullptr;   // [B] pbdg: sign(det M) of the chains (+-1, 0 singular); psi = sign exp(logit - shift)
+  float* sign = nullptr;   // [B] pbdg: sign(det M) of the chains (+-1, 0 singular); psi = sign exp(logit - shift); ed_vector: psi itself
   // psi only: the buffers the NEXT sampler launch writes (see vmc_ctx::configs_alt)
   float *z1_alt = nullptr, *onsite_alt = nullptr, *logit_alt = nullptr, *sign_alt = nullptr;
   float* eloc = nullptr;   // [B]
@@ -68,6 +68,13 @@ struct vmc_ctx {
   long long nnb_rows = 0;
   float *nnb_out = nullptr, *nnb_delta = nullptr, *nnb_cl = nullptr, *nnb_cs = nullptr;
   int nnb_wg_slices = 1;
+  // FullVector (edvec.hip): theta is the state vector, ed_top / ed_bot the Lin tables [2^(N/2)] (null until
+  // vmc_set_lin_tables).  ParamSet::sign holds the chains' amplitudes themselves (psi, not a sign), logit = ln|psi|,
+  // the shift stays 0.  ed_keys / ed_keys_sorted [B], ed_sort_tmp: the gradient scatter's sort (launch_edvec_grad)
+  bool edvec = false, ed_tables_lds = false;
+  int *ed_top = nullptr, *ed_bot = nullptr;
+  unsigned long long *ed_keys = nullptr, *ed_keys_sorted = nullptr;
+  void* ed_sort_tmp = nullptr; size_t ed_sort_bytes = 0;
   // Conv2DNetwork / ResNet2D (conv.hip).  The dense-ansatz members below keep harmless minimal
   // shapes (H = filters, Hp = 64, no H x H layer); acts_valid tells whether the forward tapes
   // hold the inputs of every convolution for psi on the current chains.

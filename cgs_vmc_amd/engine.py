@@ -52,13 +52,16 @@ class VmcEngine:
                nonlinearity: str = 'relu', output_activation: str = 'exp', device: int = 0,
                chain_offset: int = 0, seed: int = 2024, stream: int = 0,
                ansatz: str = 'fully_connected', kernel_size: int = 0, size_x: int = 0,
-               size_y: int = 0, adjacency=None):
+               size_y: int = 0, adjacency=None, lin_tables=None):
     """Dense ansatz types: num_layers / layer_size = num_fc_layers / fc_layer_size.  Convolutional
     ones ('conv_2d', 'res_net_2d'): num_layers = num_conv_layers or num_resnet_blocks, layer_size =
     num_conv_filters, plus kernel_size and the lattice size_x x size_y (= n_sites).  'gnn':
     num_layers = num_conv_layers, layer_size = num_conv_filters and `adjacency`, the [n_sites][k]
     int table (or its int32 bytes, as GraphConvNetwork._engine_spec carries it); kernel_size may
-    be left 0 (k is read off the table)."""
+    be left 0 (k is read off the table).  'ed_vector': layer_size = the vector's length and
+    `lin_tables`, the pair (top, bot) of int tables [2^(n_sites/2)] (or their concatenated int32
+    bytes, as FullVector._engine_spec carries them); without them the ctx refuses every forward
+    entry until set_lin_tables is called."""
     self._lib = _hip.load()
     self._ctx = C.c_void_p()
     adj = None
@@ -90,6 +93,15 @@ class VmcEngine:
       self._ctx = C.c_void_p()
       self._raise(rc, msg)
     _LIVE_ENGINES.add(self)
+    if ansatz == 'ed_vector' and lin_tables is not None:
+      if isinstance(lin_tables, (bytes, bytearray)):
+        both = np.frombuffer(lin_tables, dtype=np.int32)
+        lin_tables = (both[:both.size // 2], both[both.size // 2:])
+      try:
+        self.set_lin_tables(*lin_tables)
+      except Exception:
+        self.close()
+        raise
     if adj is not None:       # the graph is part of the ansatz: set before anything can run on the ctx
       rc = self._lib.vmc_set_adjacency(self._ctx, adj.shape[0], adj.shape[1], _iptr(adj))
       if rc != _hip.VMC_OK:
@@ -151,6 +163,14 @@ class VmcEngine:
     jz = np.ascontiguousarray(np.broadcast_to(np.asarray(j_z, np.float32), (nb,)))
     self._check(self._lib.vmc_set_bonds(self._ctx, nb, _iptr(ij), _fptr(jx), _fptr(jz)))
     self.n_bonds = nb
+
+  def set_lin_tables(self, top, bot):
+    """The Lin tables of an 'ed_vector' ctx (vmc_set_lin_tables validates them against the vector's length)."""
+    top = np.ascontiguousarray(top, dtype=np.int32).ravel()
+    bot = np.ascontiguousarray(bot, dtype=np.int32).ravel()
+    if top.size != bot.size:
+      raise ValueError('ed_vector: the two Lin tables differ in length (%d, %d)' % (top.size, bot.size))
+    self._check(self._lib.vmc_set_lin_tables(self._ctx, top.size, _iptr(top), _iptr(bot)))
 
   def set_params(self, theta: np.ndarray, which: int = _hip.VMC_PSI):
     theta = np.ascontiguousarray(theta, dtype=np.float32).ravel()

@@ -831,6 +831,102 @@ class FullyConnectedNNB(FullyConnectedNetwork):
     return cls(**params)
 
 
+def check_lin_tables(num_sites, top_lin_table, bot_lin_table, length):
+  """The two Lin tables of FullVector as int32 arrays, or ValueError naming the offender: num_sites odd, a table that
+  is not a 1-D integer array of 2^(num_sites/2) entries, an Sz = 0 configuration whose index top[t] + bot[b] leaves
+  [0, length).  A configuration pairs an upper half-word of N/2 - k set bits with a lower one of k, so per popcount
+  class the smallest and the largest entry decide (plan.hpp plan_edvec_check_tables)."""
+  num_sites = int(num_sites)
+  if num_sites < 2 or num_sites % 2:
+    raise ValueError('ed_vector: num_sites must be even (the Lin tables address the Sz = 0 sector), got %d' % num_sites)
+  h = num_sites // 2
+  tables = []
+  for label, table in (('top_lin_table', top_lin_table), ('bot_lin_table', bot_lin_table)):
+    table = np.asarray(table)
+    if table.ndim != 1 or table.size != 1 << h:
+      raise ValueError('ed_vector: %s must be a 1-D table of 2^(num_sites/2) = %d entries, got shape %s'
+                       % (label, 1 << h, table.shape))
+    if not np.issubdtype(table.dtype, np.integer):
+      raise ValueError('ed_vector: %s must hold integers, got %s' % (label, table.dtype))
+    if table.min() < -2 ** 31 or table.max() >= 2 ** 31:
+      raise ValueError('ed_vector: %s has entries beyond 32 bits' % label)
+    tables.append(np.ascontiguousarray(table, dtype=np.int32))
+  top, bot = tables
+  halves = np.arange(1 << h)
+  pop = np.zeros(1 << h, np.int64)
+  for i in range(h):
+    pop += (halves >> i) & 1
+  for k in range(h + 1):
+    t, b = top[pop == h - k].astype(np.int64), bot[pop == k].astype(np.int64)
+    lo, hi = t.min() + b.min(), t.max() + b.max()
+    if lo < 0 or hi >= length:
+      raise ValueError('ed_vector: an Sz = 0 configuration with %d up spins in its lower half has index %d outside '
+                       '[0, %d)' % (k, lo if lo < 0 else hi, length))
+  return top, bot
+
+
+class FullVector(FullyConnectedNetwork):
+  """State vector addressed through Lin's two tables (wavefunctions.py:1001-1080): with bot = sum_{i < N/2} [s_i > 0] 2^i
+  and top = sum_{i < N/2} [s_{N/2+i} > 0] 2^i, psi(x) = ed_vector[top_lin_table[top] + bot_lin_table[bot]] -- the entry
+  itself, signed and possibly zero, the only variable (full_vector/ed_vector [len]).  No exponent shift:
+  normalize_batch / update_norm return None.  An exact (or Lanczos) eigenstate loaded here has E_loc = E0 on every
+  configuration; trained, it bounds what any ansatz can reach on the cluster.  The kernels (csrc/edvec.hip) are
+  dependent gathers and a collision-safe scatter."""
+  _ansatz = 'ed_vector'
+  MAX_SITES = 28                      # plan.hpp PLAN_EDVEC_MAX_SITES
+
+  def __init__(self, num_sites: int, top_lin_table, bot_lin_table, initial_vector, name: str = 'full_vector'):
+    num_sites = int(num_sites)
+    initial_vector = np.asarray(initial_vector)
+    if initial_vector.ndim != 1 or initial_vector.size < 1:
+      raise ValueError('ed_vector: the vector must be 1-D and not empty, got shape %s' % (initial_vector.shape,))
+    top, bot = check_lin_tables(num_sites, top_lin_table, bot_lin_table, initial_vector.size)
+    if num_sites > self.MAX_SITES:
+      raise NotImplementedError('ed_vector: num_sites > %d is not supported by the HIP kernels' % self.MAX_SITES)
+    super(FullVector, self).__init__(num_layers=1, layer_size=int(initial_vector.size), name=name)
+    self._exp_norm_shift = None          # no add_exp_normalization: psi is the entry itself
+    self._num_sites = num_sites
+    self._top_lin_table, self._bot_lin_table = top, bot
+    self._initial_vector = np.ascontiguousarray(initial_vector, dtype=np.float32)
+
+  def _shapes(self):
+    if self._n_sites is not None and self._n_sites != self._num_sites:
+      raise ValueError('Input tensor has wrong shape.')
+    return ['%s/ed_vector' % self._unique_name], [(self._initial_vector.size,)]
+
+  def initialize(self, seed=None):
+    """The variable's initializer is the vector the ansatz was built from."""
+    self._set_theta(self._initial_vector.copy())
+
+  def _maybe_initialize(self):
+    if self._n_sites is not None and self._get_theta(allow_none=True) is None:
+      self.initialize()
+
+  def _engine_spec(self):
+    # the tables as bytes: hashable and compared by value, so psi and its dc_ copy share one ctx
+    return dict(ansatz=self._ansatz, num_layers=1, layer_size=int(self._initial_vector.size), nonlinearity='relu',
+                output_activation='exp', lin_tables=self._top_lin_table.tobytes() + self._bot_lin_table.tobytes())
+
+  def _bind(self, configs_var):
+    if configs_var.shape[1] != self._num_sites:
+      raise ValueError('Input tensor has wrong shape.')
+    return super(FullVector, self)._bind(configs_var)
+
+  @classmethod
+  def from_hparams(cls, hparams, name: str = '') -> 'Wavefunction':
+    """wavefunctions.py:1062-1080: the three files are read from hparams.checkpoint_dir."""
+    path = lambda f: os.path.join(hparams.checkpoint_dir, f)
+    params = {
+        'num_sites': hparams.num_sites,
+        'top_lin_table': np.atleast_1d(np.genfromtxt(path(hparams.top_lin_table_file), dtype=int)),
+        'bot_lin_table': np.atleast_1d(np.genfromtxt(path(hparams.bot_lin_table_file), dtype=int)),
+        'initial_vector': np.atleast_1d(np.genfromtxt(path(hparams.ed_vector_file), dtype=np.float32)),
+    }
+    if name:
+      params['name'] = name
+    return cls(**params)
+
+
 class AmplitudeTensor(session_lib.Tensor):
   """psi = wavefunction(inputs); evaluates to a float32 array [rows]."""
 
@@ -855,7 +951,7 @@ class _OutOfScope(Wavefunction):
   def from_hparams(cls, hparams, name: str = ''):
     raise NotImplementedError(
         "wavefunction_type '%s' is outside the MI355X hot path (SURVEY.md 2); only "
-        "'fully_connected', 'rbm', 'conv_1d', 'conv_2d', 'res_net_1d', 'res_net_2d', 'gnn', 'pbdg' and 'fully_connected_nnb' have "
+        "'fully_connected', 'rbm', 'conv_1d', 'conv_2d', 'res_net_1d', 'res_net_2d', 'gnn', 'pbdg', 'fully_connected_nnb' and 'ed_vector' have "
         "HIP kernels" % cls._kind)
 
 
@@ -883,6 +979,6 @@ WAVEFUNCTION_TYPES = {
     'fully_connected_nnb': FullyConnectedNNB,
     'res_net_1d': ResNet1D,
     'res_net_2d': ResNet2D,
-    'ed_vector': _stub('ed_vector'),
+    'ed_vector': FullVector,
     'gnn': GraphConvNetwork,
 }

@@ -52,6 +52,18 @@
  * layer_size at most 512, num_layers at most 16 and batch_size * N*N at most 2^30
  * (VMC_ERR_UNSUPPORTED); configurations must have as many up as down spins (VMC_ERR_INVALID).
  * Stochastic reconfiguration is not available (vmc_sr_reserve: VMC_ERR_UNSUPPORTED).
+ * FullVector ('ed_vector', VMC_ANSATZ_ED_VECTOR, wavefunctions.py:1001-1080): one trainable state vector
+ * full_vector/ed_vector [len], theta[k] = entry k; vmc_desc.layer_size carries len, P = len; num_layers
+ * and the activations are ignored.  The up spins of a configuration set bits: bot = sum_{i < N/2}
+ * [s_i > 0] 2^i, top = sum_{i < N/2} [s_{N/2+i} > 0] 2^i, idx = top_table[top] + bot_table[bot] (Lin's
+ * two tables, vmc_set_lin_tables), psi = theta[idx]: the gathered entry bit for bit, signed, possibly 0;
+ * logit = ln|psi| (-inf at psi = 0).  Two configurations the tables send to one entry share a
+ * parameter; O_k(b) = delta(k, idx_b) / psi_b, and chains with psi_b = 0 add nothing to the gradient
+ * sums.  There is no exponent shift (vmc_set_shift and vmc_update_norm leave it at 0 and return VMC_OK).
+ * n_sites must be even (VMC_ERR_INVALID) and at most 28 (VMC_ERR_UNSUPPORTED: the largest size the
+ * kernels are tested at -- C(28,14) = 40,116,600 entries; the 32-bit index itself reaches N = 32),
+ * 1 <= len < 2^31; configurations must have as many up as down spins (VMC_ERR_INVALID).  Stochastic
+ * reconfiguration is not available (vmc_sr_reserve: VMC_ERR_UNSUPPORTED).
  */
 #ifndef CGSVMC_H_
 #define CGSVMC_H_
@@ -82,7 +94,7 @@ enum { VMC_MODE_ENERGY_GRADIENT = 0, VMC_MODE_LOG_OVERLAP_ITSWO = 1 };
 /* wavefunctions.WAVEFUNCTION_TYPES with kernels (wavefunctions.py:1157-1170) */
 enum { VMC_ANSATZ_FULLY_CONNECTED = 0, VMC_ANSATZ_RBM = 1, VMC_ANSATZ_CONV_2D = 2,
        VMC_ANSATZ_RES_NET_2D = 3, VMC_ANSATZ_CONV_1D = 4, VMC_ANSATZ_RES_NET_1D = 5,
-       VMC_ANSATZ_GNN = 6, VMC_ANSATZ_PBDG = 7, VMC_ANSATZ_NNB = 9 /* 8 is unassigned */ };
+       VMC_ANSATZ_GNN = 6, VMC_ANSATZ_PBDG = 7, VMC_ANSATZ_NNB = 9 /* 8 is unassigned */, VMC_ANSATZ_ED_VECTOR = 10 };
 
 /* layers.NONLINEARITIES ids (layers.py:13-21).  Every id is accepted as hidden and as output
  * activation of every ansatz type with kernels. */
@@ -145,6 +157,13 @@ int vmc_set_bonds(vmc_ctx* ctx, int32_t n_bonds, const int32_t* ij /*[n_bonds][2
  * gradient or SR entry of a gnn ctx returns VMC_ERR_INVALID until the table is set; other ansatz
  * types refuse the call (VMC_ERR_INVALID). */
 int vmc_set_adjacency(vmc_ctx* ctx, int32_t n_sites, int32_t k, const int32_t* adj /*[n_sites][k]*/);
+/* The ed_vector ansatz's Lin tables (FullVector, wavefunctions.py:1001-1080): top[t] + bot[b] is the
+ * entry of the configuration with upper half-word t and lower half-word b.  n_half must be
+ * 2^(num_sites / 2), and every configuration with as many up as down spins must land in [0, len)
+ * (VMC_ERR_INVALID otherwise; two configurations may share an entry).  Every forward, sampler,
+ * local-energy, gradient or evaluation entry of an ed_vector ctx returns VMC_ERR_INVALID until the
+ * tables are set; other ansatz types refuse the call (VMC_ERR_INVALID). */
+int vmc_set_lin_tables(vmc_ctx* ctx, int32_t n_half /*2^(N/2)*/, const int32_t* top, const int32_t* bot);
 /* Variable assignment / read-back (tf.train.Saver restore/save, run_training.py:134-146;
  * module_transfer_ops, wavefunctions.py:300-325). theta has P floats. */
 int vmc_set_params(vmc_ctx* ctx, int which, const float* theta);
@@ -381,7 +400,8 @@ int vmc_last_connected_rows(vmc_ctx* ctx, int64_t* rows);
  * (CGS_VMC_SPLIT_BF16=1: fully_connected, relu, 193 .. 256 units; fp32 results from the bf16 matrix cores,
  * cgs_vmc_amd/csrc/tail_split.hip -- never the headline configuration); 5: the split sampler as well; 6: the
  * general convolution path; 7: the projected BCS determinant kernels of pbdg (cgs_vmc_amd/csrc/pbdg.hip); 8: neural-network backflow -- the
- * general dense path into the determinant rows of cgs_vmc_amd/csrc/nnb.hip. */
+ * general dense path into the determinant rows of cgs_vmc_amd/csrc/nnb.hip; 9: the Lin-table state vector
+ * of ed_vector (cgs_vmc_amd/csrc/edvec.hip). */
 int vmc_debug_kernel_path(vmc_ctx* ctx, int32_t* path);
 /* Chains per workgroup of the fused dense sampler: 16 (k_sweep16, sweep16.hpp) or 8 (k_sweep8, sweep8.hip: chosen by
  * vmc_create when sixteen-chain tiles would occupy at most half of the CUs -- BASELINE configs 2 and 5 -- or by

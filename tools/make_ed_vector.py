@@ -1,0 +1,138 @@
+#!/usr/bin/env python3
+"""Writes what --wavefunction_type=ed_vector reads: top_lin_table.txt, bot_lin_table.txt, ed_vector.txt and a matching
+J.txt in a directory, plus hparams.pbtxt and a first checkpoint (model_prior_0_epochs.npz) so that
+`python -m cgs_vmc_amd.run_energy_evaluation --checkpoint_dir DIR --heisenberg_jx JX` evaluates the state as it stands.
+
+  python tools/make_ed_vector.py DIR --lattice chain --size 16 [--jx 1.0] [--jz 1.0]
+  python tools/make_ed_vector.py DIR --lattice square --size 4 4
+  python tools/make_ed_vector.py DIR --lattice triangular --size 4 4
+  python tools/make_ed_vector.py DIR --lattice chain --size 28 --random [--seed 0]
+
+The vector is the ground state of sum_<ij> jz Sz_i Sz_j + jx/2 (S+_i S-_j + h.c.) in the Sz = 0 sector by scipy's
+eigsh (a few thousand to a few million entries: up to about 24 sites), or with --random a positive random vector of
+unit norm for sizes exact diagonalisation does not reach.  Lin's tables enumerate the sector in ascending (top, bot)
+order: a configuration's up spins set bits, bot = the lower N/2 sites, top = the upper N/2, index = top_table[top] +
+bot_table[bot].  CPU only."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def popcounts(h):
+  w = np.arange(1 << h)
+  return sum((w >> i) & 1 for i in range(h))
+
+
+def lin_tables(n):
+  h = n // 2
+  pop = popcounts(h)
+  cls = np.array([np.sum(pop == k) for k in range(h + 1)], np.int64)
+  per_top = cls[h - pop]
+  top = np.concatenate([[0], np.cumsum(per_top)])[:-1]
+  bot = np.zeros(1 << h, np.int64)
+  for k in range(h + 1):
+    bot[pop == k] = np.arange(cls[k])
+  return top, bot, int(per_top.sum())
+
+
+def sector_words(n):
+  """The sector's configurations as words (bot in the low n/2 bits), in index order."""
+  h = n // 2
+  pop = popcounts(h)
+  by_pop = [np.flatnonzero(pop == k) for k in range(h + 1)]
+  return np.concatenate([(t << h) | by_pop[h - pop[t]] for t in range(1 << h)])
+
+
+def bonds_of(lattice, size):
+  from cgs_vmc_amd import lattice as lat
+  if lattice == 'chain':
+    return lat.chain_bonds(size[0])
+  lx, ly = size
+  if lattice == 'square':
+    return sorted({(min(i, j), max(i, j)) for i, j in lat.torus_bonds(lx, ly) if i != j})
+  bonds = set()
+  for a1 in range(lx):
+    for a2 in range(ly):
+      i = a1 * ly + a2
+      for d1, d2 in ((1, 0), (0, 1), (1, -1)):
+        j = ((a1 + d1) % lx) * ly + (a2 + d2) % ly
+        if i != j:
+          bonds.add((min(i, j), max(i, j)))
+  return sorted(bonds)
+
+
+def ground_state(n, bonds, jx, jz):
+  import scipy.sparse as sp
+  import scipy.sparse.linalg as spla
+  top, bot, length = lin_tables(n)
+  words = sector_words(n)
+  h = n // 2
+  lookup = lambda w: top[w >> h] + bot[w & ((1 << h) - 1)]
+  diag = np.zeros(length)
+  rows, cols = [], []
+  for i, j in bonds:
+    si, sj = (words >> i) & 1, (words >> j) & 1
+    diag += 0.25 * jz * np.where(si == sj, 1.0, -1.0)
+    anti = np.flatnonzero(si != sj)
+    rows.append(anti)
+    cols.append(lookup(words[anti] ^ (1 << i) ^ (1 << j)))
+  rows, cols = np.concatenate(rows), np.concatenate(cols)
+  hmat = sp.csr_matrix((np.full(len(rows), 0.5 * jx), (rows, cols)), shape=(length, length)) + sp.diags(diag)
+  w, v = spla.eigsh(hmat, k=1, which='SA')
+  vec = v[:, 0]
+  return float(w[0]), vec * np.sign(vec[np.argmax(np.abs(vec))])
+
+
+def main(argv=None):
+  ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+  ap.add_argument('directory')
+  ap.add_argument('--lattice', choices=('chain', 'square', 'triangular'), default='chain')
+  ap.add_argument('--size', type=int, nargs='+', required=True, help='sites of the chain, or the two sides of the torus')
+  ap.add_argument('--jx', type=float, default=1.0)
+  ap.add_argument('--jz', type=float, default=1.0)
+  ap.add_argument('--random', action='store_true', help='a positive random vector instead of the ground state')
+  ap.add_argument('--seed', type=int, default=0)
+  args = ap.parse_args(argv)
+  if len(args.size) != (1 if args.lattice == 'chain' else 2):
+    ap.error('--size takes one number for a chain and two for a torus')
+  n = int(np.prod(args.size))
+  if n < 2 or n % 2:
+    ap.error('the number of sites must be even')
+  if args.jz != 1.0 and not args.random:
+    print('note: the drivers run HeisenbergHamiltonian with jz = 1; this state belongs to jz = %g' % args.jz)
+  bonds = bonds_of(args.lattice, args.size)
+  top, bot, length = lin_tables(n)
+  if args.random:
+    vec = np.random.default_rng(args.seed).uniform(0.5, 1.5, length)
+    vec /= np.linalg.norm(vec)
+    e0 = None
+  else:
+    e0, vec = ground_state(n, bonds, args.jx, args.jz)
+  from cgs_vmc_amd import lattice as lat, utils
+  os.makedirs(args.directory, exist_ok=True)
+  np.savetxt(os.path.join(args.directory, 'top_lin_table.txt'), top, fmt='%d')
+  np.savetxt(os.path.join(args.directory, 'bot_lin_table.txt'), bot, fmt='%d')
+  np.savetxt(os.path.join(args.directory, 'ed_vector.txt'), vec.astype(np.float32), fmt='%.9g')
+  lat.write_bonds(args.directory, bonds)
+  hp = utils.create_hparams()
+  for field, value in (('checkpoint_dir', args.directory), ('num_sites', n), ('wavefunction_type', 'ed_vector'),
+                       ('top_lin_table_file', 'top_lin_table.txt'), ('bot_lin_table_file', 'bot_lin_table.txt'),
+                       ('ed_vector_file', 'ed_vector.txt')):
+    hp.set_hparam(field, value)
+  with open(os.path.join(args.directory, 'hparams.pbtxt'), 'w') as out:
+    out.write(str(hp.to_proto()))
+  np.savez(os.path.join(args.directory, 'model_prior_0_epochs.npz'), **{'full_vector/ed_vector': vec.astype(np.float32)})
+  with open(os.path.join(args.directory, 'checkpoint'), 'w') as out:
+    out.write('model_checkpoint_path: "model_prior_0_epochs"\n')
+  print('%d sites, %d bonds, %d entries%s -> %s' % (n, len(bonds), length,
+                                                    '' if e0 is None else ', E0 = %.10f' % e0, args.directory))
+  return e0
+
+
+if __name__ == '__main__':
+  main()
