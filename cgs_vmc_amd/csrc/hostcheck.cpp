@@ -695,7 +695,9 @@ static void nnb_grid() {
   vmc_desc d = dense_desc(8, 16, 64, 2, 32, VMC_ACT_RELU, VMC_ACT_EXP);        // id 8 stays unassigned
   DescPlan p;
   CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_UNSUPPORTED);
-  d = dense_desc(11, 16, 64, 2, 32, VMC_ACT_RELU, VMC_ACT_EXP);                 // the first id past ed_vector
+  d = dense_desc(11, 16, 64, 2, 32, VMC_ACT_RELU, VMC_ACT_EXP);                 // the product: vmc_create_product only
+  CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_INVALID);
+  d = dense_desc(12, 16, 64, 2, 32, VMC_ACT_RELU, VMC_ACT_EXP);                 // the first id past the product
   CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_UNSUPPORTED);
 }
 
@@ -758,8 +760,35 @@ static void edvec_grid() {
   CHECK(plan_edvec_sweep_threads(4096, 256) == 64 && plan_edvec_sweep_threads(65536, 256) == 256);
 }
 
+// product ctx (plan_prod_*): which factors are taken, the accumulator size, grids that cover every chain / element,
+// and vmc_create refusing the id
+static void prod_grid() {
+  char msg[256];
+  for (int ansatz = 0; ansatz <= VMC_ANSATZ_PRODUCT; ++ansatz)
+    for (int oact = 0; oact <= 6; ++oact) {
+      const int rc = plan_prod_child_check(ansatz, oact, false, msg, sizeof(msg));
+      const bool dense = ansatz == VMC_ANSATZ_FULLY_CONNECTED || ansatz == VMC_ANSATZ_RBM;
+      const bool taken = ansatz == VMC_ANSATZ_PBDG || ansatz == VMC_ANSATZ_ED_VECTOR || (dense && oact == VMC_ACT_EXP);
+      CHECK(rc == (taken ? VMC_OK : VMC_ERR_UNSUPPORTED));
+      CHECK(plan_prod_child_check(ansatz, oact, true, msg, sizeof(msg)) == VMC_ERR_UNSUPPORTED);
+    }
+  CHECK(plan_prod_acc_floats(256, 577) == 2 * 833 + 8);
+  for (long long B : {1LL, 3LL, 4LL, 40LL, 64LL, 4097LL}) {
+    CHECK((long long)plan_prod_chain_grid(B) * PLAN_PROD_CHAINS_PER_WG >= B);
+    CHECK(((long long)plan_prod_chain_grid(B) - 1) * PLAN_PROD_CHAINS_PER_WG < B);
+    CHECK((long long)plan_prod_elem_grid(B * 16) * 256 >= B * 16);
+  }
+  vmc_desc d;
+  memset(&d, 0, sizeof(d));
+  d.n_sites = 16; d.batch_size = 64; d.num_layers = 1; d.layer_size = 32; d.output_activation = VMC_ACT_EXP;
+  d.ansatz = VMC_ANSATZ_PRODUCT;
+  DescPlan p;
+  CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_INVALID);
+}
+
 int main() {
   check_block_maps();
+  prod_grid();
   edvec_grid();
   nnb_grid();
   pbdg_grid();

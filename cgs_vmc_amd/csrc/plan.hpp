@@ -611,6 +611,30 @@ inline int plan_edvec_check_tables(int N, int n_half, const int32_t* top, const 
   return VMC_OK;
 }
 
+// ------------------------------------------------------------------------------- product ctx (vmc_api_prod.hip, prod.hip)
+// psi = psi_a psi_b over one set of chains: theta = [a | b], accumulators [g1_a g1_b | g2_a g2_b | 8 scalars].
+#define PLAN_PROD_CHAINS_PER_WG 4     // one wave per chain (k_prod_accept, the arithmetic of k_wide_propose)
+#define PLAN_PROD_FOLD_THREADS 1024   // the single workgroup that folds the chains' acceptance counts in a fixed order
+inline long long plan_prod_acc_floats(long long Pa, long long Pb) { return 2 * (Pa + Pb) + 8; }
+inline unsigned plan_prod_chain_grid(long long B) { return (unsigned)((B + PLAN_PROD_CHAINS_PER_WG - 1) / PLAN_PROD_CHAINS_PER_WG); }
+inline unsigned plan_prod_elem_grid(long long n) { return (unsigned)((n + 255) / 256); }    // 256 threads, one element each
+// Which ctx may be a factor: fully_connected / rbm with the exp output (every width), pbdg, ed_vector.  The convolutional
+// types, gnn and fully_connected_nnb keep their gradient sums inside block loops of their own and are refused.
+inline int plan_prod_child_check(int ansatz, int output_activation, bool is_product, char* msg, size_t msg_len) {
+  if (is_product) { snprintf(msg, msg_len, "prod: a product ctx cannot be a factor of another product"); return VMC_ERR_UNSUPPORTED; }
+  if (ansatz == VMC_ANSATZ_PBDG || ansatz == VMC_ANSATZ_ED_VECTOR) { if (msg_len) msg[0] = 0; return VMC_OK; }
+  if (ansatz == VMC_ANSATZ_FULLY_CONNECTED || ansatz == VMC_ANSATZ_RBM) {
+    if (output_activation != 1 /* VMC_ACT_EXP */) {
+      snprintf(msg, msg_len, "prod: a dense factor needs the exp output activation (a positive amplitude with a shift)");
+      return VMC_ERR_UNSUPPORTED;
+    }
+    if (msg_len) msg[0] = 0;
+    return VMC_OK;
+  }
+  snprintf(msg, msg_len, "prod: factors are fully_connected, rbm, pbdg or ed_vector ctxs (the convolutional types, gnn and fully_connected_nnb are not taken)");
+  return VMC_ERR_UNSUPPORTED;
+}
+
 // ------------------------------------------------------------------------------- vmc_create
 struct DescPlan {
   int rbm, conv, resnet, one_d;
@@ -634,6 +658,8 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
                      int conv_general_pref = 0) {
   memset(out, 0, sizeof(*out));
 #define PLAN_FAIL(code, text) do { snprintf(msg, msg_len, "%s", text); return code; } while (0)
+  if (d->ansatz == VMC_ANSATZ_PRODUCT)
+    PLAN_FAIL(VMC_ERR_INVALID, "a product ctx is made by vmc_create_product from two ctxs, not by vmc_create");
   if (d->ansatz < VMC_ANSATZ_FULLY_CONNECTED ||
       (d->ansatz > VMC_ANSATZ_PBDG && d->ansatz != VMC_ANSATZ_NNB && d->ansatz != VMC_ANSATZ_ED_VECTOR))
     PLAN_FAIL(VMC_ERR_UNSUPPORTED, "only the fully_connected, rbm, conv_1d/2d, res_net_1d/2d, gnn, pbdg, fully_connected_nnb and ed_vector ansatz types have HIP kernels");

@@ -250,6 +250,7 @@ void invalidate_configs(vmc_ctx* c) {
   c->ps[0].cache_valid = c->ps[1].cache_valid = false;
   c->list_valid = false;
   c->cnt_valid = false;
+  if (c->prod) prod_chains_changed(c);
 }
 
 int ensure_list(vmc_ctx* c) {
@@ -267,6 +268,7 @@ int ensure_list(vmc_ctx* c) {
 // dependent launch less per step); *deferred tells whether that is still owed
 int local_energy_device(vmc_ctx* c, int which, bool defer_reduce, bool* deferred) {
   if (deferred) *deferred = false;
+  if (c->prod) return prod_local_energy(c, which);
   PROPAGATE(ensure_cache(c, which));
   PROPAGATE(ensure_list(c));
   ParamSet& p = c->ps[which];
@@ -360,7 +362,7 @@ int pbdg_check_sz(vmc_ctx* c, const float* configs, long long n_rows) {
     for (int i = 0; i < c->N; ++i) m += configs[r * c->N + i];
     if (m != 0.0) {
       char msg[160];
-      snprintf(msg, sizeof(msg), "%s: configuration %lld has magnetisation %g; the ansatz needs as many up as down spins", c->edvec ? "ed_vector" : c->nnb ? "fully_connected_nnb" : "pbdg", r, m);
+      snprintf(msg, sizeof(msg), "%s: configuration %lld has magnetisation %g; the ansatz needs as many up as down spins", c->prod ? "prod (a signed factor)" : c->edvec ? "ed_vector" : c->nnb ? "fully_connected_nnb" : "pbdg", r, m);
       return fail(c, VMC_ERR_INVALID, msg);
     }
   }
@@ -536,6 +538,8 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
     CA(hipMemsetAsync(c->dact_all, 0, L * B * Hp * sizeof(float), c->stream));
     CA(hipMemsetAsync(c->dact_alt, 0, L * B * Hp * sizeof(float), c->stream));
   }
+  // (vmc_create_product re-sizes every member sized by P -- theta of both sets, acc, adam_m, adam_v, grad_tmp -- to
+  // P_a + P_b: a new P-sized member goes into its list in vmc_api_prod.hip as well)
   CA(dalloc(&c->acc, 2 * P + 8)); CA(dalloc(&c->adam_m, P)); CA(dalloc(&c->adam_v, P));
   CA(dalloc(&c->grad_tmp, P));
   CA(hipMemsetAsync(c->acc, 0, (2 * P + 8) * sizeof(float), c->stream));
@@ -656,6 +660,8 @@ void vmc_destroy(vmc_ctx* c) {
   DeviceGuard device_guard_(c->d.device);
   if (c->sweep_stream) hipStreamSynchronize(c->sweep_stream);
   hipStreamSynchronize(c->stream);
+  if (c->prod) prod_release(c);            // the factors are borrowed: they stay alive, free again
+  if (c->owner) prod_child_destroyed(c);   // (a factor destroyed before its product: the product refuses from now on)
   drain_timings(c);
   if (c->sweep_stream) hipStreamDestroy(c->sweep_stream);
   for (hipStream_t q : c->cg_grp_stream) if (q) { hipStreamSynchronize(q); hipStreamDestroy(q); }
@@ -730,6 +736,7 @@ int vmc_set_bonds(vmc_ctx* c, int32_t n_bonds, const int32_t* ij, const float* j
   HIPCHK(c, hipMemcpy(c->quarter_jz, qz.data(), n_bonds * sizeof(float), hipMemcpyHostToDevice));
   c->list_valid = false;
   c->cnt_valid = false;
+  if (c->prod) PROPAGATE(prod_set_bonds(c, n_bonds, ij, j_x, j_z));
   return VMC_OK;
 }
 
@@ -782,12 +789,15 @@ int vmc_set_params(vmc_ctx* c, int which, const float* theta) {
   c->ps[which].has_params = true;
   c->ps[which].packed_valid = c->ps[which].cache_valid = false;
   if (which == VMC_PSI) c->acts_valid = false;
+  if (c->prod) PROPAGATE(prod_scatter_params(c, which));      // theta = a's floats followed by b's
+  if (c->owner) prod_child_params_changed(c, which);
   return VMC_OK;
 }
 
 int vmc_get_params(vmc_ctx* c, int which, float* theta) {
   ENTER(c);
   if ((which != 0 && which != 1) || !theta) return fail(c, VMC_ERR_INVALID, "bad arguments");
+  if (c->prod) PROPAGATE(prod_gather_params(c, which));
   if (!c->ps[which].has_params) return fail(c, VMC_ERR_STATE, "parameters not set");
   HIPCHK(c, hipMemcpyAsync(theta, c->ps[which].theta, c->P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -796,6 +806,8 @@ int vmc_get_params(vmc_ctx* c, int which, float* theta) {
 
 int vmc_transfer_params(vmc_ctx* c) {
   ENTER(c);
+  if (c->prod) return prod_transfer_params(c);
+  if (c->owner) prod_child_params_changed(c, VMC_OMEGA);
   if (!c->ps[0].has_params) return fail(c, VMC_ERR_STATE, "parameters not set");
   HIPCHK(c, hipMemcpyAsync(c->ps[1].theta, c->ps[0].theta, c->P * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   c->ps[1].has_params = true;
@@ -805,6 +817,7 @@ int vmc_transfer_params(vmc_ctx* c) {
 
 int vmc_set_configs(vmc_ctx* c, const float* configs) {
   ENTER(c);
+  REFUSE_COMPOSED(c);
   if (!configs) return fail(c, VMC_ERR_INVALID, "null configs");
   PROPAGATE(pbdg_check_sz(c, configs, c->B));
   const long long n = (long long)c->B * c->N;
@@ -833,6 +846,7 @@ int vmc_get_configs(vmc_ctx* c, float* configs) {
 int vmc_set_shift(vmc_ctx* c, int which, float shift) {
   CHECK_CTX(c);
   if (which != 0 && which != 1) return fail(c, VMC_ERR_INVALID, "bad which");
+  if (c->prod) return fail(c, VMC_ERR_INVALID, "prod: the product has no exponent shift of its own (set the factors')");
   if (!c->nnb && !c->edvec) c->ps[which].shift = shift;     // (neural-network backflow, ed_vector: no exponent shift, it stays 0)
   return VMC_OK;
 }
@@ -846,6 +860,8 @@ int vmc_get_shift(vmc_ctx* c, int which, float* shift) {
 
 int vmc_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, float* logit, float* psi) {
   ENTER(c);
+  if (c->prod) return prod_amplitude(c, which, configs, n_rows, logit, psi);
+  if (!configs) REFUSE_COMPOSED(c);
   if (which != 0 && which != 1) return fail(c, VMC_ERR_INVALID, "bad which");
   if (n_rows < 0) return fail(c, VMC_ERR_INVALID, "n_rows < 0");
   std::vector<float> host((size_t)n_rows), hsign(c->sgn ? (size_t)n_rows : 0);
@@ -916,6 +932,7 @@ int vmc_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, f
 
 int vmc_local_energy(vmc_ctx* c, int which, float* eloc, double* mean) {
   ENTER(c);
+  REFUSE_COMPOSED(c);
   if (which != 0 && which != 1) return fail(c, VMC_ERR_INVALID, "bad which");
   PROPAGATE(local_energy_device(c, which));
   if (mean) HIPCHK(c, launch_sum(c->stream, c->ps[which].eloc, c->B, c->d_sum));
@@ -932,6 +949,7 @@ int vmc_local_energy(vmc_ctx* c, int which, float* eloc, double* mean) {
 
 int vmc_local_energy_terms(vmc_ctx* c, int which, float* diag, float* offdiag_over_psi) {
   ENTER(c);
+  REFUSE_COMPOSED(c);
   if (which != 0 && which != 1) return fail(c, VMC_ERR_INVALID, "bad which");
   PROPAGATE(local_energy_device(c, which));
   if (diag) HIPCHK(c, hipMemcpyAsync(diag, c->diag, c->B * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -943,12 +961,13 @@ int vmc_local_energy_terms(vmc_ctx* c, int which, float* diag, float* offdiag_ov
 int vmc_debug_kernel_path(vmc_ctx* c, int32_t* path) {
   CHECK_CTX(c);
   if (!path) return fail(c, VMC_ERR_INVALID, "null");
-  *path = c->edvec ? 9 : c->nnb ? 8 : c->pbdg ? 7 : c->conv ? (c->conv_general ? 6 : 3) : (c->wide ? (c->wide_fast ? 1 : 2) : (c->split ? (c->split_sweep ? 5 : 4) : 0));
+  *path = c->prod ? 10 : c->edvec ? 9 : c->nnb ? 8 : c->pbdg ? 7 : c->conv ? (c->conv_general ? 6 : 3) : (c->wide ? (c->wide_fast ? 1 : 2) : (c->split ? (c->split_sweep ? 5 : 4) : 0));
   return VMC_OK;
 }
 
 int vmc_debug_sweep_tile(vmc_ctx* c, int32_t set, int32_t* chains) {
   ENTER(c);
+  REFUSE_PRODUCT(c, "vmc_debug_sweep_tile");
   if (set != 0 && set != 8 && set != 16) return fail(c, VMC_ERR_INVALID, "sweep tile: 0 (query), 8 or 16");
   if (set == 8 && !c->sweep8_ok) return fail(c, VMC_ERR_UNSUPPORTED, "no eight-chain sampler for this shape (fully_connected + relu, 128 or 256 padded units, n_sites <= units)");
   if (set) { PROPAGATE(join_sweep(c)); c->sweep_tile = set; }

@@ -132,13 +132,14 @@ int vmc_accumulators_devptr(vmc_ctx* c, void** dev_ptr, int64_t* n_floats) {
 // back by the world size so that sharded and unsharded gradients agree (cgs_vmc_amd/parallel.py).
 int vmc_allreduce_accumulators(vmc_ctx* c, void* nccl_comm, int32_t world_size) {
   CHECK_CTX(c);
+  if (c->prod && world_size > 1) return fail(c, VMC_ERR_UNSUPPORTED, "vmc_allreduce_accumulators with world_size > 1 is not available on a product ctx ('prod')");
   PROPAGATE(acc_zeros(c));
   PROPAGATE(reduce_accumulators(c, nccl_comm, world_size));
   return VMC_OK;
 }
 
 int vmc_set_host_allreduce(vmc_ctx* c, vmc_host_allreduce_fn hook, void* user) {
-  CHECK_CTX(c);
+  CHECK_CTX(c); REFUSE_PRODUCT(c, "vmc_set_host_allreduce");
   c->host_reduce = hook;
   c->host_reduce_user = user;
   c->host_reduce_caps = 0;          // a new hook has declared nothing yet
@@ -146,14 +147,14 @@ int vmc_set_host_allreduce(vmc_ctx* c, vmc_host_allreduce_fn hook, void* user) {
 }
 
 int vmc_set_host_allreduce_caps(vmc_ctx* c, int32_t caps) {
-  CHECK_CTX(c);
+  CHECK_CTX(c); REFUSE_PRODUCT(c, "vmc_set_host_allreduce_caps");
   if (caps & ~VMC_HOST_REDUCE_CAP_F64) return fail(c, VMC_ERR_INVALID, "unknown capability bits");
   c->host_reduce_caps = caps;
   return VMC_OK;
 }
 
 int vmc_set_device_allreduce(vmc_ctx* c, vmc_device_allreduce_fn hook, void* user) {
-  CHECK_CTX(c);
+  CHECK_CTX(c); REFUSE_PRODUCT(c, "vmc_set_device_allreduce");
   c->dev_reduce = hook;
   c->dev_reduce_user = user;
   return VMC_OK;
@@ -226,6 +227,7 @@ int vmc_rccl_comm_destroy(void* nccl_comm) {
 
 int vmc_debug_allreduce(vmc_ctx* c, void* nccl_comm, int32_t world_size, float* host, int64_t n, int32_t op) {
   ENTER(c);
+  if (c->prod && world_size > 1) return fail(c, VMC_ERR_UNSUPPORTED, "vmc_debug_allreduce with world_size > 1 is not available on a product ctx ('prod')");
   if (!host || n < 1 || (op != VMC_REDUCE_SUM && op != VMC_REDUCE_MAX)) return fail(c, VMC_ERR_INVALID, "bad arguments");
   if (n > c->d_stage_n) {
     HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -8,7 +8,7 @@ extern "C" {
 
 // ------------------------------------------------------------------ stochastic reconfiguration
 int vmc_sr_reserve(vmc_ctx* c, int32_t n_batches) {
-  ENTER(c);
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_reserve)");
   if (n_batches < 0) return fail(c, VMC_ERR_INVALID, "n_batches < 0");
   if (n_batches > 0 && c->nnb)
     return fail(c, VMC_ERR_UNSUPPORTED, "stochastic reconfiguration is not implemented for the fully_connected_nnb ansatz (use EnergyGradient or LogOverlapITSWO)");
@@ -80,7 +80,7 @@ int vmc_sr_reserve(vmc_ctx* c, int32_t n_batches) {
 }
 
 int vmc_sr_num_stored(vmc_ctx* c, int32_t* n) {
-  CHECK_CTX(c);
+  CHECK_CTX(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_num_stored)");
   if (!n) return fail(c, VMC_ERR_INVALID, "null");
   *n = c->sr_n;
   return VMC_OK;
@@ -94,7 +94,7 @@ static int sr_read_rr(vmc_ctx* c, int idx, double* rr) {
 }
 
 int vmc_sr_begin(vmc_ctx* c, double* rr0) {
-  ENTER(c);
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_begin)");
   c->cg_sr_tape_rows = 0;        // a new solve: the general convolution path re-runs the stored chains' taped forward once
   if (c->sr_cap <= 0) return fail(c, VMC_ERR_STATE, "vmc_sr_reserve first");
   if (c->sr_n <= 0) return fail(c, VMC_ERR_STATE, "no samples recorded (vmc_accumulate in ENERGY_GRADIENT mode)");
@@ -106,7 +106,7 @@ int vmc_sr_begin(vmc_ctx* c, double* rr0) {
 
 // u[0..P) = sum over this rank's stored samples of (O_b . p) O_b,  u[P] = sum (O_b . p)
 int vmc_sr_matvec_partial(vmc_ctx* c) {
-  ENTER(c);
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_matvec_partial)");
   if (!c->sr_begun) return fail(c, VMC_ERR_STATE, "vmc_sr_begin first");
   const int B = c->B, N = c->N, H = c->H, Hp = c->Hp, L = c->A;
   const long long R = (long long)c->sr_cap * B;   // row stride between layers of the store
@@ -194,7 +194,7 @@ int vmc_sr_matvec_partial(vmc_ctx* c) {
 }
 
 int vmc_sr_buffer_devptr(vmc_ctx* c, void** dev_ptr, int64_t* n_floats) {
-  CHECK_CTX(c);
+  CHECK_CTX(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_buffer_devptr)");
   if (!c->sr_u) return fail(c, VMC_ERR_STATE, "vmc_sr_reserve first");
   if (dev_ptr) *dev_ptr = c->sr_u;
   if (n_floats) *n_floats = c->P + 1;
@@ -202,7 +202,7 @@ int vmc_sr_buffer_devptr(vmc_ctx* c, void** dev_ptr, int64_t* n_floats) {
 }
 
 int vmc_sr_get_buffer(vmc_ctx* c, float* host) {
-  ENTER(c);
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_get_buffer)");
   if (!host || !c->sr_u) return fail(c, VMC_ERR_INVALID, "null / vmc_sr_reserve first");
   HIPCHK(c, hipMemcpyAsync(host, c->sr_u, (c->P + 1) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -210,7 +210,7 @@ int vmc_sr_get_buffer(vmc_ctx* c, float* host) {
 }
 
 int vmc_sr_set_buffer(vmc_ctx* c, const float* host) {
-  ENTER(c);
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_set_buffer)");
   if (!host || !c->sr_u) return fail(c, VMC_ERR_INVALID, "null / vmc_sr_reserve first");
   HIPCHK(c, hipMemcpyAsync(c->sr_u, host, (c->P + 1) * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -218,7 +218,7 @@ int vmc_sr_set_buffer(vmc_ctx* c, const float* host) {
 }
 
 int vmc_sr_cg_update(vmc_ctx* c, float diag_shift, double* rr) {
-  ENTER(c);
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_cg_update)");
   if (!c->sr_begun) return fail(c, VMC_ERR_STATE, "vmc_sr_begin first");
   const int cur = c->sr_iter & 1;
   HIPCHK(c, launch_sr_q(c->stream, c->sr_u, c->acc, (int)c->P, c->sr_p, diag_shift, c->sr_q, c->sr_partial, c->sr_sc));
@@ -246,7 +246,7 @@ struct SrCentreScope {
 //            sum_b (t_b - mean) O_b; elsewhere vmc_sr_matvec_partial
 // followed, as after vmc_sr_matvec_partial, by the all-reduce of the whole buffer and vmc_sr_cg_update.
 int vmc_sr_matvec_phase1(vmc_ctx* c) {
-  ENTER(c);
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_matvec_phase1)");
   if (!c->sr_begun) return fail(c, VMC_ERR_STATE, "vmc_sr_begin first");
   if (!c->conv_general) return VMC_OK;
   const int rows = c->sr_n * c->B;
@@ -259,7 +259,7 @@ int vmc_sr_matvec_phase1(vmc_ctx* c) {
 }
 
 int vmc_sr_matvec_phase2(vmc_ctx* c) {
-  ENTER(c);
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_matvec_phase2)");
   if (!c->sr_begun) return fail(c, VMC_ERR_STATE, "vmc_sr_begin first");
   if (!c->conv_general) return vmc_sr_matvec_partial(c);
   if (!c->sr_phase1_done) return fail(c, VMC_ERR_STATE, "vmc_sr_matvec_phase1 first");
@@ -304,18 +304,18 @@ static int sr_solve_impl(vmc_ctx* c, void* comm, int world, float diag_shift, fl
 }
 
 int vmc_sr_solve(vmc_ctx* c, float diag_shift, float tol, int32_t max_iter, int32_t* iters, double* rel_residual) {
-  ENTER(c);
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_solve)");
   return sr_solve_impl(c, nullptr, 1, diag_shift, tol, max_iter, iters, rel_residual);
 }
 
 int vmc_sr_solve_dist(vmc_ctx* c, void* nccl_comm, int32_t world_size, float diag_shift, float tol,
                       int32_t max_iter, int32_t* iters, double* rel_residual) {
-  ENTER(c);
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_solve_dist)");
   return sr_solve_impl(c, nccl_comm, world_size, diag_shift, tol, max_iter, iters, rel_residual);
 }
 
 int vmc_sr_get_solution(vmc_ctx* c, float* x) {
-  ENTER(c);
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_get_solution)");
   if (!x || !c->sr_x) return fail(c, VMC_ERR_INVALID, "null / vmc_sr_reserve first");
   HIPCHK(c, hipMemcpyAsync(x, c->sr_x, c->P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -323,7 +323,7 @@ int vmc_sr_get_solution(vmc_ctx* c, float* x) {
 }
 
 int vmc_sr_apply(vmc_ctx* c, float lr, double* energy) {
-  ENTER(c);
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_apply)");
   if (!c->sr_begun) return fail(c, VMC_ERR_STATE, "vmc_sr_begin / vmc_sr_solve first");
   HIPCHK(c, launch_sr_apply(c->stream, c->ps[0].theta, c->sr_x, lr, (int)c->P));
   c->ps[0].packed_valid = c->ps[0].cache_valid = false;
@@ -334,7 +334,7 @@ int vmc_sr_apply(vmc_ctx* c, float lr, double* energy) {
 }
 
 int vmc_sr_debug_matvec(vmc_ctx* c, const float* v, float diag_shift, float* out) {
-  ENTER(c);
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_debug_matvec)");
   if (!v || !out) return fail(c, VMC_ERR_INVALID, "null");
   PROPAGATE(vmc_sr_begin(c, nullptr));
   HIPCHK(c, hipMemcpyAsync(c->sr_p, v, c->P * sizeof(float), hipMemcpyHostToDevice, c->stream));

@@ -334,6 +334,7 @@ static int run_sweep_nnb(vmc_ctx* c, long long n_steps, bool injected, bool dbg,
 static int run_sweep(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn,
                      float* dbg_u, unsigned long long step0, bool count_accepted = false,
                      bool overtake = false, hipEvent_t dep = nullptr) {
+  if (c->prod) return prod_run_sweep(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
   PROPAGATE(ensure_packed(c, 0));
   if (!dbg) c->cnt_valid = false;   // the chains change (set again below when this launch leaves their census)
   if (c->edvec)
@@ -415,6 +416,7 @@ extern "C" {
 
 int vmc_debug_conv_patch(vmc_ctx* c, int64_t n_steps, int32_t* patch) {
   CHECK_CTX(c);
+  REFUSE_PRODUCT(c, "vmc_debug_conv_patch");
   if (!patch) return fail(c, VMC_ERR_INVALID, "null");
   *patch = cgen_patch_use(c, n_steps) ? 1 : 0;
   return VMC_OK;
@@ -422,6 +424,7 @@ int vmc_debug_conv_patch(vmc_ctx* c, int64_t n_steps, int32_t* patch) {
 
 int vmc_mc_steps(vmc_ctx* c, int64_t n_steps, int64_t* accepted) {
   CHECK_CTX(c);
+  REFUSE_COMPOSED(c);
   if (n_steps < 0) return fail(c, VMC_ERR_INVALID, "n_steps < 0");
   if (n_steps == 0) {               // `for _ in range(0)`: nothing runs, nothing is launched
     c->side_sweep_once = false;     // (a request for the side stream does not outlive the call it was made for)
@@ -468,6 +471,7 @@ int vmc_mc_steps(vmc_ctx* c, int64_t n_steps, int64_t* accepted) {
 
 int vmc_mc_step_injected(vmc_ctx* c, const int32_t* i_up, const int32_t* i_dn, const float* u, uint8_t* accept_mask) {
   ENTER(c);
+  REFUSE_COMPOSED(c);
   if (!i_up || !i_dn || !u) return fail(c, VMC_ERR_INVALID, "null proposals");
   for (int b = 0; b < c->B; ++b)
     if (i_up[b] < 0 || i_up[b] >= c->N || i_dn[b] < 0 || i_dn[b] >= c->N)
@@ -497,6 +501,8 @@ int vmc_debug_proposals(vmc_ctx* c, uint64_t step, int32_t* i_up, int32_t* i_dn,
 
 int vmc_debug_sweep_profile(vmc_ctx* c, int64_t n_steps, double* phase_cycles) {
   ENTER(c);
+  REFUSE_COMPOSED(c);
+  REFUSE_PRODUCT(c, "vmc_debug_sweep_profile");
   if (n_steps < 1 || !phase_cycles) return fail(c, VMC_ERR_INVALID, "bad arguments");
   if (c->rbm || c->conv || c->wide || c->pbdg || c->edvec) return fail(c, VMC_ERR_UNSUPPORTED, "the diagnostic sweep build exists for fully_connected (<= 256 units) only");
   PROPAGATE(ensure_packed(c, 0));

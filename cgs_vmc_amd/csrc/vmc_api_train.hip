@@ -10,12 +10,14 @@ extern "C" {
 // `e` / `mode`: the scalar accumulators (sum E, counts, sum ratio) ride in the reduction launch of the
 // dense weight-gradient GEMMs; *scalars_done tells the caller whether they did
 static int gradient_sums(vmc_ctx* c, const float* w, bool fresh, const float* e, int mode, bool* scalars_done,
-                         bool fold_eloc = false, float beta = 0.f) {
+                         bool fold_eloc = false, float beta = 0.f, float* g1_ext = nullptr, float* g2_ext = nullptr) {
   *scalars_done = false;
   ParamSet& p = c->ps[0];
   const int B = c->B, N = c->N, H = c->H, Hp = c->Hp, NH = c->n_hh;
-  float* g1 = c->acc;
-  float* g2 = c->acc + c->P;
+  // g1_ext / g2_ext: the sums go to a caller's accumulators (a product ctx's segment of this factor) and the scalar
+  // accumulators stay with the caller
+  float* g1 = g1_ext ? g1_ext : c->acc;
+  float* g2 = g1_ext ? g2_ext : c->acc + c->P;
   Timer t(c, "grad");
   if (c->edvec) {
     // O_k(b) = delta(k, idx_b) / psi_b: a scatter of 1 / psi_b and w_b / psi_b, every entry summed in chain order (edvec.hip)
@@ -163,12 +165,26 @@ static int gradient_sums(vmc_ctx* c, const float* w, bool fresh, const float* e,
     L.slices = c->nnb ? c->nnb_wg_slices
                       : plan_wgrad_slices(c->wg_tiles, B, c->num_cus, 1 + (c->wg_out_partials ? plan_wgrad_fold_blocks(H) : 0), forced);
     L.K = B; L.w = w; L.g1 = g1; L.g2 = g2; L.ws = c->gemm_ws; L.tickets = c->wg_tickets; L.fresh = fresh;
-    L.sc_eloc = e; L.sc_ratio = mode == 1 ? c->ratio : nullptr; L.sc_out = c->acc + 2 * c->P; L.sc_B = B; L.sc_mode = mode;
+    L.sc_eloc = e; L.sc_ratio = mode == 1 ? c->ratio : nullptr; L.sc_out = g1_ext ? nullptr : c->acc + 2 * c->P; L.sc_B = B; L.sc_mode = mode;
     HIPCHK(c, launch_wgrad(c->stream, L));
   }
-  *scalars_done = true;
+  *scalars_done = g1_ext == nullptr;
   return VMC_OK;
 }
+
+}  // extern "C"
+
+namespace vmcapi {
+// The gradient path of a factor of a product ctx: sum_b O_k(b) -> g1 +=, sum_b w_b O_k(b) -> g2 += for psi on the ctx's
+// `configs` (whose cache the caller has made valid), with the caller's weights and accumulators
+int child_gradient_sums(vmc_ctx* c, const float* w, float* g1, float* g2) {
+  if (c->conv || c->nnb) return fail(c, VMC_ERR_UNSUPPORTED, "prod: this ansatz type cannot be a factor");
+  bool scalars_done = false;
+  return gradient_sums(c, w, false, nullptr, VMC_MODE_ENERGY_GRADIENT, &scalars_done, false, 0.f, g1, g2);
+}
+}  // namespace vmcapi
+
+extern "C" {
 
 // SR sample store: the chains of this accumulate call with their activations a_l and
 // back-propagated d logit / d z_l, which gradient_sums has just left in act[] / delta[]
@@ -200,8 +216,10 @@ static int sr_record(vmc_ctx* c) {
 
 int vmc_accumulate(vmc_ctx* c, int mode, float beta) {
   ENTER(c);
+  REFUSE_COMPOSED(c);
   if (mode != VMC_MODE_ENERGY_GRADIENT && mode != VMC_MODE_LOG_OVERLAP_ITSWO)
     return fail(c, VMC_ERR_INVALID, "bad mode");
+  if (c->prod) return prod_accumulate(c, mode, beta);
   const float* w = nullptr;
   const float* e = nullptr;
   // everything this call enqueues comes after ev_mark; a sampler launch that follows directly
@@ -298,7 +316,9 @@ int vmc_get_gradient(vmc_ctx* c, int mode, float* grad) {
 
 int vmc_apply_adam(vmc_ctx* c, int mode, float lr, float beta1, float beta2, float eps, double* energy) {
   ENTER(c);
+  REFUSE_COMPOSED(c);
   if (mode != 0 && mode != 1) return fail(c, VMC_ERR_INVALID, "bad mode");
+  if (c->prod) PROPAGATE(prod_gather_params(c, VMC_PSI));      // theta = [a | b] from the factors
   if (!c->ps[0].has_params) return fail(c, VMC_ERR_STATE, "parameters not set");
   PROPAGATE(acc_zeros(c));
   c->adam_t += 1;
@@ -310,6 +330,7 @@ int vmc_apply_adam(vmc_ctx* c, int mode, float lr, float beta1, float beta2, flo
   }
   c->ps[0].packed_valid = c->ps[0].cache_valid = false;
   c->acts_valid = false;
+  if (c->prod) PROPAGATE(prod_scatter_params(c, VMC_PSI));     // ... and back
   if (energy) PROPAGATE(vmc_mean_energy(c, energy));
   return VMC_OK;
 }
@@ -334,6 +355,7 @@ int vmc_set_adam_state(vmc_ctx* c, const float* m, const float* v, int64_t t) {
 
 // Wavefunction.update_norm (wavefunctions.py:261-288); max_b psi over the chains of all ranks
 static int update_norm_impl(vmc_ctx* c, void* comm, int world, float max_value) {
+  if (c->prod) return VMC_OK;      // the product has no shift of its own; the factors' stay where they are (log domain)
   if (c->oact != VMC_ACT_EXP_ || c->nnb || c->edvec) return VMC_OK;   // wavefunctions.py:276-277: no exp_norm_shift, nothing to do
   PROPAGATE(ensure_cache(c, VMC_PSI));
   // pbdg: max_b psi_b of the SIGNED amplitudes (wavefunctions.py:283): the largest logit among the chains with psi > 0
@@ -357,11 +379,14 @@ static int update_norm_impl(vmc_ctx* c, void* comm, int world, float max_value) 
 
 int vmc_update_norm(vmc_ctx* c, float max_value) {
   ENTER(c);
+  REFUSE_COMPOSED(c);
   return update_norm_impl(c, nullptr, 1, max_value);
 }
 
 int vmc_update_norm_dist(vmc_ctx* c, void* nccl_comm, int32_t world_size, float max_value) {
   ENTER(c);
+  REFUSE_COMPOSED(c);
+  REFUSE_PRODUCT(c, "vmc_update_norm_dist");
   return update_norm_impl(c, nccl_comm, world_size, max_value);
 }
 
@@ -393,12 +418,15 @@ static int epoch_energy_gradient_impl(vmc_ctx* c, void* comm, int world, int64_t
 int vmc_epoch_energy_gradient(vmc_ctx* c, int64_t n_eq_steps, int32_t n_batches, int64_t n_mc_steps,
                               float max_value) {
   ENTER(c);
+  REFUSE_COMPOSED(c);
   return epoch_energy_gradient_impl(c, nullptr, 1, n_eq_steps, n_batches, n_mc_steps, max_value);
 }
 
 int vmc_epoch_energy_gradient_dist(vmc_ctx* c, void* nccl_comm, int32_t world_size, int64_t n_eq_steps,
                                    int32_t n_batches, int64_t n_mc_steps, float max_value) {
   ENTER(c);
+  REFUSE_COMPOSED(c);
+  REFUSE_PRODUCT(c, "vmc_epoch_energy_gradient_dist");
   return epoch_energy_gradient_impl(c, nccl_comm, world_size, n_eq_steps, n_batches, n_mc_steps, max_value);
 }
 
@@ -427,6 +455,7 @@ int vmc_epoch_log_overlap(vmc_ctx* c, float beta, int64_t n_eq_steps, int32_t n_
                           int64_t n_mc_steps, float max_value, float lr, float beta1, float beta2,
                           float eps, double* energy) {
   ENTER(c);
+  REFUSE_COMPOSED(c);
   return epoch_log_overlap_impl(c, nullptr, 1, beta, n_eq_steps, n_batches, n_mc_steps, max_value, lr, beta1, beta2,
                                 eps, energy);
 }
@@ -435,6 +464,8 @@ int vmc_epoch_log_overlap_dist(vmc_ctx* c, void* nccl_comm, int32_t world_size, 
                                int32_t n_batches, int64_t n_mc_steps, float max_value, float lr, float beta1,
                                float beta2, float eps, double* energy) {
   ENTER(c);
+  REFUSE_COMPOSED(c);
+  REFUSE_PRODUCT(c, "vmc_epoch_log_overlap_dist");
   return epoch_log_overlap_impl(c, nccl_comm, world_size, beta, n_eq_steps, n_batches, n_mc_steps, max_value, lr,
                                 beta1, beta2, eps, energy);
 }
@@ -444,6 +475,9 @@ int vmc_epoch_log_overlap_dist(vmc_ctx* c, void* nccl_comm, int32_t world_size, 
 int vmc_evaluate(vmc_ctx* c, void* nccl_comm, int32_t world_size, int64_t n_eq_steps, int32_t n_samples,
                  int64_t n_mc_steps, double* means, int64_t* accepted) {
   ENTER(c);
+  REFUSE_COMPOSED(c);
+  if (c->prod && (nccl_comm || world_size > 1))
+    return fail(c, VMC_ERR_UNSUPPORTED, "vmc_evaluate over sharded chains is not available on a product ctx ('prod')");
   if (n_eq_steps < 0 || n_samples < 0 || n_mc_steps < 0) return fail(c, VMC_ERR_INVALID, "negative count");
   if (n_samples > 0 && !means) return fail(c, VMC_ERR_INVALID, "null means");
   if (c->n_bonds <= 0) return fail(c, VMC_ERR_STATE, "bonds not set (vmc_set_bonds)");

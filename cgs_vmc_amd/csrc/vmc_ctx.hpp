@@ -49,8 +49,16 @@ struct TimedRegion {
 using vmcapi::ParamSet;
 using vmcapi::TimedRegion;
 
+struct ProdState;      // vmc_api_prod.hip: what a product ctx keeps beside the members below
+
 struct vmc_ctx {
   vmc_desc d;
+  // ProductOfWavefunctions (vmc_api_prod.hip, prod.hip): a ctx made by vmc_create_product owns the chains, the accumulators
+  // and the Adam state of psi = psi_a psi_b and borrows its two factors (prod: its state; null on every other ctx).  owner:
+  // set on a factor while it is composed -- its chain-state entries return VMC_ERR_STATE, its parameter entries invalidate
+  // the owner's caches.  The dense members of a product ctx keep minimal shapes (unused); P = P_a + P_b.
+  ProdState* prod = nullptr;
+  vmc_ctx* owner = nullptr;
   int N = 0, B = 0, L = 0, H = 0, Hp = 0;
   bool rbm = false;        // RestrictedBoltzmannNetwork instead of FullyConnectedNetwork
   // ProjectedBDG (pbdg.hip): theta is the pairing matrix; the network members keep minimal shapes (unused).  The
@@ -284,6 +292,13 @@ struct DeviceGuard {
 #define PROPAGATE(expr) \
   do { int rc_ = (expr); if (rc_ != VMC_OK) return rc_; } while (0)
 
+// a factor of a product ctx: its chains, accumulators and sampler state belong to the product
+#define REFUSE_COMPOSED(c) \
+  do { if ((c)->owner) return fail((c), VMC_ERR_STATE, "the ctx is a factor of a product ctx (vmc_create_product): its chain-state entries are the product's"); } while (0)
+// entries a product ctx does not have
+#define REFUSE_PRODUCT(c, what) \
+  do { if ((c)->prod) return fail((c), VMC_ERR_UNSUPPORTED, what " is not available on a product ctx ('prod')"); } while (0)
+
 // CUs a sampler launch occupies (8 waves at 255 registers, or LDS, fill a CU per workgroup)
 inline int sweep_cus(const vmc_ctx* c) { return c->sweep_tile == 8 ? (c->B + 7) / 8 : (c->B + 15) / 16; }
 
@@ -427,6 +442,23 @@ int cgen_sr_matvec(vmc_ctx* c, const float* v, int n_rows);
 int reduce_buffer(vmc_ctx* c, void* comm, int world, void* buf, long long n, int op);
 bool sharded(void* comm, int world);
 int reduce_accumulators(vmc_ctx* c, void* comm, int world);
+// vmc_api_train.hip: the gradient sums of a factor for an external weight vector into external accumulators (+=)
+int child_gradient_sums(vmc_ctx* c, const float* w, float* g1, float* g2);
+// vmc_api_prod.hip (the product ctx; every function takes the PRODUCT unless named child)
+int prod_ensure_cache(vmc_ctx* c, int which);
+int prod_local_energy(vmc_ctx* c, int which);
+int prod_run_sweep(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn, float* dbg_u,
+                   unsigned long long step0, bool count_accepted);
+int prod_accumulate(vmc_ctx* c, int mode, float beta);
+int prod_set_bonds(vmc_ctx* c, int32_t n_bonds, const int32_t* ij, const float* j_x, const float* j_z);
+int prod_gather_params(vmc_ctx* c, int which);      // the factors' theta -> the product's [a | b]
+int prod_scatter_params(vmc_ctx* c, int which);     // ... and back
+int prod_transfer_params(vmc_ctx* c);
+int prod_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, float* logit, float* psi);
+void prod_chains_changed(vmc_ctx* c);
+void prod_child_params_changed(vmc_ctx* child, int which);
+void prod_release(vmc_ctx* c);                       // vmc_destroy of a product: the factors are free again
+void prod_child_destroyed(vmc_ctx* child);           // vmc_destroy of a factor that is still composed
 // vmc_api_sweep.hip
 bool sampler_refresh_ok(const vmc_ctx* c);
 int refresh_cache_by_sampler(vmc_ctx* c, int which);

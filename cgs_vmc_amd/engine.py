@@ -52,7 +52,7 @@ class VmcEngine:
                nonlinearity: str = 'relu', output_activation: str = 'exp', device: int = 0,
                chain_offset: int = 0, seed: int = 2024, stream: int = 0,
                ansatz: str = 'fully_connected', kernel_size: int = 0, size_x: int = 0,
-               size_y: int = 0, adjacency=None, lin_tables=None):
+               size_y: int = 0, adjacency=None, lin_tables=None, children=None):
     """Dense ansatz types: num_layers / layer_size = num_fc_layers / fc_layer_size.  Convolutional
     ones ('conv_2d', 'res_net_2d'): num_layers = num_conv_layers or num_resnet_blocks, layer_size =
     num_conv_filters, plus kernel_size and the lattice size_x x size_y (= n_sites).  'gnn':
@@ -61,9 +61,16 @@ class VmcEngine:
     be left 0 (k is read off the table).  'ed_vector': layer_size = the vector's length and
     `lin_tables`, the pair (top, bot) of int tables [2^(n_sites/2)] (or their concatenated int32
     bytes, as FullVector._engine_spec carries them); without them the ctx refuses every forward
-    entry until set_lin_tables is called."""
+    entry until set_lin_tables is called.  'prod': `children`, the two factors' own keyword arguments (dicts, or
+    tuples of sorted items as ProductOfWavefunctions._engine_spec carries them); the engine creates both factors as
+    ordinary engines (self.children) with this engine's shape, device, seed and stream and composes them with
+    vmc_create_product.  num_params = a's + b's."""
     self._lib = _hip.load()
     self._ctx = C.c_void_p()
+    self.children = ()
+    if ansatz == 'prod':
+      self._init_product(n_sites, batch_size, device, chain_offset, seed, stream, children)
+      return
     adj = None
     if ansatz == 'gnn':
       if adjacency is None:
@@ -122,6 +129,34 @@ class VmcEngine:
                                                             layer_size, num_layers))
     self.n_bonds = 0
 
+  def _init_product(self, n_sites, batch_size, device, chain_offset, seed, stream, children):
+    if children is None or len(children) != 2:
+      raise ValueError("the 'prod' ansatz needs the specs of its two factors")
+    made = []
+    try:
+      for spec in children:
+        made.append(VmcEngine(n_sites=n_sites, batch_size=batch_size, device=device, chain_offset=chain_offset,
+                              seed=seed, stream=stream, **dict(spec)))
+      rc = self._lib.vmc_create_product(made[0]._ctx, made[1]._ctx, C.byref(self._ctx))
+      if rc != _hip.VMC_OK:
+        msg = self._lib.vmc_last_error(None).decode()
+        self._ctx = C.c_void_p()
+        self._raise(rc, msg)
+    except Exception:
+      for eng in made:
+        eng.close()
+      raise
+    self.children = tuple(made)
+    _LIVE_ENGINES.add(self)
+    self.n_sites, self.batch_size = n_sites, batch_size
+    self.num_layers, self.layer_size = 0, 0
+    self.chain_offset, self.seed, self.device = chain_offset, seed, device
+    self.stream = int(stream or 0)
+    self.ansatz = 'prod'
+    self.kernel_size, self.size_x, self.size_y = 0, 0, 0
+    self.num_params = made[0].num_params + made[1].num_params
+    self.n_bonds = 0
+
   # ------------------------------------------------------------------ plumbing
   @staticmethod
   def _raise(rc, msg):
@@ -133,7 +168,10 @@ class VmcEngine:
 
   def _check(self, rc):
     if rc != _hip.VMC_OK:
-      self._raise(rc, self._lib.vmc_last_error(self._ctx).decode())
+      msg = self._lib.vmc_last_error(self._ctx).decode()
+      if rc == _hip.VMC_ERR_STATE and 'factor of a product ctx' in msg:     # (REFUSE_COMPOSED, csrc/vmc_ctx.hpp)
+        raise _hip.ComposedFactorError('libcgsvmc_hip error {}: {}'.format(rc, msg))
+      self._raise(rc, msg)
 
   def close(self):
     if getattr(self, '_ctx', None) is not None and self._ctx.value:
@@ -143,6 +181,8 @@ class VmcEngine:
         self._coll = None
       self._lib.vmc_destroy(self._ctx)
       self._ctx = C.c_void_p()
+    for child in getattr(self, 'children', ()):     # a product borrows its factors: they go after it
+      child.close()
 
   def __del__(self):
     # engines still alive when the interpreter shuts down are closed by _close_live_engines (atexit,
@@ -163,6 +203,8 @@ class VmcEngine:
     jz = np.ascontiguousarray(np.broadcast_to(np.asarray(j_z, np.float32), (nb,)))
     self._check(self._lib.vmc_set_bonds(self._ctx, nb, _iptr(ij), _fptr(jx), _fptr(jz)))
     self.n_bonds = nb
+    for child in self.children:       # (vmc_set_bonds on a product ctx forwards the table to both factors)
+      child.n_bonds = nb
 
   def set_lin_tables(self, top, bot):
     """The Lin tables of an 'ed_vector' ctx (vmc_set_lin_tables validates them against the vector's length)."""
@@ -526,7 +568,8 @@ class VmcEngine:
     return float(ms.value), int(n.value)
 
   def kernel_path(self) -> int:
-    """0 fused (<= 256 units), 1 fused with LDS operands (257..512), 2 general path, 3 conv."""
+    """0 fused (<= 256 units), 1 fused with LDS operands (257..512), 2 general path, 3 conv, ... 10 a product ctx
+    (include/cgsvmc.h vmc_debug_kernel_path)."""
     v = C.c_int32()
     self._check(self._lib.vmc_debug_kernel_path(self._ctx, C.byref(v)))
     return int(v.value)

@@ -62,8 +62,15 @@ class Wavefunction:
     raise NotImplementedError('sum/diff/prod composites are outside the MI355X hot path '
                               '(SURVEY.md 2: composites OUT OF SCOPE)')
 
-  __mul__ = __add__
   __sub__ = __add__
+
+  def __mul__(self, other):
+    """wavefunctions.py:107-161: psi_a(x) psi_b(x) as one wavefunction over one set of chains.  Scalar factors (a float
+    or a session.Tensor) are out of scope."""
+    if isinstance(other, Wavefunction):
+      return ProductOfWavefunctions(self, other)
+    raise NotImplementedError('a product with a scalar factor (%s) is outside the MI355X hot path; only '
+                              'wavefunction * wavefunction has HIP kernels' % type(other).__name__)
 
   def get_trainable_variables(self) -> List[session_lib.Variable]:
     """wavefunctions.py:167-175: own variables in creation order, then sub-wavefunctions'."""
@@ -151,7 +158,7 @@ def module_transfer_ops(source_module: Wavefunction, target_module: Wavefunction
   def run():
     if (source_module._engine is not None and source_module._engine is target_module._engine
         and source_module._which == _hip.VMC_PSI and target_module._which == _hip.VMC_OMEGA):
-      source_module._engine.transfer_params()          # device-to-device
+      source_module._engine.transfer_params()          # device-to-device (a product: both factors)
       target_module._has_values, target_module._theta = True, None
       return
     src = source_module.get_trainable_variables()
@@ -927,6 +934,109 @@ class FullVector(FullyConnectedNetwork):
     return cls(**params)
 
 
+class ProductOfWavefunctions(Wavefunction):
+  """psi(x) = psi_a(x) psi_b(x) (wavefunctions.py:107-161), e.g. a positive network on a determinant state.  One engine
+  serves the product: the two factors are ordinary ctxs composed by vmc_create_product (csrc/vmc_api_prod.hip), which
+  owns the chains; each factor stays bound to its own ctx for its variables and its shift.  The variables are a's then
+  b's, each under the factor's own scope, so a checkpoint holds exactly the two factors' variables.  Like the
+  reference's, the product has no exp_norm_shift of its own: normalize_batch / update_norm return None and the factors'
+  shifts stay where they are (the library works in the log domain, nothing overflows)."""
+  _ansatz = 'prod'
+
+  def __init__(self, wf_a: Wavefunction, wf_b: Wavefunction, name: str = 'product_of_wavefunctions'):
+    for wf in (wf_a, wf_b):
+      if not isinstance(wf, Wavefunction):
+        raise NotImplementedError('a product with a scalar factor is outside the MI355X hot path')
+      if isinstance(wf, ProductOfWavefunctions):
+        raise NotImplementedError("prod: a product of products has no HIP kernels")
+      if not isinstance(wf, FullyConnectedNetwork):
+        raise NotImplementedError("prod: a factor of type %s has no HIP kernels" % type(wf).__name__)
+    if wf_a is wf_b:
+      raise ValueError('prod: the two factors must be two wavefunctions')
+    if not name.startswith('dc_'):      # (a deep copy keeps the dc_<name> its original's __deepcopy__ chose)
+      name = '_times_'.join([wf_b._unique_name, wf_a._unique_name])
+    super(ProductOfWavefunctions, self).__init__(name=name)
+    self._wf_a, self._wf_b = wf_a, wf_b
+    self._sub_wavefunctions += [wf_a, wf_b]
+
+  # omega = copy.deepcopy(psi): Wavefunction.__deepcopy__ rebuilds the product from deep copies of _wf_a / _wf_b
+
+  # training.py marks a supervisor whose values arrived on the device (vmc_transfer_params): forwarded to the factors
+  @property
+  def _has_values(self):
+    return all(wf._has_values for wf in self._sub_wavefunctions)
+
+  @_has_values.setter
+  def _has_values(self, value):
+    for wf in self._sub_wavefunctions:
+      wf._has_values = value
+
+  @property
+  def _theta(self):
+    return None
+
+  @_theta.setter
+  def _theta(self, value):
+    if value is not None:
+      raise ValueError('prod: the parameters live in the factors')
+    for wf in self._sub_wavefunctions:
+      if wf._engine is not None:
+        wf._theta = None
+
+  def _engine_spec(self):
+    freeze = lambda spec: tuple(sorted(spec.items()))
+    return dict(ansatz='prod', num_layers=0, layer_size=0,
+                children=(freeze(self._wf_a._engine_spec()), freeze(self._wf_b._engine_spec())))
+
+  def _bind(self, configs_var):
+    from . import parallel
+    if parallel.is_distributed():
+      raise NotImplementedError("wavefunction_type 'prod' runs on one rank: a product ctx has no sharded entries")
+    for wf in self._sub_wavefunctions:
+      if wf._engine_spec().get('output_activation') != 'exp':
+        raise NotImplementedError("prod: a dense factor needs the exp output activation (%s has %r)"
+                                  % (wf._unique_name, wf._engine_spec().get('output_activation')))
+    engine = configs_var._get_engine(self)
+    if self._engine is engine:
+      return engine
+    if self._engine is not None:
+      raise ValueError('wavefunction %s is already bound to another CONFIGS variable' % self._unique_name)
+    which = configs_var._claim_slot(self)
+    self._engine, self._which = engine, which
+    n_sites = configs_var.shape[1]
+    for wf, child in zip(self._sub_wavefunctions, engine.children):
+      if wf._engine is not None and wf._engine is not child:
+        raise ValueError('wavefunction %s is already bound to another CONFIGS variable' % wf._unique_name)
+      if wf._n_sites is not None and wf._n_sites != n_sites:
+        raise ValueError('Input tensor has wrong shape.')
+      wf._n_sites = n_sites
+      wf._shapes()                     # (the factor's own shape checks)
+      host_theta = wf._theta
+      wf._engine, wf._which = child, which
+      if host_theta is not None:
+        child.set_params(host_theta, which)
+        wf._theta = None
+      if wf._exp_norm_shift is not None:
+        child.set_shift(float(wf._exp_norm_shift), which)
+    return engine
+
+  def _build(self, inputs) -> session_lib.Tensor:
+    from . import graph_builders
+    if isinstance(inputs, graph_builders.ConfigsVariable):
+      return AmplitudeTensor(self, self._bind(inputs), None)
+    arr = np.asarray(inputs, np.float32)
+    if arr.ndim != 2 or (self._wf_a._n_sites is not None and arr.shape[1] != self._wf_a._n_sites):
+      raise ValueError('Input tensor has wrong shape.')
+    if self._engine is None:
+      raise ValueError('apply the wavefunction to the CONFIGS variable first '
+                       '(graph_builders.get_configs) so that it is bound to a GPU engine')
+    return AmplitudeTensor(self, self._engine, arr)
+
+  @classmethod
+  def from_hparams(cls, hparams, name: str = ''):
+    raise ValueError('Hparams initialization is not supported for product.')
+
+
 class AmplitudeTensor(session_lib.Tensor):
   """psi = wavefunction(inputs); evaluates to a float32 array [rows]."""
 
@@ -964,6 +1074,19 @@ def build_wavefunction(hparams) -> Wavefunction:
   wavefunction_type = hparams.wavefunction_type
   if wavefunction_type in WAVEFUNCTION_TYPES:
     return WAVEFUNCTION_TYPES[wavefunction_type].from_hparams(hparams)
+  if wavefunction_type == 'prod':
+    # wavefunctions.py:1178-1194: the two factors from copies of the hparams with their own type and output activation
+    children = []
+    for wf_type, activation in zip(hparams.composite_wavefunction_types, hparams.composite_output_activations):
+      if wf_type not in WAVEFUNCTION_TYPES:
+        raise ValueError('Provided wavefunction_type is not registered.')
+      child_hparams = copy.copy(hparams)
+      child_hparams.set_hparam('wavefunction_type', wf_type)
+      child_hparams.set_hparam('output_activation', activation)
+      children.append(WAVEFUNCTION_TYPES[wf_type].from_hparams(child_hparams))
+    if len(children) != 2:
+      raise ValueError("wavefunction_type 'prod' needs two composite_wavefunction_types")
+    return children[0] * children[1]
   if hparams.wavefunction_type in ('sum', 'diff', 'prod'):
     raise NotImplementedError('composite wavefunctions are outside the MI355X hot path')
   raise ValueError('Provided wavefunction_type is not registered.')

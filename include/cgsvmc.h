@@ -94,7 +94,8 @@ enum { VMC_MODE_ENERGY_GRADIENT = 0, VMC_MODE_LOG_OVERLAP_ITSWO = 1 };
 /* wavefunctions.WAVEFUNCTION_TYPES with kernels (wavefunctions.py:1157-1170) */
 enum { VMC_ANSATZ_FULLY_CONNECTED = 0, VMC_ANSATZ_RBM = 1, VMC_ANSATZ_CONV_2D = 2,
        VMC_ANSATZ_RES_NET_2D = 3, VMC_ANSATZ_CONV_1D = 4, VMC_ANSATZ_RES_NET_1D = 5,
-       VMC_ANSATZ_GNN = 6, VMC_ANSATZ_PBDG = 7, VMC_ANSATZ_NNB = 9 /* 8 is unassigned */, VMC_ANSATZ_ED_VECTOR = 10 };
+       VMC_ANSATZ_GNN = 6, VMC_ANSATZ_PBDG = 7, VMC_ANSATZ_NNB = 9 /* 8 is unassigned */, VMC_ANSATZ_ED_VECTOR = 10,
+       VMC_ANSATZ_PRODUCT = 11 /* vmc_create_product only: vmc_create refuses it (VMC_ERR_INVALID) */ };
 
 /* layers.NONLINEARITIES ids (layers.py:13-21).  Every id is accepted as hidden and as output
  * activation of every ansatz type with kernels. */
@@ -141,6 +142,27 @@ int64_t vmc_num_params_conv(int32_t ansatz, int32_t num_layers, int32_t num_filt
 /* FullyConnectedNetwork.__init__ + graph_builders.get_configs: allocates everything.
  * wavefunctions.py:331-353, graph_builders.py:92-125. */
 int vmc_create(const vmc_desc* desc, vmc_ctx** out);
+/* ProductOfWavefunctions ('prod', wavefunctions.py:61-165, 1178-1194): psi(x) = psi_a(x) psi_b(x) over ONE set of chains.
+ * a and b are ordinary ctxs that agree in n_sites, batch_size, device, chain_offset and stream (VMC_ERR_INVALID otherwise);
+ * the product borrows them -- vmc_destroy on it leaves them alive and free again; destroy the product first.  Factors
+ * taken: fully_connected and rbm (every width; exp output only: a positive amplitude with a shift), pbdg, ed_vector.  The
+ * convolutional types, gnn, fully_connected_nnb, a dense factor with another output activation and a product of products
+ * are refused (VMC_ERR_UNSUPPORTED).  If a factor is signed, every configuration needs Sz = 0, as for that factor alone.
+ * theta = a's floats followed by b's, P = P_a + P_b; accumulators [g1_a g1_b | g2_a g2_b | 8 scalars].
+ * The product owns the chains, the step counter, the accumulators and the Adam state; the sampler key is a's seed.  While a
+ * factor is composed its chain-state entries (vmc_set_configs, vmc_mc_steps, vmc_mc_step_injected, vmc_local_energy*,
+ * vmc_accumulate, vmc_apply_adam, vmc_update_norm, vmc_evaluate, the epoch entries, vmc_amplitude on its own chains) return
+ * VMC_ERR_STATE; its parameter, shift and host-row vmc_amplitude entries keep working.
+ * On the product: vmc_amplitude gives logit = (logit_a - shift_a) + (logit_b - shift_b) and psi = sign_a sign_b exp(logit)
+ * (psi = 0, logit = -inf where a factor is zero or singular); vmc_get_shift returns 0, vmc_set_shift VMC_ERR_INVALID,
+ * vmc_update_norm changes nothing (the factors' shifts stay where they are: everything runs in the log domain).  The
+ * sampler draws the proposals every sampler draws, evaluates both factors in full on the candidates and accepts where
+ * dlogit_a + dlogit_b > 0.5 log u; a candidate with psi = 0 is rejected, a chain at psi = 0 accepts any candidate that is
+ * not (what the pbdg, fully_connected_nnb and ed_vector samplers do).  Local energies: the off-diagonal row term is the
+ * product of the factors' ratios times the bond's coupling, taken once.  The vmc_sr_* entries, the _dist entries, every
+ * entry with world_size > 1, the reduce hooks, vmc_debug_sweep_profile, vmc_debug_sweep_tile and vmc_debug_conv_patch
+ * return VMC_ERR_UNSUPPORTED.  The vmc_timing_* entries report the product's own regions ("sweep", "eloc_reduce", "grad"). */
+int vmc_create_product(vmc_ctx* a, vmc_ctx* b, vmc_ctx** out);
 void vmc_destroy(vmc_ctx* ctx);
 const char* vmc_last_error(const vmc_ctx* ctx); /* ctx may be NULL: last create error */
 
@@ -401,7 +423,7 @@ int vmc_last_connected_rows(vmc_ctx* ctx, int64_t* rows);
  * cgs_vmc_amd/csrc/tail_split.hip -- never the headline configuration); 5: the split sampler as well; 6: the
  * general convolution path; 7: the projected BCS determinant kernels of pbdg (cgs_vmc_amd/csrc/pbdg.hip); 8: neural-network backflow -- the
  * general dense path into the determinant rows of cgs_vmc_amd/csrc/nnb.hip; 9: the Lin-table state vector
- * of ed_vector (cgs_vmc_amd/csrc/edvec.hip). */
+ * of ed_vector (cgs_vmc_amd/csrc/edvec.hip); 10: a product ctx (cgs_vmc_amd/csrc/prod.hip over the factors' own kernels). */
 int vmc_debug_kernel_path(vmc_ctx* ctx, int32_t* path);
 /* Chains per workgroup of the fused dense sampler: 16 (k_sweep16, sweep16.hpp) or 8 (k_sweep8, sweep8.hip: chosen by
  * vmc_create when sixteen-chain tiles would occupy at most half of the CUs -- BASELINE configs 2 and 5 -- or by
