@@ -317,6 +317,12 @@ hipError_t launch_sum(hipStream_t s, const float* x, int n, double* out_sum);
 hipError_t launch_max(hipStream_t s, const float* x, int n, float* out_max);
 hipError_t launch_div_f64(hipStream_t s, double* x, int n, double d);
 
+// spin correlations (corr.hip): the rows of a pass of pairs (a bond set with j_x = 2: val = psi'/psi) folded per
+// pair over the chains in ascending chain order, fp64; dense [B][n_pairs] floats of scratch
+hipError_t launch_pair_fold(hipStream_t s, const float* configs, const int2* pairs, const int2* rowinfo,
+                            const float* val, const int* n_rows_dev, int B, int N, int n_pairs, int num_cus,
+                            float* dense, double* zz, double* ex);
+
 // gradient path (grad.hip)
 struct GemmArgs {
   const float* A; long long sam, sak;   // A(m,k) = A[m*sam + k*sak]

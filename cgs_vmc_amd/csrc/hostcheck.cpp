@@ -786,8 +786,31 @@ static void prod_grid() {
   CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_INVALID);
 }
 
+// spin correlations (plan_corr_*): every pass inside the row budget and the 32-bit row index, the passes cover the
+// pairs exactly, a request only ever shrinks a pass, and the fold grid covers a pass
+static void corr_grid() {
+  for (long long B : {1LL, 40LL, 64LL, 1000LL, 4096LL, 65536LL, 1LL << 24, (1LL << 24) + 1, 1LL << 30, (1LL << 30) + 1, 0x7fffffffLL})
+    for (long long n_pairs : {1LL, 7LL, 120LL, 276LL, 4950LL, 523776LL})
+      for (long long req : {0LL, 1LL, 7LL, 64LL, 276LL, 1LL << 40}) {
+        const int per = plan_corr_pairs_per_pass(B, n_pairs, req);
+        if (2 * B > 0x7fffffffLL) { CHECK(per == 0); continue; }        // not even one pair fits the row index
+        CHECK(per >= 1 && per <= n_pairs);
+        CHECK(B * per <= 0x7fffffffLL - B);                              // vmc_set_bonds' rule
+        CHECK(B * per <= PLAN_CORR_ROW_BUDGET || per == 1);
+        if (req > 0) CHECK(per <= req);
+        CHECK(per <= plan_corr_pairs_per_pass(B, n_pairs, 0));
+        const long long passes = plan_corr_passes(n_pairs, per);
+        CHECK(passes * per >= n_pairs && (passes - 1) * per < n_pairs);
+        CHECK((long long)plan_corr_fold_grid(per) * 64 >= per && ((long long)plan_corr_fold_grid(per) - 1) * 64 < per);
+      }
+  CHECK(plan_corr_pairs_per_pass(4096, 4950, 0) == 4096);                // 100 sites, all pairs: two passes
+  CHECK(plan_corr_pairs_per_pass(40, 120, 0) == 120 && plan_corr_pairs_per_pass(40, 120, 7) == 7);
+  CHECK(plan_corr_pairs_per_pass(0, 1, 0) == 0 && plan_corr_pairs_per_pass(1, 0, 0) == 0 && plan_corr_pairs_per_pass(1, 1, -1) == 0);
+}
+
 int main() {
   check_block_maps();
+  corr_grid();
   prod_grid();
   edvec_grid();
   nnb_grid();

@@ -635,6 +635,27 @@ inline int plan_prod_child_check(int ansatz, int output_activation, bool is_prod
   return VMC_ERR_UNSUPPORTED;
 }
 
+// ------------------------------------------------------------------------------- spin correlations (vmc_api_corr.hip, corr.hip)
+// A measurement runs its pairs in passes; a pass is a bond set of its own (bonds, couplings, rowinfo / val of B x pairs
+// rows) plus the dense [B][pairs] scatter target.  Row budget of a pass: 2^24 rows (rowinfo 128 MB, val and the dense
+// buffer 64 MB each), at least one pair, and never past the 32-bit row index rule of vmc_set_bonds
+// (B x pairs <= 2^31 - 1 - B).  requested > 0: at most that many pairs per pass (still inside the budget).
+// Returns 0 when not even one pair fits the row index (2 B > 2^31 - 1) or an argument is out of range.
+#define PLAN_CORR_ROW_BUDGET (1LL << 24)
+inline int plan_corr_pairs_per_pass(long long B, long long n_pairs, long long requested) {
+  if (B < 1 || n_pairs < 1 || requested < 0) return 0;
+  const long long limit = (0x7fffffffLL - B) / B;
+  if (limit < 1) return 0;
+  long long per = PLAN_CORR_ROW_BUDGET / B;
+  if (per < 1) per = 1;
+  if (per > limit) per = limit;
+  if (requested > 0 && requested < per) per = requested;
+  if (per > n_pairs) per = n_pairs;
+  return (int)per;
+}
+inline long long plan_corr_passes(long long n_pairs, int per) { return per < 1 ? 0 : (n_pairs + per - 1) / per; }
+inline unsigned plan_corr_fold_grid(int pairs) { return (unsigned)((pairs + 63) / 64); }    // 64 threads, one pair each
+
 // ------------------------------------------------------------------------------- vmc_create
 struct DescPlan {
   int rbm, conv, resnet, one_d;

@@ -271,6 +271,21 @@ int local_energy_device(vmc_ctx* c, int which, bool defer_reduce, bool* deferred
   if (c->prod) return prod_local_energy(c, which);
   PROPAGATE(ensure_cache(c, which));
   PROPAGATE(ensure_list(c));
+  PROPAGATE(connected_rows_device(c, which, true));
+  ParamSet& p = c->ps[which];
+  if (defer_reduce && deferred && !c->conv && !c->pbdg && !c->edvec && !(c->wide && !c->wide_fast)) {
+    *deferred = true;              // the fused back-propagation launch folds val into eloc
+    return VMC_OK;
+  }
+  {
+    Timer t(c, "eloc_reduce");
+    HIPCHK(c, launch_eloc_reduce(c->stream, c->off, c->diag, c->val, c->B, c->offdiag, p.eloc));
+  }
+  return VMC_OK;
+}
+
+// val[row] of every row of the list, by the ctx's kernel family (the spin-correlation passes run it over their own bond set)
+int connected_rows_device(vmc_ctx* c, int which, bool share_cus) {
   ParamSet& p = c->ps[which];
   if (c->edvec) {
     Timer t(c, "tail_eloc");
@@ -310,7 +325,7 @@ int local_energy_device(vmc_ctx* c, int which, bool defer_reduce, bool* deferred
     a.out = c->val;
     // a sampler launch is expected to overtake this accumulate: its workgroups need a whole
     // CU each, so the persistent grid leaves them free
-    if (c->expect_sweep && can_overlap(c) && c->num_cus - sweep_cus(c) >= c->num_cus / 4) {
+    if (share_cus && c->expect_sweep && can_overlap(c) && c->num_cus - sweep_cus(c) >= c->num_cus / 4) {
       a.num_cus = c->num_cus - sweep_cus(c);
       // Long row lists (config 5: 4,100 tiles of ~170 us) as SHORT-LIVED workgroups instead: a grid of
       // tiles / K workgroups of K tiles each (about CGS_VMC_TAIL_CHUNK_US of work), which the dispatcher hands to
@@ -328,14 +343,6 @@ int local_energy_device(vmc_ctx* c, int which, bool defer_reduce, bool* deferred
       }
     }
     HIPCHK(c, launch_rows(c, which, a, true));
-  }
-  if (defer_reduce && deferred && !c->conv && !c->pbdg && !c->edvec && !(c->wide && !c->wide_fast)) {
-    *deferred = true;              // the fused back-propagation launch folds val into eloc
-    return VMC_OK;
-  }
-  {
-    Timer t(c, "eloc_reduce");
-    HIPCHK(c, launch_eloc_reduce(c->stream, c->off, c->diag, c->val, c->B, c->offdiag, p.eloc));
   }
   return VMC_OK;
 }
@@ -696,6 +703,8 @@ void vmc_destroy(vmc_ctx* c) {
                   c->d_max, c->tmp_cfg, c->tmp_z1, c->tmp_out, c->tmp_on, c->tmp_rowinfo, c->rowinfo_id, c->bond_dummy, c->inj_up, c->inj_dn, c->inj_u,
                   c->acc_mask, c->wg_outpart, c->cnt_alt, c->diag_alt};
   for (void* q : ptrs) if (q) hipFree(q);
+  for (void* q : {(void*)c->corr_pairs, (void*)c->corr_hx, (void*)c->corr_qz, (void*)c->corr_rowinfo, (void*)c->corr_val,
+                  (void*)c->corr_dense, (void*)c->corr_out}) if (q) hipFree(q);
   for (float* q : {c->sr_ctape, c->sr_cdelta, c->sr_cws, c->sr_cw0, c->sr_cwf, c->sr_cwb, c->sr_cbias}) if (q) hipFree(q);
   void* sr[] = {c->sr_cfg, c->sr_act, c->sr_delta, c->sr_ws, c->sr_t, c->sr_u, c->sr_x, c->sr_r,
                 c->sr_p, c->sr_q, c->sr_partial, c->sr_sc, c->sr_ones, c->sr_tpart};

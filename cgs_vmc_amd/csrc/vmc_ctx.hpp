@@ -180,6 +180,14 @@ struct vmc_ctx {
   bool cnt_valid = false;          // cnt / diag hold the census of `configs` (left by the sampler's last launch)
   int* cnt_alt = nullptr; float* diag_alt = nullptr;   // the census the NEXT sampler launch writes (swapped with the chains)
   long long last_rows = 0;
+  // spin correlations (vmc_api_corr.hip): the bond set of a pass of pairs -- swapped with the five Hamiltonian members
+  // above for the pass -- the scatter target, the sums; sized for corr_cap pairs per pass / corr_cap_all pairs in all
+  int2* corr_pairs = nullptr;                        // [corr_cap_all] every pair of the call (a pass reads a slice)
+  float *corr_hx = nullptr, *corr_qz = nullptr;      // [corr_cap] 1 (j_x = 2) and 0 (j_z = 0)
+  int2* corr_rowinfo = nullptr;                      // [B corr_cap]
+  float *corr_val = nullptr, *corr_dense = nullptr;  // [B corr_cap] rows; [B][pairs of the pass] the rows by (chain, pair)
+  double* corr_out = nullptr;                        // [2][corr_cap_all] zz sums, exchange sums
+  long long corr_cap = 0, corr_cap_all = 0;
   // gradient path
   std::vector<float*> act;   // L views [B][Hp] into act_all
   float* act_all = nullptr;  // [L][B][Hp]
@@ -417,6 +425,9 @@ int wide_forward(vmc_ctx* c, int which, const float* z1, const int2* rowinfo, lo
 void invalidate_configs(vmc_ctx* c);
 int ensure_list(vmc_ctx* c);
 int local_energy_device(vmc_ctx* c, int which, bool defer_reduce = false, bool* deferred = nullptr);
+// the row launch of local_energy_device alone: c->val of the ctx's current bond set over the current list (ensure_cache and
+// ensure_list have run); share_cus: leave CUs to a sampler launch that is expected to overtake (expect_sweep)
+int connected_rows_device(vmc_ctx* c, int which, bool share_cus);
 int grow_tmp(vmc_ctx* c, long long rows);
 int pbdg_check_sz(vmc_ctx* c, const float* configs, long long n_rows);
 // neural-network backflow: rows {chain, bond} of a row list over `configs` and the chains' first-layer cache z1 -> logits

@@ -323,6 +323,19 @@ class VmcEngine:
     self._check(self._lib.vmc_local_energy_terms(self._ctx, which, _fptr(diag), _fptr(off)))
     return diag, off
 
+  def pair_correlations(self, pairs, which: int = _hip.VMC_PSI, pairs_per_pass: int = 0):
+    """Spin correlations over the current chains (extension, vmc_pair_correlations): for every pair (i, j) of
+    `pairs` returns (zz_sum, ex_sum), float64 [n_pairs]: sum_c s_i s_j and sum_c [s_i s_j < 0] psi(swap_ij x_c) /
+    psi(x_c).  <S_i . S_j> = (zz_sum / 4 + ex_sum / 2) / batch_size.  Moves no chain, touches neither the step
+    counter nor the accumulators nor the Hamiltonian; pairs_per_pass = 0 leaves the pass size to the library."""
+    ij = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    zz = np.empty(ij.shape[0], np.float64)
+    ex = np.empty(ij.shape[0], np.float64)
+    dp = C.POINTER(C.c_double)
+    self._check(self._lib.vmc_pair_correlations(self._ctx, int(which), ij.shape[0], _iptr(ij), int(pairs_per_pass),
+                                                zz.ctypes.data_as(dp), ex.ctypes.data_as(dp)))
+    return zz, ex
+
   def last_connected_rows(self) -> int:
     v = C.c_int64()
     self._check(self._lib.vmc_last_connected_rows(self._ctx, C.byref(v)))

@@ -109,6 +109,75 @@ class MonteCarloOperatorEvaluator(WavefunctionEvaluator):
     return list(measurements())
 
 
+class PairCorrelationTensor(session_lib.Tensor):
+  """(zz_sum, ex_sum) [n_pairs] float64 of `pairs` over THIS rank's chains (VmcEngine.pair_correlations);
+  `global_batch` is the number of chains of all ranks together."""
+
+  def __init__(self, engine, pairs, which: int, global_batch: int):
+    self.engine, self.which, self.global_batch = engine, which, int(global_batch)
+    self.pairs = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+    super(PairCorrelationTensor, self).__init__(self._value, 'pair_correlations')
+
+  def _value(self):
+    return self.engine.pair_correlations(self.pairs, self.which)
+
+
+class SpinCorrelationEvaluator(WavefunctionEvaluator):
+  """<S_i . S_j> by running MCMC (extension: the reference evaluates the energy alone).  The signatures are
+  MonteCarloOperatorEvaluator's; `operator` is the list of pairs [(i, j), ...] (None: all N (N - 1) / 2 pairs)."""
+
+  def build_eval_ops(self, wavefunction, operator, hparams,
+                     shared_resources: Dict[graph_builders.ResourceName, Any]) -> EvalOps:
+    from . import lattice
+    batch_size = hparams.batch_size
+    n_sites = hparams.num_sites
+    pairs = lattice.all_pairs(n_sites) if operator is None else operator
+    configs = graph_builders.get_configs(shared_resources, batch_size, n_sites)
+    mc_step, acc_rate = graph_builders.get_monte_carlo_sampling(shared_resources, configs, wavefunction)
+    engine = wavefunction._bind(configs)
+    return EvalOps(
+        value=PairCorrelationTensor(engine, pairs, wavefunction._which, batch_size),
+        mc_step=mc_step,
+        acceptance_rate=acc_rate,
+        placeholder_input=None,
+        wavefunction_value=None,
+    )
+
+  def run_evaluation(self, eval_ops: EvalOps, session, hparams, epoch_num: int) -> Dict[str, np.ndarray]:
+    """Thermalises for num_equilibration_sweeps sweeps, then takes num_evaluation_samples measurements,
+    num_monte_carlo_sweeps sweeps apart (the loop of MonteCarloOperatorEvaluator).  A measurement is the batch mean,
+    over the chains of ALL ranks, of s_i s_j / 4 ('szsz'), of [s_i s_j < 0] psi(swap_ij x) / (2 psi(x)) ('exchange')
+    and of their sum ('ss' = S_i . S_j) for every pair: with sharded chains the per-sample fp64 sums of the ranks are
+    added by parallel.allreduce_array before the division by the global batch.  Returns a dict: 'pairs' [n_pairs][2];
+    for each of the three names the mean over the samples, and under name + '_err' the conventional standard error of
+    that mean, std(ddof = 1) / sqrt(n_samples) of the batch means (0 for a single sample); 'samples' [n_samples][3]
+    [n_pairs], the batch means themselves."""
+    del epoch_num
+    value = eval_ops.value
+    steps_per_sweep = hparams.num_sites
+    decorrelation = hparams.num_monte_carlo_sweeps * steps_per_sweep
+    n_samples = hparams.num_evaluation_samples
+    sharded = parallel.world_size() > 1
+    self.acceptance_count = 0
+    samples = np.empty((n_samples, 3, value.pairs.shape[0]), np.float64)
+    _run_mc_steps(session, eval_ops.mc_step, hparams.num_equilibration_sweeps * steps_per_sweep)
+    for s in range(n_samples):
+      sums = np.stack(session.run(value)).astype(np.float64)        # [2][n_pairs]: zz, ex of this rank's chains
+      if sharded:
+        sums = parallel.allreduce_array(sums)
+      samples[s, 0] = 0.25 * sums[0] / value.global_batch
+      samples[s, 1] = 0.5 * sums[1] / value.global_batch
+      samples[s, 2] = (0.25 * sums[0] + 0.5 * sums[1]) / value.global_batch
+      _run_mc_steps(session, eval_ops.mc_step, decorrelation)
+      self.acceptance_count += getattr(eval_ops.mc_step, 'last_accepted', 0)
+    out = {'pairs': value.pairs.copy(), 'samples': samples}
+    for k, name in enumerate(('szsz', 'exchange', 'ss')):
+      out[name] = samples[:, k].mean(axis=0)
+      out[name + '_err'] = (samples[:, k].std(axis=0, ddof=1) / np.sqrt(n_samples) if n_samples > 1
+                            else np.zeros(samples.shape[2]))
+    return out
+
+
 class VectorWavefunctionEvaluator(WavefunctionEvaluator):
   """evaluation.py:155-246: dumps psi over a basis file.  Offline tool outside the hot path
   (SURVEY.md 2); `Wavefunction.__call__` on an array gives the same amplitudes."""

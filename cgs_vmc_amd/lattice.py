@@ -27,6 +27,50 @@ def torus_bonds(size_x, size_y, next_nearest=False):
   return bonds
 
 
+def chain_coords(n_sites):
+  """Positions [n_sites][1] of the sites of chain_bonds."""
+  return np.arange(n_sites, dtype=np.float64).reshape(n_sites, 1)
+
+
+def torus_coords(size_x, size_y):
+  """Positions [size_x * size_y][2] of the sites of torus_bonds: site = x + size_x * y sits at (x, y)."""
+  s = np.arange(size_x * size_y)
+  return np.stack([s % size_x, s // size_x], axis=1).astype(np.float64)
+
+
+def chain_momenta(n_sites):
+  """The momenta a periodic chain allows: q = 2 pi m / n_sites, m = 0 .. n_sites - 1; [n_sites][1]."""
+  return (2.0 * np.pi * np.arange(n_sites) / n_sites).reshape(n_sites, 1)
+
+
+def torus_momenta(size_x, size_y):
+  """The momenta the size_x x size_y torus allows, (2 pi m_x / size_x, 2 pi m_y / size_y), m_x fastest; [N][2]."""
+  m = np.arange(size_x * size_y)
+  return np.stack([2.0 * np.pi * (m % size_x) / size_x, 2.0 * np.pi * (m // size_x) / size_y], axis=1)
+
+
+def all_pairs(n):
+  """Every pair (i, j), i < j, of n sites: [n (n - 1) / 2][2] int32, i-major."""
+  i, j = np.triu_indices(n, k=1)
+  return np.stack([i, j], axis=1).astype(np.int32)
+
+
+def structure_factor(ss, pairs, coords, qs):
+  """S(q) = (1 / N) [3 N / 4 + 2 sum_{i<j} cos(q . (r_i - r_j)) <S_i . S_j>] for every q of `qs` [n_q][d], from
+  ss [n_pairs] = <S_i . S_j> of `pairs` [n_pairs][2] (every pair of distinct sites once, in either order; a pair that
+  is missing counts as uncorrelated) and the positions coords [N][d].  3 N / 4 is the i = j part, S (S + 1) per site."""
+  ss = np.asarray(ss, np.float64).ravel()
+  pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+  coords = np.asarray(coords, np.float64)
+  coords = coords.reshape(coords.shape[0], -1)
+  qs = np.asarray(qs, np.float64).reshape(-1, coords.shape[1])
+  if ss.size != pairs.shape[0]:
+    raise ValueError('structure_factor: {} values for {} pairs'.format(ss.size, pairs.shape[0]))
+  n = coords.shape[0]
+  dr = coords[pairs[:, 0]] - coords[pairs[:, 1]]          # [n_pairs][d]
+  return (0.75 * n + 2.0 * np.cos(qs @ dr.T) @ ss) / n
+
+
 def load_bonds(checkpoint_dir, n_sites):
   """run_training.py:103-109 / run_energy_evaluation.py:51-57: `J.txt` of integer pairs
   (extra columns ignored), else the periodic chain."""

@@ -361,6 +361,22 @@ int vmc_epoch_log_overlap_dist(vmc_ctx* ctx, void* nccl_comm, int32_t world_size
 int vmc_evaluate(vmc_ctx* ctx, void* nccl_comm, int32_t world_size, int64_t n_eq_steps,
                  int32_t n_samples, int64_t n_mc_steps, double* means, int64_t* accepted);
 
+/* Spin correlations -- EXTENSION with no reference counterpart (the reference measures the energy alone).  Over the
+ * ctx's current chains, for every pair k = (i, j) of `ij`:
+ *   zz_sum[k] = sum_c s_i s_j                                     (integers, exact)
+ *   ex_sum[k] = sum_c [s_i s_j < 0] psi(swap_ij x_c) / psi(x_c)   (chains in ascending order, fp64)
+ * so that <S_i . S_j> = (zz_sum / 4 + ex_sum / 2) / batch_size; either array may be NULL.  The ratios are the rows of the
+ * local energies, evaluated by the kernels of the ctx's ansatz type over a bond set of the pairs (j_x = 2, j_z = 0) that
+ * stands in for the Hamiltonian's during a pass and is swapped out again.  The pairs run in passes of at most
+ * pairs_per_pass pairs (0: as many as the row budget of a pass takes; a request is clamped to it); the sum of a pair
+ * does not depend on the passes or on the other pairs of the list.  A pure measurement: chains, step counter,
+ * accumulators, the Hamiltonian's bonds and couplings and the validity of the amplitude caches are as before on return
+ * (no vmc_set_bonds is needed before it).  i == j or a site out of range: VMC_ERR_INVALID; a product ctx:
+ * VMC_ERR_UNSUPPORTED; a factor of a product ctx: VMC_ERR_STATE. */
+int vmc_pair_correlations(vmc_ctx* ctx, int which, int32_t n_pairs, const int32_t* ij /*[n_pairs][2]*/,
+                          int32_t pairs_per_pass /*0: planner's choice*/,
+                          double* zz_sum /*[n_pairs]*/, double* ex_sum /*[n_pairs]*/);
+
 /* Stochastic reconfiguration -- EXTENSION: named by the north star, absent from the reference
  * (training.py has only the plain energy gradient + Adam), so these entries replace no reference
  * interface; they sit where TrainOpsTraditional.apply_gradients (training.py:560-567) sits.
