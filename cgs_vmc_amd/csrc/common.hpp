@@ -323,6 +323,15 @@ hipError_t launch_pair_fold(hipStream_t s, const float* configs, const int2* pai
                             const float* val, const int* n_rows_dev, int B, int N, int n_pairs, int num_cus,
                             float* dense, double* zz, double* ex);
 
+// Renyi-2 swap estimator (renyi.hip): the rows of a pass of regions (row = region x B + chain: the replica pair's swapped
+// configurations where the pair matches on the region, the chain's own elsewhere) and their fold per region over the pairs
+// in ascending order, fp64.  mask [n_regions][N] 0/1; sign / row_sign null: unsigned amplitudes
+hipError_t launch_swap_rows(hipStream_t s, const float* configs, const unsigned char* mask, int B, int N,
+                            int n_regions, int num_cus, float* rows);
+hipError_t launch_swap_fold(hipStream_t s, const float* configs, const unsigned char* mask, const float* logit,
+                            const float* sign, const float* row_logit, const float* row_sign, int B, int N,
+                            int n_regions, double* swap_sum, double* match_count);
+
 // gradient path (grad.hip)
 struct GemmArgs {
   const float* A; long long sam, sak;   // A(m,k) = A[m*sam + k*sak]

@@ -808,9 +808,46 @@ static void corr_grid() {
   CHECK(plan_corr_pairs_per_pass(0, 1, 0) == 0 && plan_corr_pairs_per_pass(1, 0, 0) == 0 && plan_corr_pairs_per_pass(1, 1, -1) == 0);
 }
 
+// Renyi-2 swap estimator (plan_renyi_*): every pass inside the row budget, the 32-bit row index and the ctx's own row
+// limit (one region is always taken), the passes cover the regions exactly, a request only ever shrinks a pass, the fold
+// grid covers a pass, and the row limit keeps the forward's scratch and its flat indices in range
+static void renyi_grid() {
+  for (long long B : {2LL, 40LL, 64LL, 1000LL, 4096LL, 65536LL, 1LL << 24, (1LL << 24) + 2, 1LL << 30, (1LL << 30) + 2, 0x7ffffffeLL})
+    for (long long n_regions : {1LL, 7LL, 50LL, 70LL, 4950LL, 523776LL})
+      for (long long req : {0LL, 1LL, 3LL, 64LL, 70LL, 1LL << 40})
+        for (long long lim : {0LL, 1LL, 4096LL, 100000LL, 1LL << 22, 1LL << 40}) {
+          const int per = plan_renyi_regions_per_pass(B, n_regions, req, lim);
+          if (2 * B > 0x7fffffffLL) { CHECK(per == 0); continue; }      // not even one region fits the row index
+          CHECK(per >= 1 && per <= n_regions);
+          CHECK(B * per <= 0x7fffffffLL - B);
+          CHECK(B * per <= PLAN_CORR_ROW_BUDGET || per == 1);
+          if (lim > 0) CHECK(B * per <= lim || per == 1);
+          if (req > 0) CHECK(per <= req);
+          CHECK(per <= plan_renyi_regions_per_pass(B, n_regions, 0, lim));
+          CHECK(per <= plan_renyi_regions_per_pass(B, n_regions, req, 0));
+          if (lim == 0) CHECK(per == plan_corr_pairs_per_pass(B, n_regions, req));   // the same budget and index rule
+          const long long passes = plan_renyi_passes(n_regions, per);
+          CHECK(passes * per >= n_regions && (passes - 1) * per < n_regions);
+          CHECK((long long)plan_renyi_fold_grid(per) * 64 >= per && ((long long)plan_renyi_fold_grid(per) - 1) * 64 < per);
+        }
+  for (int N : {2, 16, 100, 1024, 4096})
+    for (int Hp : {64, 256, 512, 4096}) {
+      const long long rows = plan_renyi_row_limit(N, Hp);
+      CHECK(rows >= 1);
+      CHECK(rows * (N > Hp ? N : Hp) <= 0x7fffffffLL);
+      CHECK(rows * ((long long)N + Hp + 5) <= (1LL << 30));
+    }
+  CHECK(plan_renyi_regions_per_pass(4096, 50, 0, plan_renyi_row_limit(100, 256)) == 50);      // config 3, the 50 blocks: one pass
+  CHECK(plan_renyi_regions_per_pass(40, 70, 0) == 70 && plan_renyi_regions_per_pass(40, 70, 3) == 3);
+  CHECK(plan_renyi_regions_per_pass(40, 70, 0, 100) == 2 && plan_renyi_regions_per_pass(40, 70, 0, 10) == 1);
+  CHECK(plan_renyi_regions_per_pass(0, 1, 0) == 0 && plan_renyi_regions_per_pass(2, 0, 0) == 0 &&
+        plan_renyi_regions_per_pass(2, 1, -1) == 0 && plan_renyi_regions_per_pass(2, 1, 0, -1) == 0);
+}
+
 int main() {
   check_block_maps();
   corr_grid();
+  renyi_grid();
   prod_grid();
   edvec_grid();
   nnb_grid();

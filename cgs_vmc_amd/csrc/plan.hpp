@@ -656,6 +656,40 @@ inline int plan_corr_pairs_per_pass(long long B, long long n_pairs, long long re
 inline long long plan_corr_passes(long long n_pairs, int per) { return per < 1 ? 0 : (n_pairs + per - 1) / per; }
 inline unsigned plan_corr_fold_grid(int pairs) { return (unsigned)((pairs + 63) / 64); }    // 64 threads, one pair each
 
+// ------------------------------------------------------------------------------- Renyi-2 swap estimator (vmc_api_renyi.hip, renyi.hip)
+// A measurement runs its regions in passes; a pass hands B rows per region (row = region x B + chain) to the family's
+// full forward.  Rows of a pass: the budget and the 32-bit row index rule of the spin correlations (B x regions <=
+// 2^31 - 1 - B), and never more than `row_limit` rows where the ctx states one (0: none) -- what the forward's scratch
+// takes: plan_renyi_row_limit below.  At least one region whatever the budget says; requested > 0: at most that many
+// regions per pass.  Returns 0 when not even one region fits the row index or an argument is out of range.
+inline int plan_renyi_regions_per_pass(long long B, long long n_regions, long long requested, long long row_limit = 0) {
+  if (B < 1 || n_regions < 1 || requested < 0 || row_limit < 0) return 0;
+  const long long limit = (0x7fffffffLL - B) / B;
+  if (limit < 1) return 0;
+  long long budget = PLAN_CORR_ROW_BUDGET;
+  if (row_limit > 0 && row_limit < budget) budget = row_limit;
+  long long per = budget / B;
+  if (per < 1) per = 1;
+  if (per > limit) per = limit;
+  if (requested > 0 && requested < per) per = requested;
+  if (per > n_regions) per = n_regions;
+  return (int)per;
+}
+// Rows the forward of one pass may take: the scratch per row is the configuration (N floats), the first layer's
+// output (Hp floats; the convolutional types and the table types keep the minimal Hp) and five words of row list,
+// outputs and signs -- kept within 2^30 floats (4 GiB) -- and every flat index into it (rows x max(N, Hp)) within 32
+// bits.  The blocked forwards (general dense, nnb's dense block of nnb_rows rows with its N^2 pairing layer, the general
+// convolution) walk any row count in blocks of their own, so they state no further limit.
+inline long long plan_renyi_row_limit(int N, int Hp) {
+  const long long widest = N > Hp ? N : Hp;
+  const long long by_index = 0x7fffffffLL / (widest > 0 ? widest : 1);
+  const long long by_bytes = (1LL << 30) / ((long long)N + Hp + 5);
+  const long long rows = by_index < by_bytes ? by_index : by_bytes;
+  return rows < 1 ? 1 : rows;
+}
+inline long long plan_renyi_passes(long long n_regions, int per) { return per < 1 ? 0 : (n_regions + per - 1) / per; }
+inline unsigned plan_renyi_fold_grid(int regions) { return (unsigned)((regions + 63) / 64); }    // 64 threads, one region each
+
 // ------------------------------------------------------------------------------- vmc_create
 struct DescPlan {
   int rbm, conv, resnet, one_d;

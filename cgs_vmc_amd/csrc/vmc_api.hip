@@ -1,8 +1,9 @@
 // Host side of libcgsvmc_hip.so: the C ABI of include/cgsvmc.h on top of the gfx950 kernels.  One vmc_ctx per GPU, all
 // work on ctx->stream.  This file: ctx life cycle, parameters, chains, amplitudes, local energies, timing; the other
 // entry points live in vmc_api_sweep.hip (samplers), vmc_api_train.hip (accumulators, Adam, epochs, evaluation),
-// vmc_api_coll.hip (collectives), vmc_api_sr.hip (stochastic reconfiguration); vmc_api_cgen.hip is the general
-// convolution path's machinery.  Shared state and helpers: vmc_ctx.hpp.
+// vmc_api_coll.hip (collectives), vmc_api_sr.hip (stochastic reconfiguration), vmc_api_corr.hip and vmc_api_renyi.hip (the
+// measurements beside the energy: spin correlations, Renyi-2 entropy), vmc_api_prod.hip (product ctxs); vmc_api_cgen.hip is
+// the general convolution path's machinery.  Shared state and helpers: vmc_ctx.hpp.
 #include "vmc_ctx.hpp"
 
 using namespace vmcapi;
@@ -361,6 +362,36 @@ int grow_tmp(vmc_ctx* c, long long rows) {
   return VMC_OK;
 }
 
+// The full forward of parameter set `which` on n_rows rows of a DEVICE buffer of configurations (vmc_amplitude's rows, the
+// swapped rows of vmc_renyi2_swap): log|psi| (the logit) per row into `logit`, and for the signed types the sign (ed_vector:
+// the entry itself) into `sign`.  The caller has run ensure_packed and grow_tmp(n_rows): tmp_z1 / tmp_on / tmp_rowinfo are
+// the scratch; `configs`, `logit`, `sign` may be the tmp buffers of the same rows or any others.
+int rows_forward_device(vmc_ctx* c, int which, const float* configs, long long n_rows, float* logit, float* sign) {
+  if (n_rows <= 0) return VMC_OK;
+  ParamSet& p = c->ps[which];
+  if (c->edvec) {
+    HIPCHK(c, launch_edvec_rows(c->stream, p.theta, (int)c->P, c->ed_top, c->ed_bot, c->N, configs, (int)n_rows, logit, sign));
+  } else if (c->pbdg) {
+    HIPCHK(c, launch_pbdg_rows(c->stream, p.theta, c->N, configs, (int)n_rows, logit, sign, nullptr, nullptr));
+  } else if (c->nnb) {
+    PROPAGATE(first_layer(c, p, configs, c->tmp_z1, (int)n_rows));
+    PROPAGATE(nnb_forward(c, which, c->tmp_z1, configs, c->tmp_rowinfo, n_rows, false, logit, sign));
+  } else if (c->conv) {
+    PROPAGATE(conv_rows(c, which, configs, c->tmp_rowinfo, (int)n_rows, nullptr, false, logit, false));
+  } else if (c->wide) {
+    PROPAGATE(first_layer(c, p, configs, c->tmp_z1, (int)n_rows));
+    if (c->rbm) HIPCHK(c, launch_onsite(c->stream, configs, p.won, (int)n_rows, c->N, c->tmp_on));
+    PROPAGATE(wide_forward(c, which, c->tmp_z1, c->tmp_rowinfo, n_rows, false, logit, c->tmp_on));
+  } else {
+    PROPAGATE(first_layer(c, p, configs, c->tmp_z1, (int)n_rows));
+    if (c->rbm) HIPCHK(c, launch_onsite(c->stream, configs, p.won, (int)n_rows, c->N, c->tmp_on));
+    TailArgs a = tail_args(c, which);
+    a.z1 = c->tmp_z1; a.on_base = c->tmp_on; a.n_rows = (int)n_rows; a.out = logit; a.rowinfo = c->tmp_rowinfo;
+    HIPCHK(c, launch_rows(c, which, a, false));
+  }
+  return VMC_OK;
+}
+
 // pbdg: every row must hold as many up as down spins (the projected BCS state lives at Sz = 0); host rows
 int pbdg_check_sz(vmc_ctx* c, const float* configs, long long n_rows) {
   if (!c->sgn) return VMC_OK;
@@ -705,6 +736,7 @@ void vmc_destroy(vmc_ctx* c) {
   for (void* q : ptrs) if (q) hipFree(q);
   for (void* q : {(void*)c->corr_pairs, (void*)c->corr_hx, (void*)c->corr_qz, (void*)c->corr_rowinfo, (void*)c->corr_val,
                   (void*)c->corr_dense, (void*)c->corr_out}) if (q) hipFree(q);
+  for (void* q : {(void*)c->renyi_mask, (void*)c->renyi_out}) if (q) hipFree(q);
   for (float* q : {c->sr_ctape, c->sr_cdelta, c->sr_cws, c->sr_cw0, c->sr_cwf, c->sr_cwb, c->sr_cbias}) if (q) hipFree(q);
   void* sr[] = {c->sr_cfg, c->sr_act, c->sr_delta, c->sr_ws, c->sr_t, c->sr_u, c->sr_x, c->sr_r,
                 c->sr_p, c->sr_q, c->sr_partial, c->sr_sc, c->sr_ones, c->sr_tpart};
@@ -880,52 +912,15 @@ int vmc_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, f
     HIPCHK(c, hipMemcpyAsync(host.data(), c->ps[which].logit, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (c->sgn)
       HIPCHK(c, hipMemcpyAsync(hsign.data(), c->ps[which].sign, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  } else if (n_rows > 0 && c->edvec) {
-    PROPAGATE(ensure_packed(c, which));
-    PROPAGATE(pbdg_check_sz(c, configs, n_rows));
-    PROPAGATE(grow_tmp(c, n_rows));
-    HIPCHK(c, hipMemcpyAsync(c->tmp_cfg, configs, n_rows * c->N * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_edvec_rows(c->stream, c->ps[which].theta, (int)c->P, c->ed_top, c->ed_bot, c->N, c->tmp_cfg, (int)n_rows,
-                                c->tmp_out, c->tmp_sign));
-    HIPCHK(c, hipMemcpyAsync(host.data(), c->tmp_out, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hsign.data(), c->tmp_sign, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  } else if (n_rows > 0 && c->pbdg) {
-    PROPAGATE(ensure_packed(c, which));
-    PROPAGATE(pbdg_check_sz(c, configs, n_rows));
-    PROPAGATE(grow_tmp(c, n_rows));
-    HIPCHK(c, hipMemcpyAsync(c->tmp_cfg, configs, n_rows * c->N * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_pbdg_rows(c->stream, c->ps[which].theta, c->N, c->tmp_cfg, (int)n_rows, c->tmp_out, c->tmp_sign,
-                               nullptr, nullptr));
-    HIPCHK(c, hipMemcpyAsync(host.data(), c->tmp_out, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hsign.data(), c->tmp_sign, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  } else if (n_rows > 0 && c->nnb) {
-    PROPAGATE(ensure_packed(c, which));
-    PROPAGATE(pbdg_check_sz(c, configs, n_rows));
-    PROPAGATE(grow_tmp(c, n_rows));
-    HIPCHK(c, hipMemcpyAsync(c->tmp_cfg, configs, n_rows * c->N * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    PROPAGATE(first_layer(c, c->ps[which], c->tmp_cfg, c->tmp_z1, (int)n_rows));
-    PROPAGATE(nnb_forward(c, which, c->tmp_z1, c->tmp_cfg, c->tmp_rowinfo, n_rows, false, c->tmp_out, c->tmp_sign));
-    HIPCHK(c, hipMemcpyAsync(host.data(), c->tmp_out, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hsign.data(), c->tmp_sign, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   } else if (n_rows > 0) {
     PROPAGATE(ensure_packed(c, which));
+    PROPAGATE(pbdg_check_sz(c, configs, n_rows));
     PROPAGATE(grow_tmp(c, n_rows));
     HIPCHK(c, hipMemcpyAsync(c->tmp_cfg, configs, n_rows * c->N * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    ParamSet& p = c->ps[which];
-    if (c->conv) {
-      PROPAGATE(conv_rows(c, which, c->tmp_cfg, c->tmp_rowinfo, (int)n_rows, nullptr, false, c->tmp_out, false));
-    } else if (c->wide) {
-      PROPAGATE(first_layer(c, p, c->tmp_cfg, c->tmp_z1, (int)n_rows));
-      if (c->rbm) HIPCHK(c, launch_onsite(c->stream, c->tmp_cfg, p.won, (int)n_rows, c->N, c->tmp_on));
-      PROPAGATE(wide_forward(c, which, c->tmp_z1, c->tmp_rowinfo, n_rows, false, c->tmp_out, c->tmp_on));
-    } else {
-      PROPAGATE(first_layer(c, p, c->tmp_cfg, c->tmp_z1, (int)n_rows));
-      if (c->rbm) HIPCHK(c, launch_onsite(c->stream, c->tmp_cfg, p.won, (int)n_rows, c->N, c->tmp_on));
-      TailArgs a = tail_args(c, which);
-      a.z1 = c->tmp_z1; a.on_base = c->tmp_on; a.n_rows = (int)n_rows; a.out = c->tmp_out; a.rowinfo = c->tmp_rowinfo;
-      HIPCHK(c, launch_rows(c, which, a, false));
-    }
+    PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, n_rows, c->tmp_out, c->tmp_sign));
     HIPCHK(c, hipMemcpyAsync(host.data(), c->tmp_out, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (c->sgn)
+      HIPCHK(c, hipMemcpyAsync(hsign.data(), c->tmp_sign, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const float shift = c->ps[which].shift;

@@ -188,6 +188,11 @@ struct vmc_ctx {
   float *corr_val = nullptr, *corr_dense = nullptr;  // [B corr_cap] rows; [B][pairs of the pass] the rows by (chain, pair)
   double* corr_out = nullptr;                        // [2][corr_cap_all] zz sums, exchange sums
   long long corr_cap = 0, corr_cap_all = 0;
+  // Renyi-2 swap estimator (vmc_api_renyi.hip): the region masks of a call and its sums; the rows of a pass live in the
+  // tmp_* buffers of vmc_amplitude (grow_tmp)
+  unsigned char* renyi_mask = nullptr;               // [renyi_cap][N] 0/1
+  double* renyi_out = nullptr;                       // [2][renyi_cap] swap sums, match counts
+  long long renyi_cap = 0;
   // gradient path
   std::vector<float*> act;   // L views [B][Hp] into act_all
   float* act_all = nullptr;  // [L][B][Hp]
@@ -430,6 +435,9 @@ int local_energy_device(vmc_ctx* c, int which, bool defer_reduce = false, bool* 
 int connected_rows_device(vmc_ctx* c, int which, bool share_cus);
 int grow_tmp(vmc_ctx* c, long long rows);
 int pbdg_check_sz(vmc_ctx* c, const float* configs, long long n_rows);
+// the full forward on n_rows rows of a device buffer of configurations -> log|psi| and, for the signed types, the sign per
+// row (vmc_amplitude, vmc_renyi2_swap); ensure_packed and grow_tmp(n_rows) have run
+int rows_forward_device(vmc_ctx* c, int which, const float* configs, long long n_rows, float* logit, float* sign);
 // neural-network backflow: rows {chain, bond} of a row list over `configs` and the chains' first-layer cache z1 -> logits
 // and signs (ratio == false) or the local-energy terms (ratio: out = val, out_sign unused), in blocks of c->nnb_rows
 int nnb_forward(vmc_ctx* c, int which, const float* z1, const float* configs, const int2* rowinfo, long long n_rows,

@@ -336,6 +336,24 @@ class VmcEngine:
                                                 zz.ctypes.data_as(dp), ex.ctypes.data_as(dp)))
     return zz, ex
 
+  def renyi2_swap(self, regions, which: int = _hip.VMC_PSI, regions_per_pass: int = 0):
+    """Replica swap estimator of the second Renyi entropy over the current chains (extension, vmc_renyi2_swap).
+    `regions`: a [n_regions][n_sites] 0/1 array, or a list of site lists.  The chains are the batch_size / 2 replica
+    pairs (c, c + batch_size / 2); returns (swap_sum, match_count), float64 [n_regions]: the sum over the pairs that
+    hold equal magnetisation on the region of psi(x~) psi(y~) / (psi(x) psi(y)) with the region's spins exchanged, and
+    the number of such pairs.  Tr rho_A^2 ~ swap_sum / (batch_size / 2), S2 = -ln of it.  Moves no chain, touches neither
+    the step counter nor the accumulators nor the Hamiltonian; regions_per_pass = 0 leaves the pass size to the library."""
+    from . import lattice
+    mask = lattice.region_masks(regions, self.n_sites)
+    if mask.shape[0] < 1:
+      raise ValueError('renyi2_swap needs at least one region')
+    swap = np.empty(mask.shape[0], np.float64)
+    match = np.empty(mask.shape[0], np.float64)
+    dp = C.POINTER(C.c_double)
+    self._check(self._lib.vmc_renyi2_swap(self._ctx, int(which), mask.shape[0], mask.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                          int(regions_per_pass), swap.ctypes.data_as(dp), match.ctypes.data_as(dp)))
+    return swap, match
+
   def last_connected_rows(self) -> int:
     v = C.c_int64()
     self._check(self._lib.vmc_last_connected_rows(self._ctx, C.byref(v)))

@@ -178,6 +178,82 @@ class SpinCorrelationEvaluator(WavefunctionEvaluator):
     return out
 
 
+class RenyiSwapTensor(session_lib.Tensor):
+  """(swap_sum, match_count) [n_regions] float64 of `regions` over THIS rank's chains, paired (c, c + local batch / 2)
+  (VmcEngine.renyi2_swap); `masks` [n_regions][num_sites] uint8."""
+
+  def __init__(self, engine, regions, which: int, num_sites: int):
+    from . import lattice
+    self.engine, self.which = engine, which
+    self.masks = lattice.region_masks(regions, num_sites)
+    super(RenyiSwapTensor, self).__init__(self._value, 'renyi2_swap')
+
+  def _value(self):
+    return self.engine.renyi2_swap(self.masks, self.which)
+
+
+class RenyiEntropyEvaluator(WavefunctionEvaluator):
+  """Second Renyi entanglement entropy S2(A) = -ln Tr rho_A^2 by the replica swap estimator over MCMC chains
+  (extension: the reference evaluates the energy alone).  The signatures are MonteCarloOperatorEvaluator's; `operator`
+  is the regions -- a [n_regions][num_sites] 0/1 array or a list of site lists (None: lattice.block_regions, the
+  blocks [0, l), l = 1 .. N / 2)."""
+
+  def build_eval_ops(self, wavefunction, operator, hparams,
+                     shared_resources: Dict[graph_builders.ResourceName, Any]) -> EvalOps:
+    from . import lattice
+    batch_size = hparams.batch_size
+    n_sites = hparams.num_sites
+    regions = lattice.block_regions(n_sites) if operator is None else operator
+    configs = graph_builders.get_configs(shared_resources, batch_size, n_sites)
+    mc_step, acc_rate = graph_builders.get_monte_carlo_sampling(shared_resources, configs, wavefunction)
+    engine = wavefunction._bind(configs)
+    return EvalOps(
+        value=RenyiSwapTensor(engine, regions, wavefunction._which, n_sites),
+        mc_step=mc_step,
+        acceptance_rate=acc_rate,
+        placeholder_input=None,
+        wavefunction_value=None,
+    )
+
+  def run_evaluation(self, eval_ops: EvalOps, session, hparams, epoch_num: int) -> Dict[str, np.ndarray]:
+    """Thermalises for num_equilibration_sweeps sweeps, then takes num_evaluation_samples measurements,
+    num_monte_carlo_sweeps sweeps apart (the loop of MonteCarloOperatorEvaluator).  A measurement pairs the chains of
+    every rank among themselves, (c, c + local batch / 2): both replicas of a pair live on one rank, and their Philox
+    streams are keyed by the global chain id, so they are independent.  With sharded chains the per-sample fp64 swap
+    sums, match counts and pair counts of the ranks are added by parallel.allreduce_array before the division.
+    Returns a dict: 'regions' [n_regions][num_sites] masks; 'purity' = mean over the samples of swap_sum / pairs;
+    'purity_err', the conventional standard error of that mean, std(ddof = 1) / sqrt(n_samples) of the batch means (0
+    for a single sample); 's2' = -ln purity; 's2_err' = purity_err / purity; 'match_fraction', the mean share of pairs
+    that hold equal magnetisation on the region; 'samples' [n_samples][n_regions], the batch means themselves."""
+    del epoch_num
+    value = eval_ops.value
+    steps_per_sweep = hparams.num_sites
+    decorrelation = hparams.num_monte_carlo_sweeps * steps_per_sweep
+    n_samples = hparams.num_evaluation_samples
+    sharded = parallel.world_size() > 1
+    n_regions = value.masks.shape[0]
+    self.acceptance_count = 0
+    samples = np.empty((n_samples, n_regions), np.float64)
+    matched = np.empty((n_samples, n_regions), np.float64)
+    _run_mc_steps(session, eval_ops.mc_step, hparams.num_equilibration_sweeps * steps_per_sweep)
+    for s in range(n_samples):
+      swap, match = session.run(value)                   # of this rank's chains
+      sums = np.empty((3, n_regions), np.float64)
+      sums[0], sums[1], sums[2] = swap, match, value.engine.batch_size // 2
+      if sharded:
+        sums = parallel.allreduce_array(sums)
+      samples[s] = sums[0] / sums[2]
+      matched[s] = sums[1] / sums[2]
+      _run_mc_steps(session, eval_ops.mc_step, decorrelation)
+      self.acceptance_count += getattr(eval_ops.mc_step, 'last_accepted', 0)
+    purity = samples.mean(axis=0)
+    err = samples.std(axis=0, ddof=1) / np.sqrt(n_samples) if n_samples > 1 else np.zeros(n_regions)
+    with np.errstate(divide='ignore', invalid='ignore'):
+      s2, s2_err = -np.log(purity), err / purity
+    return {'regions': value.masks.copy(), 'purity': purity, 'purity_err': err, 's2': s2, 's2_err': s2_err,
+            'match_fraction': matched.mean(axis=0), 'samples': samples}
+
+
 class VectorWavefunctionEvaluator(WavefunctionEvaluator):
   """evaluation.py:155-246: dumps psi over a basis file.  Offline tool outside the hot path
   (SURVEY.md 2); `Wavefunction.__call__` on an array gives the same amplitudes."""

@@ -71,6 +71,55 @@ def structure_factor(ss, pairs, coords, qs):
   return (0.75 * n + 2.0 * np.cos(qs @ dr.T) @ ss) / n
 
 
+def block_regions(num_sites, max_len=None):
+  """The contiguous blocks [0, l), l = 1 .. max_len (default num_sites // 2), as a list of site lists: the regions
+  whose second Renyi entropy a chain's (or a row-major cluster's) entanglement scaling is read from."""
+  max_len = num_sites // 2 if max_len is None else int(max_len)
+  if max_len < 0 or max_len > num_sites:
+    raise ValueError('block_regions: max_len {} outside 0 .. {}'.format(max_len, num_sites))
+  return [list(range(l)) for l in range(1, max_len + 1)]
+
+
+def read_regions(path):
+  """Regions from a text file: one region per line as site indices separated by blanks or commas; `#` starts a
+  comment, a line without any index is skipped (the empty region cannot be written: pass it as [])."""
+  regions = []
+  with open(path) as f:
+    for number, line in enumerate(f, 1):
+      fields = line.split('#', 1)[0].replace(',', ' ').split()
+      if not fields:
+        continue
+      try:
+        regions.append([int(x) for x in fields])
+      except ValueError:
+        raise ValueError('{}:{}: a region is a line of integer site indices, got {!r}'.format(path, number, line.strip()))
+  return regions
+
+
+def region_masks(regions, num_sites):
+  """[n_regions][num_sites] uint8 0/1 masks of `regions`: a two-dimensional array of zeros and ones (or booleans) with
+  num_sites columns is taken as the masks themselves, anything else as a list of site lists (a site out of range or
+  named twice: ValueError)."""
+  if isinstance(regions, np.ndarray) and regions.ndim == 2 and regions.shape[1] == num_sites \
+      and (regions.dtype == np.bool_ or (np.issubdtype(regions.dtype, np.number) and np.isin(regions, (0, 1)).all())):
+    return np.ascontiguousarray(regions.astype(np.uint8))
+  if isinstance(regions, np.ndarray) and regions.dtype == np.bool_:
+    raise ValueError('region masks must have shape [n_regions][{}], got {}'.format(num_sites, regions.shape))
+  regions = list(regions)
+  masks = np.zeros((len(regions), num_sites), np.uint8)
+  for k, region in enumerate(regions):
+    sites = np.asarray(region)
+    if sites.size and not np.issubdtype(sites.dtype, np.integer):
+      raise ValueError('region {}: site indices must be integers'.format(k))
+    sites = sites.astype(np.int64).ravel()
+    if sites.size and (sites.min() < 0 or sites.max() >= num_sites):
+      raise ValueError('region {}: site index out of range 0 .. {}'.format(k, num_sites - 1))
+    if np.unique(sites).size != sites.size:
+      raise ValueError('region {}: a site is named twice (a 0/1 mask must have {} columns)'.format(k, num_sites))
+    masks[k, sites] = 1
+  return masks
+
+
 def load_bonds(checkpoint_dir, n_sites):
   """run_training.py:103-109 / run_energy_evaluation.py:51-57: `J.txt` of integer pairs
   (extra columns ignored), else the periodic chain."""

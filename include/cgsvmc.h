@@ -377,6 +377,28 @@ int vmc_pair_correlations(vmc_ctx* ctx, int which, int32_t n_pairs, const int32_
                           int32_t pairs_per_pass /*0: planner's choice*/,
                           double* zz_sum /*[n_pairs]*/, double* ex_sum /*[n_pairs]*/);
 
+/* Renyi-2 entanglement entropy by the replica swap estimator -- EXTENSION with no reference counterpart.  The ctx's chains
+ * are taken as B / 2 replica pairs (c, c + B / 2) (batch_size must be even).  For every region A of `region_mask` (one 0/1
+ * byte per site) a pair MATCHES when both chains hold the same sum of spins on A; x~ is x_c with the sites of A taken from
+ * x_{c + B/2}, y~ the other way round.  With l = ln|psi|:
+ *   swap_sum[A]    = sum over matching pairs of sigma exp((l(x~) + l(y~)) - (l(x_c) + l(x_{c + B/2})))   (pairs ascending, fp64)
+ *   match_count[A] = the number of matching pairs
+ * so that Tr rho_A^2 ~ swap_sum / (B / 2) and S2 = -ln of it; either array may be NULL.  sigma is the product of the four
+ * signs for the signed types (pbdg, fully_connected_nnb, ed_vector) and 1 otherwise; a pair that does not match would
+ * leave the Sz = 0 sector (psi = 0) and contributes 0, and so does a pair with a vanishing amplitude among the four
+ * (exactly 0, never NaN).  The swapped rows go through the full forward of the ctx's ansatz type (the device path of
+ * vmc_amplitude); the chains' own l and signs are the ctx's cache.  The regions run in passes of at most regions_per_pass
+ * regions (0: as many as the row budget of a pass takes; a request is clamped to it); the sums of a region do not depend
+ * on the passes or on the other regions of the call.  The empty region and the full set of sites are legal (both give
+ * B / 2 and B / 2).  A pure measurement: chains, step counter, accumulators, the Hamiltonian's bonds and the validity of the
+ * amplitude and activation caches are as before on return.  Odd batch_size, n_regions < 1, a NULL mask, which outside
+ * {0, 1}, regions_per_pass < 0: VMC_ERR_INVALID, before anything touches the device; an output activation other than
+ * exp on an unsigned type (the logit is then not ln psi) and a product ctx: VMC_ERR_UNSUPPORTED; a factor of a product
+ * ctx: VMC_ERR_STATE, as every chain-state entry. */
+int vmc_renyi2_swap(vmc_ctx* ctx, int which, int32_t n_regions, const uint8_t* region_mask /*[n_regions][N], 0/1*/,
+                    int32_t regions_per_pass /*0: planner's choice*/,
+                    double* swap_sum /*[n_regions]*/, double* match_count /*[n_regions]*/);
+
 /* Stochastic reconfiguration -- EXTENSION: named by the north star, absent from the reference
  * (training.py has only the plain energy gradient + Adam), so these entries replace no reference
  * interface; they sit where TrainOpsTraditional.apply_gradients (training.py:560-567) sits.
