@@ -332,6 +332,22 @@ hipError_t launch_swap_fold(hipStream_t s, const float* configs, const unsigned 
                             const float* sign, const float* row_logit, const float* row_sign, int B, int N,
                             int n_regions, double* swap_sum, double* match_count);
 
+// dimer-dimer correlations (dimer.hip).  bonds [..] site pairs, pairs [..] (a, b) indices into bonds.  Rows of phase 1:
+// row = bond x B + chain, the exchanged configuration where the bond is antiparallel, the chain's own elsewhere; of a
+// pass of phase 2: row = pair x B + chain, swap_kl swap_ij x where both exchanges act, the chain's own elsewhere.  The
+// folds give one thread per bond / pair over the chains in ascending order, fp64.  logit / sign [B]: the chains' own;
+// one_logit / one_sign [n_bonds][B]: phase 1's rows; two_logit / two_sign [n_pairs][B]: the pass's; signs null: unsigned
+hipError_t launch_dimer_rows1(hipStream_t s, const float* configs, const int2* bonds, int B, int N, int n_bonds,
+                              int num_cus, float* rows);
+hipError_t launch_dimer_rows2(hipStream_t s, const float* configs, const int2* bonds, const int2* pairs, int B, int N,
+                              int n_pairs, int num_cus, float* rows);
+hipError_t launch_dimer_bond_fold(hipStream_t s, const float* configs, const int2* bonds, const float* logit,
+                                  const float* sign, const float* one_logit, const float* one_sign, int B, int N,
+                                  int n_bonds, double* bond_sum);
+hipError_t launch_dimer_fold(hipStream_t s, const float* configs, const int2* bonds, const int2* pairs,
+                             const float* logit, const float* sign, const float* one_logit, const float* one_sign,
+                             const float* two_logit, const float* two_sign, int B, int N, int n_pairs, double* dd_sum);
+
 // gradient path (grad.hip)
 struct GemmArgs {
   const float* A; long long sam, sak;   // A(m,k) = A[m*sam + k*sak]

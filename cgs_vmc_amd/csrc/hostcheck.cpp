@@ -844,10 +844,50 @@ static void renyi_grid() {
         plan_renyi_regions_per_pass(2, 1, -1) == 0 && plan_renyi_regions_per_pass(2, 1, 0, -1) == 0);
 }
 
+// dimer-dimer correlations (plan_dimer_*): both phases' passes inside the row budget, the 32-bit row index and the ctx's
+// row limit (one item is always taken), the passes cover the items exactly, a request only ever shrinks a pass, the fold
+// grid covers a pass, every index into the [n_bonds][B] buffer of phase 1 and into a pass's rows x sites fits 32 bits
+static void dimer_grid() {
+  for (long long B : {1LL, 40LL, 64LL, 1000LL, 4096LL, 65536LL, 1LL << 24, (1LL << 24) + 1, 1LL << 30, (1LL << 30) + 1, 0x7fffffffLL})
+    for (long long n_items : {1LL, 7LL, 34LL, 70LL, 200LL, 1024LL, 40000LL, 523776LL})
+      for (long long req : {0LL, 1LL, 7LL, 64LL, 70LL, 1LL << 40})
+        for (long long lim : {0LL, 1LL, 4096LL, 100000LL, 1LL << 22, 1LL << 40}) {
+          const int per = plan_dimer_pairs_per_pass(B, n_items, req, lim);
+          if (2 * B > 0x7fffffffLL) { CHECK(per == 0); CHECK(!plan_dimer_bond_rows_ok(B, n_items)); continue; }
+          CHECK(per >= 1 && per <= n_items);
+          CHECK(B * per <= 0x7fffffffLL - B);
+          CHECK(B * per <= PLAN_CORR_ROW_BUDGET || per == 1);
+          if (lim > 0) CHECK(B * per <= lim || per == 1);
+          if (req > 0) CHECK(per <= req);
+          CHECK(per <= plan_dimer_pairs_per_pass(B, n_items, 0, lim));
+          CHECK(per <= plan_dimer_pairs_per_pass(B, n_items, req, 0));
+          const long long passes = plan_dimer_passes(n_items, per);
+          CHECK(passes * per >= n_items && (passes - 1) * per < n_items);
+          CHECK((long long)plan_dimer_fold_grid(per) * 64 >= per && ((long long)plan_dimer_fold_grid(per) - 1) * 64 < per);
+          CHECK((long long)plan_dimer_fold_grid((int)n_items) * 64 >= n_items);          // the bond fold takes every bond at once
+          if (plan_dimer_bond_rows_ok(B, n_items)) CHECK(B * n_items + B <= 0x7fffffffLL);
+          else CHECK(B * n_items + B > 0x7fffffffLL);
+        }
+  for (int N : {2, 16, 100, 1024, 4096})
+    for (int Hp : {64, 256, 512, 4096}) {
+      const long long rows = plan_dimer_row_limit(N, Hp);
+      CHECK(rows >= 1 && rows == plan_renyi_row_limit(N, Hp));
+      CHECK(rows * (N > Hp ? N : Hp) <= 0x7fffffffLL);
+    }
+  // config 3's shape, one reference bond against the 200 bonds: each phase is one pass of 819,200 rows
+  CHECK(plan_dimer_pairs_per_pass(4096, 200, 0, plan_dimer_row_limit(100, 256)) == 200);
+  CHECK(plan_dimer_pairs_per_pass(40, 70, 0) == 70 && plan_dimer_pairs_per_pass(40, 70, 7) == 7 && plan_dimer_pairs_per_pass(40, 70, 64) == 64);
+  CHECK(plan_dimer_pairs_per_pass(40, 1024, 0, 100) == 2 && plan_dimer_pairs_per_pass(40, 1024, 0, 10) == 1);
+  CHECK(plan_dimer_pairs_per_pass(40, 0, 0) == 0 && plan_dimer_pairs_per_pass(0, 1, 0) == 0 &&
+        plan_dimer_pairs_per_pass(40, 1, -1) == 0 && plan_dimer_pairs_per_pass(40, 1, 0, -1) == 0);
+  CHECK(!plan_dimer_bond_rows_ok(40, 0) && !plan_dimer_bond_rows_ok(0, 1) && plan_dimer_bond_rows_ok(40, 34));
+}
+
 int main() {
   check_block_maps();
   corr_grid();
   renyi_grid();
+  dimer_grid();
   prod_grid();
   edvec_grid();
   nnb_grid();

@@ -690,6 +690,23 @@ inline long long plan_renyi_row_limit(int N, int Hp) {
 inline long long plan_renyi_passes(long long n_regions, int per) { return per < 1 ? 0 : (n_regions + per - 1) / per; }
 inline unsigned plan_renyi_fold_grid(int regions) { return (unsigned)((regions + 63) / 64); }    // 64 threads, one region each
 
+// ------------------------------------------------------------------------------- dimer-dimer correlations (vmc_api_dimer.hip, dimer.hip)
+// Phase 1 hands B rows per bond (row = bond x B + chain) to the family's full forward and keeps every row's ln|psi| in
+// a buffer [n_bonds][B]; phase 2 hands B rows per pair of a pass (row = pair x B + chain).  Both run in passes under the
+// rules of the Renyi-2 rows: the row budget, the 32-bit row index (B x items <= 2^31 - 1 - B), the ctx's row limit, at
+// least one item, requested > 0: at most that many.  0: not even one item fits the row index, or an argument is out of
+// range (n_items < 1 included: a call without pairs runs no phase 2 and does not ask).
+inline int plan_dimer_pairs_per_pass(long long B, long long n_items, long long requested, long long row_limit = 0) {
+  return plan_renyi_regions_per_pass(B, n_items, requested, row_limit);
+}
+inline long long plan_dimer_row_limit(int N, int Hp) { return plan_renyi_row_limit(N, Hp); }
+// the phase-1 buffer is indexed bond x B + chain by the fold: all of its rows stay within the 32-bit row index
+inline bool plan_dimer_bond_rows_ok(long long B, long long n_bonds) {
+  return B >= 1 && n_bonds >= 1 && n_bonds <= (0x7fffffffLL - B) / B;
+}
+inline long long plan_dimer_passes(long long n_items, int per) { return per < 1 ? 0 : (n_items + per - 1) / per; }
+inline unsigned plan_dimer_fold_grid(int items) { return (unsigned)((items + 63) / 64); }    // 64 threads, one pair (or bond) each
+
 // ------------------------------------------------------------------------------- vmc_create
 struct DescPlan {
   int rbm, conv, resnet, one_d;

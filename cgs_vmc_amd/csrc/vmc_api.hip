@@ -1,8 +1,8 @@
 // Host side of libcgsvmc_hip.so: the C ABI of include/cgsvmc.h on top of the gfx950 kernels.  One vmc_ctx per GPU, all
 // work on ctx->stream.  This file: ctx life cycle, parameters, chains, amplitudes, local energies, timing; the other
 // entry points live in vmc_api_sweep.hip (samplers), vmc_api_train.hip (accumulators, Adam, epochs, evaluation),
-// vmc_api_coll.hip (collectives), vmc_api_sr.hip (stochastic reconfiguration), vmc_api_corr.hip and vmc_api_renyi.hip (the
-// measurements beside the energy: spin correlations, Renyi-2 entropy), vmc_api_prod.hip (product ctxs); vmc_api_cgen.hip is
+// vmc_api_coll.hip (collectives), vmc_api_sr.hip (stochastic reconfiguration), vmc_api_corr.hip, vmc_api_renyi.hip and vmc_api_dimer.hip (the
+// measurements beside the energy: spin correlations, Renyi-2 entropy, dimer-dimer correlations), vmc_api_prod.hip (product ctxs); vmc_api_cgen.hip is
 // the general convolution path's machinery.  Shared state and helpers: vmc_ctx.hpp.
 #include "vmc_ctx.hpp"
 
@@ -737,6 +737,8 @@ void vmc_destroy(vmc_ctx* c) {
   for (void* q : {(void*)c->corr_pairs, (void*)c->corr_hx, (void*)c->corr_qz, (void*)c->corr_rowinfo, (void*)c->corr_val,
                   (void*)c->corr_dense, (void*)c->corr_out}) if (q) hipFree(q);
   for (void* q : {(void*)c->renyi_mask, (void*)c->renyi_out}) if (q) hipFree(q);
+  for (void* q : {(void*)c->dimer_bonds, (void*)c->dimer_pairs, (void*)c->dimer_logit, (void*)c->dimer_sign,
+                  (void*)c->dimer_out}) if (q) hipFree(q);
   for (float* q : {c->sr_ctape, c->sr_cdelta, c->sr_cws, c->sr_cw0, c->sr_cwf, c->sr_cwb, c->sr_cbias}) if (q) hipFree(q);
   void* sr[] = {c->sr_cfg, c->sr_act, c->sr_delta, c->sr_ws, c->sr_t, c->sr_u, c->sr_x, c->sr_r,
                 c->sr_p, c->sr_q, c->sr_partial, c->sr_sc, c->sr_ones, c->sr_tpart};

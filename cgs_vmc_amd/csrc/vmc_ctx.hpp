@@ -193,6 +193,13 @@ struct vmc_ctx {
   unsigned char* renyi_mask = nullptr;               // [renyi_cap][N] 0/1
   double* renyi_out = nullptr;                       // [2][renyi_cap] swap sums, match counts
   long long renyi_cap = 0;
+  // dimer-dimer correlations (vmc_api_dimer.hip): the two lists of a call, ln|psi| (and, signed types, the sign) of
+  // every single exchange, and the sums; the rows of a pass live in the tmp_* buffers of vmc_amplitude (grow_tmp)
+  int2* dimer_bonds = nullptr;                       // [dimer_cap_bonds] sites (i, j)
+  int2* dimer_pairs = nullptr;                       // [dimer_cap_pairs] indices (a, b) into dimer_bonds
+  float *dimer_logit = nullptr, *dimer_sign = nullptr;   // [dimer_cap_bonds][B]; dimer_sign: signed types only
+  double* dimer_out = nullptr;                       // [dimer_cap_bonds + dimer_cap_pairs] bond sums, then dd sums
+  long long dimer_cap_bonds = 0, dimer_cap_pairs = 0;
   // gradient path
   std::vector<float*> act;   // L views [B][Hp] into act_all
   float* act_all = nullptr;  // [L][B][Hp]

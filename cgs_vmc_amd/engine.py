@@ -354,6 +354,25 @@ class VmcEngine:
                                           int(regions_per_pass), swap.ctypes.data_as(dp), match.ctypes.data_as(dp)))
     return swap, match
 
+  def dimer_correlations(self, bonds, pairs=None, which: int = _hip.VMC_PSI, pairs_per_pass: int = 0):
+    """Dimer-dimer correlations over the current chains (extension, vmc_dimer_correlations).  `bonds`: [n_bonds][2]
+    site pairs; `pairs`: [n_pairs][2] indices (a, b) into `bonds` (None: all n_bonds^2 ordered pairs, a-major).  Returns
+    (bond_sum [n_bonds], dd_sum [n_pairs]), float64: the sums over the chains of the local values of S_i . S_j and of
+    (S_i . S_j)(S_k . S_l), so that <A B> ~ dd_sum / batch_size and <A> ~ bond_sum / batch_size.  Moves no chain, touches
+    neither the step counter nor the accumulators nor the Hamiltonian; pairs_per_pass = 0 leaves the pass size to the
+    library."""
+    from . import lattice
+    ij = np.ascontiguousarray(np.asarray(bonds, dtype=np.int32).reshape(-1, 2))
+    ab = lattice.all_bond_pairs(ij.shape[0]) if pairs is None else \
+        np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    bond_sum = np.empty(ij.shape[0], np.float64)
+    dd_sum = np.empty(ab.shape[0], np.float64)
+    dp = C.POINTER(C.c_double)
+    self._check(self._lib.vmc_dimer_correlations(self._ctx, int(which), ij.shape[0], _iptr(ij), ab.shape[0], _iptr(ab),
+                                                 int(pairs_per_pass), bond_sum.ctypes.data_as(dp),
+                                                 dd_sum.ctypes.data_as(dp)))
+    return bond_sum, dd_sum
+
   def last_connected_rows(self) -> int:
     v = C.c_int64()
     self._check(self._lib.vmc_last_connected_rows(self._ctx, C.byref(v)))

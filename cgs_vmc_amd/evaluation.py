@@ -254,6 +254,95 @@ class RenyiEntropyEvaluator(WavefunctionEvaluator):
             'match_fraction': matched.mean(axis=0), 'samples': samples}
 
 
+class DimerCorrelationTensor(session_lib.Tensor):
+  """(bond_sum [n_bonds], dd_sum [n_pairs]) float64 of `bonds` and of the pairs (a, b) of them over THIS rank's chains
+  (VmcEngine.dimer_correlations); `global_batch` is the number of chains of all ranks together."""
+
+  def __init__(self, engine, bonds, pairs, which: int, global_batch: int):
+    from . import lattice
+    self.engine, self.which, self.global_batch = engine, which, int(global_batch)
+    self.bonds = np.ascontiguousarray(np.asarray(bonds, np.int32).reshape(-1, 2))
+    self.pairs = lattice.all_bond_pairs(self.bonds.shape[0]) if pairs is None else \
+        np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+    if self.bonds.shape[0] < 1:
+      raise ValueError('dimer correlations need at least one bond')
+    if self.pairs.size and (self.pairs.min() < 0 or self.pairs.max() >= self.bonds.shape[0]):
+      raise ValueError('a pair names a bond outside 0 .. {}'.format(self.bonds.shape[0] - 1))
+    super(DimerCorrelationTensor, self).__init__(self._value, 'dimer_correlations')
+
+  def _value(self):
+    return self.engine.dimer_correlations(self.bonds, self.pairs, self.which)
+
+
+class DimerCorrelationEvaluator(WavefunctionEvaluator):
+  """<(S_i . S_j)(S_k . S_l)> by running MCMC (extension: the reference evaluates the energy alone).  The signatures are
+  MonteCarloOperatorEvaluator's; `operator` is (bonds, pairs): bonds [(i, j), ...] and pairs [(a, b), ...] of indices
+  into them (pairs None: all ordered pairs).  operator None: the Hamiltonian's bonds (`J.txt` of hparams.checkpoint_dir,
+  else the periodic chain), each paired with bond 0."""
+
+  def build_eval_ops(self, wavefunction, operator, hparams,
+                     shared_resources: Dict[graph_builders.ResourceName, Any]) -> EvalOps:
+    from . import lattice
+    batch_size = hparams.batch_size
+    n_sites = hparams.num_sites
+    if operator is None:
+      bonds = lattice.load_bonds(getattr(hparams, 'checkpoint_dir', '') or '', n_sites)
+      pairs = [(0, b) for b in range(len(bonds))]
+    else:
+      bonds, pairs = operator
+    configs = graph_builders.get_configs(shared_resources, batch_size, n_sites)
+    mc_step, acc_rate = graph_builders.get_monte_carlo_sampling(shared_resources, configs, wavefunction)
+    engine = wavefunction._bind(configs)
+    return EvalOps(
+        value=DimerCorrelationTensor(engine, bonds, pairs, wavefunction._which, batch_size),
+        mc_step=mc_step,
+        acceptance_rate=acc_rate,
+        placeholder_input=None,
+        wavefunction_value=None,
+    )
+
+  def run_evaluation(self, eval_ops: EvalOps, session, hparams, epoch_num: int) -> Dict[str, np.ndarray]:
+    """Thermalises for num_equilibration_sweeps sweeps, then takes num_evaluation_samples measurements,
+    num_monte_carlo_sweeps sweeps apart (the loop of MonteCarloOperatorEvaluator).  A measurement is the batch mean,
+    over the chains of ALL ranks, of the local value of S_i . S_j per bond and of (S_i . S_j)(S_k . S_l) per pair: with
+    sharded chains the per-sample fp64 sums of the ranks are added by parallel.allreduce_array before the division by
+    the global batch.  Returns a dict: 'bonds' [n_bonds][2]; 'pairs' [n_pairs][2]; 'bond' [n_bonds] = <A>; 'dd' [n_pairs]
+    = <A B>; 'connected' [n_pairs] = <A B> - <A><B>, formed per sample from that sample's batch means; under name +
+    '_err' the conventional standard error of each mean, std(ddof = 1) / sqrt(n_samples) of the batch means (0 for a
+    single sample); 'samples' [n_samples][2][n_pairs], the batch means of dd and connected, and 'bond_samples'
+    [n_samples][n_bonds]."""
+    del epoch_num
+    value = eval_ops.value
+    steps_per_sweep = hparams.num_sites
+    decorrelation = hparams.num_monte_carlo_sweeps * steps_per_sweep
+    n_samples = hparams.num_evaluation_samples
+    sharded = parallel.world_size() > 1
+    n_bonds, n_pairs = value.bonds.shape[0], value.pairs.shape[0]
+    self.acceptance_count = 0
+    samples = np.empty((n_samples, 2, n_pairs), np.float64)
+    bond_samples = np.empty((n_samples, n_bonds), np.float64)
+    _run_mc_steps(session, eval_ops.mc_step, hparams.num_equilibration_sweeps * steps_per_sweep)
+    for s in range(n_samples):
+      sums = np.concatenate(session.run(value)).astype(np.float64)      # [n_bonds + n_pairs] of this rank's chains
+      if sharded:
+        sums = parallel.allreduce_array(sums)
+      bond = sums[:n_bonds] / value.global_batch
+      bond_samples[s] = bond
+      samples[s, 0] = sums[n_bonds:] / value.global_batch
+      samples[s, 1] = samples[s, 0] - bond[value.pairs[:, 0]] * bond[value.pairs[:, 1]]
+      _run_mc_steps(session, eval_ops.mc_step, decorrelation)
+      self.acceptance_count += getattr(eval_ops.mc_step, 'last_accepted', 0)
+
+    def err(x):
+      return x.std(axis=0, ddof=1) / np.sqrt(n_samples) if n_samples > 1 else np.zeros(x.shape[1])
+    out = {'bonds': value.bonds.copy(), 'pairs': value.pairs.copy(), 'samples': samples, 'bond_samples': bond_samples,
+           'bond': bond_samples.mean(axis=0), 'bond_err': err(bond_samples)}
+    for k, name in enumerate(('dd', 'connected')):
+      out[name] = samples[:, k].mean(axis=0)
+      out[name + '_err'] = err(samples[:, k])
+    return out
+
+
 class VectorWavefunctionEvaluator(WavefunctionEvaluator):
   """evaluation.py:155-246: dumps psi over a basis file.  Offline tool outside the hot path
   (SURVEY.md 2); `Wavefunction.__call__` on an array gives the same amplitudes."""

@@ -120,6 +120,97 @@ def region_masks(regions, num_sites):
   return masks
 
 
+def all_bond_pairs(n_bonds):
+  """Every ordered pair (a, b) of n_bonds bonds, a == b included: [n_bonds^2][2] int32, a-major."""
+  a, b = np.divmod(np.arange(n_bonds * n_bonds), max(n_bonds, 1))
+  return np.ascontiguousarray(np.stack([a, b], axis=1).astype(np.int32))
+
+
+def read_bond_pairs(path):
+  """(bonds, pairs) from a text file for the dimer-dimer correlations: a line `i j` names a bond, a line `i j k l` the
+  pair of the bonds (i, j) and (k, l); blanks or commas separate, `#` starts a comment, a line without any index is
+  skipped.  bonds: the distinct (i, j), as written, in the order of their first appearance; pairs: (a, b) indices into
+  bonds, one per four-index line, in the file's order (empty when the file names bonds only)."""
+  bonds, index, pairs = [], {}, []
+
+  def bond(i, j):
+    if (i, j) not in index:
+      index[(i, j)] = len(bonds)
+      bonds.append([i, j])
+    return index[(i, j)]
+  with open(path) as f:
+    for number, line in enumerate(f, 1):
+      fields = line.split('#', 1)[0].replace(',', ' ').split()
+      if not fields:
+        continue
+      try:
+        sites = [int(x) for x in fields]
+      except ValueError:
+        sites = []
+      if len(sites) not in (2, 4):
+        raise ValueError('{}:{}: a line is a bond `i j` or a pair of bonds `i j k l` of integer site indices, got {!r}'
+                         .format(path, number, line.strip()))
+      a = bond(sites[0], sites[1])
+      if len(sites) == 4:
+        pairs.append([a, bond(sites[2], sites[3])])
+  return bonds, pairs
+
+
+def bond_orientations(bonds, size_x, size_y=1):
+  """(axis [n_bonds], origin [n_bonds]) of `bonds` on the size_x x size_y torus of torus_bonds (site = x + size_x * y;
+  size_y = 1: the periodic chain): axis 0 / 1 for a nearest-neighbour bond along x / y with `origin` the site it leaves
+  in the positive direction, axis -1 (origin -1) for any other pair of sites."""
+  bonds = np.asarray(bonds, np.int64).reshape(-1, 2)
+  axis = np.full(len(bonds), -1, np.int64)
+  origin = np.full(len(bonds), -1, np.int64)
+  for n, (i, j) in enumerate(bonds.tolist()):
+    for s, t in ((i, j), (j, i)):
+      xs, ys, xt, yt = s % size_x, s // size_x, t % size_x, t // size_x
+      if axis[n] < 0 and ys == yt and xt == (xs + 1) % size_x and size_x > 1:
+        axis[n], origin[n] = 0, s
+      if axis[n] < 0 and xs == xt and yt == (ys + 1) % size_y and size_y > 1:
+        axis[n], origin[n] = 1, s
+  return axis, origin
+
+
+def dimer_structure_factor(bonds, pairs, connected, size_x, size_y=1, qs=None):
+  """Dimer structure factors of the nearest-neighbour bonds of the size_x x size_y torus (size_y = 1: the periodic
+  chain) from connected [n_pairs] = <A B> - <A><B> of the bond pairs `pairs` [n_pairs][2] (indices into `bonds`):
+    D_alpha(q) = (1 / n_alpha) sum over the pairs (a, b) of two alpha-oriented bonds of cos(q . (r_a - r_b)) connected(a, b)
+  with r_a the site bond a leaves in the positive direction (bond_orientations) and n_alpha the number of distinct
+  first bonds a among those pairs: all ordered pairs give the usual (1 / N_bonds) sum_{a, b}, one reference bond
+  against all gives sum_b cos(q . (r_b - r_0)) connected(0, b) -- the same number on a translation-invariant state.
+  Pairs of differently oriented bonds and pairs with a bond that is no nearest-neighbour bond do not enter.  Returns
+  (qs [n_q][d], D [d][n_q]) with d = 1 (chain) or 2, row 0 the x-oriented and row 1 the y-oriented bonds, at the momenta
+  the cluster allows (chain_momenta / torus_momenta) unless `qs` gives others."""
+  bonds = np.asarray(bonds, np.int64).reshape(-1, 2)
+  pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+  connected = np.asarray(connected, np.float64).ravel()
+  if connected.size != pairs.shape[0]:
+    raise ValueError('dimer_structure_factor: {} values for {} pairs'.format(connected.size, pairs.shape[0]))
+  if pairs.size and (pairs.min() < 0 or pairs.max() >= len(bonds)):
+    raise ValueError('dimer_structure_factor: a pair names a bond outside 0 .. {}'.format(len(bonds) - 1))
+  if size_x < 1 or size_y < 1:
+    raise ValueError('dimer_structure_factor: lattice sizes must be positive')
+  chain = size_y == 1
+  coords = chain_coords(size_x) if chain else torus_coords(size_x, size_y)
+  if qs is None:
+    qs = chain_momenta(size_x) if chain else torus_momenta(size_x, size_y)
+  qs = np.asarray(qs, np.float64).reshape(-1, coords.shape[1])
+  if bonds.size and (bonds.min() < 0 or bonds.max() >= len(coords)):
+    raise ValueError('dimer_structure_factor: a bond names a site outside the {} x {} lattice'.format(size_x, size_y))
+  axis, origin = bond_orientations(bonds, size_x, size_y)
+  out = np.zeros((coords.shape[1], len(qs)))
+  for alpha in range(coords.shape[1]):
+    use = (axis[pairs[:, 0]] == alpha) & (axis[pairs[:, 1]] == alpha)
+    if not use.any():
+      continue
+    a, b = pairs[use, 0], pairs[use, 1]
+    dr = coords[origin[a]] - coords[origin[b]]              # [n_used][d]
+    out[alpha] = np.cos(qs @ dr.T) @ connected[use] / np.unique(a).size
+  return qs, out
+
+
 def load_bonds(checkpoint_dir, n_sites):
   """run_training.py:103-109 / run_energy_evaluation.py:51-57: `J.txt` of integer pairs
   (extra columns ignored), else the periodic chain."""

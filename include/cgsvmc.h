@@ -399,6 +399,31 @@ int vmc_renyi2_swap(vmc_ctx* ctx, int which, int32_t n_regions, const uint8_t* r
                     int32_t regions_per_pass /*0: planner's choice*/,
                     double* swap_sum /*[n_regions]*/, double* match_count /*[n_regions]*/);
 
+/* Dimer-dimer correlations <(S_i . S_j)(S_k . S_l)> -- EXTENSION with no reference counterpart.  `bonds` lists site pairs
+ * (any two distinct sites, not only the Hamiltonian's), `pairs` lists ordered pairs (a, b) of indices into `bonds`.  With
+ * r(y) = psi(y) / psi(x), [p != q] = 1 when the spins of sites p and q differ, x' = swap_ij x and s' the spins of x':
+ *   bond(a; x)  = s_i s_j / 4 + [s_i != s_j] r(swap_ij x) / 2                                  a = (i, j)
+ *   dd(a, b; x) = s_i s_j / 4 (s_k s_l / 4 + [s_k != s_l] r(swap_kl x) / 2)                    b = (k, l)
+ *               + [s_i != s_j] / 2 (s'_k s'_l r(x') / 4 + [s'_k != s'_l] r(swap_kl x') / 2)
+ * which is <x| (S_i . S_j)(S_k . S_l) |psi> / psi(x): the second bond acts on the intermediate configuration x', so bonds
+ * that share a site and a == b need no form of their own.  Over the ctx's current chains, ascending, in fp64:
+ *   bond_sum[a] = sum_c bond(a; x_c)            dd_sum[p] = sum_c dd(a_p, b_p; x_c)
+ * so that <A B> ~ dd_sum / batch_size, <A> ~ bond_sum / batch_size; either array may be NULL, n_pairs = 0 gives the bonds
+ * alone.  The ratios are exp of differences of ln|psi| times the signs of the signed types; every exchanged configuration
+ * goes through the full forward of the ctx's ansatz type (the device path of vmc_amplitude): n_bonds x B single exchanges,
+ * kept per (bond, chain) on the device, then B double exchanges per pair in passes of at most pairs_per_pass pairs (0: as
+ * many as the row budget of a pass takes; a request is clamped to it).  A sum depends neither on the passes nor on the
+ * other entries of the two lists.  A vanishing amplitude of a row gives the ratio 0 and a chain whose own amplitude
+ * vanishes adds 0 to every sum (exactly, never NaN).  A pure measurement: chains, step counter, accumulators, the
+ * Hamiltonian's bonds and couplings and the validity of the amplitude and activation caches are as before on return.
+ * A bond with i == j, a site or a bond index out of range, n_bonds < 1, n_pairs < 0, pairs_per_pass < 0, a NULL list
+ * that is not empty, which outside {0, 1}: VMC_ERR_INVALID, before anything touches the device; an output activation
+ * other than exp on an unsigned type and a product ctx: VMC_ERR_UNSUPPORTED; a factor of a product ctx: VMC_ERR_STATE. */
+int vmc_dimer_correlations(vmc_ctx* ctx, int which, int32_t n_bonds, const int32_t* bonds /*[n_bonds][2] sites*/,
+                           int32_t n_pairs, const int32_t* pairs /*[n_pairs][2] indices into bonds: (a, b)*/,
+                           int32_t pairs_per_pass /*0: planner's choice*/,
+                           double* bond_sum /*[n_bonds]*/, double* dd_sum /*[n_pairs]*/);
+
 /* Stochastic reconfiguration -- EXTENSION: named by the north star, absent from the reference
  * (training.py has only the plain energy gradient + Adam), so these entries replace no reference
  * interface; they sit where TrainOpsTraditional.apply_gradients (training.py:560-567) sits.
