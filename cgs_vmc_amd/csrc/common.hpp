@@ -211,6 +211,10 @@ struct TailArgs {
   const int2* rowinfo;      // [n_rows] {chain, signed bond+1 or 0}; never null (launch_iota_rows)
   const int2* bonds;        // [n_bonds] {i, j}
   const float* half_jx;     // [n_bonds] 0.5 * j_x
+  // bond-difference table of (pp, bonds) (launch_bond_diff; k_tail16 only, the other row kernels form the
+  // differences themselves): bdiff[b][u] = w1p[i_b][u] - w1p[j_b][u], bdiff_on[b] = won[i_b] - won[j_b] (RBM)
+  const float* bdiff;       // [max(n_bonds, 1)][Hp]
+  const float* bdiff_on;    // [max(n_bonds, 1)]
   const int* n_rows_dev;    // device row count (list mode) or nullptr
   int n_rows;               // host row count / upper bound
   int n_hidden;             // L-1
@@ -262,6 +266,10 @@ struct SweepArgs {
 hipError_t launch_pack(hipStream_t s, const float* theta, int N, int H, int Hp,
                        const ParamLayout& lay, float* w1p, float* b1p, float* bh, float* p16,
                        float* p16t, float* woutp, float* bout, float* won);
+// bond-difference table of one packed parameter set and one bond list (TailArgs::bdiff / bdiff_on): the fp32
+// differences k_tail16 would otherwise form for every connected row; won / bdiff_on: RBM only, else nullptr
+hipError_t launch_bond_diff(hipStream_t s, const float* w1p, const float* won, const int2* bonds, int n_bonds,
+                            int Hp, float* bdiff, float* bdiff_on);
 // d logit / d z_l of every layer: act_all / delta_all are [n_hidden + 1][B][Hp]
 // act: hidden activation id; dact_all: f'(z) arrays (cosine only) or nullptr; oscale: [B]
 // (1/psi) d psi / d x of a non-exp output activation or nullptr

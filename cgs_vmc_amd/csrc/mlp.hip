@@ -74,6 +74,33 @@ hipError_t launch_pack(hipStream_t s, const float* theta, int N, int H, int Hp,
   return hipGetLastError();
 }
 
+// Bond-difference table of k_tail16's rank-2 gather: row b = W1p[i_b] - W1p[j_b], formed once per (parameter set,
+// bond list) instead of once per connected row.  The same single fp32 subtraction the row kernels perform, so a
+// row's act(fmaf(coef, D[b][u], z1[chain][u])) keeps its bits.  [n_bonds][Hp] floats: L2 resident.
+__global__ __launch_bounds__(256) void k_bond_diff(const float* __restrict__ w1p, const float* __restrict__ won,
+                                                   const int2* __restrict__ bonds, int n_bonds, int Hp,
+                                                   float* __restrict__ bdiff, float* __restrict__ bdiff_on) {
+  const int q = Hp / 4;     // f32x4 per row
+  const int n = n_bonds * q;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int b = i / q, c = 4 * (i % q);
+    const int2 ab = bonds[b];
+    const f32x4 x = *(const f32x4*)(w1p + (long long)ab.x * Hp + c);
+    const f32x4 y = *(const f32x4*)(w1p + (long long)ab.y * Hp + c);
+    *(f32x4*)(bdiff + (long long)b * Hp + c) = x - y;
+    if (won && c == 0) bdiff_on[b] = won[ab.x] - won[ab.y];
+  }
+}
+
+hipError_t launch_bond_diff(hipStream_t s, const float* w1p, const float* won, const int2* bonds, int n_bonds,
+                            int Hp, float* bdiff, float* bdiff_on) {
+  if (n_bonds <= 0) return hipSuccess;
+  const int blocks = (n_bonds * (Hp / 4) + 255) / 256;
+  hipLaunchKernelGGL(k_bond_diff, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, s, w1p, won, bonds, n_bonds,
+                     Hp, bdiff, bdiff_on);
+  return hipGetLastError();
+}
+
 // onsite term of the RBM ansatz (wavefunctions.py:436): out[r] = x_r . w_on, one wave per row
 // (the bias b_on travels as `bout`)
 __global__ __launch_bounds__(256) void k_onsite(const float* __restrict__ configs,

@@ -13,6 +13,14 @@
 #define TAIL_RD 8     // stages of k_tail16's weight-fragment ring (items of 8 MFMAs each)
 #endif
 
+// One v_fma_f32, the value of fmaf(a, b, c), opaque to the SLP vectoriser: left to itself it pairs the fmas of
+// k_tail16's gather and output dot into v_pk_fma_f32, each dearer beside MFMAs than the two plain ones it replaces.
+__device__ __forceinline__ float vmc_fma1(float a, float b, float c) {
+  float r;
+  asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+
 // ---------------------------------------------------------------------------------- tail16
 // Layers 2..L + output for a list of rows.  Persistent: one 256-thread workgroup per CU walks
 // the row tiles b, b + gridDim.x, ...; each of its 4 waves owns 32 rows of a tile, as two 16-row
@@ -48,19 +56,26 @@ __global__ __launch_bounds__(256) void k_tail16(TailArgs a) {
   constexpr int NI = NT * NT, RD = TAIL_RD;
   static_assert(NI % RD == 0, "ring slots continue across layers only if RD divides the items per layer");
   f32x4 ring[RD];
-  const unsigned lane_off = (unsigned)lane * 16u;
-  const char* p16c = (const char*)a.pp.p16;   // re-made opaque every tile (an opaque per-tile copy keeps LICM from hoisting ~256 per-item 64-bit addresses, which spill)
-  typedef const __attribute__((address_space(1))) char* gchar_p;
-  typedef const __attribute__((address_space(1))) f32x4* gf32x4_p;
-  auto issue = [&](int l, int item) {
-    gchar_p base = (gchar_p)p16c + ((size_t)l * Hp * Hp + (size_t)item * 256) * sizeof(float);
-    return *(gf32x4_p)(base + lane_off);
+  // Buffer loads over the p16 image: the lane's constant 16-byte offset is the only vector address, the item's
+  // offset travels in an SGPR / the immediate field (scalar adds instead of a 64-bit vector add per four items);
+  // compiler-visible loads, so vmcnt stays the compiler's to count.  The image is n_hidden * Hp * Hp floats: the
+  // descriptor's bounds check covers every issue, also the one that wraps to layer 0 of the next tile.
+  const int lane_off = lane * 16;
+  const char* p16c = (const char*)a.pp.p16;   // re-made opaque every tile (keeps LICM from hoisting the per-item offsets)
+  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+  // (`base`: byte offset of the layer, an SGPR the layer loops re-make opaque per output tile so that the item
+  // offsets are formed next to their loads by scalar adds instead of being hoisted and spilled)
+  auto issue = [&](int base, int item) {
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p16c, 0, n_hidden * Hp * Hp * 4, 0x00020000);
+    const u32x4_t w = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_off + (item % 4) * 1024, base + (item / 4) * 4096, 0);
+    return __builtin_bit_cast(f32x4, w);
   };
 #pragma unroll
   for (int i = 0; i < RD - 1; ++i) ring[i] = issue(0, i);
 
   // descriptor of one of this lane's two rows (half 0: row j, half 1: row 16 + j of the wave)
-  struct Desc { const float* zb; const float* wa; const float* wb; float coef, on, lbase, hjx; int row, chain, bond, valid; };
+  // (db: the bond's row of the difference table W1p[i] - W1p[j], TailArgs::bdiff)
+  struct Desc { const float* zb; const float* db; float coef, on, lbase, hjx; int row, chain, bond, valid; };
   auto describe = [&](int tile, int half) {   // first two tiles of a wave only
     Desc d;
     d.row = tile * 128 + wave * 32 + 16 * half + j;
@@ -70,12 +85,10 @@ __global__ __launch_bounds__(256) void k_tail16(TailArgs a) {
     const int bs = ri.y;
     d.bond = (bs > 0 ? bs : -bs) - (bs != 0 ? 1 : 0);
     d.coef = bs > 0 ? -2.f : (bs < 0 ? 2.f : 0.f);          // -2 * s_i, 0 for a plain row
-    const int2 ab = a.bonds[d.bond];
-    d.wa = a.pp.w1p + (long long)ab.x * Hp;
-    d.wb = a.pp.w1p + (long long)ab.y * Hp;
+    d.db = a.bdiff + (long long)d.bond * Hp;
     d.zb = a.z1 + (long long)d.chain * Hp;
     d.on = 0.f;
-    if (RBM) d.on = fmaf(d.coef, a.pp.won[ab.x] - a.pp.won[ab.y], a.on_base[d.chain]);
+    if (RBM) d.on = fmaf(d.coef, a.bdiff_on[d.bond], a.on_base[d.chain]);
     d.lbase = RATIO ? a.logit_base[d.chain] : 0.f;
     d.hjx = RATIO ? a.half_jx[d.bond] : 0.f;
     return d;
@@ -104,10 +117,9 @@ __global__ __launch_bounds__(256) void k_tail16(TailArgs a) {
     for (int t = 0; t < NT; ++t) {
       const int off = 16 * t + 4 * g;
       const f32x4 z = *(const f32x4*)(cur[hf].zb + off);
-      const f32x4 x = *(const f32x4*)(cur[hf].wa + off);
-      const f32x4 y = *(const f32x4*)(cur[hf].wb + off);
+      const f32x4 d = *(const f32x4*)(cur[hf].db + off);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) in[hf][t][e] = vmc_act<ACT>(fmaf(cur[hf].coef, x[e] - y[e], z[e]));
+      for (int e = 0; e < 4; ++e) in[hf][t][e] = vmc_act<ACT>(vmc_fma1(cur[hf].coef, d[e], z[e]));
     }
 
   for (;;) {
@@ -116,27 +128,28 @@ __global__ __launch_bounds__(256) void k_tail16(TailArgs a) {
     int opaque0 = 0;
     asm volatile("" : "+s"(opaque0));   // keeps tile-invariant bias / w_out loads inside the loop
     asm volatile("" : "+s"(p16c));      // same for the per-item weight addresses
-    // descriptors of the tile after next: built in three steps inside the last layer
+    // descriptors of the tile after next: built in steps inside the last layer
     Desc nn_d[2];
-    int2 nn_ri[2], nn_ab[2];
-    float nn_onb[2];
+    int2 nn_ri[2];
+    float nn_onb[2], nn_ond[2];
 #pragma unroll
-    for (int hf = 0; hf < 2; ++hf) { nn_d[hf] = nxt_d[hf]; nn_ri[hf] = make_int2(0, 0); nn_ab[hf] = make_int2(0, 0); nn_onb[hf] = 0.f; }
+    for (int hf = 0; hf < 2; ++hf) { nn_d[hf] = nxt_d[hf]; nn_ri[hf] = make_int2(0, 0); nn_onb[hf] = 0.f; nn_ond[hf] = 0.f; }
 
     // ---- all but the last H x H layer: in -> out -> in
     for (int l = 0; l + 1 < n_hidden; ++l) {
       const float* __restrict__ bl = a.pp.bh + l * Hp + opaque0;
       f32x4 out[2][NT];
       f32x4 bias = *(const f32x4*)(bl + 4 * g);
+      int wbase = l * (NI * 1024);
 #pragma unroll
       for (int to = 0; to < NT; ++to) {
+        asm volatile("" : "+s"(wbase));
         f32x4 acc0 = bias, acc1 = bias;
         if (to + 1 < NT) bias = *(const f32x4*)(bl + 16 * (to + 1) + 4 * g);
 #pragma unroll
         for (int ti = 0; ti < NT; ++ti) {
           const int item = to * NT + ti, nxt = item + RD - 1;
-          if (nxt < NI) ring[nxt % RD] = issue(l, nxt);
-          else ring[nxt % RD] = issue(l + 1, nxt - NI);
+          ring[nxt % RD] = issue(wbase, nxt);      // (past NI: the next layer's image follows this one's)
           __builtin_amdgcn_sched_barrier(0);   // keep the prefetch RD-1 items ahead
           const f32x4 w = ring[item % RD];
 #pragma unroll
@@ -165,21 +178,22 @@ __global__ __launch_bounds__(256) void k_tail16(TailArgs a) {
       const float* __restrict__ wop = a.pp.woutp + opaque0;
       constexpr int SEG = NT / 2;
       f32x4 bias = *(const f32x4*)(bl + 4 * g);
+      int wbase = l * (NI * 1024), wbase0 = 0;
 #pragma unroll
       for (int to = 0; to < NT; ++to) {
+        asm volatile("" : "+s"(wbase), "+s"(wbase0));
         f32x4 wo;
         if (!RBM) wo = *(const f32x4*)(wop + 16 * to + 4 * g);
         f32x4 acc0 = bias, acc1 = bias;
         if (to + 1 < NT) bias = *(const f32x4*)(bl + 16 * (to + 1) + 4 * g);
-        f32x4 gz, gx, gy;
+        f32x4 gz, gd;
 #pragma unroll
         for (int ti = 0; ti < NT; ++ti) {
           const int hf = ti / SEG;
           if (ti % SEG == 0) {
             const int off = 16 * to + 4 * g;
             gz = *(const f32x4*)(nxt_d[hf].zb + off);
-            gx = *(const f32x4*)(nxt_d[hf].wa + off);
-            gy = *(const f32x4*)(nxt_d[hf].wb + off);
+            gd = *(const f32x4*)(nxt_d[hf].db + off);
           }
           const int item = to * NT + ti, nxt = item + RD - 1;
           if (item == 0) {                      // step A: rowinfo of the tile after next
@@ -190,31 +204,29 @@ __global__ __launch_bounds__(256) void k_tail16(TailArgs a) {
               nn_ri[q] = a.rowinfo[nn_d[q].valid ? nn_d[q].row : n_rows - 1];
             }
           }
-          if (item == NI / 4) {                 // step B: chain / bond -> bond table, z1 row
+          if (item == NI / 4) {                 // step B: chain / bond -> rows of z1 and of the difference table
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
               nn_d[q].chain = nn_ri[q].x;
               const int bs = nn_ri[q].y;
               nn_d[q].bond = (bs > 0 ? bs : -bs) - (bs != 0 ? 1 : 0);
               nn_d[q].coef = bs > 0 ? -2.f : (bs < 0 ? 2.f : 0.f);
-              nn_ab[q] = a.bonds[nn_d[q].bond];
+              nn_d[q].db = a.bdiff + (long long)nn_d[q].bond * Hp;
               nn_d[q].zb = a.z1 + (long long)nn_d[q].chain * Hp;
-              if (RBM) nn_onb[q] = a.on_base[nn_d[q].chain];
+              if (RBM) { nn_onb[q] = a.on_base[nn_d[q].chain]; nn_ond[q] = a.bdiff_on[nn_d[q].bond]; }
               nn_d[q].lbase = RATIO ? a.logit_base[nn_d[q].chain] : 0.f;
               nn_d[q].hjx = RATIO ? a.half_jx[nn_d[q].bond] : 0.f;
             }
           }
-          if (item == NI / 2) {                 // step C: W1 rows of the exchanged sites
+          if (item == NI / 2) {                 // step C (RBM): the onsite term, once step B's loads have landed
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-              nn_d[q].wa = a.pp.w1p + (long long)nn_ab[q].x * Hp;
-              nn_d[q].wb = a.pp.w1p + (long long)nn_ab[q].y * Hp;
               nn_d[q].on = 0.f;
-              if (RBM) nn_d[q].on = fmaf(nn_d[q].coef, a.pp.won[nn_ab[q].x] - a.pp.won[nn_ab[q].y], nn_onb[q]);
+              if (RBM) nn_d[q].on = fmaf(nn_d[q].coef, nn_ond[q], nn_onb[q]);
             }
           }
-          if (nxt < NI) ring[nxt % RD] = issue(l, nxt);
-          else ring[nxt % RD] = issue(0, nxt - NI);          // next tile's first layer
+          if (nxt < NI) ring[nxt % RD] = issue(wbase, nxt);
+          else ring[nxt % RD] = issue(wbase0, nxt - NI);     // next tile's first layer
           __builtin_amdgcn_sched_barrier(0);
           const f32x4 w = ring[item % RD];
 #pragma unroll
@@ -225,7 +237,7 @@ __global__ __launch_bounds__(256) void k_tail16(TailArgs a) {
           if (ti % SEG == SEG - 1) {
             f32x4 v;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = vmc_act<ACT>(fmaf(nxt_d[hf].coef, gx[e] - gy[e], gz[e]));
+            for (int e = 0; e < 4; ++e) v[e] = vmc_act<ACT>(vmc_fma1(nxt_d[hf].coef, gd[e], gz[e]));
             stage[(to * 2 + hf) * 64] = v;
           }
         }
@@ -236,8 +248,11 @@ __global__ __launch_bounds__(256) void k_tail16(TailArgs a) {
             part[0] += ok ? vmc_logcosh(acc0[e]) : 0.f;
             part[1] += ok ? vmc_logcosh(acc1[e]) : 0.f;
           } else {
-            part[0] = fmaf(vmc_act<ACT>(acc0[e]), wo[e], part[0]);
-            part[1] = fmaf(vmc_act<ACT>(acc1[e]), wo[e], part[1]);
+            // (relu only: its v_max_f32 stands between the accumulator and the asm; an activation that hands the
+            // accumulator through must stay visible to the compiler's MFMA hazard recogniser)
+            const float r0 = vmc_act<ACT>(acc0[e]), r1 = vmc_act<ACT>(acc1[e]);
+            part[0] = ACT == VMC_ACT_RELU_ ? vmc_fma1(r0, wo[e], part[0]) : fmaf(r0, wo[e], part[0]);
+            part[1] = ACT == VMC_ACT_RELU_ ? vmc_fma1(r1, wo[e], part[1]) : fmaf(r1, wo[e], part[1]);
           }
         }
       }
@@ -327,6 +342,7 @@ static hipError_t launch_tail16_h(hipStream_t s, const TailArgs& a) {
 template <bool RATIO, bool RBM, int ACT>
 static hipError_t launch_tail_t(hipStream_t s, const TailArgs& a, int Hp) {
   if (a.n_rows <= 0) return hipSuccess;
+  if (a.n_hidden > 0 && !a.bdiff) return hipErrorInvalidValue;   // k_tail16 gathers through the difference table
   if (a.n_hidden == 0) {
     const int blocks = (a.n_rows + 3) / 4;      // one wave per row, 8 workgroups per CU's worth of rows in flight
     hipLaunchKernelGGL((k_tail0<RATIO, RBM, ACT>), dim3(blocks < 4096 ? blocks : 4096), dim3(256), 0, s, a, Hp);

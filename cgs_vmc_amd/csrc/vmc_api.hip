@@ -34,13 +34,42 @@ int ensure_packed(vmc_ctx* c, int which) {
                         p.p16t, p.woutp, p.bout, p.won));
   if (c->split) HIPCHK(c, launch_pack_split(c->stream, p.theta, c->H, c->lay, p.p16s));
   p.packed_valid = true;
+  p.bdiff_valid = false;      // (differences of the image just replaced)
   return VMC_OK;
+}
+
+// The bond-difference table of parameter set `which` for the bond list `bonds` the row launch is about to read
+// (the Hamiltonian's, a spin-correlation pass's, or the dummy bond before vmc_set_bonds): built on `stream` in front
+// of the first row launch after a re-pack or a change of the list, constant until the next one.
+static hipError_t ensure_bond_diff(vmc_ctx* c, int which, const int2* bonds) {
+  ParamSet& p = c->ps[which];
+  if (p.bdiff_valid && p.bdiff_epoch == c->bonds_epoch) return hipSuccess;
+  const int nb = c->bonds ? c->n_bonds : 1;
+  if (nb > p.bdiff_cap) {
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return e;
+    if (p.bdiff) hipFree(p.bdiff);
+    if (p.bdiff_on) hipFree(p.bdiff_on);
+    p.bdiff = p.bdiff_on = nullptr; p.bdiff_cap = 0;
+    if ((e = dalloc(&p.bdiff, (long long)nb * c->Hp)) != hipSuccess) return e;
+    if ((e = dalloc(&p.bdiff_on, nb)) != hipSuccess) return e;
+    p.bdiff_cap = nb;
+  }
+  hipError_t e = launch_bond_diff(c->stream, p.w1p, c->rbm ? p.won : nullptr, bonds, nb, c->Hp, p.bdiff, p.bdiff_on);
+  if (e != hipSuccess) return e;
+  p.bdiff_valid = true; p.bdiff_epoch = c->bonds_epoch;
+  return hipSuccess;
 }
 
 // rows through the fused row kernel of this ctx (the 3 x bf16 split experiment when it is switched on)
 hipError_t launch_rows(vmc_ctx* c, int which, const TailArgs& a, bool ratio) {
   if (c->split) return launch_tail16_split(c->stream, a, c->ps[which].p16s, ratio);
-  return launch_tail(c->stream, a, c->Hp, ratio, c->rbm);
+  if (a.n_hidden == 0) return launch_tail(c->stream, a, c->Hp, ratio, c->rbm);     // k_tail0 reads w1p itself
+  TailArgs t = a;
+  hipError_t e = ensure_bond_diff(c, which, a.bonds);
+  if (e != hipSuccess) return e;
+  t.bdiff = c->ps[which].bdiff; t.bdiff_on = c->ps[which].bdiff_on;
+  return launch_tail(c->stream, t, c->Hp, ratio, c->rbm);
 }
 
 TailArgs tail_args(vmc_ctx* c, int which) {
@@ -709,7 +738,7 @@ void vmc_destroy(vmc_ctx* c) {
   for (int w = 0; w < 2; ++w) {
     ParamSet& p = c->ps[w];
     float* ptrs[] = {p.theta, p.w1p, p.b1p, p.bh, p.p16, p.p16t, p.woutp, p.bout, p.z1, p.logit, p.eloc, p.won, p.onsite,
-                     p.z1_alt, p.logit_alt, p.onsite_alt, p.cw0, p.cwf, p.cwb, p.cbias};
+                     p.z1_alt, p.logit_alt, p.onsite_alt, p.cw0, p.cwf, p.cwb, p.cbias, p.bdiff, p.bdiff_on};
     for (float* q : ptrs) if (q) hipFree(q);
     if (p.p16s) hipFree(p.p16s);
   }
@@ -770,6 +799,7 @@ int vmc_set_bonds(vmc_ctx* c, int32_t n_bonds, const int32_t* ij, const float* j
   for (void* q : old) if (q) hipFree(q);
   c->bonds = nullptr; c->half_jx = c->quarter_jz = c->val = nullptr; c->rowinfo = nullptr;
   c->n_bonds = n_bonds;
+  c->bonds_epoch += 1;
   HIPCHK(c, dalloc(&c->bonds, n_bonds)); HIPCHK(c, dalloc(&c->half_jx, n_bonds));
   HIPCHK(c, dalloc(&c->quarter_jz, n_bonds));
   HIPCHK(c, dalloc(&c->rowinfo, (long long)c->B * n_bonds));

@@ -23,6 +23,7 @@ BondSet current_set(const vmc_ctx* c) { return BondSet{c->n_bonds, c->bonds, c->
 void install_set(vmc_ctx* c, const BondSet& s) {
   c->n_bonds = s.n_bonds; c->bonds = s.bonds; c->half_jx = s.half_jx; c->quarter_jz = s.quarter_jz;
   c->rowinfo = s.rowinfo; c->val = s.val;
+  c->bonds_epoch += 1;        // (the bond-difference tables of the row kernel belong to the list they were built from)
   c->list_valid = false;
   c->cnt_valid = false;
 }

@@ -35,6 +35,13 @@ struct ParamSet {
   // convolutional ansatz types: fragment images of conv.hpp ConvParams
   float *cw0 = nullptr, *cwf = nullptr, *cwb = nullptr, *cbias = nullptr;
   unsigned* p16s = nullptr;   // CGS_VMC_SPLIT_BF16=1: the H x H layers as three bf16 terms (tail_split.hip)
+  // bond-difference table of k_tail16 (launch_bond_diff): the differences of the packed w1p / won over the bond
+  // list `bdiff_bonds`.  Rebuilt by launch_rows when the image was re-packed (ensure_packed clears bdiff_valid) or
+  // another bond list is current (vmc_set_bonds and the spin-correlation passes bump vmc_ctx::bonds_epoch)
+  float *bdiff = nullptr, *bdiff_on = nullptr;
+  long long bdiff_cap = 0;            // rows allocated
+  bool bdiff_valid = false;
+  unsigned long long bdiff_epoch = 0; // vmc_ctx::bonds_epoch the table was built at
   bool packed_valid = false, cache_valid = false, has_params = false;
   float shift = -10.f;     // wavefunctions.py:209
   PackedParams packed() const { return PackedParams{w1p, b1p, bh, p16, woutp, bout, won}; }
@@ -176,6 +183,7 @@ struct vmc_ctx {
   int2* bond_dummy = nullptr;   // {0,0}: stands in for the bond table before vmc_set_bonds
   int2* rowinfo_id = nullptr;   // identity list {r, 0} for plain rows (cache refresh)
   int2* tmp_rowinfo = nullptr;
+  unsigned long long bonds_epoch = 1;   // bumped whenever `bonds` / `n_bonds` name another list (ParamSet::bdiff)
   bool list_valid = false;
   bool cnt_valid = false;          // cnt / diag hold the census of `configs` (left by the sampler's last launch)
   int* cnt_alt = nullptr; float* diag_alt = nullptr;   // the census the NEXT sampler launch writes (swapped with the chains)
