@@ -4,7 +4,8 @@
 // and the connected part.
 //
 // Phase 1: B rows per bond, the single exchanges (k_dimer_rows1), through the family's own full forward
-// (rows_forward_device, vmc_api.hip) in as many passes as the row buffer of vmc_amplitude takes; their ln|psi| and signs
+// (rows_forward_device, vmc_api.hip) in as many passes as the row buffer of vmc_amplitude takes (fewer bonds per pass
+// where pairs_per_pass asks for fewer); their ln|psi| and signs
 // stay in the ctx's [n_bonds][B] buffers.  Phase 2: passes of pairs, B rows per pair, the double exchanges
 // (k_dimer_rows2), forwarded the same way and folded per pair (k_dimer_fold) against phase 1's buffers and the chains'
 // cached ln|psi| and signs.  (n_bonds + n_pairs) B full forwards in all.  The call is a pure measurement: chains, step
@@ -101,7 +102,7 @@ int vmc_dimer_correlations(vmc_ctx* c, int which, int32_t n_bonds, const int32_t
   if (!c->sgn && c->oact != VMC_ACT_EXP_)
     return fail(c, VMC_ERR_UNSUPPORTED, "vmc_dimer_correlations needs the exp output activation (the logit is ln psi only then)");
   const long long row_limit = plan_dimer_row_limit(c->N, c->Hp);
-  const int per1 = plan_dimer_pairs_per_pass(c->B, n_bonds, 0, row_limit);
+  const int per1 = plan_dimer_pairs_per_pass(c->B, n_bonds, pairs_per_pass, row_limit);    // (a request splits both phases)
   const int per2 = n_pairs > 0 ? plan_dimer_pairs_per_pass(c->B, n_pairs, pairs_per_pass, row_limit) : 0;
   if (per1 < 1 || (n_pairs > 0 && per2 < 1) || !plan_dimer_bond_rows_ok(c->B, n_bonds))
     return fail(c, VMC_ERR_UNSUPPORTED, "batch_size x bonds does not fit the 32-bit row index");

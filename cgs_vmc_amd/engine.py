@@ -360,7 +360,8 @@ class VmcEngine:
     (bond_sum [n_bonds], dd_sum [n_pairs]), float64: the sums over the chains of the local values of S_i . S_j and of
     (S_i . S_j)(S_k . S_l), so that <A B> ~ dd_sum / batch_size and <A> ~ bond_sum / batch_size.  Moves no chain, touches
     neither the step counter nor the accumulators nor the Hamiltonian; pairs_per_pass = 0 leaves the pass size to the
-    library."""
+    library, a positive value caps the bonds per pass of the single exchanges and the pairs per pass of the double
+    exchanges alike (the sums are the same bits either way)."""
     from . import lattice
     ij = np.ascontiguousarray(np.asarray(bonds, dtype=np.int32).reshape(-1, 2))
     ab = lattice.all_bond_pairs(ij.shape[0]) if pairs is None else \

@@ -410,9 +410,10 @@ int vmc_renyi2_swap(vmc_ctx* ctx, int which, int32_t n_regions, const uint8_t* r
  *   bond_sum[a] = sum_c bond(a; x_c)            dd_sum[p] = sum_c dd(a_p, b_p; x_c)
  * so that <A B> ~ dd_sum / batch_size, <A> ~ bond_sum / batch_size; either array may be NULL, n_pairs = 0 gives the bonds
  * alone.  The ratios are exp of differences of ln|psi| times the signs of the signed types; every exchanged configuration
- * goes through the full forward of the ctx's ansatz type (the device path of vmc_amplitude): n_bonds x B single exchanges,
- * kept per (bond, chain) on the device, then B double exchanges per pair in passes of at most pairs_per_pass pairs (0: as
- * many as the row budget of a pass takes; a request is clamped to it).  A sum depends neither on the passes nor on the
+ * goes through the full forward of the ctx's ansatz type (the device path of vmc_amplitude): n_bonds x B single exchanges
+ * in passes of at most pairs_per_pass bonds, kept per (bond, chain) on the device, then B double exchanges per pair in
+ * passes of at most pairs_per_pass pairs (0: as many as the row budget of a pass takes, in either phase; a request is
+ * clamped to it, for each phase by itself).  A sum depends neither on the passes nor on the
  * other entries of the two lists.  A vanishing amplitude of a row gives the ratio 0 and a chain whose own amplitude
  * vanishes adds 0 to every sum (exactly, never NaN).  A pure measurement: chains, step counter, accumulators, the
  * Hamiltonian's bonds and couplings and the validity of the amplitude and activation caches are as before on return.

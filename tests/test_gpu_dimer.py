@@ -176,6 +176,15 @@ def test_pass_splits_repeats_subsets_and_longer_lists_are_bit_identical_on_70_pa
       bond_sum, dd_sum = eng.dimer_correlations(BONDS34, pairs, pairs_per_pass=per)
       np.testing.assert_array_equal(bond_sum, base[0], err_msg='pairs_per_pass=%d' % per)
       np.testing.assert_array_equal(dd_sum, base[1], err_msg='pairs_per_pass=%d' % per)
+  # a request splits phase 1 too: 34 bonds at 7 per pass are five passes of single exchanges (the last of 6 bonds, written
+  # at dimer_bonds + 28, dimer_logit + 28 B) next to the ten passes of 70 pairs -- one `dimer_rows` region per pass
+  eng.timing_enable(True); eng.timing_reset()
+  bond_sum, dd_sum = eng.dimer_correlations(BONDS34, pairs, pairs_per_pass=7)
+  eng.synchronize()
+  passes = eng.timing_get('dimer_rows')[1]
+  eng.timing_enable(False)
+  assert passes - (70 + 6) // 7 == 5, passes
+  np.testing.assert_array_equal(bond_sum, base[0]); np.testing.assert_array_equal(dd_sum, base[1])
   # ... nor on which other pairs are in the list, or where
   pick = rng.permutation(70)[:25]
   bond_sum, dd_sum = eng.dimer_correlations(BONDS34, pairs[pick], pairs_per_pass=4)
