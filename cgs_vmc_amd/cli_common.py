@@ -1,5 +1,5 @@
-"""Shared plumbing of the two command-line drivers (flag tables, system construction,
-parameter broadcast).  The drivers keep the reference's command-line contract
+"""Shared plumbing of the command-line drivers (flag tables, system construction,
+parameter broadcast, the skeleton of the measurement drivers).  The drivers keep the reference's command-line contract
 (cgs_vmc/run_training.py:21-68, run_energy_evaluation.py:19-37) but are organised around
 these helpers instead of one long main()."""
 from __future__ import annotations
@@ -11,6 +11,8 @@ from typing import Dict, Sequence, Tuple
 from . import lattice
 from . import operators
 from . import parallel
+from . import session as session_lib
+from . import utils
 from . import wavefunctions
 
 
@@ -60,3 +62,45 @@ def graph_kwargs(**parts) -> Dict[str, object]:
   reference, run_training.py:120-127)."""
   parts.setdefault('shared_resources', {})
   return parts
+
+
+def measurement_flag_table(own_rows, outputs: str):
+  """The flag table of a measurement driver (run_correlation_evaluation, run_entanglement_evaluation,
+  run_dimer_evaluation): --checkpoint_dir, the driver's own rows, --output_dir for `outputs`, --hparams."""
+  return (('checkpoint_dir', str, '', 'Full path to the checkpoint directory.'),) + tuple(own_rows) + (
+      ('output_dir', str, '', 'Where {} (default: the checkpoint directory).'.format(outputs)),
+      ('hparams', str, '', 'Comma-separated name=value overrides of the hyper-parameters.'),
+  )
+
+
+def evaluate_measurement(flags, evaluator, load_operator):
+  """A measurement driver's evaluation: `hparams.pbtxt` with the --hparams overrides, the Heisenberg system of the
+  checkpoint directory, operator = load_operator(hparams, the Hamiltonian's bonds), the latest checkpoint restored.
+  -> (hparams, the Hamiltonian's bonds, the result of evaluator.run_evaluation)."""
+  hp = utils.load_hparams(os.path.join(flags.checkpoint_dir, 'hparams.pbtxt'))
+  hp.parse(flags.hparams)
+  ansatz, hamiltonian = heisenberg_system(hp, flags.checkpoint_dir, 1.0)
+  operator = load_operator(hp, hamiltonian._bonds_list)
+  eval_ops = evaluator.build_eval_ops(**graph_kwargs(wavefunction=ansatz, operator=operator, hparams=hp))
+  sess = session_lib.Session()
+  sess.run(session_lib.global_variables_initializer())
+  session_lib.Saver(ansatz.get_trainable_variables()).restore(
+      sess, session_lib.latest_checkpoint(hp.checkpoint_dir))
+  return hp, hamiltonian._bonds_list, evaluator.run_evaluation(eval_ops, sess, hp, epoch_num=0)
+
+
+def measurement_main(doc: str, table, argv, evaluate, write):
+  """main() of a measurement driver: evaluate(flags) -> (..., result) on every rank; rank 0 alone writes
+  write(output directory, ..., result) -> paths, and prints them.  -> (result, paths written)."""
+  flags = parser_from_table(doc, table).parse_args(argv)
+  parallel.init_from_env('nccl')
+  evaluated = evaluate(flags)
+  result = evaluated[-1]
+  written = []
+  if parallel.rank() == 0:
+    out_dir = flags.output_dir or flags.checkpoint_dir
+    ensure_directory(out_dir)
+    written = write(out_dir, *evaluated)
+    for path in written:
+      print('wrote {}'.format(path))
+  return result, written

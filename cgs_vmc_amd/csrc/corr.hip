@@ -1,4 +1,4 @@
-// Spin-correlation measurement (vmc_pair_correlations, vmc_api_corr.hip): the TRANSPOSED reduction of the
+// Spin-correlation measurement (vmc_pair_correlations, vmc_api_measure.hip): the TRANSPOSED reduction of the
 // connected-row list -- per pair over chains, where k_eloc_reduce (eloc.hip) sums per chain over bonds.
 //
 // A pass of pairs is a bond set like the Hamiltonian's (j_x = 2, j_z = 0), so after the family's row launch
@@ -67,7 +67,7 @@ hipError_t launch_pair_fold(hipStream_t s, const float* configs, const int2* pai
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(k_pair_scatter, dim3((unsigned)blocks), dim3(256), 0, s, rowinfo, val, n_rows_dev, B, n_pairs,
                      dense);
-  hipLaunchKernelGGL(k_pair_fold, dim3(plan_corr_fold_grid(n_pairs)), dim3(64), 0, s, configs, pairs, dense, B, N,
+  hipLaunchKernelGGL(k_pair_fold, dim3(plan_measure_fold_grid(n_pairs)), dim3(64), 0, s, configs, pairs, dense, B, N,
                      n_pairs, zz, ex);
   return hipGetLastError();
 }

@@ -1,4 +1,4 @@
-// Dimer-dimer correlations <(S_i . S_j)(S_k . S_l)> (vmc_dimer_correlations, vmc_api_dimer.hip).  With a = (i, j),
+// Dimer-dimer correlations <(S_i . S_j)(S_k . S_l)> (vmc_dimer_correlations, vmc_api_measure.hip).  With a = (i, j),
 // b = (k, l), r(y) = psi(y) / psi(x), x' = swap_ij x and s' the spins of x':
 //   bond(a; x)  = s_i s_j / 4 + [s_i != s_j] r(x') / 2
 //   dd(a, b; x) = s_i s_j / 4 (s_k s_l / 4 + [s_k != s_l] r(swap_kl x) / 2)
@@ -67,19 +67,6 @@ __global__ __launch_bounds__(256) void k_dimer_rows2(const float* __restrict__ c
   }
 }
 
-// sign of a stored sign / amplitude: +-1, 0 for a vanishing amplitude
-__device__ inline int dimer_sgn(float v) { return (v > 0.f) - (v < 0.f); }
-
-// psi(row) / psi(x) from ln|psi| and, signed types, the signs (own_sgn = +-1: the caller has dropped a chain whose own
-// amplitude vanishes).  A vanishing amplitude of the row gives 0 exactly: its logarithm is never read.
-__device__ inline double dimer_ratio(const float* __restrict__ row_logit, const float* __restrict__ row_sign, long long at,
-                                     double own_logit, int own_sgn) {
-  int sg = own_sgn;
-  if (row_sign) sg *= dimer_sgn(row_sign[at]);
-  if (sg == 0) return 0.0;
-  return (double)sg * exp((double)row_logit[at] - own_logit);
-}
-
 // One thread per bond a: bond_sum[a] = sum_c s_i s_j / 4 + [s_i != s_j] r(swap_ij x_c) / 2, chains ascending, fp64
 __global__ __launch_bounds__(64) void k_dimer_bond_fold(const float* __restrict__ configs, const int2* __restrict__ bonds,
                                                         const float* __restrict__ logit, const float* __restrict__ sign,
@@ -92,12 +79,12 @@ __global__ __launch_bounds__(64) void k_dimer_bond_fold(const float* __restrict_
   double sum = 0.0;
   for (int c = 0; c < B; ++c) {
     const float* x = configs + (long long)c * N;
-    const int own = sign ? dimer_sgn(sign[c]) : 1;
+    const int own = sign ? sgn_of(sign[c]) : 1;
     double term = 0.0;
     if (own != 0) {
       const float si = x[ij.x], sj = x[ij.y];
       term = 0.25 * (double)(si * sj);
-      if (si != sj) term += 0.5 * dimer_ratio(one_logit, one_sign, (long long)a * B + c, (double)logit[c], own);
+      if (si != sj) term += 0.5 * measure_ratio(one_logit, one_sign, (long long)a * B + c, (double)logit[c], own);
     }
     sum += term;
   }
@@ -119,21 +106,21 @@ __global__ __launch_bounds__(64) void k_dimer_fold(const float* __restrict__ con
   double sum = 0.0;
   for (int c = 0; c < B; ++c) {
     const float* x = configs + (long long)c * N;
-    const int own = sign ? dimer_sgn(sign[c]) : 1;
+    const int own = sign ? sgn_of(sign[c]) : 1;
     double term = 0.0;
     if (own != 0) {
       const double l0 = (double)logit[c];
       const float si = x[ij.x], sj = x[ij.y], sk = x[kl.x], sl = x[kl.y];
       // B on x, weighted by the diagonal part of A
       double inner = 0.25 * (double)(sk * sl);
-      if (sk != sl) inner += 0.5 * dimer_ratio(one_logit, one_sign, (long long)ab.y * B + c, l0, own);
+      if (sk != sl) inner += 0.5 * measure_ratio(one_logit, one_sign, (long long)ab.y * B + c, l0, own);
       term = 0.25 * (double)(si * sj) * inner;
       if (si != sj) {
         // B on x' = swap_ij x
         const float tk = kl.x == ij.x ? sj : (kl.x == ij.y ? si : sk);
         const float tl = kl.y == ij.x ? sj : (kl.y == ij.y ? si : sl);
-        double outer = 0.25 * (double)(tk * tl) * dimer_ratio(one_logit, one_sign, (long long)ab.x * B + c, l0, own);
-        if (tk != tl) outer += 0.5 * dimer_ratio(two_logit, two_sign, (long long)p * B + c, l0, own);
+        double outer = 0.25 * (double)(tk * tl) * measure_ratio(one_logit, one_sign, (long long)ab.x * B + c, l0, own);
+        if (tk != tl) outer += 0.5 * measure_ratio(two_logit, two_sign, (long long)p * B + c, l0, own);
         term += 0.5 * outer;
       }
     }
@@ -142,24 +129,16 @@ __global__ __launch_bounds__(64) void k_dimer_fold(const float* __restrict__ con
   dd_sum[p] = sum;
 }
 
-static unsigned dimer_rows_grid(long long items, int num_cus) {
-  long long blocks = (items + 3) / 4;
-  const long long cap = 16LL * (num_cus > 0 ? num_cus : 1);
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (unsigned)blocks;
-}
-
 hipError_t launch_dimer_rows1(hipStream_t s, const float* configs, const int2* bonds, int B, int N, int n_bonds,
                               int num_cus, float* rows) {
-  hipLaunchKernelGGL(k_dimer_rows1, dim3(dimer_rows_grid((long long)n_bonds * B, num_cus)), dim3(256), 0, s, configs,
+  hipLaunchKernelGGL(k_dimer_rows1, dim3(measure_rows_grid((long long)n_bonds * B, num_cus)), dim3(256), 0, s, configs,
                      bonds, B, N, n_bonds, rows);
   return hipGetLastError();
 }
 
 hipError_t launch_dimer_rows2(hipStream_t s, const float* configs, const int2* bonds, const int2* pairs, int B, int N,
                               int n_pairs, int num_cus, float* rows) {
-  hipLaunchKernelGGL(k_dimer_rows2, dim3(dimer_rows_grid((long long)n_pairs * B, num_cus)), dim3(256), 0, s, configs,
+  hipLaunchKernelGGL(k_dimer_rows2, dim3(measure_rows_grid((long long)n_pairs * B, num_cus)), dim3(256), 0, s, configs,
                      bonds, pairs, B, N, n_pairs, rows);
   return hipGetLastError();
 }
@@ -167,7 +146,7 @@ hipError_t launch_dimer_rows2(hipStream_t s, const float* configs, const int2* b
 hipError_t launch_dimer_bond_fold(hipStream_t s, const float* configs, const int2* bonds, const float* logit,
                                   const float* sign, const float* one_logit, const float* one_sign, int B, int N,
                                   int n_bonds, double* bond_sum) {
-  hipLaunchKernelGGL(k_dimer_bond_fold, dim3(plan_dimer_fold_grid(n_bonds)), dim3(64), 0, s, configs, bonds, logit, sign,
+  hipLaunchKernelGGL(k_dimer_bond_fold, dim3(plan_measure_fold_grid(n_bonds)), dim3(64), 0, s, configs, bonds, logit, sign,
                      one_logit, one_sign, B, N, n_bonds, bond_sum);
   return hipGetLastError();
 }
@@ -175,7 +154,7 @@ hipError_t launch_dimer_bond_fold(hipStream_t s, const float* configs, const int
 hipError_t launch_dimer_fold(hipStream_t s, const float* configs, const int2* bonds, const int2* pairs,
                              const float* logit, const float* sign, const float* one_logit, const float* one_sign,
                              const float* two_logit, const float* two_sign, int B, int N, int n_pairs, double* dd_sum) {
-  hipLaunchKernelGGL(k_dimer_fold, dim3(plan_dimer_fold_grid(n_pairs)), dim3(64), 0, s, configs, bonds, pairs, logit, sign,
+  hipLaunchKernelGGL(k_dimer_fold, dim3(plan_measure_fold_grid(n_pairs)), dim3(64), 0, s, configs, bonds, pairs, logit, sign,
                      one_logit, one_sign, two_logit, two_sign, B, N, n_pairs, dd_sum);
   return hipGetLastError();
 }

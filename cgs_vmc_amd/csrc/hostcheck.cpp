@@ -786,108 +786,59 @@ static void prod_grid() {
   CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_INVALID);
 }
 
-// spin correlations (plan_corr_*): every pass inside the row budget and the 32-bit row index, the passes cover the
-// pairs exactly, a request only ever shrinks a pass, and the fold grid covers a pass
-static void corr_grid() {
-  for (long long B : {1LL, 40LL, 64LL, 1000LL, 4096LL, 65536LL, 1LL << 24, (1LL << 24) + 1, 1LL << 30, (1LL << 30) + 1, 0x7fffffffLL})
-    for (long long n_pairs : {1LL, 7LL, 120LL, 276LL, 4950LL, 523776LL})
-      for (long long req : {0LL, 1LL, 7LL, 64LL, 276LL, 1LL << 40}) {
-        const int per = plan_corr_pairs_per_pass(B, n_pairs, req);
-        if (2 * B > 0x7fffffffLL) { CHECK(per == 0); continue; }        // not even one pair fits the row index
-        CHECK(per >= 1 && per <= n_pairs);
-        CHECK(B * per <= 0x7fffffffLL - B);                              // vmc_set_bonds' rule
-        CHECK(B * per <= PLAN_CORR_ROW_BUDGET || per == 1);
-        if (req > 0) CHECK(per <= req);
-        CHECK(per <= plan_corr_pairs_per_pass(B, n_pairs, 0));
-        const long long passes = plan_corr_passes(n_pairs, per);
-        CHECK(passes * per >= n_pairs && (passes - 1) * per < n_pairs);
-        CHECK((long long)plan_corr_fold_grid(per) * 64 >= per && ((long long)plan_corr_fold_grid(per) - 1) * 64 < per);
-      }
-  CHECK(plan_corr_pairs_per_pass(4096, 4950, 0) == 4096);                // 100 sites, all pairs: two passes
-  CHECK(plan_corr_pairs_per_pass(40, 120, 0) == 120 && plan_corr_pairs_per_pass(40, 120, 7) == 7);
-  CHECK(plan_corr_pairs_per_pass(0, 1, 0) == 0 && plan_corr_pairs_per_pass(1, 0, 0) == 0 && plan_corr_pairs_per_pass(1, 1, -1) == 0);
-}
-
-// Renyi-2 swap estimator (plan_renyi_*): every pass inside the row budget, the 32-bit row index and the ctx's own row
-// limit (one region is always taken), the passes cover the regions exactly, a request only ever shrinks a pass, the fold
-// grid covers a pass, and the row limit keeps the forward's scratch and its flat indices in range
-static void renyi_grid() {
-  for (long long B : {2LL, 40LL, 64LL, 1000LL, 4096LL, 65536LL, 1LL << 24, (1LL << 24) + 2, 1LL << 30, (1LL << 30) + 2, 0x7ffffffeLL})
-    for (long long n_regions : {1LL, 7LL, 50LL, 70LL, 4950LL, 523776LL})
-      for (long long req : {0LL, 1LL, 3LL, 64LL, 70LL, 1LL << 40})
+// the measurements (plan_measure_*): every pass inside the row budget, the 32-bit row index and the caller's row limit
+// (one item is always taken), the passes cover the items exactly, a request only ever shrinks a pass, the fold grid
+// covers a pass and a whole list, every index into an [n_items][B] buffer and into a pass's rows x sites fits 32 bits,
+// and the row limit keeps the forward's scratch and its flat indices in range
+static void measure_grid() {
+  for (long long B : {1LL, 2LL, 40LL, 64LL, 1000LL, 4096LL, 65536LL, 1LL << 24, (1LL << 24) + 1, (1LL << 24) + 2, 1LL << 30,
+                      (1LL << 30) + 1, (1LL << 30) + 2, 0x7ffffffeLL, 0x7fffffffLL})
+    for (long long n_items : {1LL, 7LL, 34LL, 50LL, 70LL, 120LL, 200LL, 276LL, 1024LL, 4950LL, 40000LL, 523776LL})
+      for (long long req : {0LL, 1LL, 3LL, 7LL, 64LL, 70LL, 276LL, 1LL << 40})
         for (long long lim : {0LL, 1LL, 4096LL, 100000LL, 1LL << 22, 1LL << 40}) {
-          const int per = plan_renyi_regions_per_pass(B, n_regions, req, lim);
-          if (2 * B > 0x7fffffffLL) { CHECK(per == 0); continue; }      // not even one region fits the row index
-          CHECK(per >= 1 && per <= n_regions);
-          CHECK(B * per <= 0x7fffffffLL - B);
-          CHECK(B * per <= PLAN_CORR_ROW_BUDGET || per == 1);
-          if (lim > 0) CHECK(B * per <= lim || per == 1);
-          if (req > 0) CHECK(per <= req);
-          CHECK(per <= plan_renyi_regions_per_pass(B, n_regions, 0, lim));
-          CHECK(per <= plan_renyi_regions_per_pass(B, n_regions, req, 0));
-          if (lim == 0) CHECK(per == plan_corr_pairs_per_pass(B, n_regions, req));   // the same budget and index rule
-          const long long passes = plan_renyi_passes(n_regions, per);
-          CHECK(passes * per >= n_regions && (passes - 1) * per < n_regions);
-          CHECK((long long)plan_renyi_fold_grid(per) * 64 >= per && ((long long)plan_renyi_fold_grid(per) - 1) * 64 < per);
-        }
-  for (int N : {2, 16, 100, 1024, 4096})
-    for (int Hp : {64, 256, 512, 4096}) {
-      const long long rows = plan_renyi_row_limit(N, Hp);
-      CHECK(rows >= 1);
-      CHECK(rows * (N > Hp ? N : Hp) <= 0x7fffffffLL);
-      CHECK(rows * ((long long)N + Hp + 5) <= (1LL << 30));
-    }
-  CHECK(plan_renyi_regions_per_pass(4096, 50, 0, plan_renyi_row_limit(100, 256)) == 50);      // config 3, the 50 blocks: one pass
-  CHECK(plan_renyi_regions_per_pass(40, 70, 0) == 70 && plan_renyi_regions_per_pass(40, 70, 3) == 3);
-  CHECK(plan_renyi_regions_per_pass(40, 70, 0, 100) == 2 && plan_renyi_regions_per_pass(40, 70, 0, 10) == 1);
-  CHECK(plan_renyi_regions_per_pass(0, 1, 0) == 0 && plan_renyi_regions_per_pass(2, 0, 0) == 0 &&
-        plan_renyi_regions_per_pass(2, 1, -1) == 0 && plan_renyi_regions_per_pass(2, 1, 0, -1) == 0);
-}
-
-// dimer-dimer correlations (plan_dimer_*): both phases' passes inside the row budget, the 32-bit row index and the ctx's
-// row limit (one item is always taken), the passes cover the items exactly, a request only ever shrinks a pass, the fold
-// grid covers a pass, every index into the [n_bonds][B] buffer of phase 1 and into a pass's rows x sites fits 32 bits
-static void dimer_grid() {
-  for (long long B : {1LL, 40LL, 64LL, 1000LL, 4096LL, 65536LL, 1LL << 24, (1LL << 24) + 1, 1LL << 30, (1LL << 30) + 1, 0x7fffffffLL})
-    for (long long n_items : {1LL, 7LL, 34LL, 70LL, 200LL, 1024LL, 40000LL, 523776LL})
-      for (long long req : {0LL, 1LL, 7LL, 64LL, 70LL, 1LL << 40})
-        for (long long lim : {0LL, 1LL, 4096LL, 100000LL, 1LL << 22, 1LL << 40}) {
-          const int per = plan_dimer_pairs_per_pass(B, n_items, req, lim);
-          if (2 * B > 0x7fffffffLL) { CHECK(per == 0); CHECK(!plan_dimer_bond_rows_ok(B, n_items)); continue; }
+          const int per = plan_measure_per_pass(B, n_items, req, lim);
+          // not even one item fits the row index
+          if (2 * B > 0x7fffffffLL) { CHECK(per == 0); CHECK(!plan_measure_rows_ok(B, n_items)); continue; }
           CHECK(per >= 1 && per <= n_items);
-          CHECK(B * per <= 0x7fffffffLL - B);
-          CHECK(B * per <= PLAN_CORR_ROW_BUDGET || per == 1);
+          CHECK(B * per <= 0x7fffffffLL - B);                              // vmc_set_bonds' rule
+          CHECK(B * per <= PLAN_MEASURE_ROW_BUDGET || per == 1);
           if (lim > 0) CHECK(B * per <= lim || per == 1);
           if (req > 0) CHECK(per <= req);
-          CHECK(per <= plan_dimer_pairs_per_pass(B, n_items, 0, lim));
-          CHECK(per <= plan_dimer_pairs_per_pass(B, n_items, req, 0));
-          const long long passes = plan_dimer_passes(n_items, per);
+          CHECK(per <= plan_measure_per_pass(B, n_items, 0, lim));
+          CHECK(per <= plan_measure_per_pass(B, n_items, req, 0));
+          if (lim == 0) CHECK(per == plan_measure_per_pass(B, n_items, req));   // no row limit is the default
+          const long long passes = plan_measure_passes(n_items, per);
           CHECK(passes * per >= n_items && (passes - 1) * per < n_items);
-          CHECK((long long)plan_dimer_fold_grid(per) * 64 >= per && ((long long)plan_dimer_fold_grid(per) - 1) * 64 < per);
-          CHECK((long long)plan_dimer_fold_grid((int)n_items) * 64 >= n_items);          // the bond fold takes every bond at once
-          if (plan_dimer_bond_rows_ok(B, n_items)) CHECK(B * n_items + B <= 0x7fffffffLL);
+          CHECK((long long)plan_measure_fold_grid(per) * 64 >= per && ((long long)plan_measure_fold_grid(per) - 1) * 64 < per);
+          CHECK((long long)plan_measure_fold_grid((int)n_items) * 64 >= n_items);        // the bond fold takes every bond at once
+          if (plan_measure_rows_ok(B, n_items)) CHECK(B * n_items + B <= 0x7fffffffLL);
           else CHECK(B * n_items + B > 0x7fffffffLL);
         }
   for (int N : {2, 16, 100, 1024, 4096})
     for (int Hp : {64, 256, 512, 4096}) {
-      const long long rows = plan_dimer_row_limit(N, Hp);
-      CHECK(rows >= 1 && rows == plan_renyi_row_limit(N, Hp));
+      const long long rows = plan_measure_row_limit(N, Hp);
+      CHECK(rows >= 1);
       CHECK(rows * (N > Hp ? N : Hp) <= 0x7fffffffLL);
+      CHECK(rows * ((long long)N + Hp + 5) <= (1LL << 30));
     }
+  CHECK(plan_measure_per_pass(4096, 4950, 0) == 4096);                // 100 sites, all pairs: two passes
+  CHECK(plan_measure_per_pass(40, 120, 0) == 120 && plan_measure_per_pass(40, 120, 7) == 7);
+  CHECK(plan_measure_per_pass(0, 1, 0) == 0 && plan_measure_per_pass(1, 0, 0) == 0 && plan_measure_per_pass(1, 1, -1) == 0);
+  CHECK(plan_measure_per_pass(4096, 50, 0, plan_measure_row_limit(100, 256)) == 50);      // config 3, the 50 blocks: one pass
+  CHECK(plan_measure_per_pass(40, 70, 0) == 70 && plan_measure_per_pass(40, 70, 3) == 3);
+  CHECK(plan_measure_per_pass(40, 70, 0, 100) == 2 && plan_measure_per_pass(40, 70, 0, 10) == 1);
+  CHECK(plan_measure_per_pass(2, 0, 0) == 0 && plan_measure_per_pass(2, 1, -1) == 0 && plan_measure_per_pass(2, 1, 0, -1) == 0);
   // config 3's shape, one reference bond against the 200 bonds: each phase is one pass of 819,200 rows
-  CHECK(plan_dimer_pairs_per_pass(4096, 200, 0, plan_dimer_row_limit(100, 256)) == 200);
-  CHECK(plan_dimer_pairs_per_pass(40, 70, 0) == 70 && plan_dimer_pairs_per_pass(40, 70, 7) == 7 && plan_dimer_pairs_per_pass(40, 70, 64) == 64);
-  CHECK(plan_dimer_pairs_per_pass(40, 1024, 0, 100) == 2 && plan_dimer_pairs_per_pass(40, 1024, 0, 10) == 1);
-  CHECK(plan_dimer_pairs_per_pass(40, 0, 0) == 0 && plan_dimer_pairs_per_pass(0, 1, 0) == 0 &&
-        plan_dimer_pairs_per_pass(40, 1, -1) == 0 && plan_dimer_pairs_per_pass(40, 1, 0, -1) == 0);
-  CHECK(!plan_dimer_bond_rows_ok(40, 0) && !plan_dimer_bond_rows_ok(0, 1) && plan_dimer_bond_rows_ok(40, 34));
+  CHECK(plan_measure_per_pass(4096, 200, 0, plan_measure_row_limit(100, 256)) == 200);
+  CHECK(plan_measure_per_pass(40, 70, 7) == 7 && plan_measure_per_pass(40, 70, 64) == 64);
+  CHECK(plan_measure_per_pass(40, 1024, 0, 100) == 2 && plan_measure_per_pass(40, 1024, 0, 10) == 1);
+  CHECK(plan_measure_per_pass(40, 0, 0) == 0 && plan_measure_per_pass(40, 1, -1) == 0 && plan_measure_per_pass(40, 1, 0, -1) == 0);
+  CHECK(!plan_measure_rows_ok(40, 0) && !plan_measure_rows_ok(0, 1) && plan_measure_rows_ok(40, 34));
 }
 
 int main() {
   check_block_maps();
-  corr_grid();
-  renyi_grid();
-  dimer_grid();
+  measure_grid();
   prod_grid();
   edvec_grid();
   nnb_grid();

@@ -635,44 +635,28 @@ inline int plan_prod_child_check(int ansatz, int output_activation, bool is_prod
   return VMC_ERR_UNSUPPORTED;
 }
 
-// ------------------------------------------------------------------------------- spin correlations (vmc_api_corr.hip, corr.hip)
-// A measurement runs its pairs in passes; a pass is a bond set of its own (bonds, couplings, rowinfo / val of B x pairs
-// rows) plus the dense [B][pairs] scatter target.  Row budget of a pass: 2^24 rows (rowinfo 128 MB, val and the dense
-// buffer 64 MB each), at least one pair, and never past the 32-bit row index rule of vmc_set_bonds
-// (B x pairs <= 2^31 - 1 - B).  requested > 0: at most that many pairs per pass (still inside the budget).
-// Returns 0 when not even one pair fits the row index (2 B > 2^31 - 1) or an argument is out of range.
-#define PLAN_CORR_ROW_BUDGET (1LL << 24)
-inline int plan_corr_pairs_per_pass(long long B, long long n_pairs, long long requested) {
-  if (B < 1 || n_pairs < 1 || requested < 0) return 0;
+// ------------------------------------------------------------------------------- the measurements (vmc_api_measure.hip; corr.hip, renyi.hip, dimer.hip)
+// A measurement runs its items -- pairs of sites, regions, bonds, pairs of bonds -- in passes; a pass is B rows per item
+// (row = item x B + chain): for the spin correlations a bond set of its own (bonds, couplings, rowinfo / val) plus the
+// dense [B][pairs] scatter target, for the others rows handed to the family's full forward.  Rows of a pass: the budget
+// of 2^24 rows (rowinfo 128 MB, val and the dense buffer 64 MB each), never past the 32-bit row index rule of
+// vmc_set_bonds (B x items <= 2^31 - 1 - B), and never more than `row_limit` rows where the caller states one (0: none)
+// -- what the forward's scratch takes: plan_measure_row_limit below; the spin correlations state none.  At least one
+// item whatever the budget says; requested > 0: at most that many items per pass.  Returns 0 when not even one item
+// fits the row index (2 B > 2^31 - 1) or an argument is out of range (n_items < 1 included: a dimer call without pairs
+// runs no phase 2 and does not ask).
+#define PLAN_MEASURE_ROW_BUDGET (1LL << 24)
+inline int plan_measure_per_pass(long long B, long long n_items, long long requested, long long row_limit = 0) {
+  if (B < 1 || n_items < 1 || requested < 0 || row_limit < 0) return 0;
   const long long limit = (0x7fffffffLL - B) / B;
   if (limit < 1) return 0;
-  long long per = PLAN_CORR_ROW_BUDGET / B;
-  if (per < 1) per = 1;
-  if (per > limit) per = limit;
-  if (requested > 0 && requested < per) per = requested;
-  if (per > n_pairs) per = n_pairs;
-  return (int)per;
-}
-inline long long plan_corr_passes(long long n_pairs, int per) { return per < 1 ? 0 : (n_pairs + per - 1) / per; }
-inline unsigned plan_corr_fold_grid(int pairs) { return (unsigned)((pairs + 63) / 64); }    // 64 threads, one pair each
-
-// ------------------------------------------------------------------------------- Renyi-2 swap estimator (vmc_api_renyi.hip, renyi.hip)
-// A measurement runs its regions in passes; a pass hands B rows per region (row = region x B + chain) to the family's
-// full forward.  Rows of a pass: the budget and the 32-bit row index rule of the spin correlations (B x regions <=
-// 2^31 - 1 - B), and never more than `row_limit` rows where the ctx states one (0: none) -- what the forward's scratch
-// takes: plan_renyi_row_limit below.  At least one region whatever the budget says; requested > 0: at most that many
-// regions per pass.  Returns 0 when not even one region fits the row index or an argument is out of range.
-inline int plan_renyi_regions_per_pass(long long B, long long n_regions, long long requested, long long row_limit = 0) {
-  if (B < 1 || n_regions < 1 || requested < 0 || row_limit < 0) return 0;
-  const long long limit = (0x7fffffffLL - B) / B;
-  if (limit < 1) return 0;
-  long long budget = PLAN_CORR_ROW_BUDGET;
+  long long budget = PLAN_MEASURE_ROW_BUDGET;
   if (row_limit > 0 && row_limit < budget) budget = row_limit;
   long long per = budget / B;
   if (per < 1) per = 1;
   if (per > limit) per = limit;
   if (requested > 0 && requested < per) per = requested;
-  if (per > n_regions) per = n_regions;
+  if (per > n_items) per = n_items;
   return (int)per;
 }
 // Rows the forward of one pass may take: the scratch per row is the configuration (N floats), the first layer's
@@ -680,32 +664,20 @@ inline int plan_renyi_regions_per_pass(long long B, long long n_regions, long lo
 // outputs and signs -- kept within 2^30 floats (4 GiB) -- and every flat index into it (rows x max(N, Hp)) within 32
 // bits.  The blocked forwards (general dense, nnb's dense block of nnb_rows rows with its N^2 pairing layer, the general
 // convolution) walk any row count in blocks of their own, so they state no further limit.
-inline long long plan_renyi_row_limit(int N, int Hp) {
+inline long long plan_measure_row_limit(int N, int Hp) {
   const long long widest = N > Hp ? N : Hp;
   const long long by_index = 0x7fffffffLL / (widest > 0 ? widest : 1);
   const long long by_bytes = (1LL << 30) / ((long long)N + Hp + 5);
   const long long rows = by_index < by_bytes ? by_index : by_bytes;
   return rows < 1 ? 1 : rows;
 }
-inline long long plan_renyi_passes(long long n_regions, int per) { return per < 1 ? 0 : (n_regions + per - 1) / per; }
-inline unsigned plan_renyi_fold_grid(int regions) { return (unsigned)((regions + 63) / 64); }    // 64 threads, one region each
-
-// ------------------------------------------------------------------------------- dimer-dimer correlations (vmc_api_dimer.hip, dimer.hip)
-// Phase 1 hands B rows per bond (row = bond x B + chain) to the family's full forward and keeps every row's ln|psi| in
-// a buffer [n_bonds][B]; phase 2 hands B rows per pair of a pass (row = pair x B + chain).  Both run in passes under the
-// rules of the Renyi-2 rows: the row budget, the 32-bit row index (B x items <= 2^31 - 1 - B), the ctx's row limit, at
-// least one item, requested > 0: at most that many.  0: not even one item fits the row index, or an argument is out of
-// range (n_items < 1 included: a call without pairs runs no phase 2 and does not ask).
-inline int plan_dimer_pairs_per_pass(long long B, long long n_items, long long requested, long long row_limit = 0) {
-  return plan_renyi_regions_per_pass(B, n_items, requested, row_limit);
+// a buffer [n_items][B] that a fold indexes item x B + chain (the dimers' phase 1): all of its rows stay within the
+// 32-bit row index
+inline bool plan_measure_rows_ok(long long B, long long n_items) {
+  return B >= 1 && n_items >= 1 && n_items <= (0x7fffffffLL - B) / B;
 }
-inline long long plan_dimer_row_limit(int N, int Hp) { return plan_renyi_row_limit(N, Hp); }
-// the phase-1 buffer is indexed bond x B + chain by the fold: all of its rows stay within the 32-bit row index
-inline bool plan_dimer_bond_rows_ok(long long B, long long n_bonds) {
-  return B >= 1 && n_bonds >= 1 && n_bonds <= (0x7fffffffLL - B) / B;
-}
-inline long long plan_dimer_passes(long long n_items, int per) { return per < 1 ? 0 : (n_items + per - 1) / per; }
-inline unsigned plan_dimer_fold_grid(int items) { return (unsigned)((items + 63) / 64); }    // 64 threads, one pair (or bond) each
+inline long long plan_measure_passes(long long n_items, int per) { return per < 1 ? 0 : (n_items + per - 1) / per; }
+inline unsigned plan_measure_fold_grid(int items) { return (unsigned)((items + 63) / 64); }    // 64 threads, one item each
 
 // ------------------------------------------------------------------------------- vmc_create
 struct DescPlan {

@@ -1,4 +1,4 @@
-// Renyi-2 entanglement entropy by the replica swap estimator (vmc_renyi2_swap, vmc_api_renyi.hip).  The replica pairs
+// Renyi-2 entanglement entropy by the replica swap estimator (vmc_renyi2_swap, vmc_api_measure.hip).  The replica pairs
 // are the chains (c, c + B/2); for a region A (a 0/1 mask over the sites) pair c MATCHES when both chains hold the same
 // sum of spins on A, and then contributes psi(x~) psi(y~) / (psi(x) psi(y)) with the spins of A exchanged between the
 // two; a pair that does not match would leave the Sz = 0 sector (psi = 0) and contributes 0.
@@ -40,9 +40,6 @@ __global__ __launch_bounds__(256) void k_swap_rows(const float* __restrict__ con
   }
 }
 
-// sign of a stored sign / amplitude: +-1, 0 for a vanishing amplitude
-__device__ inline int sgn_of(float v) { return (v > 0.f) - (v < 0.f); }
-
 // One thread per region k: swap_sum[k] = sum over matching pairs of sigma exp((l(x~) + l(y~)) - (l(x) + l(y))), pairs
 // ascending, fp64; match_count[k] = the number of matching pairs.  logit / sign [B]: the chains' own (the ctx's
 // cache); row_logit / row_sign [n_regions][B]: the swapped rows'.  sign / row_sign == nullptr: unsigned amplitudes.
@@ -83,18 +80,15 @@ __global__ __launch_bounds__(64) void k_swap_fold(const float* __restrict__ conf
 
 hipError_t launch_swap_rows(hipStream_t s, const float* configs, const unsigned char* mask, int B, int N,
                             int n_regions, int num_cus, float* rows) {
-  long long blocks = ((long long)n_regions * (B / 2) + 3) / 4;
-  const long long cap = 16LL * (num_cus > 0 ? num_cus : 1);
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_swap_rows, dim3((unsigned)blocks), dim3(256), 0, s, configs, mask, B, N, n_regions, rows);
+  hipLaunchKernelGGL(k_swap_rows, dim3(measure_rows_grid((long long)n_regions * (B / 2), num_cus)), dim3(256), 0, s, configs,
+                     mask, B, N, n_regions, rows);
   return hipGetLastError();
 }
 
 hipError_t launch_swap_fold(hipStream_t s, const float* configs, const unsigned char* mask, const float* logit,
                             const float* sign, const float* row_logit, const float* row_sign, int B, int N,
                             int n_regions, double* swap_sum, double* match_count) {
-  hipLaunchKernelGGL(k_swap_fold, dim3(plan_renyi_fold_grid(n_regions)), dim3(64), 0, s, configs, mask, logit, sign,
+  hipLaunchKernelGGL(k_swap_fold, dim3(plan_measure_fold_grid(n_regions)), dim3(64), 0, s, configs, mask, logit, sign,
                      row_logit, row_sign, B, N, n_regions, swap_sum, match_count);
   return hipGetLastError();
 }

@@ -1,0 +1,337 @@
+// The measurements over the ctx's current chains (extensions, no reference counterpart): vmc_pair_correlations,
+// vmc_renyi2_swap and vmc_dimer_correlations.  Each is a pure measurement: chains, step counter, accumulators, the
+// Hamiltonian's bond set and the validity of the amplitude and activation caches are as before when it returns.
+//
+// One scaffold serves the three.  MEASURE_GATE is the shared front of the refusals; PureMeasurement records which caches
+// were valid and un-vouches on every way out for those that were not; upload copies a host list into its device buffer;
+// for_passes walks the items in passes of plan_measure_per_pass (plan.hpp); read_back brings the fp64 sums down and
+// synchronises, on a failed call too.  The device buffers are the grow-only DevBufs of vmc_ctx.hpp.  What differs per
+// measurement is its own checks, what a pass launches and how the sums are handed out:
+//
+// Spin correlations.  Per pair (i, j): zz = sum_c s_i s_j and ex = sum_c [s_i s_j < 0] psi(swap_ij x_c) / psi(x_c); the
+// host forms <S_i . S_j> = (zz / 4 + ex / 2) / B.  The ratios are the rows the local energies already evaluate: a pass of
+// pairs is a bond set of its own (j_x = 2, so that val is the bare ratio; j_z = 0) that takes the place of the
+// Hamiltonian's five buffers + n_bonds in the ctx while ensure_list and the family's row launch (connected_rows_device)
+// run, and is swapped out again afterwards.  The fold per pair over chains is corr.hip.
+//
+// Renyi-2 entanglement entropy, the replica swap estimator over the chains taken as the B / 2 pairs (c, c + B / 2).  Per
+// region A: swap_sum = sum over the pairs that hold the same sum of spins on A of psi(x~) psi(y~) / (psi(x) psi(y)), with
+// the spins of A exchanged between the two chains, and match_count = the number of such pairs; the host forms
+// Tr rho_A^2 ~ swap_sum / (B / 2) and S2 = -ln of it.  A pass of regions is B rows per region in the row buffer of
+// vmc_amplitude (renyi.hip: k_swap_rows), evaluated by the family's own full forward (rows_forward_device, vmc_api.hip)
+// and folded per region (k_swap_fold) against the chains' cached ln|psi| and signs.
+//
+// Dimer-dimer correlations.  Per bond a = (i, j): bond_sum = sum_c bond(a; x_c); per ordered pair of bonds (a, b):
+// dd_sum = sum_c dd(a, b; x_c), the local value of (S_i . S_j)(S_k . S_l) (dimer.hip states both); the host forms
+// <A B> ~ dd_sum / B, <A> ~ bond_sum / B and the connected part.  Phase 1: B rows per bond, the single exchanges
+// (k_dimer_rows1), through the full forward in as many passes as the row buffer of vmc_amplitude takes (fewer bonds per
+// pass where pairs_per_pass asks for fewer); their ln|psi| and signs stay in the ctx's [n_bonds][B] buffers.  Phase 2:
+// passes of pairs, B rows per pair, the double exchanges (k_dimer_rows2), forwarded the same way and folded per pair
+// (k_dimer_fold) against phase 1's buffers and the chains' cached ln|psi| and signs.  (n_bonds + n_pairs) B full
+// forwards in all.
+#include "vmc_ctx.hpp"
+
+using namespace vmcapi;
+
+namespace {
+
+// the front of every measurement's refusals; returns from the entry
+#define MEASURE_GATE(c, which, name)                                                     \
+  ENTER(c);                                                                              \
+  REFUSE_PRODUCT(c, name);                                                               \
+  REFUSE_COMPOSED(c);                                                                    \
+  if ((which) != 0 && (which) != 1) return fail((c), VMC_ERR_INVALID, "bad which")
+
+// what was not valid before the measurement is not vouched for after it either: the next consumer fills it exactly as
+// it would have
+struct PureMeasurement {
+  vmc_ctx* c;
+  const bool cache_was[2], acts_were;
+  explicit PureMeasurement(vmc_ctx* ctx)
+      : c(ctx), cache_was{ctx->ps[0].cache_valid, ctx->ps[1].cache_valid}, acts_were(ctx->acts_valid) {}
+  ~PureMeasurement() {
+    for (int w = 0; w < 2; ++w) if (!cache_was[w]) c->ps[w].cache_valid = false;
+    if (!acts_were) c->acts_valid = false;
+  }
+  PureMeasurement(const PureMeasurement&) = delete;
+  PureMeasurement& operator=(const PureMeasurement&) = delete;
+};
+
+template <class T>
+int upload(vmc_ctx* c, T* dst, const std::vector<T>& src) {
+  hipError_t e = hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, c->stream);
+  return e == hipSuccess ? VMC_OK : fail(c, VMC_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+}
+
+// items [k0, k0 + n) per call of pass(k0, n), `per` at a time, until one fails; rc: the call so far
+template <class Pass>
+int for_passes(long long n_items, int per, int rc, Pass pass) {
+  for (long long k0 = 0; k0 < n_items && rc == VMC_OK; k0 += per)
+    rc = pass(k0, (int)(n_items - k0 < per ? n_items - k0 : per));
+  return rc;
+}
+
+// the end of every measurement: n sums to the host.  The stream is synchronised on a failed call (rc) too -- the host
+// lists of the entry are the sources of asynchronous copies
+int read_back(vmc_ctx* c, int rc, const char* entry, const double* sums, size_t n, std::vector<double>* out) {
+  hipError_t e = hipSuccess;
+  if (rc == VMC_OK) {
+    out->resize(n);
+    e = hipMemcpyAsync(out->data(), sums, n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  }
+  const hipError_t e_sync = hipStreamSynchronize(c->stream);
+  if (rc != VMC_OK) return rc;
+  if (e == hipSuccess) e = e_sync;
+  return e == hipSuccess ? VMC_OK : fail(c, VMC_ERR_HIP, std::string(entry) + " read-back: " + hipGetErrorString(e));
+}
+
+// ---- spin correlations
+
+struct BondSet {
+  int n_bonds; int2* bonds; float *half_jx, *quarter_jz; int2* rowinfo; float* val;
+};
+
+BondSet current_set(const vmc_ctx* c) { return BondSet{c->n_bonds, c->bonds, c->half_jx, c->quarter_jz, c->rowinfo, c->val}; }
+
+// cnt / diag / off / the list belong to whichever set was counted last: nothing of them survives a swap
+void install_set(vmc_ctx* c, const BondSet& s) {
+  c->n_bonds = s.n_bonds; c->bonds = s.bonds; c->half_jx = s.half_jx; c->quarter_jz = s.quarter_jz;
+  c->rowinfo = s.rowinfo; c->val = s.val;
+  c->bonds_epoch += 1;        // (the bond-difference tables of the row kernel belong to the list they were built from)
+  c->list_valid = false;
+  c->cnt_valid = false;
+}
+
+// the set of a pass for `per` pairs; hx and qz are (re)filled whenever one of the five grew
+int corr_reserve_pass(vmc_ctx* c, long long per) {
+  CorrBufs& m = c->corr;
+  const long long rows = (long long)c->B * per;
+  bool g[5];
+  PROPAGATE(m.hx.reserve(c, per, "corr.hx", &g[0]));
+  PROPAGATE(m.qz.reserve(c, per, "corr.qz", &g[1]));
+  PROPAGATE(m.rowinfo.reserve(c, rows, "corr.rowinfo", &g[2]));
+  PROPAGATE(m.val.reserve(c, rows, "corr.val", &g[3]));
+  PROPAGATE(m.dense.reserve(c, rows, "corr.dense", &g[4]));
+  if (!(g[0] || g[1] || g[2] || g[3] || g[4])) return VMC_OK;
+  HIPCHK(c, launch_fill(c->stream, m.hx.p, 1.f, (int)m.hx.cap));      // 0.5 j_x with j_x = 2
+  HIPCHK(c, hipMemsetAsync(m.qz.p, 0, (size_t)m.qz.cap * sizeof(float), c->stream));
+  return VMC_OK;
+}
+
+int corr_reserve(vmc_ctx* c, long long per, long long n_pairs) {
+  PROPAGATE(c->corr.pairs.reserve(c, n_pairs, "corr.pairs"));
+  PROPAGATE(c->corr.out.reserve(c, 2 * n_pairs, "corr.out"));
+  const int rc = corr_reserve_pass(c, per);
+  // a set that did not grow, or was not filled, as a whole is no set: the next call allocates and fills it afresh
+  if (rc != VMC_OK) { hipStreamSynchronize(c->stream); c->corr.release_pass(); }
+  return rc;
+}
+
+// pairs [k0, k0 + n) with their set installed: list, rows, fold
+int corr_pass(vmc_ctx* c, int which, long long k0, int n, long long n_pairs) {
+  PROPAGATE(ensure_list(c));
+  PROPAGATE(connected_rows_device(c, which, false));
+  Timer t(c, "corr_fold");
+  HIPCHK(c, launch_pair_fold(c->stream, c->configs, c->bonds, c->rowinfo, c->val, c->off + c->B, c->B, c->N, n,
+                             c->num_cus, c->corr.dense.p, c->corr.out.p + k0, c->corr.out.p + n_pairs + k0));
+  return VMC_OK;
+}
+
+// ---- Renyi-2 swap estimator
+
+int renyi_reserve(vmc_ctx* c, long long n_regions) {
+  PROPAGATE(c->renyi.mask.reserve(c, n_regions * c->N, "renyi.mask"));
+  return c->renyi.out.reserve(c, 2 * n_regions, "renyi.out");
+}
+
+// regions [k0, k0 + n): rows, forward, fold
+int renyi_pass(vmc_ctx* c, int which, long long k0, int n, long long n_regions) {
+  const ParamSet& p = c->ps[which];
+  const unsigned char* mask = c->renyi.mask.p + k0 * c->N;
+  double* out = c->renyi.out.p;
+  const long long rows = (long long)n * c->B;
+  {
+    Timer t(c, "renyi_rows");
+    HIPCHK(c, launch_swap_rows(c->stream, c->configs, mask, c->B, c->N, n, c->num_cus, c->tmp_cfg));
+  }
+  {
+    Timer t(c, "renyi_forward");
+    PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, rows, c->tmp_out, c->tmp_sign));
+  }
+  Timer t(c, "renyi_fold");
+  HIPCHK(c, launch_swap_fold(c->stream, c->configs, mask, p.logit, c->sgn ? p.sign : nullptr, c->tmp_out,
+                             c->sgn ? c->tmp_sign : nullptr, c->B, c->N, n, out + k0, out + n_regions + k0));
+  return VMC_OK;
+}
+
+// ---- dimer-dimer correlations
+
+int dimer_reserve(vmc_ctx* c, long long n_bonds, long long n_pairs) {
+  DimerBufs& m = c->dimer;
+  PROPAGATE(m.bonds.reserve(c, n_bonds, "dimer.bonds"));
+  PROPAGATE(m.pairs.reserve(c, n_pairs, "dimer.pairs"));
+  PROPAGATE(m.logit.reserve(c, n_bonds * c->B, "dimer.logit"));
+  if (c->sgn) PROPAGATE(m.sign.reserve(c, n_bonds * c->B, "dimer.sign"));
+  return m.out.reserve(c, n_bonds + n_pairs, "dimer.out");
+}
+
+// bonds [a0, a0 + n): rows, forward into the [n_bonds][B] buffers
+int dimer_single_pass(vmc_ctx* c, int which, long long a0, int n) {
+  const DimerBufs& m = c->dimer;
+  const long long rows = (long long)n * c->B;
+  {
+    Timer t(c, "dimer_rows");
+    HIPCHK(c, launch_dimer_rows1(c->stream, c->configs, m.bonds.p + a0, c->B, c->N, n, c->num_cus, c->tmp_cfg));
+  }
+  Timer t(c, "dimer_forward");
+  PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, rows, m.logit.p + a0 * c->B,
+                                c->sgn ? m.sign.p + a0 * c->B : c->tmp_sign));
+  return VMC_OK;
+}
+
+// pairs [p0, p0 + n): rows, forward, fold
+int dimer_double_pass(vmc_ctx* c, int which, long long p0, int n, double* dd_out) {
+  const ParamSet& p = c->ps[which];
+  const DimerBufs& m = c->dimer;
+  const long long rows = (long long)n * c->B;
+  {
+    Timer t(c, "dimer_rows");
+    HIPCHK(c, launch_dimer_rows2(c->stream, c->configs, m.bonds.p, m.pairs.p + p0, c->B, c->N, n, c->num_cus, c->tmp_cfg));
+  }
+  {
+    Timer t(c, "dimer_forward");
+    PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, rows, c->tmp_out, c->tmp_sign));
+  }
+  Timer t(c, "dimer_fold");
+  HIPCHK(c, launch_dimer_fold(c->stream, c->configs, m.bonds.p, m.pairs.p + p0, p.logit, c->sgn ? p.sign : nullptr,
+                              m.logit.p, c->sgn ? m.sign.p : nullptr, c->tmp_out, c->sgn ? c->tmp_sign : nullptr, c->B,
+                              c->N, n, dd_out + p0));
+  return VMC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vmc_pair_correlations(vmc_ctx* c, int which, int32_t n_pairs, const int32_t* ij, int32_t pairs_per_pass,
+                          double* zz_sum, double* ex_sum) {
+  MEASURE_GATE(c, which, "vmc_pair_correlations");
+  if (n_pairs < 1 || !ij || pairs_per_pass < 0) return fail(c, VMC_ERR_INVALID, "bad pair arguments");
+  std::vector<int2> pairs((size_t)n_pairs);
+  for (int k = 0; k < n_pairs; ++k) {
+    const int i = ij[2 * k], j = ij[2 * k + 1];
+    if (i < 0 || j < 0 || i >= c->N || j >= c->N || i == j)
+      return fail(c, VMC_ERR_INVALID, "pair site index out of range (or i == j)");
+    pairs[(size_t)k] = make_int2(i, j);
+  }
+  const int per = plan_measure_per_pass(c->B, n_pairs, pairs_per_pass);
+  if (per < 1) return fail(c, VMC_ERR_UNSUPPORTED, "batch_size does not leave room for one pair in the 32-bit row index");
+  PureMeasurement pure(c);
+  int rc = ensure_cache(c, which);           // (before the swap: it reads no bond set; gnn / ed_vector readiness, parameters)
+  if (rc == VMC_OK) rc = corr_reserve(c, per, n_pairs);
+  if (rc == VMC_OK) rc = upload(c, c->corr.pairs.p, pairs);
+  if (rc == VMC_OK) {
+    const CorrBufs& m = c->corr;
+    const BondSet hamiltonian = current_set(c);
+    rc = for_passes(n_pairs, per, rc, [&](long long k0, int n) {
+      install_set(c, BondSet{n, m.pairs.p + k0, m.hx.p, m.qz.p, m.rowinfo.p, m.val.p});
+      return corr_pass(c, which, k0, n, n_pairs);
+    });
+    install_set(c, hamiltonian);
+  }
+  std::vector<double> out;
+  rc = read_back(c, rc, "vmc_pair_correlations", c->corr.out.p, 2 * (size_t)n_pairs, &out);
+  if (rc != VMC_OK) return rc;
+  for (int k = 0; k < n_pairs; ++k) {
+    if (zz_sum) zz_sum[k] = out[(size_t)k];
+    if (ex_sum) ex_sum[k] = out[(size_t)n_pairs + (size_t)k];
+  }
+  return VMC_OK;
+}
+
+int vmc_renyi2_swap(vmc_ctx* c, int which, int32_t n_regions, const uint8_t* region_mask, int32_t regions_per_pass,
+                    double* swap_sum, double* match_count) {
+  MEASURE_GATE(c, which, "vmc_renyi2_swap");
+  if (n_regions < 1 || !region_mask || regions_per_pass < 0) return fail(c, VMC_ERR_INVALID, "bad region arguments");
+  if (c->B % 2 != 0) return fail(c, VMC_ERR_INVALID, "vmc_renyi2_swap pairs chain c with chain c + batch_size / 2: batch_size must be even");
+  if (!c->sgn && c->oact != VMC_ACT_EXP_)
+    return fail(c, VMC_ERR_UNSUPPORTED, "vmc_renyi2_swap needs the exp output activation (the logit is ln psi only then)");
+  std::vector<unsigned char> mask((size_t)n_regions * (size_t)c->N);
+  for (size_t k = 0; k < mask.size(); ++k) {
+    if (region_mask[k] > 1) return fail(c, VMC_ERR_INVALID, "region mask entries are 0 or 1");
+    mask[k] = region_mask[k];
+  }
+  const int per = plan_measure_per_pass(c->B, n_regions, regions_per_pass, plan_measure_row_limit(c->N, c->Hp));
+  if (per < 1) return fail(c, VMC_ERR_UNSUPPORTED, "batch_size does not leave room for one region in the 32-bit row index");
+  PureMeasurement pure(c);
+  int rc = ensure_cache(c, which);           // l(x), l(y) and their signs, as the local energies take them
+  if (rc == VMC_OK) rc = renyi_reserve(c, n_regions);
+  if (rc == VMC_OK) rc = grow_tmp(c, (long long)per * c->B);
+  if (rc == VMC_OK) rc = upload(c, c->renyi.mask.p, mask);
+  rc = for_passes(n_regions, per, rc, [&](long long k0, int n) { return renyi_pass(c, which, k0, n, n_regions); });
+  std::vector<double> out;
+  rc = read_back(c, rc, "vmc_renyi2_swap", c->renyi.out.p, 2 * (size_t)n_regions, &out);
+  if (rc != VMC_OK) return rc;
+  for (int k = 0; k < n_regions; ++k) {
+    if (swap_sum) swap_sum[k] = out[(size_t)k];
+    if (match_count) match_count[k] = out[(size_t)n_regions + (size_t)k];
+  }
+  return VMC_OK;
+}
+
+int vmc_dimer_correlations(vmc_ctx* c, int which, int32_t n_bonds, const int32_t* bonds, int32_t n_pairs,
+                           const int32_t* pairs, int32_t pairs_per_pass, double* bond_sum, double* dd_sum) {
+  MEASURE_GATE(c, which, "vmc_dimer_correlations");
+  if (n_bonds < 1 || !bonds || n_pairs < 0 || (n_pairs > 0 && !pairs) || pairs_per_pass < 0)
+    return fail(c, VMC_ERR_INVALID, "bad bond / pair arguments");
+  std::vector<int2> hb((size_t)n_bonds), hp((size_t)n_pairs);
+  for (int a = 0; a < n_bonds; ++a) {
+    const int i = bonds[2 * a], j = bonds[2 * a + 1];
+    if (i < 0 || j < 0 || i >= c->N || j >= c->N || i == j) {
+      char msg[128];
+      snprintf(msg, sizeof(msg), "bond %d = (%d, %d): two distinct sites in 0 .. %d required", a, i, j, c->N - 1);
+      return fail(c, VMC_ERR_INVALID, msg);
+    }
+    hb[(size_t)a] = make_int2(i, j);
+  }
+  for (int p = 0; p < n_pairs; ++p) {
+    const int a = pairs[2 * p], b = pairs[2 * p + 1];
+    if (a < 0 || b < 0 || a >= n_bonds || b >= n_bonds) {
+      char msg[128];
+      snprintf(msg, sizeof(msg), "pair %d = (%d, %d): bond indices in 0 .. %d required", p, a, b, n_bonds - 1);
+      return fail(c, VMC_ERR_INVALID, msg);
+    }
+    hp[(size_t)p] = make_int2(a, b);
+  }
+  if (!c->sgn && c->oact != VMC_ACT_EXP_)
+    return fail(c, VMC_ERR_UNSUPPORTED, "vmc_dimer_correlations needs the exp output activation (the logit is ln psi only then)");
+  const long long row_limit = plan_measure_row_limit(c->N, c->Hp);
+  const int per1 = plan_measure_per_pass(c->B, n_bonds, pairs_per_pass, row_limit);    // (a request splits both phases)
+  const int per2 = n_pairs > 0 ? plan_measure_per_pass(c->B, n_pairs, pairs_per_pass, row_limit) : 0;
+  if (per1 < 1 || (n_pairs > 0 && per2 < 1) || !plan_measure_rows_ok(c->B, n_bonds))
+    return fail(c, VMC_ERR_UNSUPPORTED, "batch_size x bonds does not fit the 32-bit row index");
+  PureMeasurement pure(c);
+  const DimerBufs& m = c->dimer;
+  int rc = ensure_cache(c, which);           // ln|psi(x_c)| and the signs, as the local energies take them
+  if (rc == VMC_OK) rc = dimer_reserve(c, n_bonds, n_pairs);
+  if (rc == VMC_OK) rc = grow_tmp(c, (long long)(per1 > per2 ? per1 : per2) * c->B);
+  if (rc == VMC_OK) rc = upload(c, m.bonds.p, hb);
+  if (rc == VMC_OK && n_pairs > 0) rc = upload(c, m.pairs.p, hp);
+  rc = for_passes(n_bonds, per1, rc, [&](long long a0, int n) { return dimer_single_pass(c, which, a0, n); });
+  if (rc == VMC_OK) {
+    const ParamSet& p = c->ps[which];
+    Timer t(c, "dimer_fold");
+    hipError_t e = launch_dimer_bond_fold(c->stream, c->configs, m.bonds.p, p.logit, c->sgn ? p.sign : nullptr, m.logit.p,
+                                          c->sgn ? m.sign.p : nullptr, c->B, c->N, n_bonds, m.out.p);
+    if (e != hipSuccess) rc = fail(c, VMC_ERR_HIP, std::string("k_dimer_bond_fold: ") + hipGetErrorString(e));
+  }
+  rc = for_passes(n_pairs, per2, rc, [&](long long p0, int n) { return dimer_double_pass(c, which, p0, n, m.out.p + n_bonds); });
+  std::vector<double> out;
+  rc = read_back(c, rc, "vmc_dimer_correlations", m.out.p, (size_t)n_bonds + (size_t)n_pairs, &out);
+  if (rc != VMC_OK) return rc;
+  for (int a = 0; a < n_bonds && bond_sum; ++a) bond_sum[a] = out[(size_t)a];
+  for (int p = 0; p < n_pairs && dd_sum; ++p) dd_sum[p] = out[(size_t)n_bonds + (size_t)p];
+  return VMC_OK;
+}
+
+}  // extern "C"

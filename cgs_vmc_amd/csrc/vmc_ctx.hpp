@@ -58,6 +58,44 @@ using vmcapi::TimedRegion;
 
 struct ProdState;      // vmc_api_prod.hip: what a product ctx keeps beside the members below
 
+// A grow-only device buffer.  reserve(c, n, name): room for n elements (at least one); a no-op while n <= cap, otherwise
+// the stream is synchronised (work in flight may read the old buffer), the buffer freed and a larger one allocated --
+// the contents are not kept, `grew` tells.  A failed allocation leaves the buffer empty (cap 0) and names it in the
+// message.  It never shrinks.  (Definition: the end of this file.)
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  long long cap = 0;
+  int reserve(vmc_ctx* c, long long n, const char* name, bool* grew = nullptr);
+  void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
+};
+// spin correlations: the bond set of a pass of pairs -- swapped with the five Hamiltonian members of the ctx for the
+// pass -- the scatter target, the sums
+struct CorrBufs {
+  DevBuf<int2> pairs;            // every pair of the call (a pass reads a slice)
+  DevBuf<float> hx, qz;          // [pairs per pass] 1 (j_x = 2) and 0 (j_z = 0); these five are the set of a pass
+  DevBuf<int2> rowinfo;          // [B pairs per pass]
+  DevBuf<float> val, dense;      // [B pairs per pass] rows; [B][pairs of the pass] the rows by (chain, pair)
+  DevBuf<double> out;            // [2][n_pairs] zz sums, exchange sums
+  void release_pass() { hx.release(); qz.release(); rowinfo.release(); val.release(); dense.release(); }
+  void release() { pairs.release(); out.release(); release_pass(); }
+};
+// Renyi-2 swap estimator: the region masks of a call and its sums
+struct RenyiBufs {
+  DevBuf<unsigned char> mask;    // [n_regions][N] 0/1
+  DevBuf<double> out;            // [2][n_regions] swap sums, match counts
+  void release() { mask.release(); out.release(); }
+};
+// dimer-dimer correlations: the two lists of a call, ln|psi| (and, signed types, the sign) of every single exchange,
+// and the sums
+struct DimerBufs {
+  DevBuf<int2> bonds;            // sites (i, j)
+  DevBuf<int2> pairs;            // indices (a, b) into bonds
+  DevBuf<float> logit, sign;     // [n_bonds][B]; sign: signed types only
+  DevBuf<double> out;            // [n_bonds + n_pairs] bond sums, then dd sums
+  void release() { bonds.release(); pairs.release(); logit.release(); sign.release(); out.release(); }
+};
+
 struct vmc_ctx {
   vmc_desc d;
   // ProductOfWavefunctions (vmc_api_prod.hip, prod.hip): a ctx made by vmc_create_product owns the chains, the accumulators
@@ -188,26 +226,10 @@ struct vmc_ctx {
   bool cnt_valid = false;          // cnt / diag hold the census of `configs` (left by the sampler's last launch)
   int* cnt_alt = nullptr; float* diag_alt = nullptr;   // the census the NEXT sampler launch writes (swapped with the chains)
   long long last_rows = 0;
-  // spin correlations (vmc_api_corr.hip): the bond set of a pass of pairs -- swapped with the five Hamiltonian members
-  // above for the pass -- the scatter target, the sums; sized for corr_cap pairs per pass / corr_cap_all pairs in all
-  int2* corr_pairs = nullptr;                        // [corr_cap_all] every pair of the call (a pass reads a slice)
-  float *corr_hx = nullptr, *corr_qz = nullptr;      // [corr_cap] 1 (j_x = 2) and 0 (j_z = 0)
-  int2* corr_rowinfo = nullptr;                      // [B corr_cap]
-  float *corr_val = nullptr, *corr_dense = nullptr;  // [B corr_cap] rows; [B][pairs of the pass] the rows by (chain, pair)
-  double* corr_out = nullptr;                        // [2][corr_cap_all] zz sums, exchange sums
-  long long corr_cap = 0, corr_cap_all = 0;
-  // Renyi-2 swap estimator (vmc_api_renyi.hip): the region masks of a call and its sums; the rows of a pass live in the
-  // tmp_* buffers of vmc_amplitude (grow_tmp)
-  unsigned char* renyi_mask = nullptr;               // [renyi_cap][N] 0/1
-  double* renyi_out = nullptr;                       // [2][renyi_cap] swap sums, match counts
-  long long renyi_cap = 0;
-  // dimer-dimer correlations (vmc_api_dimer.hip): the two lists of a call, ln|psi| (and, signed types, the sign) of
-  // every single exchange, and the sums; the rows of a pass live in the tmp_* buffers of vmc_amplitude (grow_tmp)
-  int2* dimer_bonds = nullptr;                       // [dimer_cap_bonds] sites (i, j)
-  int2* dimer_pairs = nullptr;                       // [dimer_cap_pairs] indices (a, b) into dimer_bonds
-  float *dimer_logit = nullptr, *dimer_sign = nullptr;   // [dimer_cap_bonds][B]; dimer_sign: signed types only
-  double* dimer_out = nullptr;                       // [dimer_cap_bonds + dimer_cap_pairs] bond sums, then dd sums
-  long long dimer_cap_bonds = 0, dimer_cap_pairs = 0;
+  // the measurements (vmc_api_measure.hip); the rows of a Renyi-2 / dimer pass live in the tmp_* buffers of vmc_amplitude
+  CorrBufs corr;
+  RenyiBufs renyi;
+  DimerBufs dimer;
   // gradient path
   std::vector<float*> act;   // L views [B][Hp] into act_all
   float* act_all = nullptr;  // [L][B][Hp]
@@ -497,3 +519,21 @@ void prod_child_destroyed(vmc_ctx* child);           // vmc_destroy of a factor 
 bool sampler_refresh_ok(const vmc_ctx* c);
 int refresh_cache_by_sampler(vmc_ctx* c, int which);
 }  // namespace vmcapi
+
+template <class T>
+int DevBuf<T>::reserve(vmc_ctx* c, long long n, const char* name, bool* grew) {
+  if (grew) *grew = false;
+  if (n < 1) n = 1;
+  if (n <= cap) return VMC_OK;
+  using vmcapi::fail;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  release();
+  const hipError_t e = vmcapi::dalloc(&p, n);
+  if (e != hipSuccess) {
+    p = nullptr;
+    return fail(c, VMC_ERR_HIP, std::string("dalloc(&c->") + name + "): " + hipGetErrorString(e));
+  }
+  cap = n;
+  if (grew) *grew = true;
+  return VMC_OK;
+}

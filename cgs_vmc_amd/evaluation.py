@@ -109,6 +109,48 @@ class MonteCarloOperatorEvaluator(WavefunctionEvaluator):
     return list(measurements())
 
 
+def _sampling_eval_ops(wavefunction, hparams, shared_resources, make_value) -> EvalOps:
+  """The EvalOps of a measurement over the sampler's chains: make_value(engine) is its value tensor, `engine` the one
+  that holds the CONFIGS variable mc_step moves."""
+  configs = graph_builders.get_configs(shared_resources, hparams.batch_size, hparams.num_sites)
+  mc_step, acc_rate = graph_builders.get_monte_carlo_sampling(shared_resources, configs, wavefunction)
+  engine = wavefunction._bind(configs)
+  return EvalOps(
+      value=make_value(engine),
+      mc_step=mc_step,
+      acceptance_rate=acc_rate,
+      placeholder_input=None,
+      wavefunction_value=None,
+  )
+
+
+def _sampled(eval_ops, session, hparams, stack, per_sample) -> int:
+  """The sample loop of the three measurement evaluators, on the same schedule as MonteCarloOperatorEvaluator's (which
+  keeps its own loop: no all-reduce, and a fused path): thermalises for num_equilibration_sweeps sweeps, then takes
+  num_evaluation_samples measurements, num_monte_carlo_sweeps sweeps apart.
+  stack(session.run(value)) is the fp64 array of this rank's sums; with sharded chains the ranks' arrays are added by one
+  parallel.allreduce_array per sample before per_sample(s, sums) sees them.  Returns the acceptance count."""
+  steps_per_sweep = hparams.num_sites
+  decorrelation = hparams.num_monte_carlo_sweeps * steps_per_sweep
+  sharded = parallel.world_size() > 1
+  accepted = 0
+  _run_mc_steps(session, eval_ops.mc_step, hparams.num_equilibration_sweeps * steps_per_sweep)
+  for s in range(hparams.num_evaluation_samples):
+    sums = stack(session.run(eval_ops.value))
+    if sharded:
+      sums = parallel.allreduce_array(sums)
+    per_sample(s, sums)
+    _run_mc_steps(session, eval_ops.mc_step, decorrelation)
+    accepted += getattr(eval_ops.mc_step, 'last_accepted', 0)
+  return accepted
+
+
+def _std_err(samples):
+  """The conventional standard error of the mean over axis 0: std(ddof = 1) / sqrt(n_samples), 0 for a single sample."""
+  n = samples.shape[0]
+  return samples.std(axis=0, ddof=1) / np.sqrt(n) if n > 1 else np.zeros(samples.shape[1:])
+
+
 class PairCorrelationTensor(session_lib.Tensor):
   """(zz_sum, ex_sum) [n_pairs] float64 of `pairs` over THIS rank's chains (VmcEngine.pair_correlations);
   `global_batch` is the number of chains of all ranks together."""
@@ -129,19 +171,9 @@ class SpinCorrelationEvaluator(WavefunctionEvaluator):
   def build_eval_ops(self, wavefunction, operator, hparams,
                      shared_resources: Dict[graph_builders.ResourceName, Any]) -> EvalOps:
     from . import lattice
-    batch_size = hparams.batch_size
-    n_sites = hparams.num_sites
-    pairs = lattice.all_pairs(n_sites) if operator is None else operator
-    configs = graph_builders.get_configs(shared_resources, batch_size, n_sites)
-    mc_step, acc_rate = graph_builders.get_monte_carlo_sampling(shared_resources, configs, wavefunction)
-    engine = wavefunction._bind(configs)
-    return EvalOps(
-        value=PairCorrelationTensor(engine, pairs, wavefunction._which, batch_size),
-        mc_step=mc_step,
-        acceptance_rate=acc_rate,
-        placeholder_input=None,
-        wavefunction_value=None,
-    )
+    pairs = lattice.all_pairs(hparams.num_sites) if operator is None else operator
+    return _sampling_eval_ops(wavefunction, hparams, shared_resources, lambda engine: PairCorrelationTensor(
+        engine, pairs, wavefunction._which, hparams.batch_size))
 
   def run_evaluation(self, eval_ops: EvalOps, session, hparams, epoch_num: int) -> Dict[str, np.ndarray]:
     """Thermalises for num_equilibration_sweeps sweeps, then takes num_evaluation_samples measurements,
@@ -154,27 +186,17 @@ class SpinCorrelationEvaluator(WavefunctionEvaluator):
     [n_pairs], the batch means themselves."""
     del epoch_num
     value = eval_ops.value
-    steps_per_sweep = hparams.num_sites
-    decorrelation = hparams.num_monte_carlo_sweeps * steps_per_sweep
-    n_samples = hparams.num_evaluation_samples
-    sharded = parallel.world_size() > 1
-    self.acceptance_count = 0
-    samples = np.empty((n_samples, 3, value.pairs.shape[0]), np.float64)
-    _run_mc_steps(session, eval_ops.mc_step, hparams.num_equilibration_sweeps * steps_per_sweep)
-    for s in range(n_samples):
-      sums = np.stack(session.run(value)).astype(np.float64)        # [2][n_pairs]: zz, ex of this rank's chains
-      if sharded:
-        sums = parallel.allreduce_array(sums)
+    samples = np.empty((hparams.num_evaluation_samples, 3, value.pairs.shape[0]), np.float64)
+
+    def per_sample(s, sums):                              # [2][n_pairs]: zz, ex
       samples[s, 0] = 0.25 * sums[0] / value.global_batch
       samples[s, 1] = 0.5 * sums[1] / value.global_batch
       samples[s, 2] = (0.25 * sums[0] + 0.5 * sums[1]) / value.global_batch
-      _run_mc_steps(session, eval_ops.mc_step, decorrelation)
-      self.acceptance_count += getattr(eval_ops.mc_step, 'last_accepted', 0)
+    self.acceptance_count = _sampled(eval_ops, session, hparams, lambda v: np.stack(v).astype(np.float64), per_sample)
     out = {'pairs': value.pairs.copy(), 'samples': samples}
     for k, name in enumerate(('szsz', 'exchange', 'ss')):
       out[name] = samples[:, k].mean(axis=0)
-      out[name + '_err'] = (samples[:, k].std(axis=0, ddof=1) / np.sqrt(n_samples) if n_samples > 1
-                            else np.zeros(samples.shape[2]))
+      out[name + '_err'] = _std_err(samples[:, k])
     return out
 
 
@@ -201,19 +223,9 @@ class RenyiEntropyEvaluator(WavefunctionEvaluator):
   def build_eval_ops(self, wavefunction, operator, hparams,
                      shared_resources: Dict[graph_builders.ResourceName, Any]) -> EvalOps:
     from . import lattice
-    batch_size = hparams.batch_size
-    n_sites = hparams.num_sites
-    regions = lattice.block_regions(n_sites) if operator is None else operator
-    configs = graph_builders.get_configs(shared_resources, batch_size, n_sites)
-    mc_step, acc_rate = graph_builders.get_monte_carlo_sampling(shared_resources, configs, wavefunction)
-    engine = wavefunction._bind(configs)
-    return EvalOps(
-        value=RenyiSwapTensor(engine, regions, wavefunction._which, n_sites),
-        mc_step=mc_step,
-        acceptance_rate=acc_rate,
-        placeholder_input=None,
-        wavefunction_value=None,
-    )
+    regions = lattice.block_regions(hparams.num_sites) if operator is None else operator
+    return _sampling_eval_ops(wavefunction, hparams, shared_resources, lambda engine: RenyiSwapTensor(
+        engine, regions, wavefunction._which, hparams.num_sites))
 
   def run_evaluation(self, eval_ops: EvalOps, session, hparams, epoch_num: int) -> Dict[str, np.ndarray]:
     """Thermalises for num_equilibration_sweeps sweeps, then takes num_evaluation_samples measurements,
@@ -227,27 +239,21 @@ class RenyiEntropyEvaluator(WavefunctionEvaluator):
     that hold equal magnetisation on the region; 'samples' [n_samples][n_regions], the batch means themselves."""
     del epoch_num
     value = eval_ops.value
-    steps_per_sweep = hparams.num_sites
-    decorrelation = hparams.num_monte_carlo_sweeps * steps_per_sweep
-    n_samples = hparams.num_evaluation_samples
-    sharded = parallel.world_size() > 1
     n_regions = value.masks.shape[0]
-    self.acceptance_count = 0
-    samples = np.empty((n_samples, n_regions), np.float64)
-    matched = np.empty((n_samples, n_regions), np.float64)
-    _run_mc_steps(session, eval_ops.mc_step, hparams.num_equilibration_sweeps * steps_per_sweep)
-    for s in range(n_samples):
-      swap, match = session.run(value)                   # of this rank's chains
+    samples = np.empty((hparams.num_evaluation_samples, n_regions), np.float64)
+    matched = np.empty_like(samples)
+
+    def stack(swap_match):                                # [3][n_regions]: swap sums, match counts, pairs of this rank
       sums = np.empty((3, n_regions), np.float64)
-      sums[0], sums[1], sums[2] = swap, match, value.engine.batch_size // 2
-      if sharded:
-        sums = parallel.allreduce_array(sums)
+      sums[0], sums[1], sums[2] = swap_match[0], swap_match[1], value.engine.batch_size // 2
+      return sums
+
+    def per_sample(s, sums):
       samples[s] = sums[0] / sums[2]
       matched[s] = sums[1] / sums[2]
-      _run_mc_steps(session, eval_ops.mc_step, decorrelation)
-      self.acceptance_count += getattr(eval_ops.mc_step, 'last_accepted', 0)
+    self.acceptance_count = _sampled(eval_ops, session, hparams, stack, per_sample)
     purity = samples.mean(axis=0)
-    err = samples.std(axis=0, ddof=1) / np.sqrt(n_samples) if n_samples > 1 else np.zeros(n_regions)
+    err = _std_err(samples)
     with np.errstate(divide='ignore', invalid='ignore'):
       s2, s2_err = -np.log(purity), err / purity
     return {'regions': value.masks.copy(), 'purity': purity, 'purity_err': err, 's2': s2, 's2_err': s2_err,
@@ -283,23 +289,13 @@ class DimerCorrelationEvaluator(WavefunctionEvaluator):
   def build_eval_ops(self, wavefunction, operator, hparams,
                      shared_resources: Dict[graph_builders.ResourceName, Any]) -> EvalOps:
     from . import lattice
-    batch_size = hparams.batch_size
-    n_sites = hparams.num_sites
     if operator is None:
-      bonds = lattice.load_bonds(getattr(hparams, 'checkpoint_dir', '') or '', n_sites)
+      bonds = lattice.load_bonds(getattr(hparams, 'checkpoint_dir', '') or '', hparams.num_sites)
       pairs = [(0, b) for b in range(len(bonds))]
     else:
       bonds, pairs = operator
-    configs = graph_builders.get_configs(shared_resources, batch_size, n_sites)
-    mc_step, acc_rate = graph_builders.get_monte_carlo_sampling(shared_resources, configs, wavefunction)
-    engine = wavefunction._bind(configs)
-    return EvalOps(
-        value=DimerCorrelationTensor(engine, bonds, pairs, wavefunction._which, batch_size),
-        mc_step=mc_step,
-        acceptance_rate=acc_rate,
-        placeholder_input=None,
-        wavefunction_value=None,
-    )
+    return _sampling_eval_ops(wavefunction, hparams, shared_resources, lambda engine: DimerCorrelationTensor(
+        engine, bonds, pairs, wavefunction._which, hparams.batch_size))
 
   def run_evaluation(self, eval_ops: EvalOps, session, hparams, epoch_num: int) -> Dict[str, np.ndarray]:
     """Thermalises for num_equilibration_sweeps sweeps, then takes num_evaluation_samples measurements,
@@ -313,33 +309,21 @@ class DimerCorrelationEvaluator(WavefunctionEvaluator):
     [n_samples][n_bonds]."""
     del epoch_num
     value = eval_ops.value
-    steps_per_sweep = hparams.num_sites
-    decorrelation = hparams.num_monte_carlo_sweeps * steps_per_sweep
-    n_samples = hparams.num_evaluation_samples
-    sharded = parallel.world_size() > 1
     n_bonds, n_pairs = value.bonds.shape[0], value.pairs.shape[0]
-    self.acceptance_count = 0
-    samples = np.empty((n_samples, 2, n_pairs), np.float64)
-    bond_samples = np.empty((n_samples, n_bonds), np.float64)
-    _run_mc_steps(session, eval_ops.mc_step, hparams.num_equilibration_sweeps * steps_per_sweep)
-    for s in range(n_samples):
-      sums = np.concatenate(session.run(value)).astype(np.float64)      # [n_bonds + n_pairs] of this rank's chains
-      if sharded:
-        sums = parallel.allreduce_array(sums)
+    samples = np.empty((hparams.num_evaluation_samples, 2, n_pairs), np.float64)
+    bond_samples = np.empty((hparams.num_evaluation_samples, n_bonds), np.float64)
+
+    def per_sample(s, sums):                              # [n_bonds + n_pairs]: bond sums, then dd sums
       bond = sums[:n_bonds] / value.global_batch
       bond_samples[s] = bond
       samples[s, 0] = sums[n_bonds:] / value.global_batch
       samples[s, 1] = samples[s, 0] - bond[value.pairs[:, 0]] * bond[value.pairs[:, 1]]
-      _run_mc_steps(session, eval_ops.mc_step, decorrelation)
-      self.acceptance_count += getattr(eval_ops.mc_step, 'last_accepted', 0)
-
-    def err(x):
-      return x.std(axis=0, ddof=1) / np.sqrt(n_samples) if n_samples > 1 else np.zeros(x.shape[1])
+    self.acceptance_count = _sampled(eval_ops, session, hparams, lambda v: np.concatenate(v).astype(np.float64), per_sample)
     out = {'bonds': value.bonds.copy(), 'pairs': value.pairs.copy(), 'samples': samples, 'bond_samples': bond_samples,
-           'bond': bond_samples.mean(axis=0), 'bond_err': err(bond_samples)}
+           'bond': bond_samples.mean(axis=0), 'bond_err': _std_err(bond_samples)}
     for k, name in enumerate(('dd', 'connected')):
       out[name] = samples[:, k].mean(axis=0)
-      out[name + '_err'] = err(samples[:, k])
+      out[name + '_err'] = _std_err(samples[:, k])
     return out
 
 

@@ -18,16 +18,10 @@ import numpy as np
 from . import cli_common
 from . import evaluation
 from . import lattice
-from . import parallel
-from . import session as session_lib
-from . import utils
 
-FLAG_TABLE = (
-    ('checkpoint_dir', str, '', 'Full path to the checkpoint directory.'),
+FLAG_TABLE = cli_common.measurement_flag_table((
     ('pairs_file', str, '', 'Text file of site pairs, one `i j` per line (default: all pairs).'),
-    ('output_dir', str, '', 'Where the two files go (default: the checkpoint directory).'),
-    ('hparams', str, '', 'Comma-separated name=value overrides of the hyper-parameters.'),
-)
+), 'the two files go')
 
 
 def load_pairs(path: str, n_sites: int) -> np.ndarray:
@@ -69,38 +63,24 @@ def write_structure_factor(directory: str, qs, s_q) -> str:
 
 def evaluate(flags):
   """-> (hparams, bonds, result dict of SpinCorrelationEvaluator.run_evaluation)."""
-  hp = utils.load_hparams(os.path.join(flags.checkpoint_dir, 'hparams.pbtxt'))
-  hp.parse(flags.hparams)
-  ansatz, hamiltonian = cli_common.heisenberg_system(hp, flags.checkpoint_dir, 1.0)
-  pairs = load_pairs(flags.pairs_file, hp.num_sites)
-  evaluator = evaluation.SpinCorrelationEvaluator()
-  eval_ops = evaluator.build_eval_ops(**cli_common.graph_kwargs(wavefunction=ansatz, operator=pairs, hparams=hp))
-  sess = session_lib.Session()
-  sess.run(session_lib.global_variables_initializer())
-  session_lib.Saver(ansatz.get_trainable_variables()).restore(
-      sess, session_lib.latest_checkpoint(hp.checkpoint_dir))
-  return hp, hamiltonian._bonds_list, evaluator.run_evaluation(eval_ops, sess, hp, epoch_num=0)
+  return cli_common.evaluate_measurement(flags, evaluation.SpinCorrelationEvaluator(),
+                                         lambda hp, bonds: load_pairs(flags.pairs_file, hp.num_sites))
+
+
+def write_files(out_dir: str, hp, bonds, result):
+  written = [write_correlations(out_dir, result)]
+  geometry = lattice_geometry(hp, bonds)
+  n = hp.num_sites
+  pairs = result['pairs']
+  every_pair = len({(min(i, j), max(i, j)) for i, j in pairs.tolist()}) == len(pairs) == n * (n - 1) // 2
+  if geometry is not None and every_pair:
+    coords, qs = geometry
+    written.append(write_structure_factor(out_dir, qs, lattice.structure_factor(result['ss'], pairs, coords, qs)))
+  return written
 
 
 def main(argv=None):
-  flags = cli_common.parser_from_table(__doc__, FLAG_TABLE).parse_args(argv)
-  parallel.init_from_env('nccl')
-  hp, bonds, result = evaluate(flags)
-  written = []
-  if parallel.rank() == 0:
-    out_dir = flags.output_dir or flags.checkpoint_dir
-    cli_common.ensure_directory(out_dir)
-    written.append(write_correlations(out_dir, result))
-    geometry = lattice_geometry(hp, bonds)
-    n = hp.num_sites
-    pairs = result['pairs']
-    every_pair = len({(min(i, j), max(i, j)) for i, j in pairs.tolist()}) == len(pairs) == n * (n - 1) // 2
-    if geometry is not None and every_pair:
-      coords, qs = geometry
-      written.append(write_structure_factor(out_dir, qs, lattice.structure_factor(result['ss'], pairs, coords, qs)))
-    for path in written:
-      print('wrote {}'.format(path))
-  return result, written
+  return cli_common.measurement_main(__doc__, FLAG_TABLE, argv, evaluate, write_files)
 
 
 if __name__ == '__main__':

@@ -20,17 +20,11 @@ import numpy as np
 from . import cli_common
 from . import evaluation
 from . import lattice
-from . import parallel
-from . import session as session_lib
-from . import utils
 
-FLAG_TABLE = (
-    ('checkpoint_dir', str, '', 'Full path to the checkpoint directory.'),
+FLAG_TABLE = cli_common.measurement_flag_table((
     ('bonds_file', str, '', 'Text file of bonds `i j` (or of pairs of bonds `i j k l`); default: the bonds of J.txt.'),
     ('reference_bond', int, 0, 'Index of the bond every bond of the list is paired with.'),
-    ('output_dir', str, '', 'Where the two files go (default: the checkpoint directory).'),
-    ('hparams', str, '', 'Comma-separated name=value overrides of the hyper-parameters.'),
-)
+), 'the two files go')
 
 
 def load_bond_pairs(path: str, reference_bond: int, hamiltonian_bonds, n_sites: int):
@@ -88,35 +82,22 @@ def write_dimer_structure_factor(directory: str, qs, d_q) -> str:
 
 def evaluate(flags):
   """-> (hparams, the Hamiltonian's bonds, result dict of DimerCorrelationEvaluator.run_evaluation)."""
-  hp = utils.load_hparams(os.path.join(flags.checkpoint_dir, 'hparams.pbtxt'))
-  hp.parse(flags.hparams)
-  ansatz, hamiltonian = cli_common.heisenberg_system(hp, flags.checkpoint_dir, 1.0)
-  operator = load_bond_pairs(flags.bonds_file, flags.reference_bond, hamiltonian._bonds_list, hp.num_sites)
-  evaluator = evaluation.DimerCorrelationEvaluator()
-  eval_ops = evaluator.build_eval_ops(**cli_common.graph_kwargs(wavefunction=ansatz, operator=operator, hparams=hp))
-  sess = session_lib.Session()
-  sess.run(session_lib.global_variables_initializer())
-  session_lib.Saver(ansatz.get_trainable_variables()).restore(
-      sess, session_lib.latest_checkpoint(hp.checkpoint_dir))
-  return hp, hamiltonian._bonds_list, evaluator.run_evaluation(eval_ops, sess, hp, epoch_num=0)
+  return cli_common.evaluate_measurement(
+      flags, evaluation.DimerCorrelationEvaluator(),
+      lambda hp, bonds: load_bond_pairs(flags.bonds_file, flags.reference_bond, bonds, hp.num_sites))
+
+
+def write_files(out_dir: str, hp, bonds, result):
+  written = [write_dimer_correlations(out_dir, result)]
+  sizes = lattice_sizes(hp, bonds)
+  if sizes is not None:
+    qs, d_q = lattice.dimer_structure_factor(result['bonds'], result['pairs'], result['connected'], *sizes)
+    written.append(write_dimer_structure_factor(out_dir, qs, d_q))
+  return written
 
 
 def main(argv=None):
-  flags = cli_common.parser_from_table(__doc__, FLAG_TABLE).parse_args(argv)
-  parallel.init_from_env('nccl')
-  hp, bonds, result = evaluate(flags)
-  written = []
-  if parallel.rank() == 0:
-    out_dir = flags.output_dir or flags.checkpoint_dir
-    cli_common.ensure_directory(out_dir)
-    written.append(write_dimer_correlations(out_dir, result))
-    sizes = lattice_sizes(hp, bonds)
-    if sizes is not None:
-      qs, d_q = lattice.dimer_structure_factor(result['bonds'], result['pairs'], result['connected'], *sizes)
-      written.append(write_dimer_structure_factor(out_dir, qs, d_q))
-    for path in written:
-      print('wrote {}'.format(path))
-  return result, written
+  return cli_common.measurement_main(__doc__, FLAG_TABLE, argv, evaluate, write_files)
 
 
 if __name__ == '__main__':

@@ -14,16 +14,10 @@ import os
 from . import cli_common
 from . import evaluation
 from . import lattice
-from . import parallel
-from . import session as session_lib
-from . import utils
 
-FLAG_TABLE = (
-    ('checkpoint_dir', str, '', 'Full path to the checkpoint directory.'),
+FLAG_TABLE = cli_common.measurement_flag_table((
     ('regions_file', str, '', 'Text file of regions, one per line as site indices (default: the blocks [0, l)).'),
-    ('output_dir', str, '', 'Where entanglement.txt goes (default: the checkpoint directory).'),
-    ('hparams', str, '', 'Comma-separated name=value overrides of the hyper-parameters.'),
-)
+), 'entanglement.txt goes')
 
 
 def load_regions(path: str, n_sites: int):
@@ -45,31 +39,14 @@ def write_entanglement(directory: str, result) -> str:
 
 def evaluate(flags):
   """-> (hparams, result dict of RenyiEntropyEvaluator.run_evaluation)."""
-  hp = utils.load_hparams(os.path.join(flags.checkpoint_dir, 'hparams.pbtxt'))
-  hp.parse(flags.hparams)
-  ansatz, _ = cli_common.heisenberg_system(hp, flags.checkpoint_dir, 1.0)
-  regions = load_regions(flags.regions_file, hp.num_sites)
-  evaluator = evaluation.RenyiEntropyEvaluator()
-  eval_ops = evaluator.build_eval_ops(**cli_common.graph_kwargs(wavefunction=ansatz, operator=regions, hparams=hp))
-  sess = session_lib.Session()
-  sess.run(session_lib.global_variables_initializer())
-  session_lib.Saver(ansatz.get_trainable_variables()).restore(
-      sess, session_lib.latest_checkpoint(hp.checkpoint_dir))
-  return hp, evaluator.run_evaluation(eval_ops, sess, hp, epoch_num=0)
+  hp, _, result = cli_common.evaluate_measurement(flags, evaluation.RenyiEntropyEvaluator(),
+                                                  lambda hp, bonds: load_regions(flags.regions_file, hp.num_sites))
+  return hp, result
 
 
 def main(argv=None):
-  flags = cli_common.parser_from_table(__doc__, FLAG_TABLE).parse_args(argv)
-  parallel.init_from_env('nccl')
-  _, result = evaluate(flags)
-  written = []
-  if parallel.rank() == 0:
-    out_dir = flags.output_dir or flags.checkpoint_dir
-    cli_common.ensure_directory(out_dir)
-    written.append(write_entanglement(out_dir, result))
-    for path in written:
-      print('wrote {}'.format(path))
-  return result, written
+  return cli_common.measurement_main(__doc__, FLAG_TABLE, argv, evaluate,
+                                     lambda out_dir, hp, result: [write_entanglement(out_dir, result)])
 
 
 if __name__ == '__main__':

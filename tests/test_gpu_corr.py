@@ -1,4 +1,4 @@
-"""GPU: spin correlations (vmc_pair_correlations: csrc/vmc_api_corr.hip + corr.hip; SpinCorrelationEvaluator).
+"""GPU: spin correlations (vmc_pair_correlations: csrc/vmc_api_measure.hip + corr.hip; SpinCorrelationEvaluator).
 
 Bounds.  The rows a measurement folds are the local-energy rows of the ansatz type, so the per-pair MEANS are held to the
 bounds the types' own local-energy tests apply (tests/test_gpu_engine.py, test_gpu_conv.py, test_gpu_pbdg.py,

@@ -1,4 +1,4 @@
-"""GPU: dimer-dimer correlations (vmc_dimer_correlations: csrc/vmc_api_dimer.hip + dimer.hip; DimerCorrelationEvaluator;
+"""GPU: dimer-dimer correlations (vmc_dimer_correlations: csrc/vmc_api_measure.hip + dimer.hip; DimerCorrelationEvaluator;
 run_dimer_evaluation) against the fp64 oracle tests/dimer_oracle.py.  Families, shapes and per-row bounds are those of
 tests/test_gpu_renyi.py: the 4 x 4 torus, N = 16, H = 32, B = 40 chains (no multiple of the 8- or 16-chain tiles).
 
@@ -177,7 +177,7 @@ def test_pass_splits_repeats_subsets_and_longer_lists_are_bit_identical_on_70_pa
       np.testing.assert_array_equal(bond_sum, base[0], err_msg='pairs_per_pass=%d' % per)
       np.testing.assert_array_equal(dd_sum, base[1], err_msg='pairs_per_pass=%d' % per)
   # a request splits phase 1 too: 34 bonds at 7 per pass are five passes of single exchanges (the last of 6 bonds, written
-  # at dimer_bonds + 28, dimer_logit + 28 B) next to the ten passes of 70 pairs -- one `dimer_rows` region per pass
+  # at dimer.bonds + 28, dimer.logit + 28 B) next to the ten passes of 70 pairs -- one `dimer_rows` region per pass
   eng.timing_enable(True); eng.timing_reset()
   bond_sum, dd_sum = eng.dimer_correlations(BONDS34, pairs, pairs_per_pass=7)
   eng.synchronize()

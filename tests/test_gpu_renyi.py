@@ -1,4 +1,4 @@
-"""GPU: the replica swap estimator of the second Renyi entropy (vmc_renyi2_swap: csrc/vmc_api_renyi.hip + renyi.hip;
+"""GPU: the replica swap estimator of the second Renyi entropy (vmc_renyi2_swap: csrc/vmc_api_measure.hip + renyi.hip;
 RenyiEntropyEvaluator; run_entanglement_evaluation) against the fp64 oracle tests/renyi_oracle.py.
 
 Bound.  A pair's term is exp of the sum of four fp32 logs ln|psi| (two swapped rows minus the two chains), formed in fp64.
