@@ -356,7 +356,15 @@ hipError_t launch_dimer_fold(hipStream_t s, const float* configs, const int2* bo
                              const float* logit, const float* sign, const float* one_logit, const float* one_sign,
                              const float* two_logit, const float* two_sign, int B, int N, int n_pairs, double* dd_sum);
 
-// device helpers and the grid rule the Renyi-2 and dimer kernels share
+// symmetry expectation values (symm.hip): the rows of a pass of ops (row = op x B + chain: f_k x_c[perm_k[i]], f_k = -1
+// where flip[k]) and their fold per op over the chains -- one wavefront per op, lane l the chains l, l + 64, ...
+// ascending, then a fixed butterfly, fp64.  perm [n_ops][N] bijections (plan_symm_check_ops); signs null: unsigned
+hipError_t launch_symm_rows(hipStream_t s, const float* configs, const int* perm, const unsigned char* flip, int B,
+                            int N, int n_ops, int num_cus, float* rows);
+hipError_t launch_symm_fold(hipStream_t s, const float* logit, const float* sign, const float* row_logit,
+                            const float* row_sign, int B, int n_ops, double* ratio_sum);
+
+// device helpers and the grid rule the Renyi-2, dimer and symmetry kernels share
 // sign of a stored sign / amplitude: +-1, 0 for a vanishing amplitude
 __device__ inline int sgn_of(float v) { return (v > 0.f) - (v < 0.f); }
 // psi(row) / psi(x) from ln|psi| and, signed types, the signs (own_sgn = +-1: the caller has dropped a chain whose own
@@ -368,7 +376,7 @@ __device__ inline double measure_ratio(const float* __restrict__ row_logit, cons
   if (sg == 0) return 0.0;
   return (double)sg * exp((double)row_logit[at] - own_logit);
 }
-// the row writers (k_swap_rows, k_dimer_rows1 / 2): blocks of 4 wavefronts, one item per wavefront, at most 16 blocks per CU
+// the row writers (k_swap_rows, k_dimer_rows1 / 2, k_symm_rows): blocks of 4 wavefronts, one item per wavefront, at most 16 blocks per CU
 inline unsigned measure_rows_grid(long long items, int num_cus) {
   long long blocks = (items + 3) / 4;
   const long long cap = 16LL * (num_cus > 0 ? num_cus : 1);

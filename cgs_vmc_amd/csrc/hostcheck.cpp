@@ -836,9 +836,60 @@ static void measure_grid() {
   CHECK(!plan_measure_rows_ok(40, 0) && !plan_measure_rows_ok(0, 1) && plan_measure_rows_ok(40, 34));
 }
 
+// the ops of vmc_symmetry_expectations (plan_symm_check_ops): random bijections with and without flips pass; a
+// duplicated, a negative and an == N entry, and a flip above 1, are each refused with the op named
+static void symm_ops() {
+  char msg[160];
+  unsigned long long state = 0x9e3779b97f4a7c15ULL;
+  auto next = [&]() { state = state * 6364136223846793005ULL + 1442695040888963407ULL; return (unsigned)(state >> 33); };
+  for (int N : {1, 2, 6, 16, 64, 65, 100, 1023})
+    for (int n_ops : {1, 3, 8, 70}) {
+      std::vector<int32_t> perm((size_t)n_ops * (size_t)N);
+      std::vector<uint8_t> flip((size_t)n_ops);
+      for (int k = 0; k < n_ops; ++k) {
+        int32_t* g = perm.data() + (size_t)k * (size_t)N;
+        for (int i = 0; i < N; ++i) g[i] = i;
+        for (int i = N - 1; i > 0; --i) std::swap(g[i], g[next() % (unsigned)(i + 1)]);      // Fisher-Yates
+        flip[(size_t)k] = (uint8_t)(next() & 1);
+      }
+      CHECK(plan_symm_check_ops(N, n_ops, perm.data(), flip.data(), msg, sizeof(msg)) == VMC_OK && msg[0] == 0);
+      CHECK(plan_symm_check_ops(N, n_ops, perm.data(), nullptr, msg, sizeof(msg)) == VMC_OK);
+      const int k = (int)(next() % (unsigned)n_ops), i = (int)(next() % (unsigned)N);
+      char want[32];
+      snprintf(want, sizeof(want), "op %d:", k);
+      int32_t* g = perm.data() + (size_t)k * (size_t)N;
+      const int32_t kept = g[i];
+      for (int32_t bad : {(int32_t)-1, (int32_t)N, (int32_t)0x7fffffff, (int32_t)(-0x7fffffff - 1)}) {
+        g[i] = bad;
+        CHECK(plan_symm_check_ops(N, n_ops, perm.data(), flip.data(), msg, sizeof(msg)) == VMC_ERR_INVALID);
+        CHECK(strstr(msg, want) == msg);
+      }
+      g[i] = kept;
+      if (N > 1) {
+        g[i] = g[(i + 1) % N];                                                                // a duplicate
+        CHECK(plan_symm_check_ops(N, n_ops, perm.data(), flip.data(), msg, sizeof(msg)) == VMC_ERR_INVALID);
+        CHECK(strstr(msg, want) == msg && strstr(msg, "second time"));
+        g[i] = kept;
+      }
+      flip[(size_t)k] = 2;
+      CHECK(plan_symm_check_ops(N, n_ops, perm.data(), flip.data(), msg, sizeof(msg)) == VMC_ERR_INVALID);
+      CHECK(strstr(msg, want) == msg && strstr(msg, "flip"));
+      flip[(size_t)k] = 1;
+      CHECK(plan_symm_check_ops(N, n_ops, perm.data(), flip.data(), msg, sizeof(msg)) == VMC_OK);
+    }
+  int32_t one = 0;
+  CHECK(plan_symm_check_ops(1, 0, &one, nullptr, msg, sizeof(msg)) == VMC_ERR_INVALID);
+  CHECK(plan_symm_check_ops(0, 1, &one, nullptr, msg, sizeof(msg)) == VMC_ERR_INVALID);
+  CHECK(plan_symm_check_ops(1, 1, nullptr, nullptr, msg, sizeof(msg)) == VMC_ERR_INVALID);
+  CHECK(plan_symm_check_ops(1, 1, &one, nullptr, nullptr, 0) == VMC_OK);
+  // config 3's shape, the 100 translations with and without the flip: one pass of 819,200 rows
+  CHECK(plan_measure_per_pass(4096, 200, 0, plan_measure_row_limit(100, 256)) == 200);
+}
+
 int main() {
   check_block_maps();
   measure_grid();
+  symm_ops();
   prod_grid();
   edvec_grid();
   nnb_grid();

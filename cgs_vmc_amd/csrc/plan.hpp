@@ -12,6 +12,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <vector>
+
 #include "../../include/cgsvmc.h"
 
 #if defined(__HIPCC__)
@@ -635,7 +637,7 @@ inline int plan_prod_child_check(int ansatz, int output_activation, bool is_prod
   return VMC_ERR_UNSUPPORTED;
 }
 
-// ------------------------------------------------------------------------------- the measurements (vmc_api_measure.hip; corr.hip, renyi.hip, dimer.hip)
+// ------------------------------------------------------------------------------- the measurements (vmc_api_measure.hip; corr.hip, renyi.hip, dimer.hip, symm.hip)
 // A measurement runs its items -- pairs of sites, regions, bonds, pairs of bonds -- in passes; a pass is B rows per item
 // (row = item x B + chain): for the spin correlations a bond set of its own (bonds, couplings, rowinfo / val) plus the
 // dense [B][pairs] scatter target, for the others rows handed to the family's full forward.  Rows of a pass: the budget
@@ -678,6 +680,39 @@ inline bool plan_measure_rows_ok(long long B, long long n_items) {
 }
 inline long long plan_measure_passes(long long n_items, int per) { return per < 1 ? 0 : (n_items + per - 1) / per; }
 inline unsigned plan_measure_fold_grid(int items) { return (unsigned)((items + 63) / 64); }    // 64 threads, one item each
+
+// The ops of vmc_symmetry_expectations (symm.hip): perm [n_ops][N] site permutations, flip [n_ops] 0 / 1 (null: no
+// flips).  Every perm_k must be a bijection of 0 .. N - 1 -- k_symm_rows gathers x[perm_k[i]], and pbdg, nnb and ed_vector
+// index by up / down counts: a bijection and a global flip keep a row at Sz = 0, anything else may not.  VMC_OK, or
+// VMC_ERR_INVALID with the op and the entry named in msg.
+inline int plan_symm_check_ops(int N, int n_ops, const int32_t* perm, const uint8_t* flip, char* msg, size_t msg_len) {
+  if (msg_len) msg[0] = 0;
+  if (N < 1 || n_ops < 1 || !perm) {
+    snprintf(msg, msg_len, "bad symmetry op arguments");
+    return VMC_ERR_INVALID;
+  }
+  std::vector<unsigned char> seen((size_t)N);
+  for (int k = 0; k < n_ops; ++k) {
+    if (flip && flip[k] > 1) {
+      snprintf(msg, msg_len, "op %d: flip = %d, 0 or 1 required", k, (int)flip[k]);
+      return VMC_ERR_INVALID;
+    }
+    const int32_t* g = perm + (size_t)k * (size_t)N;
+    seen.assign((size_t)N, 0);
+    for (int i = 0; i < N; ++i) {
+      if (g[i] < 0 || g[i] >= N) {
+        snprintf(msg, msg_len, "op %d: entry %d = %d is no site in 0 .. %d", k, i, (int)g[i], N - 1);
+        return VMC_ERR_INVALID;
+      }
+      if (seen[(size_t)g[i]]) {
+        snprintf(msg, msg_len, "op %d: entry %d names site %d a second time (a permutation of 0 .. %d required)", k, i, (int)g[i], N - 1);
+        return VMC_ERR_INVALID;
+      }
+      seen[(size_t)g[i]] = 1;
+    }
+  }
+  return VMC_OK;
+}
 
 // ------------------------------------------------------------------------------- vmc_create
 struct DescPlan {

@@ -2,7 +2,7 @@
 // work on ctx->stream.  This file: ctx life cycle, parameters, chains, amplitudes, local energies, timing; the other
 // entry points live in vmc_api_sweep.hip (samplers), vmc_api_train.hip (accumulators, Adam, epochs, evaluation),
 // vmc_api_coll.hip (collectives), vmc_api_sr.hip (stochastic reconfiguration), vmc_api_measure.hip (the measurements
-// beside the energy: spin correlations, Renyi-2 entropy, dimer-dimer correlations), vmc_api_prod.hip (product ctxs);
+// beside the energy: spin correlations, Renyi-2 entropy, dimer-dimer correlations, symmetry expectation values), vmc_api_prod.hip (product ctxs);
 // vmc_api_cgen.hip is the general convolution path's machinery.  Shared state and helpers: vmc_ctx.hpp.
 #include "vmc_ctx.hpp"
 
@@ -763,7 +763,7 @@ void vmc_destroy(vmc_ctx* c) {
                   c->d_max, c->tmp_cfg, c->tmp_z1, c->tmp_out, c->tmp_on, c->tmp_rowinfo, c->rowinfo_id, c->bond_dummy, c->inj_up, c->inj_dn, c->inj_u,
                   c->acc_mask, c->wg_outpart, c->cnt_alt, c->diag_alt};
   for (void* q : ptrs) if (q) hipFree(q);
-  c->corr.release(); c->renyi.release(); c->dimer.release();
+  c->corr.release(); c->renyi.release(); c->dimer.release(); c->symm.release();
   for (float* q : {c->sr_ctape, c->sr_cdelta, c->sr_cws, c->sr_cw0, c->sr_cwf, c->sr_cwb, c->sr_cbias}) if (q) hipFree(q);
   void* sr[] = {c->sr_cfg, c->sr_act, c->sr_delta, c->sr_ws, c->sr_t, c->sr_u, c->sr_x, c->sr_r,
                 c->sr_p, c->sr_q, c->sr_partial, c->sr_sc, c->sr_ones, c->sr_tpart};

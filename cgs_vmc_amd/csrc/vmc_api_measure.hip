@@ -1,8 +1,8 @@
 // The measurements over the ctx's current chains (extensions, no reference counterpart): vmc_pair_correlations,
-// vmc_renyi2_swap and vmc_dimer_correlations.  Each is a pure measurement: chains, step counter, accumulators, the
+// vmc_renyi2_swap, vmc_dimer_correlations and vmc_symmetry_expectations.  Each is a pure measurement: chains, step counter, accumulators, the
 // Hamiltonian's bond set and the validity of the amplitude and activation caches are as before when it returns.
 //
-// One scaffold serves the three.  MEASURE_GATE is the shared front of the refusals; PureMeasurement records which caches
+// One scaffold serves the four.  MEASURE_GATE is the shared front of the refusals; PureMeasurement records which caches
 // were valid and un-vouches on every way out for those that were not; upload copies a host list into its device buffer;
 // for_passes walks the items in passes of plan_measure_per_pass (plan.hpp); read_back brings the fp64 sums down and
 // synchronises, on a failed call too.  The device buffers are the grow-only DevBufs of vmc_ctx.hpp.  What differs per
@@ -29,6 +29,12 @@
 // passes of pairs, B rows per pair, the double exchanges (k_dimer_rows2), forwarded the same way and folded per pair
 // (k_dimer_fold) against phase 1's buffers and the chains' cached ln|psi| and signs.  (n_bonds + n_pairs) B full
 // forwards in all.
+//
+// Symmetry expectation values.  Per op k -- a site permutation perm_k, optionally followed by the global spin flip:
+// ratio_sum = sum_c psi(row_{k,c}) / psi(x_c) with row[i] = f_k x_c[perm_k[i]]; the host forms <P_k> ~ ratio_sum / B.  A
+// pass of ops is B rows per op in the row buffer of vmc_amplitude (symm.hip: k_symm_rows), evaluated by the family's own
+// full forward and folded per op (k_symm_fold) against the chains' cached ln|psi| and signs.  Every perm_k is checked
+// to be a bijection before anything is launched (plan_symm_check_ops): the rows must stay at Sz = 0.
 #include "vmc_ctx.hpp"
 
 using namespace vmcapi;
@@ -209,6 +215,34 @@ int dimer_double_pass(vmc_ctx* c, int which, long long p0, int n, double* dd_out
   return VMC_OK;
 }
 
+// ---- symmetry expectation values
+
+int symm_reserve(vmc_ctx* c, long long n_ops) {
+  PROPAGATE(c->symm.perm.reserve(c, n_ops * c->N, "symm.perm"));
+  PROPAGATE(c->symm.flip.reserve(c, n_ops, "symm.flip"));
+  return c->symm.out.reserve(c, n_ops, "symm.out");
+}
+
+// ops [k0, k0 + n): rows, forward, fold
+int symm_pass(vmc_ctx* c, int which, long long k0, int n) {
+  const ParamSet& p = c->ps[which];
+  const SymmBufs& m = c->symm;
+  const long long rows = (long long)n * c->B;
+  {
+    Timer t(c, "symm_rows");
+    HIPCHK(c, launch_symm_rows(c->stream, c->configs, m.perm.p + k0 * c->N, m.flip.p + k0, c->B, c->N, n, c->num_cus,
+                               c->tmp_cfg));
+  }
+  {
+    Timer t(c, "symm_forward");
+    PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, rows, c->tmp_out, c->tmp_sign));
+  }
+  Timer t(c, "symm_fold");
+  HIPCHK(c, launch_symm_fold(c->stream, p.logit, c->sgn ? p.sign : nullptr, c->tmp_out, c->sgn ? c->tmp_sign : nullptr,
+                             c->B, n, m.out.p + k0));
+  return VMC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -331,6 +365,33 @@ int vmc_dimer_correlations(vmc_ctx* c, int which, int32_t n_bonds, const int32_t
   if (rc != VMC_OK) return rc;
   for (int a = 0; a < n_bonds && bond_sum; ++a) bond_sum[a] = out[(size_t)a];
   for (int p = 0; p < n_pairs && dd_sum; ++p) dd_sum[p] = out[(size_t)n_bonds + (size_t)p];
+  return VMC_OK;
+}
+
+int vmc_symmetry_expectations(vmc_ctx* c, int which, int32_t n_ops, const int32_t* perm, const uint8_t* flip,
+                              int32_t ops_per_pass, double* ratio_sum) {
+  MEASURE_GATE(c, which, "vmc_symmetry_expectations");
+  if (n_ops < 1 || !perm || ops_per_pass < 0) return fail(c, VMC_ERR_INVALID, "bad symmetry op arguments");
+  char msg[160];
+  if (plan_symm_check_ops(c->N, n_ops, perm, flip, msg, sizeof(msg)) != VMC_OK) return fail(c, VMC_ERR_INVALID, msg);
+  if (!c->sgn && c->oact != VMC_ACT_EXP_)
+    return fail(c, VMC_ERR_UNSUPPORTED, "vmc_symmetry_expectations needs the exp output activation (the logit is ln psi only then)");
+  const std::vector<int> hperm(perm, perm + (size_t)n_ops * (size_t)c->N);
+  std::vector<unsigned char> hflip((size_t)n_ops, 0);
+  if (flip) hflip.assign(flip, flip + n_ops);
+  const int per = plan_measure_per_pass(c->B, n_ops, ops_per_pass, plan_measure_row_limit(c->N, c->Hp));
+  if (per < 1) return fail(c, VMC_ERR_UNSUPPORTED, "batch_size does not leave room for one op in the 32-bit row index");
+  PureMeasurement pure(c);
+  int rc = ensure_cache(c, which);           // ln|psi(x_c)| and the signs, as the local energies take them
+  if (rc == VMC_OK) rc = symm_reserve(c, n_ops);
+  if (rc == VMC_OK) rc = grow_tmp(c, (long long)per * c->B);
+  if (rc == VMC_OK) rc = upload(c, c->symm.perm.p, hperm);
+  if (rc == VMC_OK) rc = upload(c, c->symm.flip.p, hflip);
+  rc = for_passes(n_ops, per, rc, [&](long long k0, int n) { return symm_pass(c, which, k0, n); });
+  std::vector<double> out;
+  rc = read_back(c, rc, "vmc_symmetry_expectations", c->symm.out.p, (size_t)n_ops, &out);
+  if (rc != VMC_OK) return rc;
+  for (int k = 0; k < n_ops && ratio_sum; ++k) ratio_sum[k] = out[(size_t)k];
   return VMC_OK;
 }
 

@@ -86,6 +86,13 @@ struct RenyiBufs {
   DevBuf<double> out;            // [2][n_regions] swap sums, match counts
   void release() { mask.release(); out.release(); }
 };
+// symmetry expectation values: the ops of a call and their sums
+struct SymmBufs {
+  DevBuf<int> perm;              // [n_ops][N] site permutations
+  DevBuf<unsigned char> flip;    // [n_ops] 0/1
+  DevBuf<double> out;            // [n_ops] ratio sums
+  void release() { perm.release(); flip.release(); out.release(); }
+};
 // dimer-dimer correlations: the two lists of a call, ln|psi| (and, signed types, the sign) of every single exchange,
 // and the sums
 struct DimerBufs {
@@ -230,6 +237,7 @@ struct vmc_ctx {
   CorrBufs corr;
   RenyiBufs renyi;
   DimerBufs dimer;
+  SymmBufs symm;
   // gradient path
   std::vector<float*> act;   // L views [B][Hp] into act_all
   float* act_all = nullptr;  // [L][B][Hp]

@@ -374,6 +374,22 @@ class VmcEngine:
                                                  dd_sum.ctypes.data_as(dp)))
     return bond_sum, dd_sum
 
+  def symmetry_expectations(self, perms, flips=None, which: int = _hip.VMC_PSI, ops_per_pass: int = 0):
+    """Symmetry expectation values over the current chains (extension, vmc_symmetry_expectations).  `perms`:
+    [n_ops][n_sites] site permutations (lattice.translations, lattice.point_group, ...), `flips`: one 0 / 1 per op, the
+    global spin flip after the permutation (None: no flips).  Returns ratio_sum, float64 [n_ops]: the sum over the chains
+    of psi(row) / psi(x) with row[i] = f x[perm[i]], f = -1 where the op flips, so that <P> ~ ratio_sum / batch_size.  A
+    permutation that is no bijection is a ValueError before the library is called (lattice.check_symmetry_ops).  Moves
+    no chain, touches neither the step counter nor the accumulators nor the Hamiltonian; ops_per_pass = 0 leaves the
+    pass size to the library (the sums are the same bits either way)."""
+    from . import lattice
+    perm, flip = lattice.check_symmetry_ops(perms, flips, self.n_sites)
+    out = np.empty(perm.shape[0], np.float64)
+    self._check(self._lib.vmc_symmetry_expectations(self._ctx, int(which), perm.shape[0], _iptr(perm),
+                                                    flip.ctypes.data_as(C.POINTER(C.c_uint8)), int(ops_per_pass),
+                                                    out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
   def last_connected_rows(self) -> int:
     v = C.c_int64()
     self._check(self._lib.vmc_last_connected_rows(self._ctx, C.byref(v)))

@@ -125,7 +125,7 @@ def _sampling_eval_ops(wavefunction, hparams, shared_resources, make_value) -> E
 
 
 def _sampled(eval_ops, session, hparams, stack, per_sample) -> int:
-  """The sample loop of the three measurement evaluators, on the same schedule as MonteCarloOperatorEvaluator's (which
+  """The sample loop of the four measurement evaluators, on the same schedule as MonteCarloOperatorEvaluator's (which
   keeps its own loop: no all-reduce, and a fused path): thermalises for num_equilibration_sweeps sweeps, then takes
   num_evaluation_samples measurements, num_monte_carlo_sweeps sweeps apart.
   stack(session.run(value)) is the fp64 array of this rank's sums; with sharded chains the ranks' arrays are added by one
@@ -325,6 +325,60 @@ class DimerCorrelationEvaluator(WavefunctionEvaluator):
       out[name] = samples[:, k].mean(axis=0)
       out[name + '_err'] = _std_err(samples[:, k])
     return out
+
+
+class SymmetryTensor(session_lib.Tensor):
+  """ratio_sum [n_ops] float64 of the ops (`perms` [n_ops][num_sites] int32, `flips` [n_ops] uint8) over THIS rank's
+  chains (VmcEngine.symmetry_expectations); `global_batch` is the number of chains of all ranks together."""
+
+  def __init__(self, engine, perms, flips, which: int, num_sites: int, global_batch: int):
+    from . import lattice
+    self.engine, self.which, self.global_batch = engine, which, int(global_batch)
+    self.perms, self.flips = lattice.check_symmetry_ops(perms, flips, num_sites)
+    super(SymmetryTensor, self).__init__(self._value, 'symmetry_expectations')
+
+  def _value(self):
+    return self.engine.symmetry_expectations(self.perms, self.flips, self.which)
+
+
+class SymmetryEvaluator(WavefunctionEvaluator):
+  """<P_g> = <psi(g x) / psi(x)> of site permutations g, optionally followed by the global spin flip, by running MCMC: the
+  characters of the state under translations, point-group elements and spin inversion (extension: the reference evaluates
+  the energy alone).  The signatures are MonteCarloOperatorEvaluator's; `operator` is (perms, flips) (flips None: no
+  flips).  operator None: the translations of the hparams.size_x x hparams.size_y torus (lattice.translations) when
+  size_x * size_y = num_sites, otherwise ValueError."""
+
+  def build_eval_ops(self, wavefunction, operator, hparams,
+                     shared_resources: Dict[graph_builders.ResourceName, Any]) -> EvalOps:
+    from . import lattice
+    if operator is None:
+      size_x, size_y = getattr(hparams, 'size_x', 0), getattr(hparams, 'size_y', 0)
+      if min(size_x, size_y) < 1 or size_x * size_y != hparams.num_sites:
+        raise ValueError('SymmetryEvaluator: no ops given and size_x * size_y = {} x {} is not num_sites = {}'.format(
+            size_x, size_y, hparams.num_sites))
+      perms, flips = lattice.translations(size_x, size_y), None
+    else:
+      perms, flips = operator
+    return _sampling_eval_ops(wavefunction, hparams, shared_resources, lambda engine: SymmetryTensor(
+        engine, perms, flips, wavefunction._which, hparams.num_sites, hparams.batch_size))
+
+  def run_evaluation(self, eval_ops: EvalOps, session, hparams, epoch_num: int) -> Dict[str, np.ndarray]:
+    """Thermalises for num_equilibration_sweeps sweeps, then takes num_evaluation_samples measurements,
+    num_monte_carlo_sweeps sweeps apart (the loop of MonteCarloOperatorEvaluator).  A measurement is the batch mean, over
+    the chains of ALL ranks, of psi(g x) / psi(x) per op: with sharded chains the per-sample fp64 sums of the ranks are
+    added by parallel.allreduce_array before the division by the global batch.  Returns a dict: 'perms' [n_ops][num_sites];
+    'flips' [n_ops]; 'value' [n_ops], the mean over the samples; 'value_err', the conventional standard error of that mean,
+    std(ddof = 1) / sqrt(n_samples) of the batch means (0 for a single sample); 'samples' [n_samples][n_ops], the batch
+    means themselves."""
+    del epoch_num
+    value = eval_ops.value
+    samples = np.empty((hparams.num_evaluation_samples, value.perms.shape[0]), np.float64)
+
+    def per_sample(s, sums):
+      samples[s] = sums / value.global_batch
+    self.acceptance_count = _sampled(eval_ops, session, hparams, lambda v: np.asarray(v, np.float64), per_sample)
+    return {'perms': value.perms.copy(), 'flips': value.flips.copy(), 'value': samples.mean(axis=0),
+            'value_err': _std_err(samples), 'samples': samples}
 
 
 class VectorWavefunctionEvaluator(WavefunctionEvaluator):

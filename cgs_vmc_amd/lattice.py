@@ -211,6 +211,124 @@ def dimer_structure_factor(bonds, pairs, connected, size_x, size_y=1, qs=None):
   return qs, out
 
 
+def translations(size_x, size_y=1):
+  """The N = size_x * size_y translations of the size_x x size_y torus of torus_bonds (site = x + size_x * y; size_y = 1:
+  the periodic chain) as site permutations, [N][N] int32: op r = r_x + size_x * r_y has
+  perm[x + size_x * y] = (x + r_x) mod size_x + size_x * ((y + r_y) mod size_y), so that the row of a configuration s is
+  row[i] = s[perm[i]] (VmcEngine.symmetry_expectations).  Op 0 is the identity."""
+  if size_x < 1 or size_y < 1:
+    raise ValueError('translations: lattice sizes must be positive')
+  s = np.arange(size_x * size_y)
+  x, y = s % size_x, s // size_x
+  r_x, r_y = x[:, None], y[:, None]
+  return np.ascontiguousarray(((x[None, :] + r_x) % size_x + size_x * ((y[None, :] + r_y) % size_y)).astype(np.int32))
+
+
+def point_group(size_x, size_y=1):
+  """(labels, perms [n][N] int32) of the point group about site 0 of the size_x x size_y torus (site = x + size_x * y), as
+  site permutations in the convention of `translations`: the periodic chain (size_y = 1) has the identity and the mirror
+  x -> -x; a rectangle the identity, mirror_x (x -> -x), mirror_y (y -> -y) and the inversion; a square the eight elements of
+  C4v: identity, rot90 ((x, y) -> (-y, x)), rot180, rot270, mirror_x, mirror_y, mirror_diag ((x, y) -> (y, x)) and
+  mirror_antidiag ((x, y) -> (-y, -x)).  The identity comes first."""
+  if size_x < 1 or size_y < 1:
+    raise ValueError('point_group: lattice sizes must be positive')
+  s = np.arange(size_x * size_y)
+  x, y = s % size_x, s // size_x
+  site = lambda u, v: ((u % size_x) + size_x * (v % size_y)).astype(np.int32)
+  if size_y == 1:
+    ops = [('identity', site(x, y)), ('mirror', site(-x, y))]
+  elif size_x != size_y:
+    ops = [('identity', site(x, y)), ('mirror_x', site(-x, y)), ('mirror_y', site(x, -y)), ('inversion', site(-x, -y))]
+  else:
+    ops = [('identity', site(x, y)), ('rot90', site(-y, x)), ('rot180', site(-x, -y)), ('rot270', site(y, -x)),
+           ('mirror_x', site(-x, y)), ('mirror_y', site(x, -y)), ('mirror_diag', site(y, x)),
+           ('mirror_antidiag', site(-y, -x))]
+  return [name for name, _ in ops], np.ascontiguousarray(np.stack([p for _, p in ops]))
+
+
+def check_symmetry_ops(perms, flips, num_sites):
+  """(perms int32 [n_ops][num_sites], flips uint8 [n_ops]), contiguous, of the ops of VmcEngine.symmetry_expectations:
+  every row of `perms` must be a permutation of 0 .. num_sites - 1 (one row alone is taken as one op), `flips` one 0 / 1
+  (or boolean) per op, None: no flips.  Anything else is a ValueError that names the op: the rows of pbdg,
+  fully_connected_nnb and ed_vector must stay at Sz = 0, which a bijection and a global flip keep and nothing else need."""
+  p = np.asarray(perms)
+  if p.ndim == 1 and p.size:
+    p = p.reshape(1, -1)
+  if p.ndim != 2 or p.shape[0] < 1:
+    raise ValueError('symmetry ops: at least one site permutation of shape [{}] required'.format(num_sites))
+  if not (np.issubdtype(p.dtype, np.integer) or (np.issubdtype(p.dtype, np.floating) and (p == np.rint(p)).all())):
+    raise ValueError('symmetry ops: site indices must be integers')
+  if p.shape[1] != num_sites:
+    raise ValueError('symmetry ops: op 0 has {} entries, {} sites required'.format(p.shape[1], num_sites))
+  p = p.astype(np.int64)
+  for k, g in enumerate(p):
+    if g.min() < 0 or g.max() >= num_sites:
+      i = int(np.flatnonzero((g < 0) | (g >= num_sites))[0])
+      raise ValueError('symmetry ops: op {}: entry {} = {} is no site in 0 .. {}'.format(k, i, int(g[i]), num_sites - 1))
+    if np.unique(g).size != num_sites:
+      raise ValueError('symmetry ops: op {}: a site is named twice (a permutation of 0 .. {} required)'.format(k, num_sites - 1))
+  if flips is None:
+    f = np.zeros(p.shape[0], np.int64)
+  else:
+    f = np.asarray(flips)
+    if f.dtype != np.bool_ and not np.issubdtype(f.dtype, np.integer):
+      raise ValueError('symmetry ops: flips are 0 or 1')
+    f = f.astype(np.int64).ravel()
+    if f.size != p.shape[0]:
+      raise ValueError('symmetry ops: {} flips for {} ops'.format(f.size, p.shape[0]))
+    bad = np.flatnonzero((f < 0) | (f > 1))
+    if bad.size:
+      raise ValueError('symmetry ops: op {}: flip = {}, 0 or 1 required'.format(int(bad[0]), int(f[bad[0]])))
+  return np.ascontiguousarray(p.astype(np.int32)), np.ascontiguousarray(f.astype(np.uint8))
+
+
+def read_symmetry_ops(path):
+  """(perms, flips) from a text file: one op per line, an optional leading word `flip` (the global spin flip follows the
+  permutation), then the site indices perm[0] perm[1] ... separated by blanks or commas; `#` starts a comment, a line
+  without any field is skipped.  Lists, in the file's order; check_symmetry_ops validates them."""
+  perms, flips = [], []
+  with open(path) as f:
+    for number, line in enumerate(f, 1):
+      fields = line.split('#', 1)[0].replace(',', ' ').split()
+      if not fields:
+        continue
+      flip = fields[0].lower() == 'flip'
+      try:
+        perm = [int(x) for x in fields[1 if flip else 0:]]
+      except ValueError:
+        perm = []
+      if not perm:
+        raise ValueError('{}:{}: an op is a line of integer site indices, optionally after the word `flip`, got {!r}'
+                         .format(path, number, line.strip()))
+      perms.append(perm)
+      flips.append(int(flip))
+  return perms, flips
+
+
+def write_symmetry_ops(path, perms, flips=None, labels=None):
+  """Writes what read_symmetry_ops reads; `labels` go into a trailing comment per line."""
+  with open(path, 'w') as f:
+    for k, perm in enumerate(perms):
+      f.write('{}{}{}\n'.format('flip ' if flips is not None and flips[k] else '', ' '.join(str(int(i)) for i in perm),
+                                '' if labels is None else '   # {}'.format(labels[k])))
+
+
+def momentum_weights(values, size_x, size_y=1):
+  """w[m] = (1 / N) sum_r cos(q_m . r) values[r] over the N = size_x * size_y values <T_r> of `translations` (the last axis
+  of `values`; leading axes -- samples -- are kept), at the momenta q_m of torus_momenta (size_y = 1: chain_momenta), in
+  their order.  For a real psi <T_r> = <T_-r>, so the cosine transform is the weight of the state at each momentum; the
+  weights of q and -q are equal and each carries its own share; the weights sum to values[0]."""
+  values = np.asarray(values, np.float64)
+  n = size_x * size_y
+  if size_x < 1 or size_y < 1 or values.ndim < 1 or values.shape[-1] != n:
+    raise ValueError('momentum_weights: {} values for the {} x {} lattice'.format(values.shape[-1] if values.ndim else 0,
+                                                                                   size_x, size_y))
+  chain = size_y == 1
+  coords = chain_coords(size_x) if chain else torus_coords(size_x, size_y)
+  qs = chain_momenta(size_x) if chain else torus_momenta(size_x, size_y)
+  return values @ np.cos(coords @ qs.T) / n
+
+
 def load_bonds(checkpoint_dir, n_sites):
   """run_training.py:103-109 / run_energy_evaluation.py:51-57: `J.txt` of integer pairs
   (extra columns ignored), else the periodic chain."""

@@ -425,6 +425,26 @@ int vmc_dimer_correlations(vmc_ctx* ctx, int which, int32_t n_bonds, const int32
                            int32_t pairs_per_pass /*0: planner's choice*/,
                            double* bond_sum /*[n_bonds]*/, double* dd_sum /*[n_pairs]*/);
 
+/* Symmetry expectation values -- EXTENSION with no reference counterpart.  An op k is the site permutation perm_k,
+ * followed by the global spin flip where flip[k] is 1 (flip NULL: no flips): row_{k,c}[i] = f_k x_c[perm_k[i]] with
+ * f_k = -1 where flip[k] and +1 otherwise.  Over the ctx's current chains, with l = ln|psi|:
+ *   ratio_sum[k] = sum_c sigma exp(l(row_{k,c}) - l(x_c))                                        (fp64)
+ * so that <P_k> ~ ratio_sum[k] / batch_size: the character of the state under a translation, a point-group element or
+ * spin inversion.  sigma is the product of the two signs for the signed types (pbdg, fully_connected_nnb, ed_vector)
+ * and 1 otherwise; a vanishing amplitude on either side gives exactly 0 (never NaN).  The rows go through the full
+ * forward of the ctx's ansatz type (the device path of vmc_amplitude); the chains' own l and signs are the ctx's cache.
+ * The ops run in passes of at most ops_per_pass ops (0: as many as the row budget of a pass takes; a request is clamped
+ * to it); the sum of an op is added in one fixed order (chains c = l mod 64 ascending per lane l, then a butterfly over
+ * the lanes) and does not depend on the passes or on the other ops of the call.  A pure measurement: chains, step counter,
+ * accumulators, the Hamiltonian's bonds and the validity of the amplitude and activation caches are as before on return,
+ * on a failed call too.  which outside {0, 1}, n_ops < 1, a NULL perm, ops_per_pass < 0, a perm_k that is no bijection
+ * of 0 .. N - 1 (the message names the op and the entry; the rows of pbdg, fully_connected_nnb and ed_vector must stay
+ * at Sz = 0) or a flip entry above 1: VMC_ERR_INVALID, before anything touches the device; an output activation other
+ * than exp on an unsigned type and a product ctx: VMC_ERR_UNSUPPORTED; a factor of a product ctx: VMC_ERR_STATE. */
+int vmc_symmetry_expectations(vmc_ctx* ctx, int which, int32_t n_ops, const int32_t* perm /*[n_ops][N]*/,
+                              const uint8_t* flip /*[n_ops], 0/1; NULL: no flips*/,
+                              int32_t ops_per_pass /*0: the library decides*/, double* ratio_sum /*[n_ops]*/);
+
 /* Stochastic reconfiguration -- EXTENSION: named by the north star, absent from the reference
  * (training.py has only the plain energy gradient + Adam), so these entries replace no reference
  * interface; they sit where TrainOpsTraditional.apply_gradients (training.py:560-567) sits.
