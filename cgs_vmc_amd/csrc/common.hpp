@@ -32,8 +32,10 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
 
 // The same ten rounds with each 32 x 32 -> 64 bit product as ONE v_mad_u64_u32 (the form above compiles to
 // v_mul_hi_u32 + v_mul_lo_u32, both quarter rate): 272 against 356 clocks per un-overlapped call
-// (tools/ubench/philox_rate.hip).  For callers that draw OUTSIDE an MFMA phase (k_sweep8); k_sweep16's Philox pieces
-// between MFMA groups were tuned around the form above and ran ~1 % slower with this one.
+// (tools/ubench/philox_rate.hip).  For callers that draw OUTSIDE an MFMA phase: k_sweep8, and k_sweep16's hand-over
+// draw (waves 4-7 at the top of a pass, and the launch's first draw).  k_sweep16's Philox pieces BETWEEN MFMA groups
+// (layer 0 of the variants without hand-over) were tuned around the form above and ran ~1 % slower with this one.
+// Each v_mad_u64_u32 also writes a carry to an SGPR pair: in a scalar-register-bound kernel that costs a pair.
 __device__ __forceinline__ uint4 philox4x32_10_wide(uint4 c, uint2 k) {
 #pragma unroll
   for (int r = 0; r < 10; ++r) {

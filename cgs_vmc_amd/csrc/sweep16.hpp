@@ -313,7 +313,13 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
     else if (ND == UPRE && d == UPRE - 1 && j + 16 * d >= nblk) blk = VMC_ACCEPT_BLOCK;
     return make_uint4(blk, my_gid, (uint32_t)step, (uint32_t)(step >> 32));
   };
-  auto finish_draw = [&](const uint4 (&cs)[ND], unsigned long long step) {
+  // wide_c: the draw is not interleaved with MFMAs (the hand-over variants' draw_all), so each 32 x 32 -> 64 bit
+  // product is one v_mad_u64_u32 (philox4x32_10_wide, common.hpp: the same bits in fewer issue slots)
+  auto philox10 = [&](const uint4& ctr, auto wide_c) __attribute__((always_inline)) {
+    if constexpr (decltype(wide_c)::value) return philox4x32_10_wide(ctr, key);
+    else return philox4x32_10(ctr, key);
+  };
+  auto finish_draw = [&](const uint4 (&cs)[ND], unsigned long long step, auto wide_c) __attribute__((always_inline)) {
 #pragma unroll
     for (int d = 0; d < UPRE; ++d) {
       u_pre[4 * d + 0] = u32_to_uniform(cs[d].x); u_pre[4 * d + 1] = u32_to_uniform(cs[d].y);
@@ -324,16 +330,15 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
     } else if (acc_in_b) {
       u_pre_acc = u_pre[4 * (UPRE - 1)];
     } else {
-      const uint4 r = philox4x32_10(
-          make_uint4(VMC_ACCEPT_BLOCK, my_gid, (uint32_t)step, (uint32_t)(step >> 32)), key);
+      const uint4 r = philox10(make_uint4(VMC_ACCEPT_BLOCK, my_gid, (uint32_t)step, (uint32_t)(step >> 32)), wide_c);
       u_pre_acc = u32_to_uniform(r.x);
     }
   };
-  auto draw_all = [&](unsigned long long step) {     // un-overlapped form
+  auto draw_all = [&](unsigned long long step, auto wide_c) __attribute__((always_inline)) {     // un-overlapped form
     uint4 cs[ND];
 #pragma unroll
-    for (int d = 0; d < ND; ++d) cs[d] = philox4x32_10(ctr_of(d, step), key);
-    finish_draw(cs, step);
+    for (int d = 0; d < ND; ++d) cs[d] = philox10(ctr_of(d, step), wide_c);
+    finish_draw(cs, step, wide_c);
   };
 
   // branch-free (v_cndmask) argmax / argmin combine with the first-index tie rule of
@@ -393,7 +398,7 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
     }
   };
   // proposals of absolute step `step` into s_iup / s_idn / s_u
-  auto proposals = [&](unsigned long long step) {
+  auto proposals = [&](unsigned long long step) __attribute__((always_inline)) {
     if (NW > 4 && wave >= 4) return;   // chains 4w..4w+3 belong to waves 0-3
     if (!FAST && a.inj_up) {
       if (tid < 16) {
@@ -485,7 +490,7 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
   };
 
   if (!FAST && a.dbg_up != nullptr) {   // debug_proposals: dump the draw of step0, do not move
-    if (use_pref) draw_all(a.step0);
+    if (use_pref) draw_all(a.step0, std::false_type{});
     proposals(a.step0);
     __syncthreads();
     if (tid < 16 && chain0 + tid < a.B) {
@@ -506,8 +511,11 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
 #define SWEEP_STAMP(k) \
   if (STAMP) { const unsigned long long t1_ = vmc_stamp(); if (stamp_on) cyc[k] += t1_ - t0; t0 = t1_; }
 
+  // The passes of a launch (leading cache pass, steady-state steps, final refresh) are separate copies of ONE set
+  // of lambdas: what tells them apart is a compile-time argument (step_c: an mc_step, not a refresh) or a constant
+  // at the call (save: the final refresh also writes the activations for the gradient path), and every lambda is
+  // inlined into each pass, so the steady-state loop carries none of the other passes' paths.
   // builds the layer-2 input operand (and the candidate z1 when with_delta)
-  bool save_acts = false;   // final refresh: also write the activations for the gradient path
   auto save_own = [&](int l) {
     if (chain0 + j < a.B) {
       float* dst = a.act_out + ((long long)l * a.B + chain0 + j) * Hp;
@@ -549,11 +557,11 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
     }
   };
   f32x4 zreg[TO];    // committed z1 of this thread's columns (W1L build)
-  bool z_valid = false;
   f32x4 dprev[TO];   // W1[i_dn] - W1[i_up] of the previous proposal (W1L build)
 #pragma unroll
   for (int to = 0; to < TO; ++to) dprev[to] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto build = [&](bool with_delta) {
+  auto build = [&](auto step_c, bool save) __attribute__((always_inline)) {
+    constexpr bool with_delta = decltype(step_c)::value;
     if (W1L) {
       // single z1 buffer; the previous step's accepted move is folded in first (each thread
       // owns fixed elements of z1, so no barrier is needed for the read-modify-write).
@@ -563,13 +571,14 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
       // accepted move adds: no second pair of row reads.
       float* zrow = s_z1 + j * ZS;
       const float cp = s_pacc[j] != 0 ? 2.f : 0.f;
-      const float cd = with_delta ? 2.f : 0.f;
+      const float cd = with_delta ? 2.f : 0.f;   // (a refresh keeps its fused multiply-add: 0 * d + z is not z for z = -0)
       const float* wa = s_w1 + (with_delta ? s_idn[j] : 0) * W1S;
       const float* wb = s_w1 + (with_delta ? s_iup[j] : 0) * W1S;
       // The committed z1 of this thread's columns lives in registers (zreg) between steps; LDS
       // holds it only where another phase produces or consumes it: the launch's cache load, the
-      // exact refresh passes (z1_direct) and the final write-back, which follows a refresh.
-      const bool from_lds = !with_delta || !z_valid;
+      // exact refresh passes (z1_direct) and the final write-back, which follows a refresh.  A step never reads
+      // it from there: the pass before its first one left zreg behind (a refresh's build, or load_zreg below).
+      constexpr bool from_lds = !with_delta;
       f32x4 x1[TO], y1[TO];
 #pragma unroll
       for (int to = 0; to < TO; ++to) {
@@ -577,7 +586,6 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
         if (from_lds) zreg[to] = *(const f32x4*)(zrow + col);
         x1[to] = *(const f32x4*)(wa + col); y1[to] = *(const f32x4*)(wb + col);
       }
-      z_valid = true;
 #pragma unroll
       for (int to = 0; to < TO; ++to) {
         const int t = wave * TO + to;
@@ -591,7 +599,7 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
         finish_own(to, zc, n_hidden == 0);
         *(f32x4*)(s_x + (t * 64 + lane) * 4) = own[to];
       }
-      if (save_acts) save_own(0);
+      if (save) save_own(0);
       return;
     }
     const int sel = s_sel[j];
@@ -618,7 +626,14 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
       if (!SW) *(f32x4*)(s_x + (t * 64 + lane) * 4) = own[to];
     }
     if constexpr (SW) sw_publish(s_x);
-    if (save_acts) save_own(0);
+    if (save) save_own(0);
+  };
+  // committed z1 of this thread's columns from the cache a launch loaded into LDS (W1L build)
+  auto load_zreg = [&]() {
+    if (W1L) {
+#pragma unroll
+      for (int to = 0; to < TO; ++to) zreg[to] = *(const f32x4*)(s_z1 + j * ZS + 16 * (wave * TO + to) + 4 * g);
+    }
   };
 
   // layers 2..L + output dot; leaves per-wave partial logits in s_part.
@@ -661,12 +676,12 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
     for (int to = 0; to < TO; ++to) ring_s[slot][to] = sw_frag(l, kt, to);
   };
   if (SW && n_hidden > 0) sw_issue(0, RES, RES & 1);
-  auto forward = [&](unsigned long long next_step) {
+  auto forward = [&](unsigned long long next_step, bool save) __attribute__((always_inline)) {
     // Every issue below is unconditional so that the compiler can count vmcnt exactly; a load
     // issued under a runtime condition makes it wait for ALL outstanding loads at the next use.
     int cur = 0;
     // FS = first streamed k-tile of the layer (RT for layer 0, 0 afterwards)
-    auto layer = [&](int l, auto fs_c, auto first_c, auto draw_c) {
+    auto layer = [&](int l, auto fs_c, auto first_c, auto draw_c) __attribute__((always_inline)) {
       constexpr int FS = decltype(fs_c)::value;
       // layer 0 carries the Philox pieces: in its resident k-tiles, or (no resident tile) in all.
       // DRAW: this wave owns chains (waves 0-3 of an 8-wave workgroup); with SWEEP_SPLIT the others
@@ -724,7 +739,7 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
         for (int d = 0; d < ND; ++d)
           asm volatile("" : "+v"(cs[d].x), "+v"(cs[d].y), "+v"(cs[d].z), "+v"(cs[d].w));
       };
-      if (DRAW && FS > 0) { pin_draw(); finish_draw(cs, next_step); }
+      if (DRAW && FS > 0) { pin_draw(); finish_draw(cs, next_step, std::false_type{}); }
       if (FS > 0) { SWEEP_STAMP(9) }
       // streamed k-tiles: weights PF-1 tiles ahead, activations one tile ahead
       if (FS == 0) inb[0] = xin[0];
@@ -747,7 +762,7 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
           }
         }
       }
-      if (FIRST && FS == 0) { pin_draw(); finish_draw(cs, next_step); }
+      if (FIRST && FS == 0) { pin_draw(); finish_draw(cs, next_step, std::false_type{}); }
       SWEEP_STAMP(FS > 0 ? 10 : 13)
       if (ACT == VMC_ACT_RELU_) vmc_mfma_settle_all(acc);   // the asm relu reads the accumulators (common.hpp)
       float* xout = s_x + (cur ^ 1) * NT * 256;
@@ -756,12 +771,12 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
         finish_own(to, acc[to], l + 1 == n_hidden);
         if (l + 1 < n_hidden) *(f32x4*)(xout + ((wave * TO + to) * 64 + lane) * 4) = own[to];
       }
-      if (save_acts) save_own(l + 1);
+      if (save) save_own(l + 1);
       cur ^= 1;
       SWEEP_STAMP(FS > 0 ? 11 : 14)
     };
     // split sampler: one layer = eight 32-deep k-steps; B operands (hi, mid, lo) from LDS one k-step ahead
-    auto layer_s = [&](int l, auto first_c) {
+    auto layer_s = [&](int l, auto first_c) __attribute__((always_inline)) {
       constexpr bool FIRSTL = decltype(first_c)::value;
       asm volatile("" : "+s"(sw_base));
       __syncthreads();
@@ -798,7 +813,7 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
 #pragma unroll
       for (int to = 0; to < TO; ++to) finish_own(to, acc[to], l + 1 == n_hidden);
       if (l + 1 < n_hidden) sw_publish(s_x + (cur ^ 1) * XB);
-      if (save_acts) save_own(l + 1);
+      if (save) save_own(l + 1);
       cur ^= 1;
     };
     if constexpr (SW) {
@@ -812,7 +827,7 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
   };
 
   // output dot of the last activations (own) -> per-wave partial logits in s_part
-  auto output_dot = [&]() {
+  auto output_dot = [&]() __attribute__((always_inline)) {
     float part = 0.f;
     f32x4 w[TO];
 #pragma unroll
@@ -839,16 +854,21 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
     return t + bout;
   };
 
-  // it = -1: cache of the initial spins; 0..n_steps-1: mc_steps; n_steps: exact cache of the
-  // final spins (all three share one instance of build/forward).
-  // The outcome of iteration it-1 is resolved at the TOP of iteration it by the wave that owns
+  // A launch is up to three parts that share one instance of the lambdas above:
+  //   cache pass   exact z1 / logit cache of the initial spins (skipped when the previous launch left one)
+  //   steps        0..n_steps-1, the steady state: one loop per kind of output activation
+  //   refresh      exact cache of the final spins (the only part of an n_steps = 0 launch)
+  // A step's Metropolis test is resolved at the TOP of the pass that follows it by the wave that owns
   // the chain (chains 4w..4w+3 -> wave w, all 16 lanes of a group redundantly, lane j == 0
   // writes): that wave is the only reader of the chain's spins in `proposals`, so no barrier
-  // is needed between the Metropolis accept and the next proposal.
+  // is needed between the Metropolis accept and the next proposal.  A refresh pass takes its logit
+  // at its own end (the same place in program order: what follows is the top of the next pass).
   unsigned int n_acc = 0;
-  int prev_kind = 0;   // 0 none, 1 refresh, 2 step
-  auto resolve = [&]() {
-    if (prev_kind == 0 || (NW > 4 && wave >= 4)) return;
+  // step_c: resolves an mc_step (Metropolis accept), not a refresh pass (its logit);
+  // exp_c: the output activation is known to be exp -- the accept test is one compare, no ladder of the others
+  auto resolve = [&](auto step_c, auto exp_c) __attribute__((always_inline)) {
+    constexpr bool STEP = decltype(step_c)::value, EXP = decltype(exp_c)::value;
+    if (NW > 4 && wave >= 4) return;
     const int c = my_c, gc = chain0 + c;
     // every LDS operand of the accept test is requested before the first one is used: one LDS
     // round trip for the phase instead of four (the asm pins the loads above the branches)
@@ -859,14 +879,14 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
     float on_new = 0.f;
     if (RBM) {   // onsite term of the evaluated configuration: committed value (+ exchange update)
       on_new = s_on[c];
-      if (prev_kind == 2) on_new += 2.f * (won_at(idn) - won_at(iup));
+      if (STEP) on_new += 2.f * (won_at(idn) - won_at(iup));
       ln += on_new;
     }
-    if (prev_kind == 2) {
+    if (STEP) {
       // Metropolis accept (graph_builders.py:75-88)
       // exp(dlogit) > sqrt(u)  <=>  dlogit > 0.5 log(u)  (monotone; u = 0 always accepts)
       bool acc;
-      if (a.oact == VMC_ACT_EXP_) acc = (ln - lg) > hl;
+      if (EXP || a.oact == VMC_ACT_EXP_) acc = (ln - lg) > hl;
       else acc = vmc_out_accept(a.oact, ln, lg, s_u[c], hl);
       acc = acc && (gc < a.B);
       if (j == 0) {
@@ -885,28 +905,11 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
       s_logit[c] = ln;
     }
   };
-  long long it_first = -1;
-  if (a.n_steps == 0) it_first = 0;   // a pure cache refresh (refresh_cache_by_sampler, vmc_api.hip): one pass, the final one
-  if (a.cache_in_valid && a.n_steps > 0) {
-    // the previous launch left an exact z1 / logit cache for these very chains: load it
-    // instead of recomputing it (saves one of the two refresh passes per launch)
-    for (int i = tid; i < 16 * (Hp / 4); i += NTH) {   // 16-byte loads, <= 2 per thread
-      const int c = i / (Hp / 4), c4 = i % (Hp / 4), gc = chain0 + c;
-      f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (gc < a.B) v = *(const f32x4*)(a.z1_in + (long long)gc * Hp + 4 * c4);
-      *(f32x4*)(s_z1 + c * ZS + 4 * c4) = v;
-    }
-    if (tid < 16) s_logit[tid] = chain0 + tid < a.B ? a.logit_in[chain0 + tid] : 0.f;
-    onsite_direct();
-    if (use_pref) draw_all(a.step0);
-    if (HANDOFF_T && handoff) to_keys();
-    __syncthreads();
-    it_first = 0;
-  }
-  for (long long it = it_first; it <= a.n_steps; ++it) {
-    const bool is_step = it >= 0 && it < a.n_steps;
+  // one pass: [resolve the step before it,] proposals (step) or exact z1 (refresh), build, layers, output dot
+  auto pass = [&](long long it, auto step_c, auto exp_c, bool resolve_prev, bool save) __attribute__((always_inline)) {
+    constexpr bool IS_STEP = decltype(step_c)::value;
     if (HANDOFF_T && handoff && wave >= 4) {
-      draw_all(a.step0 + (unsigned long long)(it + 1));
+      draw_all(a.step0 + (unsigned long long)(it + 1), std::true_type{});
       to_keys();
       float* dst = s_uh + ((wave - 4) * (UPRE + 1) * 64 + lane) * 4;
 #pragma unroll
@@ -914,12 +917,11 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
         *(f32x4*)(dst + 256 * b) = f32x4{u_pre[4 * b], u_pre[4 * b + 1], u_pre[4 * b + 2], u_pre[4 * b + 3]};
       dst[256 * UPRE] = u_pre_acc;
     }
-    save_acts = (it == a.n_steps) && (a.act_out != nullptr);
-    stamp_on = is_step;
+    stamp_on = IS_STEP;
     if (STAMP) t0 = vmc_stamp();
-    resolve();
+    if (resolve_prev) resolve(std::true_type{}, exp_c);
     SWEEP_STAMP(5)
-    if (is_step) {
+    if constexpr (IS_STEP) {
       proposals(a.step0 + (unsigned long long)it);
     } else {
       __syncthreads();   // z1_direct reads every chain's (possibly just updated) spins
@@ -940,20 +942,45 @@ __device__ __forceinline__ void sweep16_body(const SweepArgs& a) {
       }
       u_pre_acc = src[256 * UPRE];
     }
-    build(is_step);
+    build(step_c, save);
     SWEEP_STAMP(2)
     const unsigned long long next_step = a.step0 + (unsigned long long)(it + 1);
     // (the split layers carry no Philox pieces: without the hand-over the draws follow the layers un-overlapped)
     const bool pre_here = use_pref && n_hidden > 0 && !(SW && !(HANDOFF_T && handoff));
-    if (n_hidden > 0) forward(next_step);
-    if (use_pref && !pre_here && !(NW > 4 && wave >= 4)) draw_all(next_step);
+    if (n_hidden > 0) forward(next_step, save);
+    if (use_pref && !pre_here && !(NW > 4 && wave >= 4)) draw_all(next_step, std::false_type{});
     SWEEP_STAMP(3)
     output_dot();
     SWEEP_STAMP(4)
-    prev_kind = is_step ? 2 : 1;
+  };
+  if (a.cache_in_valid && a.n_steps > 0) {
+    // the previous launch left an exact z1 / logit cache for these very chains: load it
+    // instead of recomputing it (saves one of the two refresh passes per launch)
+    for (int i = tid; i < 16 * (Hp / 4); i += NTH) {   // 16-byte loads, <= 2 per thread
+      const int c = i / (Hp / 4), c4 = i % (Hp / 4), gc = chain0 + c;
+      f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (gc < a.B) v = *(const f32x4*)(a.z1_in + (long long)gc * Hp + 4 * c4);
+      *(f32x4*)(s_z1 + c * ZS + 4 * c4) = v;
+    }
+    if (tid < 16) s_logit[tid] = chain0 + tid < a.B ? a.logit_in[chain0 + tid] : 0.f;
+    onsite_direct();
+    if (HANDOFF_T && handoff) { draw_all(a.step0, std::true_type{}); to_keys(); }
+    else if (use_pref) draw_all(a.step0, std::false_type{});
+    __syncthreads();
+    load_zreg();
+  } else if (a.n_steps > 0) {
+    pass(-1, std::false_type{}, std::false_type{}, false, false);
+    resolve(std::false_type{}, std::false_type{});
   }
+  // the steady state; the first step has no step before it to resolve
+  if (a.oact == VMC_ACT_EXP_) {
+    for (long long it = 0; it < a.n_steps; ++it) pass(it, std::true_type{}, std::true_type{}, it > 0, false);
+  } else {
+    for (long long it = 0; it < a.n_steps; ++it) pass(it, std::true_type{}, std::false_type{}, it > 0, false);
+  }
+  pass(a.n_steps, std::false_type{}, std::false_type{}, a.n_steps > 0, a.act_out != nullptr);
   stamp_on = false;
-  resolve();          // logit of the final refresh
+  resolve(std::false_type{}, std::false_type{});   // logit of the final refresh
   __syncthreads();
 #undef SWEEP_STAMP
   if (STAMP && a.dbg_cycles && lane == 0) {
