@@ -1,25 +1,8 @@
-// ProductOfWavefunctions ('prod'): what a product ctx keeps beside the members of vmc_ctx, and the launchers of prod.hip.
+// ProductOfWavefunctions ('prod'): the launchers of prod.hip (what a product ctx keeps beside the members of vmc_ctx:
+// ProdState, vmc_api_prod.hip).
 // Included by vmc_api_prod.hip and prod.hip only.
 #pragma once
 #include "common.hpp"
-
-struct vmc_ctx;
-
-// psi = psi_a psi_b.  The product ctx owns the chains (vmc_ctx::configs); a factor reads them through a device copy in
-// its own `configs` (on_chains tells whether that copy is the chains -- the sampler overwrites it with the candidates).
-// l / s: the factors' logits and signs of the CHAINS, per parameter set; they are what vmc_ctx::ps[which].cache_valid of
-// the product vouches for.  A factor without a sign keeps s = 1; ed_vector keeps psi itself there (its sign is what counts).
-struct ProdState {
-  vmc_ctx* child[2] = {nullptr, nullptr};
-  long long P[2] = {0, 0};
-  bool on_chains = false;
-  bool dead = false;                        // a factor was destroyed while composed (its child[] entry is null): every entry refuses
-  float* l[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [which][factor][B]
-  float* s[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-  int *iup = nullptr, *idn = nullptr;       // [B] the proposal in flight
-  float* u = nullptr;
-  unsigned* acc_cnt = nullptr;              // [B] acceptances of a launch, per chain
-};
 
 // cand_a = cand_b = the chains with the proposed pair exchanged (k_nnb_candidates' rule: a proposal that would not exchange
 // an up with a down spin leaves the copy as it is; the accept kernel rejects it)

@@ -45,14 +45,10 @@ static hipError_t ensure_bond_diff(vmc_ctx* c, int which, const int2* bonds) {
   ParamSet& p = c->ps[which];
   if (p.bdiff_valid && p.bdiff_epoch == c->bonds_epoch) return hipSuccess;
   const int nb = c->bonds ? c->n_bonds : 1;
-  if (nb > p.bdiff_cap) {
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return e;
-    if (p.bdiff) hipFree(p.bdiff);
-    if (p.bdiff_on) hipFree(p.bdiff_on);
-    p.bdiff = p.bdiff_on = nullptr; p.bdiff_cap = 0;
-    if ((e = dalloc(&p.bdiff, (long long)nb * c->Hp)) != hipSuccess) return e;
-    if ((e = dalloc(&p.bdiff_on, nb)) != hipSuccess) return e;
+  if (nb > p.bdiff_cap) {      // both or neither: the table counts as allocated only once bdiff_on is there
+    p.bdiff_cap = 0;
+    if (p.bdiff.alloc(c, (long long)nb * c->Hp, "bdiff") != VMC_OK || p.bdiff_on.alloc(c, nb, "bdiff_on") != VMC_OK)
+      return hipErrorOutOfMemory;
     p.bdiff_cap = nb;
   }
   hipError_t e = launch_bond_diff(c->stream, p.w1p, c->rbm ? p.won : nullptr, bonds, nb, c->Hp, p.bdiff, p.bdiff_on);
@@ -379,14 +375,14 @@ int connected_rows_device(vmc_ctx* c, int which, bool share_cus) {
 
 int grow_tmp(vmc_ctx* c, long long rows) {
   if (rows <= c->tmp_rows) return VMC_OK;
-  if (c->tmp_cfg) { hipFree(c->tmp_cfg); hipFree(c->tmp_z1); hipFree(c->tmp_out); hipFree(c->tmp_rowinfo); hipFree(c->tmp_on); hipFree(c->tmp_sign); }
-  HIPCHK(c, dalloc(&c->tmp_on, rows));
-  HIPCHK(c, dalloc(&c->tmp_sign, rows));
-  HIPCHK(c, dalloc(&c->tmp_rowinfo, rows));
+  c->tmp_rows = 0;      // all six or none: a failure below leaves the group absent, the next call allocates it anew
+  PROPAGATE(c->tmp_on.alloc(c, rows, "tmp_on"));
+  PROPAGATE(c->tmp_sign.alloc(c, rows, "tmp_sign"));
+  PROPAGATE(c->tmp_rowinfo.alloc(c, rows, "tmp_rowinfo"));
   HIPCHK(c, launch_iota_rows(c->stream, c->tmp_rowinfo, (int)rows));
-  HIPCHK(c, dalloc(&c->tmp_cfg, rows * c->N));
-  HIPCHK(c, dalloc(&c->tmp_z1, rows * c->Hp));
-  HIPCHK(c, dalloc(&c->tmp_out, rows));
+  PROPAGATE(c->tmp_cfg.alloc(c, rows * c->N, "tmp_cfg"));
+  PROPAGATE(c->tmp_z1.alloc(c, rows * c->Hp, "tmp_z1"));
+  PROPAGATE(c->tmp_out.alloc(c, rows, "tmp_out"));
   c->tmp_rows = rows;
   return VMC_OK;
 }
@@ -544,30 +540,31 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
   const long long B = c->B, N = c->N, Hp = c->Hp, P = c->P, L = c->A, NH = c->n_hh;   // L: activation buffers
 #define CA(expr) do { hipError_t e2 = (expr); if (e2 != hipSuccess) { \
     g_create_error = std::string(#expr) + ": " + hipGetErrorString(e2); vmc_destroy(c); return VMC_ERR_HIP; } } while (0)
+#define NEW(buf, n) do { if ((buf).alloc(c, (n), #buf) != VMC_OK) { g_create_error = c->err; vmc_destroy(c); return VMC_ERR_HIP; } } while (0)
   for (int w = 0; w < 2; ++w) {
     ParamSet& p = c->ps[w];
-    CA(dalloc(&p.theta, P));
-    CA(dalloc(&p.w1p, N * Hp)); CA(dalloc(&p.b1p, Hp)); CA(dalloc(&p.bh, NH * Hp));
-    CA(dalloc(&p.p16, (NH > 0 ? NH : 1) * Hp * Hp));
-    CA(dalloc(&p.p16t, (NH > 0 ? NH : 1) * Hp * Hp));
+    NEW(p.theta, P);
+    NEW(p.w1p, N * Hp); NEW(p.b1p, Hp); NEW(p.bh, NH * Hp);
+    NEW(p.p16, (NH > 0 ? NH : 1) * Hp * Hp);
+    NEW(p.p16t, (NH > 0 ? NH : 1) * Hp * Hp);
     CA(hipMemsetAsync(p.p16t, 0, (size_t)(NH > 0 ? NH : 1) * Hp * Hp * sizeof(float), c->stream));
     CA(hipMemsetAsync(p.p16, 0, (size_t)(NH > 0 ? NH : 1) * Hp * Hp * sizeof(float), c->stream));
-    CA(dalloc(&p.won, N)); CA(dalloc(&p.onsite, B));
+    NEW(p.won, N); NEW(p.onsite, B);
     CA(hipMemsetAsync(p.won, 0, N * sizeof(float), c->stream));
     CA(hipMemsetAsync(p.onsite, 0, B * sizeof(float), c->stream));
-    CA(dalloc(&p.woutp, Hp)); CA(dalloc(&p.bout, 1));
-    if (c->split) CA(dalloc(&p.p16s, pack_split_dwords((int)NH)));
-    CA(dalloc(&p.z1, B * Hp)); CA(dalloc(&p.logit, B)); CA(dalloc(&p.eloc, B));
+    NEW(p.woutp, Hp); NEW(p.bout, 1);
+    if (c->split) NEW(p.p16s, pack_split_dwords((int)NH));
+    NEW(p.z1, B * Hp); NEW(p.logit, B); NEW(p.eloc, B);
     if (w == 0) {
-      CA(dalloc(&p.z1_alt, B * Hp)); CA(dalloc(&p.logit_alt, B)); CA(dalloc(&p.onsite_alt, B));
+      NEW(p.z1_alt, B * Hp); NEW(p.logit_alt, B); NEW(p.onsite_alt, B);
       CA(hipMemsetAsync(p.onsite_alt, 0, B * sizeof(float), c->stream));
     }
   }
-  CA(dalloc(&c->configs, B * N)); CA(dalloc(&c->configs_alt, B * N));
+  NEW(c->configs, B * N); NEW(c->configs_alt, B * N);
   CA(hipMemsetAsync(c->configs, 0, B * N * sizeof(float), c->stream));
   CA(hipMemsetAsync(c->configs_alt, 0, B * N * sizeof(float), c->stream));
   c->act.resize(L, nullptr);
-  CA(dalloc(&c->act_all, L * B * Hp)); CA(dalloc(&c->act_alt, L * B * Hp));
+  NEW(c->act_all, L * B * Hp); NEW(c->act_alt, L * B * Hp);
   CA(hipMemsetAsync(c->act_all, 0, L * B * Hp * sizeof(float), c->stream));
   CA(hipMemsetAsync(c->act_alt, 0, L * B * Hp * sizeof(float), c->stream));
   {  // the sampler's stream outranks `stream`: where both have workgroups waiting for a CU, the sampler's go first
@@ -580,10 +577,10 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
   CA(hipEventCreateWithFlags(&c->ev_sweep_done, hipEventDisableTiming));
   for (int l = 0; l < L; ++l) c->act[l] = c->act_all + l * B * Hp;
   c->delta.resize(L, nullptr);
-  CA(dalloc(&c->delta_all, L * B * Hp));
+  NEW(c->delta_all, L * B * Hp);
   CA(hipMemsetAsync(c->delta_all, 0, L * B * Hp * sizeof(float), c->stream));
   for (int l = 0; l < L; ++l) c->delta[l] = c->delta_all + l * B * Hp;
-  for (int i = 0; i < 4; ++i) CA(hipMalloc(&c->d_batch[i / 2][i % 2], (size_t)(L + 1) * wgrad_problem_bytes()));
+  for (int i = 0; i < 4; ++i) NEW(c->d_batch[i / 2][i % 2], (L + 1) * (long long)wgrad_problem_bytes());
   {  // weight-gradient launch: the tiles of all layers
     // fully_connected on the kernels that run k_backprop16: the N = 1 output layer leaves the MFMA tile grid
     // (CGS_VMC_WGRAD_OUT_TILES=1 keeps it there: A/B measurements)
@@ -593,34 +590,34 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
                       : plan_wgrad_total_tiles((int)N, c->H, (int)NH, rbm, !c->wg_out_partials);
     // (nnb: hundreds of tiles and more -- the workspace follows the planned slices, not the bound)
     if (nnb) c->nnb_wg_slices = plan_wgrad_slices(c->wg_tiles, B, c->num_cus, 1, 0);
-    if (c->wg_out_partials) CA(dalloc(&c->wg_outpart, ((B + 15) / 16) * 2 * (Hp + 4)));
-    CA(dalloc(&c->wg_tickets, c->wg_tiles > 0 ? c->wg_tiles : 1));
+    if (c->wg_out_partials) NEW(c->wg_outpart, ((B + 15) / 16) * 2 * (Hp + 4));
+    NEW(c->wg_tickets, c->wg_tiles > 0 ? c->wg_tiles : 1);
     CA(hipMemsetAsync(c->wg_tickets, 0, (size_t)(c->wg_tiles > 0 ? c->wg_tiles : 1) * sizeof(int), c->stream));
   }
-  CA(dalloc(&c->ratio, B)); CA(dalloc(&c->ones, B)); CA(dalloc(&c->oscale, B));
+  NEW(c->ratio, B); NEW(c->ones, B); NEW(c->oscale, B);
   CA(launch_fill(c->stream, c->ones, 1.f, B));
   CA(launch_fill(c->stream, c->oscale, 1.f, B));
   if (c->hact == VMC_ACT_COS_) {
-    CA(dalloc(&c->dact_all, L * B * Hp)); CA(dalloc(&c->dact_alt, L * B * Hp));
+    NEW(c->dact_all, L * B * Hp); NEW(c->dact_alt, L * B * Hp);
     CA(hipMemsetAsync(c->dact_all, 0, L * B * Hp * sizeof(float), c->stream));
     CA(hipMemsetAsync(c->dact_alt, 0, L * B * Hp * sizeof(float), c->stream));
   }
-  // (vmc_create_product re-sizes every member sized by P -- theta of both sets, acc, adam_m, adam_v, grad_tmp -- to
-  // P_a + P_b: a new P-sized member goes into its list in vmc_api_prod.hip as well)
-  CA(dalloc(&c->acc, 2 * P + 8)); CA(dalloc(&c->adam_m, P)); CA(dalloc(&c->adam_v, P));
-  CA(dalloc(&c->grad_tmp, P));
+  // (vmc_create_product allocates the members sized by P -- theta of both sets, acc, adam_m, adam_v, grad_tmp -- anew
+  // at P_a + P_b: alloc frees what vmc_create put there)
+  NEW(c->acc, 2 * P + 8); NEW(c->adam_m, P); NEW(c->adam_v, P);
+  NEW(c->grad_tmp, P);
   CA(hipMemsetAsync(c->acc, 0, (2 * P + 8) * sizeof(float), c->stream));
   CA(hipMemsetAsync(c->adam_m, 0, P * sizeof(float), c->stream));
   CA(hipMemsetAsync(c->adam_v, 0, P * sizeof(float), c->stream));
-  CA(dalloc(&c->gemm_ws, plan_wgrad_ws_floats(c->wg_tiles, nnb ? c->nnb_wg_slices : WG_MAX_SPLIT)));
-  CA(dalloc(&c->d_accepted, 1)); CA(dalloc(&c->d_sum, 1)); CA(dalloc(&c->d_max, 1));
-  CA(dalloc(&c->inj_up, B)); CA(dalloc(&c->inj_dn, B)); CA(dalloc(&c->inj_u, B));
-  CA(dalloc(&c->acc_mask, B));
-  CA(dalloc(&c->cnt, B)); CA(dalloc(&c->off, B + 1)); CA(dalloc(&c->diag, B));
-  CA(dalloc(&c->cnt_alt, B)); CA(dalloc(&c->diag_alt, B));
-  CA(dalloc(&c->rowinfo_id, B)); CA(launch_iota_rows(c->stream, c->rowinfo_id, (int)B));
-  CA(dalloc(&c->bond_dummy, 1)); CA(hipMemsetAsync(c->bond_dummy, 0, sizeof(int2), c->stream));
-  CA(dalloc(&c->offdiag, B));
+  NEW(c->gemm_ws, plan_wgrad_ws_floats(c->wg_tiles, nnb ? c->nnb_wg_slices : WG_MAX_SPLIT));
+  NEW(c->d_accepted, 1); NEW(c->d_sum, 1); NEW(c->d_max, 1);
+  NEW(c->inj_up, B); NEW(c->inj_dn, B); NEW(c->inj_u, B);
+  NEW(c->acc_mask, B);
+  NEW(c->cnt, B); NEW(c->off, B + 1); NEW(c->diag, B);
+  NEW(c->cnt_alt, B); NEW(c->diag_alt, B);
+  NEW(c->rowinfo_id, B); CA(launch_iota_rows(c->stream, c->rowinfo_id, (int)B));
+  NEW(c->bond_dummy, 1); CA(hipMemsetAsync(c->bond_dummy, 0, sizeof(int2), c->stream));
+  NEW(c->offdiag, B);
   if (wide) {
     c->wrows = B > 131072 ? B : 131072;
     if (nnb) {   // blocks of rows whose dense pairing layer takes CGS_VMC_NNB_BLOCK_MB (default 256) MiB
@@ -629,36 +626,36 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
       c->nnb_rows = plan_nnb_block_rows((int)N, mb);
       if (const char* e = getenv("CGS_VMC_NNB_BLOCK_ROWS")) { const long long r = atoll(e); if (r >= 1 && r < c->nnb_rows) c->nnb_rows = r; }   // tests: several blocks at small shapes
       c->wrows = c->nnb_rows;
-      CA(dalloc(&c->nnb_out, c->nnb_rows * N * N));
-      CA(dalloc(&c->nnb_delta, B * N * N));
-      CA(dalloc(&c->nnb_cl, B)); CA(dalloc(&c->nnb_cs, B));
+      NEW(c->nnb_out, c->nnb_rows * N * N);
+      NEW(c->nnb_delta, B * N * N);
+      NEW(c->nnb_cl, B); NEW(c->nnb_cs, B);
     }
-    CA(dalloc(&c->wbuf[0], c->wrows * Hp)); CA(dalloc(&c->wbuf[1], c->wrows * Hp));
-    CA(dalloc(&c->wide_u, B));
-    CA(dalloc(&c->wide_dot, (long long)gemm_rowdot_tiles(c->H) * c->wrows));
-    CA(dalloc(&c->wide_iup, B)); CA(dalloc(&c->wide_idn, B)); CA(dalloc(&c->wide_zero, Hp));
+    NEW(c->wbuf[0], c->wrows * Hp); NEW(c->wbuf[1], c->wrows * Hp);
+    NEW(c->wide_u, B);
+    NEW(c->wide_dot, (long long)gemm_rowdot_tiles(c->H) * c->wrows);
+    NEW(c->wide_iup, B); NEW(c->wide_idn, B); NEW(c->wide_zero, Hp);
     CA(hipMemsetAsync(c->wide_zero, 0, Hp * sizeof(float), c->stream));
   }
   if (c->sgn)
     for (int w = 0; w < 2; ++w) {
-      CA(dalloc(&c->ps[w].sign, B));
+      NEW(c->ps[w].sign, B);
       CA(hipMemsetAsync(c->ps[w].sign, 0, B * sizeof(float), c->stream));
     }
   if (edvec) {
-    CA(dalloc(&c->ps[0].sign_alt, B));
+    NEW(c->ps[0].sign_alt, B);
     CA(hipMemsetAsync(c->ps[0].sign_alt, 0, B * sizeof(float), c->stream));
-    CA(dalloc(&c->ed_keys, B)); CA(dalloc(&c->ed_keys_sorted, B));
+    NEW(c->ed_keys, B); NEW(c->ed_keys_sorted, B);
     CA(edvec_sort_bytes((int)B, (int)P, &c->ed_sort_bytes));
-    CA(hipMalloc(&c->ed_sort_tmp, c->ed_sort_bytes > 0 ? c->ed_sort_bytes : 1));
+    NEW(c->ed_sort_tmp, (long long)c->ed_sort_bytes);
     c->ed_tables_lds = plan_edvec_tables_in_lds((int)N) && !(getenv("CGS_VMC_EDVEC_TABLES_LDS") && atoi(getenv("CGS_VMC_EDVEC_TABLES_LDS")) == 0);
     if (c->ed_tables_lds) CA(edvec_sweep_reserve_lds((int)N));
   } else if (pbdg) {
     const long long n = N / 2;
-    CA(dalloc(&c->ps[0].sign_alt, B));
+    NEW(c->ps[0].sign_alt, B);
     CA(hipMemsetAsync(c->ps[0].sign_alt, 0, B * sizeof(float), c->stream));
-    CA(dalloc(&c->pbdg_inv, B * n * n)); CA(dalloc(&c->pbdg_pos, B * N));
+    NEW(c->pbdg_inv, B * n * n); NEW(c->pbdg_pos, B * N);
     c->pbdg_slices = plan_pbdg_grad_slices(P, B, c->num_cus);
-    CA(dalloc(&c->pbdg_ws, plan_pbdg_grad_ws_doubles(P, c->pbdg_slices)));
+    NEW(c->pbdg_ws, plan_pbdg_grad_ws_doubles(P, c->pbdg_slices));
   }
   if (conv && c->conv_general) {
     // blocks of at most ~768 MB of im2col rows (one row configuration at least), at least B rows when that fits
@@ -691,17 +688,17 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
       if (getenv("CGS_VMC_CONV_GENERAL_BLOCK_ROWS")) rows_fwd = rows;      // tests: several blocks at small shapes
     }
     c->cg_rows_fwd = rows_fwd;
-    for (int i = 0; i < 2; ++i) CA(dalloc(&c->cg_fm[i], rows_fwd * cg.N * cgen_fp(cg)));
-    CA(dalloc(&c->cg_sum, rows_fwd)); CA(dalloc(&c->cg_zero, 1)); CA(dalloc(&c->cg_lnew, B));
+    for (int i = 0; i < 2; ++i) NEW(c->cg_fm[i], rows_fwd * cg.N * cgen_fp(cg));
+    NEW(c->cg_sum, rows_fwd); NEW(c->cg_zero, 1); NEW(c->cg_lnew, B);
     CA(hipMemsetAsync(c->cg_zero, 0, sizeof(float), c->stream));
-    CA(dalloc(&c->wide_u, B)); CA(dalloc(&c->wide_iup, B)); CA(dalloc(&c->wide_idn, B));
+    NEW(c->wide_u, B); NEW(c->wide_iup, B); NEW(c->wide_idn, B);
   } else if (conv) {
     const long long nl = cg.n_conv > 1 ? cg.n_conv - 1 : 1;
     for (int w = 0; w < 2; ++w) {
       ParamSet& p = c->ps[w];
-      CA(dalloc(&p.cw0, plan_conv_w0_floats(cg))); CA(dalloc(&p.cwf, plan_conv_wf_floats(cg)));
-      CA(dalloc(&p.cwb, plan_conv_wf_floats(cg)));
-      CA(dalloc(&p.cbias, plan_conv_bias_floats(cg)));
+      NEW(p.cw0, plan_conv_w0_floats(cg)); NEW(p.cwf, plan_conv_wf_floats(cg));
+      NEW(p.cwb, plan_conv_wf_floats(cg));
+      NEW(p.cbias, plan_conv_bias_floats(cg));
     }
     const int nw = conv_waves(cg);
     c->cG = conv_pick_group(cg, nw);
@@ -712,11 +709,12 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
       if (G >= 1 && G <= 64 && conv_rows_lds(cg, G) <= conv_lds_cap(cg)) c->cGs = G < B ? G : (int)B;
     }
     c->ctape_stride = B * cg.CS; c->cdelta_stride = B * cg.CS;
-    CA(dalloc(&c->ctape, nl * c->ctape_stride)); CA(dalloc(&c->cdelta, (long long)cg.n_conv * c->cdelta_stride));
+    NEW(c->ctape, nl * c->ctape_stride); NEW(c->cdelta, (long long)cg.n_conv * c->cdelta_stride);
     c->c_slices = plan_conv_dw_slices(cg, B, c->num_cus);
-    CA(dalloc(&c->cws, plan_conv_dw_ws_floats(cg, c->c_slices)));
+    NEW(c->cws, plan_conv_dw_ws_floats(cg, c->c_slices));
   }
   CA(hipStreamSynchronize(c->stream));
+#undef NEW
 #undef CA
   *out = c;
   return VMC_OK;
@@ -735,43 +733,8 @@ void vmc_destroy(vmc_ctx* c) {
   for (hipEvent_t e : c->cg_grp_ev) if (e) hipEventDestroy(e);
   for (hipEvent_t e : {c->ev_mark, c->ev_now, c->ev_sweep_done}) if (e) hipEventDestroy(e);
   for (auto& e : c->event_pool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
-  for (int w = 0; w < 2; ++w) {
-    ParamSet& p = c->ps[w];
-    float* ptrs[] = {p.theta, p.w1p, p.b1p, p.bh, p.p16, p.p16t, p.woutp, p.bout, p.z1, p.logit, p.eloc, p.won, p.onsite,
-                     p.z1_alt, p.logit_alt, p.onsite_alt, p.cw0, p.cwf, p.cwb, p.cbias, p.bdiff, p.bdiff_on};
-    for (float* q : ptrs) if (q) hipFree(q);
-    if (p.p16s) hipFree(p.p16s);
-  }
-  if (c->act_all) hipFree(c->act_all);
-  if (c->act_alt) hipFree(c->act_alt);
-  for (float* q : {c->oscale, c->dact_all, c->dact_alt, c->ctape, c->cdelta, c->cws, c->wbuf[0], c->wbuf[1],
-                   c->wide_u, c->wide_zero}) if (q) hipFree(q);
-  for (int* q : {c->wide_iup, c->wide_idn}) if (q) hipFree(q);
-  if (c->wide_dot) hipFree(c->wide_dot);
-  for (float* q : {c->cg_pmaps, c->cg_A, c->cg_fm[0], c->cg_fm[1], c->cg_zero, c->cg_lnew, c->cg_tape, c->cg_gl, c->cg_g[0], c->cg_g[1], c->cg_wpos,
-                   c->cg_wt, c->cg_ws}) if (q) hipFree(q);
-  if (c->cg_sum) hipFree(c->cg_sum);
-  if (c->cg_td) hipFree(c->cg_td);
-  if (c->cg_centre) hipFree(c->cg_centre);
-  for (int* q : {c->gnn_adj, c->gnn_inv_ptr, c->gnn_inv, c->pbdg_pos, c->ed_top, c->ed_bot}) if (q) hipFree(q);
-  for (void* q : {(void*)c->ed_keys, (void*)c->ed_keys_sorted, c->ed_sort_tmp}) if (q) hipFree(q);
-  for (float* q : {c->ps[0].sign, c->ps[1].sign, c->ps[0].sign_alt, c->pbdg_inv, c->tmp_sign, c->nnb_out, c->nnb_delta, c->nnb_cl, c->nnb_cs}) if (q) hipFree(q);
-  if (c->pbdg_ws) hipFree(c->pbdg_ws);
-  void* ptrs[] = {c->configs, c->configs_alt, c->bonds, c->half_jx, c->quarter_jz, c->cnt, c->off, c->diag, c->val,
-                  c->offdiag, c->rowinfo, c->delta_all, c->d_batch[0][0], c->d_batch[0][1], c->d_batch[1][0], c->d_batch[1][1], c->ratio, c->ones, c->acc,
-                  c->adam_m, c->adam_v, c->grad_tmp, c->gemm_ws, c->wg_tickets, c->d_accepted, c->d_sum,
-                  c->d_max, c->tmp_cfg, c->tmp_z1, c->tmp_out, c->tmp_on, c->tmp_rowinfo, c->rowinfo_id, c->bond_dummy, c->inj_up, c->inj_dn, c->inj_u,
-                  c->acc_mask, c->wg_outpart, c->cnt_alt, c->diag_alt};
-  for (void* q : ptrs) if (q) hipFree(q);
-  c->corr.release(); c->renyi.release(); c->dimer.release(); c->symm.release();
-  for (float* q : {c->sr_ctape, c->sr_cdelta, c->sr_cws, c->sr_cw0, c->sr_cwf, c->sr_cwb, c->sr_cbias}) if (q) hipFree(q);
-  void* sr[] = {c->sr_cfg, c->sr_act, c->sr_delta, c->sr_ws, c->sr_t, c->sr_u, c->sr_x, c->sr_r,
-                c->sr_p, c->sr_q, c->sr_partial, c->sr_sc, c->sr_ones, c->sr_tpart};
-  for (void* q : sr) if (q) hipFree(q);
   if (c->h_stage) hipHostFree(c->h_stage);
-  if (c->d_stage) hipFree(c->d_stage);
-  if (c->d_eval) hipFree(c->d_eval);
-  delete c;
+  delete c;      // every device buffer is a DevBuf: freed here, still on the ctx's device
 }
 
 int vmc_set_bonds(vmc_ctx* c, int32_t n_bonds, const int32_t* ij, const float* j_x, const float* j_z) {
@@ -791,20 +754,23 @@ int vmc_set_bonds(vmc_ctx* c, int32_t n_bonds, const int32_t* ij, const float* j
     qz[k] = 0.25f * j_z[k];    // operators.py:169
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  void* old[] = {c->bonds, c->half_jx, c->quarter_jz, c->rowinfo, c->val};
-  for (void* q : old) if (q) hipFree(q);
+  // the five buffers of a bond list, all or none: the ctx has no bond set (n_bonds 0, null views) from here until the last
+  // allocation and copy have succeeded
+  c->n_bonds = 0;
   c->bonds = nullptr; c->half_jx = c->quarter_jz = c->val = nullptr; c->rowinfo = nullptr;
-  c->n_bonds = n_bonds;
   c->bonds_epoch += 1;
-  HIPCHK(c, dalloc(&c->bonds, n_bonds)); HIPCHK(c, dalloc(&c->half_jx, n_bonds));
-  HIPCHK(c, dalloc(&c->quarter_jz, n_bonds));
-  HIPCHK(c, dalloc(&c->rowinfo, (long long)c->B * n_bonds));
-  HIPCHK(c, dalloc(&c->val, (long long)c->B * n_bonds));
-  HIPCHK(c, hipMemcpy(c->bonds, b.data(), n_bonds * sizeof(int2), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->half_jx, hx.data(), n_bonds * sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->quarter_jz, qz.data(), n_bonds * sizeof(float), hipMemcpyHostToDevice));
   c->list_valid = false;
   c->cnt_valid = false;
+  PROPAGATE(c->ham_bonds.alloc(c, n_bonds, "ham_bonds")); PROPAGATE(c->ham_half_jx.alloc(c, n_bonds, "ham_half_jx"));
+  PROPAGATE(c->ham_quarter_jz.alloc(c, n_bonds, "ham_quarter_jz"));
+  PROPAGATE(c->ham_rowinfo.alloc(c, (long long)c->B * n_bonds, "ham_rowinfo"));
+  PROPAGATE(c->ham_val.alloc(c, (long long)c->B * n_bonds, "ham_val"));
+  HIPCHK(c, hipMemcpy(c->ham_bonds, b.data(), n_bonds * sizeof(int2), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->ham_half_jx, hx.data(), n_bonds * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->ham_quarter_jz, qz.data(), n_bonds * sizeof(float), hipMemcpyHostToDevice));
+  c->bonds = c->ham_bonds; c->half_jx = c->ham_half_jx; c->quarter_jz = c->ham_quarter_jz;
+  c->rowinfo = c->ham_rowinfo; c->val = c->ham_val;
+  c->n_bonds = n_bonds;
   if (c->prod) PROPAGATE(prod_set_bonds(c, n_bonds, ij, j_x, j_z));
   return VMC_OK;
 }
@@ -821,9 +787,9 @@ int vmc_set_adjacency(vmc_ctx* c, int32_t n_sites, int32_t k, const int32_t* adj
   plan_gnn_inverse(n_sites, k, adj, ptr.data(), inv.data());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (!c->gnn_adj) {
-    HIPCHK(c, dalloc(&c->gnn_adj, (long long)n_sites * k));
-    HIPCHK(c, dalloc(&c->gnn_inv_ptr, (long long)n_sites + 1));
-    HIPCHK(c, dalloc(&c->gnn_inv, (long long)n_sites * k));
+    PROPAGATE(c->gnn_adj.alloc(c, (long long)n_sites * k, "gnn_adj"));
+    PROPAGATE(c->gnn_inv_ptr.alloc(c, (long long)n_sites + 1, "gnn_inv_ptr"));
+    PROPAGATE(c->gnn_inv.alloc(c, (long long)n_sites * k, "gnn_inv"));
   }
   HIPCHK(c, hipMemcpy(c->gnn_adj, adj, (size_t)n_sites * k * sizeof(int32_t), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->gnn_inv_ptr, ptr.data(), ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -842,9 +808,9 @@ int vmc_set_lin_tables(vmc_ctx* c, int32_t n_half, const int32_t* top, const int
     if (rc != VMC_OK) return fail(c, rc, msg);
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (!c->ed_bot) HIPCHK(c, dalloc(&c->ed_bot, n_half));
+  if (!c->ed_bot) PROPAGATE(c->ed_bot.alloc(c, n_half, "ed_bot"));
   HIPCHK(c, hipMemcpy(c->ed_bot, bot, (size_t)n_half * sizeof(int32_t), hipMemcpyHostToDevice));
-  if (!c->ed_top) HIPCHK(c, dalloc(&c->ed_top, n_half));      // (set last: gnn_ready takes it as "tables present")
+  if (!c->ed_top) PROPAGATE(c->ed_top.alloc(c, n_half, "ed_top"));      // (set last: gnn_ready takes it as "tables present")
   HIPCHK(c, hipMemcpy(c->ed_top, top, (size_t)n_half * sizeof(int32_t), hipMemcpyHostToDevice));
   c->ps[0].cache_valid = c->ps[1].cache_valid = false;     // (the amplitudes of the chains belong to the previous tables)
   return VMC_OK;
@@ -1048,9 +1014,9 @@ int vmc_synchronize(vmc_ctx* c) {
 int vmc_debug_gemm(vmc_ctx* c, int32_t M, int32_t N, int32_t K, const float* A, int64_t sam, int64_t sak,
                    int64_t a_len, const float* B, int64_t sbk, int64_t sbn, int64_t b_len, float* C) {
   ENTER(c);
-  float *dA = nullptr, *dB = nullptr, *dC = nullptr, *ws = nullptr;
-  HIPCHK(c, dalloc(&dA, a_len)); HIPCHK(c, dalloc(&dB, b_len)); HIPCHK(c, dalloc(&dC, (long long)M * N));
-  HIPCHK(c, dalloc(&ws, 4LL * M * N));
+  DevBuf<float> dA, dB, dC, ws;
+  PROPAGATE(dA.alloc(c, a_len, "dA")); PROPAGATE(dB.alloc(c, b_len, "dB")); PROPAGATE(dC.alloc(c, (long long)M * N, "dC"));
+  PROPAGATE(ws.alloc(c, 4LL * M * N, "ws"));
   HIPCHK(c, hipMemcpy(dA, A, a_len * sizeof(float), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(dB, B, b_len * sizeof(float), hipMemcpyHostToDevice));
   GemmArgs g; memset(&g, 0, sizeof(g));
@@ -1060,7 +1026,6 @@ int vmc_debug_gemm(vmc_ctx* c, int32_t M, int32_t N, int32_t K, const float* A, 
   HIPCHK(c, launch_gemm(c->stream, g));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(C, dC, (long long)M * N * sizeof(float), hipMemcpyDeviceToHost));
-  hipFree(dA); hipFree(dB); hipFree(dC); hipFree(ws);
   return VMC_OK;
 }
 

@@ -27,8 +27,7 @@ static bool cgen_implicit_on() {      // read per call: explicit against implici
 // convolutions all take the band kernel or the implicit gather never allocates it for the forward and the sampler.
 static int cgen_need_A(vmc_ctx* c) {
   if (c->cg_A) return VMC_OK;
-  HIPCHK(c, dalloc(&c->cg_A, c->cg_rows * c->cg.N * plan_cgen_lda(c->cg)));
-  return VMC_OK;
+  return c->cg_A.alloc(c, c->cg_rows * c->cg.N * plan_cgen_lda(c->cg), "cg_A");
 }
 
 // CGS_VMC_CONV_BAND=0: the im2col + GEMM form for every filter count (read per call: A/B tests in one process)
@@ -109,7 +108,7 @@ int cgen_patch_mode(const vmc_ctx* c) {
 int cgen_patch_maps(vmc_ctx* c, int which) {
   const ConvGeom& g = c->cg;
   const long long map_floats = (long long)c->B * g.N * cgen_fp(g);
-  if (!c->cg_pmaps) HIPCHK(c, dalloc(&c->cg_pmaps, g.n_conv * map_floats));
+  if (!c->cg_pmaps) PROPAGATE(c->cg_pmaps.alloc(c, g.n_conv * map_floats, "cg_pmaps"));
   for (long long r0 = 0; r0 < c->B; r0 += c->cg_rows) {
     const long long rows = c->B - r0 < c->cg_rows ? c->B - r0 : c->cg_rows;
     PROPAGATE(cgen_forward(c, which, c->configs, nullptr, rows, nullptr, nullptr, false, nullptr,
@@ -196,20 +195,20 @@ int cgen_forward(vmc_ctx* c, int which, const float* configs, const int2* rowinf
 }
 
 // ---- gradient machinery of the general path, one block of `rows` chains (first chain `row0` of `configs`) at a time
-// buffers of the first gradient call
+// buffers of the first gradient call, all or none: cg_ws, allocated last, tells
 static int cgen_grad_buffers(vmc_ctx* c) {
   const ConvGeom& g = c->cg;
-  if (c->cg_tape) return VMC_OK;
+  if (c->cg_ws) return VMC_OK;
   const int T = g.K * g.KW, n_conv = g.n_conv;
   const long long map_floats = c->cg_rows * g.N * cgen_fp(g);
   const int kmax = T * (n_conv > 1 ? g.F : 1) + 1;                      // rows of the largest weight-gradient product
-  HIPCHK(c, dalloc(&c->cg_tape, (long long)n_conv * map_floats));
-  HIPCHK(c, dalloc(&c->cg_gl, (long long)n_conv * map_floats));
-  HIPCHK(c, dalloc(&c->cg_g[0], map_floats));
-  HIPCHK(c, dalloc(&c->cg_wpos, c->cg_rows * g.N));
-  if (n_conv > 1) HIPCHK(c, dalloc(&c->cg_wt, cgen_off_wt(g, n_conv)));
+  PROPAGATE(c->cg_tape.alloc(c, (long long)n_conv * map_floats, "cg_tape"));
+  PROPAGATE(c->cg_gl.alloc(c, (long long)n_conv * map_floats, "cg_gl"));
+  PROPAGATE(c->cg_g[0].alloc(c, map_floats, "cg_g[0]"));
+  PROPAGATE(c->cg_wpos.alloc(c, c->cg_rows * g.N, "cg_wpos"));
+  if (n_conv > 1) PROPAGATE(c->cg_wt.alloc(c, cgen_off_wt(g, n_conv), "cg_wt"));
   c->cg_ws_floats = (long long)CGEN_SPLITK * 2 * kmax * g.F;
-  HIPCHK(c, dalloc(&c->cg_ws, c->cg_ws_floats));
+  PROPAGATE(c->cg_ws.alloc(c, c->cg_ws_floats, "cg_ws"));
   return VMC_OK;
 }
 static float* cgen_tape(vmc_ctx* c, int l) { return c->cg_tape + (long long)l * c->cg_rows * c->cg.N * cgen_fp(c->cg); }
@@ -359,7 +358,7 @@ int cgen_sr_phase1(vmc_ctx* c, const float* v, int n_rows) {        // sr_t[b] =
   ParamSet& p = c->ps[0];
   PROPAGATE(gnn_ready(c));
   PROPAGATE(cgen_grad_buffers(c));
-  if (!c->cg_td) { HIPCHK(c, dalloc(&c->cg_td, c->cg_rows)); HIPCHK(c, dalloc(&c->cg_centre, 1)); }
+  if (!c->cg_centre) { PROPAGATE(c->cg_td.alloc(c, c->cg_rows, "cg_td")); PROPAGATE(c->cg_centre.alloc(c, 1, "cg_centre")); }
   const int Fp = cgen_fp(g), lda = plan_cgen_lda(g);
   for (int l = 1; l < g.n_conv && plan_cgen_periodic(g); ++l)      // (gnn: the products read theta transposed)
     HIPCHK(c, launch_cgen_pack_t(c->stream, p.theta + cgen_off_w(g, l), g.K * g.KW, g.F, c->cg_wt + cgen_off_wt(g, l)));

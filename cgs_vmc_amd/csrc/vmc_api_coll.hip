@@ -229,13 +229,7 @@ int vmc_debug_allreduce(vmc_ctx* c, void* nccl_comm, int32_t world_size, float* 
   ENTER(c);
   if (c->prod && world_size > 1) return fail(c, VMC_ERR_UNSUPPORTED, "vmc_debug_allreduce with world_size > 1 is not available on a product ctx ('prod')");
   if (!host || n < 1 || (op != VMC_REDUCE_SUM && op != VMC_REDUCE_MAX)) return fail(c, VMC_ERR_INVALID, "bad arguments");
-  if (n > c->d_stage_n) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->d_stage) hipFree(c->d_stage);
-    c->d_stage = nullptr; c->d_stage_n = 0;
-    HIPCHK(c, dalloc(&c->d_stage, n));
-    c->d_stage_n = n;
-  }
+  PROPAGATE(c->d_stage.reserve(c, n, "d_stage"));
   HIPCHK(c, hipMemcpyAsync(c->d_stage, host, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
   PROPAGATE(reduce_buffer(c, nccl_comm, world_size, c->d_stage, n, op));
   HIPCHK(c, hipMemcpyAsync(host, c->d_stage, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));

@@ -119,8 +119,8 @@ int corr_reserve_pass(vmc_ctx* c, long long per) {
   PROPAGATE(m.val.reserve(c, rows, "corr.val", &g[3]));
   PROPAGATE(m.dense.reserve(c, rows, "corr.dense", &g[4]));
   if (!(g[0] || g[1] || g[2] || g[3] || g[4])) return VMC_OK;
-  HIPCHK(c, launch_fill(c->stream, m.hx.p, 1.f, (int)m.hx.cap));      // 0.5 j_x with j_x = 2
-  HIPCHK(c, hipMemsetAsync(m.qz.p, 0, (size_t)m.qz.cap * sizeof(float), c->stream));
+  HIPCHK(c, launch_fill(c->stream, m.hx, 1.f, (int)m.hx.cap));      // 0.5 j_x with j_x = 2
+  HIPCHK(c, hipMemsetAsync(m.qz, 0, (size_t)m.qz.cap * sizeof(float), c->stream));
   return VMC_OK;
 }
 
@@ -139,7 +139,7 @@ int corr_pass(vmc_ctx* c, int which, long long k0, int n, long long n_pairs) {
   PROPAGATE(connected_rows_device(c, which, false));
   Timer t(c, "corr_fold");
   HIPCHK(c, launch_pair_fold(c->stream, c->configs, c->bonds, c->rowinfo, c->val, c->off + c->B, c->B, c->N, n,
-                             c->num_cus, c->corr.dense.p, c->corr.out.p + k0, c->corr.out.p + n_pairs + k0));
+                             c->num_cus, c->corr.dense, c->corr.out + k0, c->corr.out + n_pairs + k0));
   return VMC_OK;
 }
 
@@ -153,8 +153,8 @@ int renyi_reserve(vmc_ctx* c, long long n_regions) {
 // regions [k0, k0 + n): rows, forward, fold
 int renyi_pass(vmc_ctx* c, int which, long long k0, int n, long long n_regions) {
   const ParamSet& p = c->ps[which];
-  const unsigned char* mask = c->renyi.mask.p + k0 * c->N;
-  double* out = c->renyi.out.p;
+  const unsigned char* mask = c->renyi.mask + k0 * c->N;
+  double* out = c->renyi.out;
   const long long rows = (long long)n * c->B;
   {
     Timer t(c, "renyi_rows");
@@ -187,11 +187,11 @@ int dimer_single_pass(vmc_ctx* c, int which, long long a0, int n) {
   const long long rows = (long long)n * c->B;
   {
     Timer t(c, "dimer_rows");
-    HIPCHK(c, launch_dimer_rows1(c->stream, c->configs, m.bonds.p + a0, c->B, c->N, n, c->num_cus, c->tmp_cfg));
+    HIPCHK(c, launch_dimer_rows1(c->stream, c->configs, m.bonds + a0, c->B, c->N, n, c->num_cus, c->tmp_cfg));
   }
   Timer t(c, "dimer_forward");
-  PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, rows, m.logit.p + a0 * c->B,
-                                c->sgn ? m.sign.p + a0 * c->B : c->tmp_sign));
+  PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, rows, m.logit + a0 * c->B,
+                                c->sgn ? m.sign + a0 * c->B : c->tmp_sign));
   return VMC_OK;
 }
 
@@ -202,15 +202,15 @@ int dimer_double_pass(vmc_ctx* c, int which, long long p0, int n, double* dd_out
   const long long rows = (long long)n * c->B;
   {
     Timer t(c, "dimer_rows");
-    HIPCHK(c, launch_dimer_rows2(c->stream, c->configs, m.bonds.p, m.pairs.p + p0, c->B, c->N, n, c->num_cus, c->tmp_cfg));
+    HIPCHK(c, launch_dimer_rows2(c->stream, c->configs, m.bonds, m.pairs + p0, c->B, c->N, n, c->num_cus, c->tmp_cfg));
   }
   {
     Timer t(c, "dimer_forward");
     PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, rows, c->tmp_out, c->tmp_sign));
   }
   Timer t(c, "dimer_fold");
-  HIPCHK(c, launch_dimer_fold(c->stream, c->configs, m.bonds.p, m.pairs.p + p0, p.logit, c->sgn ? p.sign : nullptr,
-                              m.logit.p, c->sgn ? m.sign.p : nullptr, c->tmp_out, c->sgn ? c->tmp_sign : nullptr, c->B,
+  HIPCHK(c, launch_dimer_fold(c->stream, c->configs, m.bonds, m.pairs + p0, p.logit, c->sgn ? p.sign : nullptr,
+                              m.logit, c->sgn ? m.sign : nullptr, c->tmp_out, c->sgn ? c->tmp_sign : nullptr, c->B,
                               c->N, n, dd_out + p0));
   return VMC_OK;
 }
@@ -230,7 +230,7 @@ int symm_pass(vmc_ctx* c, int which, long long k0, int n) {
   const long long rows = (long long)n * c->B;
   {
     Timer t(c, "symm_rows");
-    HIPCHK(c, launch_symm_rows(c->stream, c->configs, m.perm.p + k0 * c->N, m.flip.p + k0, c->B, c->N, n, c->num_cus,
+    HIPCHK(c, launch_symm_rows(c->stream, c->configs, m.perm + k0 * c->N, m.flip + k0, c->B, c->N, n, c->num_cus,
                                c->tmp_cfg));
   }
   {
@@ -239,7 +239,7 @@ int symm_pass(vmc_ctx* c, int which, long long k0, int n) {
   }
   Timer t(c, "symm_fold");
   HIPCHK(c, launch_symm_fold(c->stream, p.logit, c->sgn ? p.sign : nullptr, c->tmp_out, c->sgn ? c->tmp_sign : nullptr,
-                             c->B, n, m.out.p + k0));
+                             c->B, n, m.out + k0));
   return VMC_OK;
 }
 
@@ -268,13 +268,13 @@ int vmc_pair_correlations(vmc_ctx* c, int which, int32_t n_pairs, const int32_t*
     const CorrBufs& m = c->corr;
     const BondSet hamiltonian = current_set(c);
     rc = for_passes(n_pairs, per, rc, [&](long long k0, int n) {
-      install_set(c, BondSet{n, m.pairs.p + k0, m.hx.p, m.qz.p, m.rowinfo.p, m.val.p});
+      install_set(c, BondSet{n, m.pairs + k0, m.hx, m.qz, m.rowinfo, m.val});
       return corr_pass(c, which, k0, n, n_pairs);
     });
     install_set(c, hamiltonian);
   }
   std::vector<double> out;
-  rc = read_back(c, rc, "vmc_pair_correlations", c->corr.out.p, 2 * (size_t)n_pairs, &out);
+  rc = read_back(c, rc, "vmc_pair_correlations", c->corr.out, 2 * (size_t)n_pairs, &out);
   if (rc != VMC_OK) return rc;
   for (int k = 0; k < n_pairs; ++k) {
     if (zz_sum) zz_sum[k] = out[(size_t)k];
@@ -304,7 +304,7 @@ int vmc_renyi2_swap(vmc_ctx* c, int which, int32_t n_regions, const uint8_t* reg
   if (rc == VMC_OK) rc = upload(c, c->renyi.mask.p, mask);
   rc = for_passes(n_regions, per, rc, [&](long long k0, int n) { return renyi_pass(c, which, k0, n, n_regions); });
   std::vector<double> out;
-  rc = read_back(c, rc, "vmc_renyi2_swap", c->renyi.out.p, 2 * (size_t)n_regions, &out);
+  rc = read_back(c, rc, "vmc_renyi2_swap", c->renyi.out, 2 * (size_t)n_regions, &out);
   if (rc != VMC_OK) return rc;
   for (int k = 0; k < n_regions; ++k) {
     if (swap_sum) swap_sum[k] = out[(size_t)k];
@@ -355,13 +355,13 @@ int vmc_dimer_correlations(vmc_ctx* c, int which, int32_t n_bonds, const int32_t
   if (rc == VMC_OK) {
     const ParamSet& p = c->ps[which];
     Timer t(c, "dimer_fold");
-    hipError_t e = launch_dimer_bond_fold(c->stream, c->configs, m.bonds.p, p.logit, c->sgn ? p.sign : nullptr, m.logit.p,
-                                          c->sgn ? m.sign.p : nullptr, c->B, c->N, n_bonds, m.out.p);
+    hipError_t e = launch_dimer_bond_fold(c->stream, c->configs, m.bonds, p.logit, c->sgn ? p.sign : nullptr, m.logit,
+                                          c->sgn ? m.sign : nullptr, c->B, c->N, n_bonds, m.out);
     if (e != hipSuccess) rc = fail(c, VMC_ERR_HIP, std::string("k_dimer_bond_fold: ") + hipGetErrorString(e));
   }
-  rc = for_passes(n_pairs, per2, rc, [&](long long p0, int n) { return dimer_double_pass(c, which, p0, n, m.out.p + n_bonds); });
+  rc = for_passes(n_pairs, per2, rc, [&](long long p0, int n) { return dimer_double_pass(c, which, p0, n, m.out + n_bonds); });
   std::vector<double> out;
-  rc = read_back(c, rc, "vmc_dimer_correlations", m.out.p, (size_t)n_bonds + (size_t)n_pairs, &out);
+  rc = read_back(c, rc, "vmc_dimer_correlations", m.out, (size_t)n_bonds + (size_t)n_pairs, &out);
   if (rc != VMC_OK) return rc;
   for (int a = 0; a < n_bonds && bond_sum; ++a) bond_sum[a] = out[(size_t)a];
   for (int p = 0; p < n_pairs && dd_sum; ++p) dd_sum[p] = out[(size_t)n_bonds + (size_t)p];
@@ -389,7 +389,7 @@ int vmc_symmetry_expectations(vmc_ctx* c, int which, int32_t n_ops, const int32_
   if (rc == VMC_OK) rc = upload(c, c->symm.flip.p, hflip);
   rc = for_passes(n_ops, per, rc, [&](long long k0, int n) { return symm_pass(c, which, k0, n); });
   std::vector<double> out;
-  rc = read_back(c, rc, "vmc_symmetry_expectations", c->symm.out.p, (size_t)n_ops, &out);
+  rc = read_back(c, rc, "vmc_symmetry_expectations", c->symm.out, (size_t)n_ops, &out);
   if (rc != VMC_OK) return rc;
   for (int k = 0; k < n_ops && ratio_sum; ++k) ratio_sum[k] = out[(size_t)k];
   return VMC_OK;

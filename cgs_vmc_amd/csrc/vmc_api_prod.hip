@@ -15,6 +15,21 @@
 
 using namespace vmcapi;
 
+// psi = psi_a psi_b.  The product ctx owns the chains (vmc_ctx::configs); a factor reads them through a device copy in
+// its own `configs` (on_chains tells whether that copy is the chains -- the sampler overwrites it with the candidates).
+// l / s: the factors' logits and signs of the CHAINS, per parameter set; they are what vmc_ctx::ps[which].cache_valid of
+// the product vouches for.  A factor without a sign keeps s = 1; ed_vector keeps psi itself there (its sign is what counts).
+struct ProdState {
+  vmc_ctx* child[2] = {nullptr, nullptr};
+  long long P[2] = {0, 0};
+  bool on_chains = false;
+  bool dead = false;                        // a factor was destroyed while composed (its child[] entry is null): every entry refuses
+  DevBuf<float> l[2][2], s[2][2];           // [which][factor][B]
+  DevBuf<int> iup, idn;                     // [B] the proposal in flight
+  DevBuf<float> u;
+  DevBuf<unsigned> acc_cnt;                 // [B] acceptances of a launch, per chain
+};
+
 namespace vmcapi {
 
 static int prod_alive(vmc_ctx* c) {
@@ -66,12 +81,6 @@ void prod_release(vmc_ctx* c) {
   if (!st) return;
   for (int i = 0; i < 2; ++i)
     if (st->child[i]) { st->child[i]->owner = nullptr; invalidate_configs(st->child[i]); }
-  for (int w = 0; w < 2; ++w)
-    for (int i = 0; i < 2; ++i) {
-      if (st->l[w][i]) hipFree(st->l[w][i]);
-      if (st->s[w][i]) hipFree(st->s[w][i]);
-    }
-  for (void* q : {(void*)st->iup, (void*)st->idn, (void*)st->u, (void*)st->acc_cnt}) if (q) hipFree(q);
   delete st;
   c->prod = nullptr;
 }
@@ -352,28 +361,26 @@ int vmc_create_product(vmc_ctx* a, vmc_ctx* b, vmc_ctx** out) {
   const long long P = a->P + b->P, B = c->B;
 #define CP(expr) do { hipError_t e2 = (expr); if (e2 != hipSuccess) { \
     g_create_error = std::string(#expr) + ": " + hipGetErrorString(e2); vmc_destroy(c); return VMC_ERR_HIP; } } while (0)
-  // everything sized by P: theta of both sets, accumulators, Adam moments, the gradient scratch
-  CP(hipStreamSynchronize(c->stream));
-  for (float** q : {&c->ps[0].theta, &c->ps[1].theta, &c->acc, &c->adam_m, &c->adam_v, &c->grad_tmp}) {
-    if (*q) hipFree(*q);
-    *q = nullptr;
-  }
+#define NEW(buf, n) do { if ((buf).alloc(c, (n), #buf) != VMC_OK) { g_create_error = c->err; vmc_destroy(c); return VMC_ERR_HIP; } } while (0)
+  // everything sized by P, allocated anew (alloc frees what vmc_create put there): theta of both sets, accumulators,
+  // Adam moments, the gradient scratch
   c->P = P;
-  CP(dalloc(&c->ps[0].theta, P)); CP(dalloc(&c->ps[1].theta, P));
-  CP(dalloc(&c->acc, plan_prod_acc_floats(a->P, b->P))); CP(dalloc(&c->adam_m, P)); CP(dalloc(&c->adam_v, P));
-  CP(dalloc(&c->grad_tmp, P));
+  NEW(c->ps[0].theta, P); NEW(c->ps[1].theta, P);
+  NEW(c->acc, plan_prod_acc_floats(a->P, b->P)); NEW(c->adam_m, P); NEW(c->adam_v, P);
+  NEW(c->grad_tmp, P);
   CP(hipMemsetAsync(c->acc, 0, (size_t)plan_prod_acc_floats(a->P, b->P) * sizeof(float), c->stream));
   CP(hipMemsetAsync(c->adam_m, 0, P * sizeof(float), c->stream));
   CP(hipMemsetAsync(c->adam_v, 0, P * sizeof(float), c->stream));
   for (int w = 0; w < 2; ++w)
     for (int i = 0; i < 2; ++i) {
-      CP(dalloc(&st->l[w][i], B)); CP(dalloc(&st->s[w][i], B));
+      NEW(st->l[w][i], B); NEW(st->s[w][i], B);
       CP(hipMemsetAsync(st->l[w][i], 0, B * sizeof(float), c->stream));
       CP(launch_fill(c->stream, st->s[w][i], 1.f, B));          // (a factor without a sign never writes it)
     }
-  CP(dalloc(&st->iup, B)); CP(dalloc(&st->idn, B)); CP(dalloc(&st->u, B)); CP(dalloc(&st->acc_cnt, B));
+  NEW(st->iup, B); NEW(st->idn, B); NEW(st->u, B); NEW(st->acc_cnt, B);
   CP(hipMemsetAsync(st->acc_cnt, 0, B * sizeof(unsigned), c->stream));
   CP(hipStreamSynchronize(c->stream));
+#undef NEW
 #undef CP
   a->owner = c; b->owner = c;
   *out = c;

@@ -4,6 +4,18 @@
 
 using namespace vmcapi;
 
+// The CG vectors of a solve: sized by P, allocated by the first vmc_sr_reserve with a store and kept from then on.  All
+// seven or none: sr_u, which every entry takes as "vmc_sr_reserve has run", is allocated last.
+static int sr_cg_vectors(vmc_ctx* c) {
+  if (c->sr_u) return VMC_OK;
+  const long long P = c->P;
+  PROPAGATE(c->sr_x.alloc(c, P, "sr_x")); PROPAGATE(c->sr_r.alloc(c, P, "sr_r"));
+  PROPAGATE(c->sr_p.alloc(c, P, "sr_p")); PROPAGATE(c->sr_q.alloc(c, P, "sr_q"));
+  PROPAGATE(c->sr_partial.alloc(c, 256, "sr_partial")); PROPAGATE(c->sr_sc.alloc(c, 4, "sr_sc"));
+  HIPCHK(c, hipMemsetAsync(c->sr_x, 0, P * sizeof(float), c->stream));
+  return c->sr_u.alloc(c, P + 1, "sr_u");
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------ stochastic reconfiguration
@@ -19,23 +31,16 @@ int vmc_sr_reserve(vmc_ctx* c, int32_t n_batches) {
   if (n_batches > 0 && c->oact != VMC_ACT_EXP_)
     return fail(c, VMC_ERR_UNSUPPORTED, "stochastic reconfiguration (an extension) covers the exp output activation (every hidden activation)");
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  void* old[] = {c->sr_cfg, c->sr_act, c->sr_delta, c->sr_ws, c->sr_t, c->sr_ones, c->sr_ctape, c->sr_cdelta, c->sr_cws, c->sr_tpart};
-  for (void* q : old) if (q) hipFree(q);
-  c->sr_cfg = c->sr_act = c->sr_delta = c->sr_ws = c->sr_t = c->sr_ones = c->sr_tpart = nullptr;
-  c->sr_ctape = c->sr_cdelta = c->sr_cws = nullptr;
-  c->sr_cap = 0; c->sr_n = 0; c->sr_begun = false;
+  c->sr_cap = 0; c->sr_n = 0; c->sr_begun = false;      // (sr_cap stays 0 until everything below is there)
+  for (DevBuf<float>* q : {&c->sr_cfg, &c->sr_act, &c->sr_delta, &c->sr_ws, &c->sr_t, &c->sr_ones, &c->sr_ctape, &c->sr_cdelta,
+                           &c->sr_cws, &c->sr_tpart}) q->release();
   if (n_batches == 0) return VMC_OK;
-  const long long B = c->B, N = c->N, Hp = c->Hp, L = c->A, P = c->P, R = (long long)n_batches * B;
+  const long long B = c->B, N = c->N, Hp = c->Hp, L = c->A, R = (long long)n_batches * B;
   if (c->conv_general) {       // the chains are all that is stored (cgen_sr_matvec; single-rank solves only)
     if (R * N >= (1LL << 31)) return fail(c, VMC_ERR_UNSUPPORTED, "SR sample store too large (rows * sites >= 2^31)");
-    HIPCHK(c, dalloc(&c->sr_cfg, R * N));
-    HIPCHK(c, dalloc(&c->sr_t, R));
-    if (!c->sr_u) {
-      HIPCHK(c, dalloc(&c->sr_u, P + 1)); HIPCHK(c, dalloc(&c->sr_x, P)); HIPCHK(c, dalloc(&c->sr_r, P));
-      HIPCHK(c, dalloc(&c->sr_p, P)); HIPCHK(c, dalloc(&c->sr_q, P));
-      HIPCHK(c, dalloc(&c->sr_partial, 256)); HIPCHK(c, dalloc(&c->sr_sc, 4));
-      HIPCHK(c, hipMemsetAsync(c->sr_x, 0, P * sizeof(float), c->stream));
-    }
+    PROPAGATE(c->sr_cfg.alloc(c, R * N, "sr_cfg"));
+    PROPAGATE(c->sr_t.alloc(c, R, "sr_t"));
+    PROPAGATE(sr_cg_vectors(c));
     c->sr_cap = n_batches;
     return VMC_OK;
   }
@@ -43,38 +48,28 @@ int vmc_sr_reserve(vmc_ctx* c, int32_t n_batches) {
     const ConvGeom& cg = c->cg;
     const long long CS = cg.CS, nc = cg.n_conv, nl = nc > 1 ? nc - 1 : 1;
     if (R * CS >= (1LL << 31)) return fail(c, VMC_ERR_UNSUPPORTED, "SR sample store too large (rows * feature-map size >= 2^31)");
-    HIPCHK(c, dalloc(&c->sr_cfg, R * N));
-    HIPCHK(c, dalloc(&c->sr_ctape, nl * R * CS)); HIPCHK(c, dalloc(&c->sr_cdelta, nc * R * CS));
-    HIPCHK(c, dalloc(&c->sr_t, R));
+    PROPAGATE(c->sr_cfg.alloc(c, R * N, "sr_cfg"));
+    PROPAGATE(c->sr_ctape.alloc(c, nl * R * CS, "sr_ctape")); PROPAGATE(c->sr_cdelta.alloc(c, nc * R * CS, "sr_cdelta"));
+    PROPAGATE(c->sr_t.alloc(c, R, "sr_t"));
     c->sr_cslices = R < 256 ? (int)R : 256;
-    HIPCHK(c, dalloc(&c->sr_cws, plan_conv_dw_ws_floats(c->cg, c->sr_cslices)));
-    if (!c->sr_cw0) {
-      HIPCHK(c, dalloc(&c->sr_cw0, plan_conv_w0_floats(cg))); HIPCHK(c, dalloc(&c->sr_cwf, plan_conv_wf_floats(cg)));
-      HIPCHK(c, dalloc(&c->sr_cwb, plan_conv_wf_floats(cg))); HIPCHK(c, dalloc(&c->sr_cbias, plan_conv_bias_floats(cg)));
+    PROPAGATE(c->sr_cws.alloc(c, plan_conv_dw_ws_floats(c->cg, c->sr_cslices), "sr_cws"));
+    if (!c->sr_cbias) {      // (the four images of the CG direction, kept: the last allocated tells)
+      PROPAGATE(c->sr_cw0.alloc(c, plan_conv_w0_floats(cg), "sr_cw0")); PROPAGATE(c->sr_cwf.alloc(c, plan_conv_wf_floats(cg), "sr_cwf"));
+      PROPAGATE(c->sr_cwb.alloc(c, plan_conv_wf_floats(cg), "sr_cwb")); PROPAGATE(c->sr_cbias.alloc(c, plan_conv_bias_floats(cg), "sr_cbias"));
     }
-    if (!c->sr_u) {
-      HIPCHK(c, dalloc(&c->sr_u, P + 1)); HIPCHK(c, dalloc(&c->sr_x, P)); HIPCHK(c, dalloc(&c->sr_r, P));
-      HIPCHK(c, dalloc(&c->sr_p, P)); HIPCHK(c, dalloc(&c->sr_q, P));
-      HIPCHK(c, dalloc(&c->sr_partial, 256)); HIPCHK(c, dalloc(&c->sr_sc, 4));
-      HIPCHK(c, hipMemsetAsync(c->sr_x, 0, P * sizeof(float), c->stream));
-    }
+    PROPAGATE(sr_cg_vectors(c));
     c->sr_cap = n_batches;
     return VMC_OK;
   }
   if (R > 0x7fffffffLL / Hp) return fail(c, VMC_ERR_UNSUPPORTED, "SR sample store too large (rows * Hp >= 2^31)");
-  HIPCHK(c, dalloc(&c->sr_cfg, R * N));
-  HIPCHK(c, dalloc(&c->sr_act, L * R * Hp));
-  HIPCHK(c, dalloc(&c->sr_delta, L * R * Hp));
-  HIPCHK(c, dalloc(&c->sr_ws, (long long)sr_wsum_slices((int)R, c->num_cus) * ((N > c->H ? N : c->H) + 1) * c->H));
-  HIPCHK(c, dalloc(&c->sr_t, R)); HIPCHK(c, dalloc(&c->sr_ones, R));
-  HIPCHK(c, dalloc(&c->sr_tpart, L * ((c->H + 255) / 256) * R));
+  PROPAGATE(c->sr_cfg.alloc(c, R * N, "sr_cfg"));
+  PROPAGATE(c->sr_act.alloc(c, L * R * Hp, "sr_act"));
+  PROPAGATE(c->sr_delta.alloc(c, L * R * Hp, "sr_delta"));
+  PROPAGATE(c->sr_ws.alloc(c, (long long)sr_wsum_slices((int)R, c->num_cus) * ((N > c->H ? N : c->H) + 1) * c->H, "sr_ws"));
+  PROPAGATE(c->sr_t.alloc(c, R, "sr_t")); PROPAGATE(c->sr_ones.alloc(c, R, "sr_ones"));
+  PROPAGATE(c->sr_tpart.alloc(c, L * ((c->H + 255) / 256) * R, "sr_tpart"));
   HIPCHK(c, launch_fill(c->stream, c->sr_ones, 1.f, R));
-  if (!c->sr_u) {
-    HIPCHK(c, dalloc(&c->sr_u, P + 1)); HIPCHK(c, dalloc(&c->sr_x, P)); HIPCHK(c, dalloc(&c->sr_r, P));
-    HIPCHK(c, dalloc(&c->sr_p, P)); HIPCHK(c, dalloc(&c->sr_q, P));
-    HIPCHK(c, dalloc(&c->sr_partial, 256)); HIPCHK(c, dalloc(&c->sr_sc, 4));
-    HIPCHK(c, hipMemsetAsync(c->sr_x, 0, P * sizeof(float), c->stream));
-  }
+  PROPAGATE(sr_cg_vectors(c));
   c->sr_cap = n_batches;
   return VMC_OK;
 }
@@ -316,7 +311,7 @@ int vmc_sr_solve_dist(vmc_ctx* c, void* nccl_comm, int32_t world_size, float dia
 
 int vmc_sr_get_solution(vmc_ctx* c, float* x) {
   ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_get_solution)");
-  if (!x || !c->sr_x) return fail(c, VMC_ERR_INVALID, "null / vmc_sr_reserve first");
+  if (!x || !c->sr_u) return fail(c, VMC_ERR_INVALID, "null / vmc_sr_reserve first");
   HIPCHK(c, hipMemcpyAsync(x, c->sr_x, c->P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return VMC_OK;

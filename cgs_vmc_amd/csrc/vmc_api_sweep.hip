@@ -155,9 +155,9 @@ static int run_sweep_cgen(vmc_ctx* c, long long n_steps, bool injected, bool dbg
       a.logit = p.logit; a.iup = c->wide_iup; a.idn = c->wide_idn; a.u = c->wide_u;
       a.accepted = c->d_accepted; a.seed_lo = seed_lo; a.seed_hi = seed_hi; a.chain_offset = c->d.chain_offset;
       a.step0 = step0; a.n_steps = n_steps;
-      unsigned long long* d_prof = nullptr;         // diagnostic: the phase clocks of chain 0 to stderr (synchronises)
+      DevBuf<unsigned long long> d_prof;            // diagnostic: the phase clocks of chain 0 to stderr (synchronises)
       if (getenv("CGS_VMC_CONV_PATCH_PROF") && atoi(getenv("CGS_VMC_CONV_PATCH_PROF")) != 0) {
-        HIPCHK(c, hipMalloc(&d_prof, 6 * sizeof(unsigned long long)));
+        PROPAGATE(d_prof.alloc(c, 6, "d_prof"));
         a.prof = d_prof;
       }
       HIPCHK(c, launch_cgen_patch_sweep(c->stream, a));
@@ -165,7 +165,6 @@ static int run_sweep_cgen(vmc_ctx* c, long long n_steps, bool injected, bool dbg
         unsigned long long h[6];
         HIPCHK(c, hipMemcpyAsync(h, d_prof, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipFree(d_prof);
         fprintf(stderr, "k_cgen_patch_sweep, clocks per step of chain 0: first convolution %.0f, staging %.0f, tiles %.0f, map sum %.0f, "
                 "test + commit %.0f, proposal %.0f\n", (double)h[0] / n_steps, (double)h[1] / n_steps, (double)h[2] / n_steps,
                 (double)h[3] / n_steps, (double)h[4] / n_steps, (double)h[5] / n_steps);
@@ -509,8 +508,8 @@ int vmc_debug_sweep_profile(vmc_ctx* c, int64_t n_steps, double* phase_cycles) {
   const bool tile8 = c->sweep_tile == 8;      // k_sweep8's stamped instantiation (phases: sweep8.hip)
   const int wpg = tile8 ? c->Hp / 32 : c->sweep_waves;
   const int grid = tile8 ? (c->B + 7) / 8 : (c->B + 15) / 16;
-  unsigned long long* d = nullptr;
-  HIPCHK(c, dalloc(&d, (long long)grid * 128));
+  DevBuf<unsigned long long> d;
+  PROPAGATE(d.alloc(c, (long long)grid * 128, "dbg_cycles"));
   HIPCHK(c, hipMemsetAsync(d, 0, (size_t)grid * 128 * sizeof(unsigned long long), c->stream));
   SweepArgs a;
   memset(&a, 0, sizeof(a));
@@ -531,7 +530,6 @@ int vmc_debug_sweep_profile(vmc_ctx* c, int64_t n_steps, double* phase_cycles) {
   std::vector<unsigned long long> h((size_t)grid * 128);
   HIPCHK(c, hipMemcpyAsync(h.data(), d, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  hipFree(d);
   // CGS_VMC_PROFILE_WAVES = bit mask of the waves of a workgroup to average over (diagnostic;
   // default all): waves 0-3 own the chains (proposals, accept, Philox), waves 4-7 do not
   unsigned wave_mask = ~0u;

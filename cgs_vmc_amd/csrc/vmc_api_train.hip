@@ -481,13 +481,7 @@ int vmc_evaluate(vmc_ctx* c, void* nccl_comm, int32_t world_size, int64_t n_eq_s
   if (n_eq_steps < 0 || n_samples < 0 || n_mc_steps < 0) return fail(c, VMC_ERR_INVALID, "negative count");
   if (n_samples > 0 && !means) return fail(c, VMC_ERR_INVALID, "null means");
   if (c->n_bonds <= 0) return fail(c, VMC_ERR_STATE, "bonds not set (vmc_set_bonds)");
-  if (n_samples > c->d_eval_n) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->d_eval) hipFree(c->d_eval);
-    c->d_eval = nullptr; c->d_eval_n = 0;
-    HIPCHK(c, dalloc(&c->d_eval, n_samples));
-    c->d_eval_n = n_samples;
-  }
+  PROPAGATE(c->d_eval.reserve(c, n_samples, "d_eval"));
   PROPAGATE(vmc_mc_steps(c, n_eq_steps, nullptr));                        // evaluation.py:135-136
   PROPAGATE(join_sweep(c));
   // the samplers add their acceptances to the device counter; it is read once, at the end

@@ -16,29 +16,52 @@
 #include <utility>
 #include <vector>
 
+// The owner of one device allocation: every device buffer of a ctx (and every local scratch buffer of an entry point) is a
+// DevBuf, freed by its destructor -- vmc_destroy is `delete c`, no list names the buffers.  It converts to T*, so call
+// sites read like a raw pointer (function templates that deduce T* take .p); kernel argument structs keep raw pointers.
+// alloc(c, n, name): exactly n elements (at least one); whatever was held is freed first, after a synchronisation of the
+// stream (work in flight may read the old buffer).  reserve(c, n, name): grow-only -- a no-op while n <= cap, otherwise
+// alloc; the contents are not kept, `grew` tells.  A failed allocation leaves the buffer empty (cap 0) and names it in
+// the message.  (Definitions: the end of this file.)
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  long long cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+  ~DevBuf() { release(); }
+  operator T*() const { return p; }
+  int alloc(vmc_ctx* c, long long n, const char* name);
+  int reserve(vmc_ctx* c, long long n, const char* name, bool* grew = nullptr);
+  void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
+};
+
 namespace vmcapi {
 
 
 extern std::string g_create_error;   // vmc_api.hip
 
 struct ParamSet {
-  float* theta = nullptr;
-  float *w1p = nullptr, *b1p = nullptr, *bh = nullptr, *p16 = nullptr, *p16t = nullptr,
-        *woutp = nullptr, *bout = nullptr, *won = nullptr;
-  float* z1 = nullptr;     // [B][Hp] cache for the ctx's chains
-  float* onsite = nullptr; // [B] cached x . w_on (RBM)
-  float* logit = nullptr;  // [B]
-  float* sign = nullptr;   // [B] pbdg: sign(det M) of the chains (+-1, 0 singular); psi = sign exp(logit - shift); ed_vector: psi itself
+  DevBuf<float> theta;
+  DevBuf<float> w1p, b1p, bh, p16, p16t,
+        woutp, bout, won;
+  DevBuf<float> z1;     // [B][Hp] cache for the ctx's chains
+  DevBuf<float> onsite; // [B] cached x . w_on (RBM)
+  DevBuf<float> logit;  // [B]
+  DevBuf<float> sign;   // [B] pbdg: sign(det M) of the chains (+-1, 0 singular); psi = sign exp(logit - shift); ed_vector: psi itself
   // psi only: the buffers the NEXT sampler launch writes (see vmc_ctx::configs_alt)
-  float *z1_alt = nullptr, *onsite_alt = nullptr, *logit_alt = nullptr, *sign_alt = nullptr;
-  float* eloc = nullptr;   // [B]
+  DevBuf<float> z1_alt, onsite_alt, logit_alt, sign_alt;
+  DevBuf<float> eloc;   // [B]
   // convolutional ansatz types: fragment images of conv.hpp ConvParams
-  float *cw0 = nullptr, *cwf = nullptr, *cwb = nullptr, *cbias = nullptr;
-  unsigned* p16s = nullptr;   // CGS_VMC_SPLIT_BF16=1: the H x H layers as three bf16 terms (tail_split.hip)
+  DevBuf<float> cw0, cwf, cwb, cbias;
+  DevBuf<unsigned> p16s;   // CGS_VMC_SPLIT_BF16=1: the H x H layers as three bf16 terms (tail_split.hip)
   // bond-difference table of k_tail16 (launch_bond_diff): the differences of the packed w1p / won over the bond
   // list `bdiff_bonds`.  Rebuilt by launch_rows when the image was re-packed (ensure_packed clears bdiff_valid) or
   // another bond list is current (vmc_set_bonds and the spin-correlation passes bump vmc_ctx::bonds_epoch)
-  float *bdiff = nullptr, *bdiff_on = nullptr;
+  DevBuf<float> bdiff, bdiff_on;
   long long bdiff_cap = 0;            // rows allocated
   bool bdiff_valid = false;
   unsigned long long bdiff_epoch = 0; // vmc_ctx::bonds_epoch the table was built at
@@ -58,17 +81,6 @@ using vmcapi::TimedRegion;
 
 struct ProdState;      // vmc_api_prod.hip: what a product ctx keeps beside the members below
 
-// A grow-only device buffer.  reserve(c, n, name): room for n elements (at least one); a no-op while n <= cap, otherwise
-// the stream is synchronised (work in flight may read the old buffer), the buffer freed and a larger one allocated --
-// the contents are not kept, `grew` tells.  A failed allocation leaves the buffer empty (cap 0) and names it in the
-// message.  It never shrinks.  (Definition: the end of this file.)
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  long long cap = 0;
-  int reserve(vmc_ctx* c, long long n, const char* name, bool* grew = nullptr);
-  void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
-};
 // spin correlations: the bond set of a pass of pairs -- swapped with the five Hamiltonian members of the ctx for the
 // pass -- the scatter target, the sums
 struct CorrBufs {
@@ -78,20 +90,17 @@ struct CorrBufs {
   DevBuf<float> val, dense;      // [B pairs per pass] rows; [B][pairs of the pass] the rows by (chain, pair)
   DevBuf<double> out;            // [2][n_pairs] zz sums, exchange sums
   void release_pass() { hx.release(); qz.release(); rowinfo.release(); val.release(); dense.release(); }
-  void release() { pairs.release(); out.release(); release_pass(); }
 };
 // Renyi-2 swap estimator: the region masks of a call and its sums
 struct RenyiBufs {
   DevBuf<unsigned char> mask;    // [n_regions][N] 0/1
   DevBuf<double> out;            // [2][n_regions] swap sums, match counts
-  void release() { mask.release(); out.release(); }
 };
 // symmetry expectation values: the ops of a call and their sums
 struct SymmBufs {
   DevBuf<int> perm;              // [n_ops][N] site permutations
   DevBuf<unsigned char> flip;    // [n_ops] 0/1
   DevBuf<double> out;            // [n_ops] ratio sums
-  void release() { perm.release(); flip.release(); out.release(); }
 };
 // dimer-dimer correlations: the two lists of a call, ln|psi| (and, signed types, the sign) of every single exchange,
 // and the sums
@@ -100,7 +109,6 @@ struct DimerBufs {
   DevBuf<int2> pairs;            // indices (a, b) into bonds
   DevBuf<float> logit, sign;     // [n_bonds][B]; sign: signed types only
   DevBuf<double> out;            // [n_bonds + n_pairs] bond sums, then dd sums
-  void release() { bonds.release(); pairs.release(); logit.release(); sign.release(); out.release(); }
 };
 
 struct vmc_ctx {
@@ -117,8 +125,8 @@ struct vmc_ctx {
   // gradient path factorises psi on the chains into pbdg_inv [B][n][n] / pbdg_pos [B][N] and folds the partial sums
   // of pbdg_slices chain slices (pbdg_ws, double) in slice order
   bool pbdg = false;
-  float* pbdg_inv = nullptr; int* pbdg_pos = nullptr; double* pbdg_ws = nullptr; int pbdg_slices = 1;
-  float* tmp_sign = nullptr;   // [tmp_rows] signs of vmc_amplitude's rows
+  DevBuf<float> pbdg_inv; DevBuf<int> pbdg_pos; DevBuf<double> pbdg_ws; int pbdg_slices = 1;
+  DevBuf<float> tmp_sign;   // [tmp_rows] signs of vmc_amplitude's rows
   // FullyConnectedNNB (nnb.hip): the general dense path (wide && !wide_fast) whose output stage is the pairing layer of a
   // block of nnb_rows rows (nnb_out [nnb_rows][N^2], wbuf[] [nnb_rows][Hp]) and the determinant rows kernel.  sgn: signed
   // amplitudes (pbdg || nnb: sign buffers, the signed ITSWO ratio, Sz = 0 configurations only).  nnb_delta [B][N^2]: the
@@ -126,22 +134,22 @@ struct vmc_ctx {
   // signs of the sampler's candidates; nnb_wg_slices: K slices of the weight-gradient launch
   bool nnb = false, sgn = false;
   long long nnb_rows = 0;
-  float *nnb_out = nullptr, *nnb_delta = nullptr, *nnb_cl = nullptr, *nnb_cs = nullptr;
+  DevBuf<float> nnb_out, nnb_delta, nnb_cl, nnb_cs;
   int nnb_wg_slices = 1;
   // FullVector (edvec.hip): theta is the state vector, ed_top / ed_bot the Lin tables [2^(N/2)] (null until
   // vmc_set_lin_tables).  ParamSet::sign holds the chains' amplitudes themselves (psi, not a sign), logit = ln|psi|,
   // the shift stays 0.  ed_keys / ed_keys_sorted [B], ed_sort_tmp: the gradient scatter's sort (launch_edvec_grad)
   bool edvec = false, ed_tables_lds = false;
-  int *ed_top = nullptr, *ed_bot = nullptr;
-  unsigned long long *ed_keys = nullptr, *ed_keys_sorted = nullptr;
-  void* ed_sort_tmp = nullptr; size_t ed_sort_bytes = 0;
+  DevBuf<int> ed_top, ed_bot;
+  DevBuf<unsigned long long> ed_keys, ed_keys_sorted;
+  DevBuf<unsigned char> ed_sort_tmp; size_t ed_sort_bytes = 0;
   // Conv2DNetwork / ResNet2D (conv.hip).  The dense-ansatz members below keep harmless minimal
   // shapes (H = filters, Hp = 64, no H x H layer); acts_valid tells whether the forward tapes
   // hold the inputs of every convolution for psi on the current chains.
   bool conv = false;
   ConvGeom cg;
   int cG = 1, cGs = 1;     // samples per workgroup pass of the row / backward kernels, of the sampler
-  float *ctape = nullptr, *cdelta = nullptr, *cws = nullptr;
+  DevBuf<float> ctape, cdelta, cws;
   long long ctape_stride = 0, cdelta_stride = 0;
   int c_slices = 64;       // sample slices of the weight-gradient kernel
   // fully_connected with more than 256 hidden units: general path (wide.hip)
@@ -155,56 +163,56 @@ struct vmc_ctx {
   bool split = false;             // CGS_VMC_SPLIT_BF16 >= 1: the row kernel on the BF16 matrix cores (3 x bf16 split, EXPERIMENT)
   bool split_sweep = false;       // CGS_VMC_SPLIT_BF16 == 2: the sampler's H x H layers too (k_sweep16s)
   long long wrows = 0;     // rows of the two activation row buffers
-  float *wbuf[2] = {nullptr, nullptr}, *wide_u = nullptr, *wide_zero = nullptr;
-  double* wide_dot = nullptr;          // [ceil(H / 128)][wrows] row-dot partials of the last H x H layer (GemmArgs epilogue 10)
+  DevBuf<float> wbuf[2], wide_u, wide_zero;
+  DevBuf<double> wide_dot;          // [ceil(H / 128)][wrows] row-dot partials of the last H x H layer (GemmArgs epilogue 10)
   // general convolution path (conv_general.hip; plan.hpp: conv beyond the fused kernels' limits): block buffers
   bool conv_general = false;
   long long cg_rows = 0;                   // row configurations per block (sized by the im2col matrix: the GEMM form, the gradient path)
   long long cg_rows_fwd = 0;               // ... of an untaped forward whose convolutions all run on the band kernel (sized by the two maps)
-  float* cg_A = nullptr;                   // im2col rows [cg_rows * N][plan_cgen_lda]
-  float* cg_fm[2] = {nullptr, nullptr};    // feature maps [cg_rows][N][Fp] (cgen_post: activations; the cosine: pre-activations)
-  double* cg_sum = nullptr;                // [cg_rows] sums of the last map
-  float* cg_zero = nullptr;                // one 0.f (the "b_out" of wide_out_finish)
-  float* cg_lnew = nullptr;                // [B] candidate logits of the sampler
+  DevBuf<float> cg_A;                   // im2col rows [cg_rows * N][plan_cgen_lda]
+  DevBuf<float> cg_fm[2];                // feature maps [cg_rows][N][Fp] (cgen_post: activations; the cosine: pre-activations)
+  DevBuf<double> cg_sum;                // [cg_rows] sums of the last map
+  DevBuf<float> cg_zero;                // one 0.f (the "b_out" of wide_out_finish)
+  DevBuf<float> cg_lnew;                // [B] candidate logits of the sampler
   // the sampler's chain groups (run_sweep_cgen): group 0 on `stream`, the others on streams of their own, so that the
   // partly filled last round of one group's launch runs beside the next launch of another
   hipStream_t cg_grp_stream[3] = {nullptr, nullptr, nullptr};
   hipEvent_t cg_grp_ev[4] = {nullptr, nullptr, nullptr, nullptr};    // [0]: `stream` is ready; [g]: group g has finished
   hipStream_t cg_stream_cur = nullptr;     // the stream cgen_conv / cgen_forward launch on (null: `stream`)
   long long cg_map_row0 = 0;               // first row of cg_fm / cg_A an untaped forward writes (a group's slice)
-  float* cg_pmaps = nullptr;               // [n_conv][B][N][Fp] the chains' maps of every convolution (the patch sampler, conv_patch.hip)
+  DevBuf<float> cg_pmaps;               // [n_conv][B][N][Fp] the chains' maps of every convolution (the patch sampler, conv_patch.hip)
   // ... its gradient path (allocated by the first gradient call): the map of every convolution (the tape), two
   // d logit / d map buffers, per-position weights, the transposed weight images, the split-K workspace
-  float* cg_tape = nullptr; float* cg_gl = nullptr; float* cg_g[2] = {nullptr, nullptr}; float* cg_wpos = nullptr; float* cg_wt = nullptr;
-  float* cg_ws = nullptr; long long cg_ws_floats = 0;
-  double* cg_td = nullptr;                 // [cg_rows] O_b . v of a block (SR)
+  DevBuf<float> cg_tape, cg_gl, cg_g[2], cg_wpos, cg_wt;
+  DevBuf<float> cg_ws; long long cg_ws_floats = 0;
+  DevBuf<double> cg_td;                 // [cg_rows] O_b . v of a block (SR)
   long long cg_sr_tape_rows = 0;           // > 0: cg_tape / cg_gl hold the taped forward and the backward of the first that many STORED chains
                                            // at the parameters of the running solve (one block: kept across its CG iterations)
-  float* cg_centre = nullptr;              // [1] mean of O_b . v over the stored samples (SR)
+  DevBuf<float> cg_centre;              // [1] mean of O_b . v over the stored samples (SR)
   // gnn (cg.graph): the adjacency list [N][k] and its inverse lists (plan_gnn_inverse: [N + 1] offsets, [N k] entries m k + t),
   // set by vmc_set_adjacency; every compute entry of a gnn ctx refuses to run without them (gnn_ready)
-  int* gnn_adj = nullptr; int* gnn_inv_ptr = nullptr; int* gnn_inv = nullptr;
+  DevBuf<int> gnn_adj, gnn_inv_ptr, gnn_inv;
   bool sr_centre = false;                  // the SR matvec may centre its weights: a single-rank solve is running
   bool sr_phase1_done = false;             // vmc_sr_matvec_phase1 has run for the current CG direction (general convolution path)
-  int *wide_iup = nullptr, *wide_idn = nullptr;
+  DevBuf<int> wide_iup, wide_idn;
   int hact = VMC_ACT_RELU_;  // hidden activation (layers.NONLINEARITIES id)
   int oact = VMC_ACT_EXP_;   // output activation; exp: psi = exp(x - shift), else psi = g(x), no shift
-  float* oscale = nullptr;   // [B] (1/psi) d psi / d x of a non-exp output activation
-  float *dact_all = nullptr, *dact_alt = nullptr;   // [L][B][Hp] f'(z) next to act_all (cosine only)
+  DevBuf<float> oscale;   // [B] (1/psi) d psi / d x of a non-exp output activation
+  DevBuf<float> dact_all, dact_alt;   // [L][B][Hp] f'(z) next to act_all (cosine only)
   int n_hh = 0;            // H x H layers: L - 1 (FC) or L (RBM)
   int A = 0;               // activation buffers = n_hh + 1
   ParamLayout lay;
   long long P = 0;
   hipStream_t stream = nullptr;
   ParamSet ps[2];
-  float* configs = nullptr;
+  DevBuf<float> configs;
   // Double-buffered chain state.  A sampler launch reads {configs, z1, logit} and writes
   // {configs_alt, z1_alt, logit_alt, onsite_alt, act_alt}; the two sets are swapped on the host
   // right after the launch.  accumulate(R_t) on `stream` and sweep(R_t -> R_t+1) on
   // `sweep_stream` therefore touch disjoint buffers and run concurrently (training.py:614-617:
   // the two ops of a batch iteration are independent given the chains R_t).
-  float* configs_alt = nullptr;
-  float* act_alt = nullptr;
+  DevBuf<float> configs_alt;
+  DevBuf<float> act_alt;
   int parity = 0;                 // which physical buffer set is current (GEMM tables are per set)
   hipStream_t sweep_stream = nullptr;   // private non-blocking stream of the sampler
   bool overlap = true;            // CGS_VMC_OVERLAP=0: everything on `stream`
@@ -219,19 +227,23 @@ struct vmc_ctx {
   bool expect_sweep = false;      // the previous accumulate was overtaken by a sweep: leave it CUs
   bool acc_since_sweep = false;   // a gradient accumulate may follow: the sampler hands over activations
   // Hamiltonian
+  // the current bond set: non-owning views -- of the Hamiltonian's buffers (ham_*, vmc_set_bonds), or of a
+  // spin-correlation pass's set while that pass runs (install_set, vmc_api_measure.hip)
   int n_bonds = 0;
   int2* bonds = nullptr;
-  float *half_jx = nullptr, *quarter_jz = nullptr;
-  int *cnt = nullptr, *off = nullptr;
-  float *diag = nullptr, *val = nullptr, *offdiag = nullptr;
+  float *half_jx = nullptr, *quarter_jz = nullptr, *val = nullptr;
   int2* rowinfo = nullptr;
-  int2* bond_dummy = nullptr;   // {0,0}: stands in for the bond table before vmc_set_bonds
-  int2* rowinfo_id = nullptr;   // identity list {r, 0} for plain rows (cache refresh)
-  int2* tmp_rowinfo = nullptr;
+  DevBuf<int2> ham_bonds, ham_rowinfo;
+  DevBuf<float> ham_half_jx, ham_quarter_jz, ham_val;
+  DevBuf<int> cnt, off;
+  DevBuf<float> diag, offdiag;
+  DevBuf<int2> bond_dummy;   // {0,0}: stands in for the bond table before vmc_set_bonds
+  DevBuf<int2> rowinfo_id;   // identity list {r, 0} for plain rows (cache refresh)
+  DevBuf<int2> tmp_rowinfo;
   unsigned long long bonds_epoch = 1;   // bumped whenever `bonds` / `n_bonds` name another list (ParamSet::bdiff)
   bool list_valid = false;
   bool cnt_valid = false;          // cnt / diag hold the census of `configs` (left by the sampler's last launch)
-  int* cnt_alt = nullptr; float* diag_alt = nullptr;   // the census the NEXT sampler launch writes (swapped with the chains)
+  DevBuf<int> cnt_alt; DevBuf<float> diag_alt;   // the census the NEXT sampler launch writes (swapped with the chains)
   long long last_rows = 0;
   // the measurements (vmc_api_measure.hip); the rows of a Renyi-2 / dimer pass live in the tmp_* buffers of vmc_amplitude
   CorrBufs corr;
@@ -240,24 +252,24 @@ struct vmc_ctx {
   SymmBufs symm;
   // gradient path
   std::vector<float*> act;   // L views [B][Hp] into act_all
-  float* act_all = nullptr;  // [L][B][Hp]
+  DevBuf<float> act_all;  // [L][B][Hp]
   bool acts_valid = false;   // act[] hold the activations of psi on the current chains
   std::vector<float*> delta;   // L views [B][Hp] into delta_all: d logit / d z_l
-  float* delta_all = nullptr;
-  void* d_batch[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // weight-gradient problem tables [w = eloc / ratio][parity]
+  DevBuf<float> delta_all;
+  DevBuf<unsigned char> d_batch[2][2];   // weight-gradient problem tables [w = eloc / ratio][parity]
   bool batch_ready[2][2] = {{false, false}, {false, false}};
   int wg_tiles = 0;                // MFMA tiles of the weight-gradient launch (plan.hpp)
   bool wg_out_partials = false;    // the output layer's sums come from k_backprop16's partials (OutLayerSums)
-  float* wg_outpart = nullptr;     // [ceil(B / 16)][2][Hp + 4]
-  int* wg_tickets = nullptr;       // [wg_tiles] arrival tickets of the split-K fold, zero between launches
-  float *ratio = nullptr, *ones = nullptr;
-  float *acc = nullptr, *adam_m = nullptr, *adam_v = nullptr, *grad_tmp = nullptr;
+  DevBuf<float> wg_outpart;     // [ceil(B / 16)][2][Hp + 4]
+  DevBuf<int> wg_tickets;       // [wg_tiles] arrival tickets of the split-K fold, zero between launches
+  DevBuf<float> ratio, ones;
+  DevBuf<float> acc, adam_m, adam_v, grad_tmp;
   // reset_gradients does not zero `acc` at once: the first dense accumulate after it WRITES its sums
   // (no 1.3 MB memset + read-modify-write per optimizer step); everything else that touches `acc`
   // materialises the zeros first (acc_zeros)
   bool acc_fresh = false;
   long long adam_t = 0;
-  float* gemm_ws = nullptr;  // partial tiles of the weight-gradient launch: plan_wgrad_ws_floats(wg_tiles, WG_MAX_SPLIT)
+  DevBuf<float> gemm_ws;  // partial tiles of the weight-gradient launch: plan_wgrad_ws_floats(wg_tiles, WG_MAX_SPLIT)
   int num_cus = 256;
   int sweep_waves = 8;       // waves per sweep workgroup at Hp = 256 (CGS_VMC_SWEEP_WAVES=4|8)
   int sweep_no_w1l = 0;      // CGS_VMC_SWEEP_W1L=0: W1 stays in L2 (smaller LDS footprint)
@@ -265,16 +277,16 @@ struct vmc_ctx {
   bool sweep8_ok = false;    // the shape has a k_sweep8
   // stochastic reconfiguration (extension, sr.hip): sample store + CG vectors
   int sr_cap = 0, sr_n = 0, sr_iter = 0;
-  float *sr_cfg = nullptr, *sr_act = nullptr, *sr_delta = nullptr;   // [cap B][N], [L][cap B][Hp] x2
+  DevBuf<float> sr_cfg, sr_act, sr_delta;   // [cap B][N], [L][cap B][Hp] x2
   // convolutional ansatz types: stored tapes / deltas [n_conv-1 | n_conv][cap B][CS], the CG direction
   // packed like a parameter set, and the slices of the weight-gradient kernel over the stored samples
-  float *sr_ctape = nullptr, *sr_cdelta = nullptr, *sr_cws = nullptr;
-  float *sr_cw0 = nullptr, *sr_cwf = nullptr, *sr_cwb = nullptr, *sr_cbias = nullptr;
+  DevBuf<float> sr_ctape, sr_cdelta, sr_cws;
+  DevBuf<float> sr_cw0, sr_cwf, sr_cwb, sr_cbias;
   int sr_cslices = 0;
-  float *sr_ws = nullptr, *sr_t = nullptr, *sr_ones = nullptr;        // [slices][(max(N,H)+1) H], [cap B] x2
-  float* sr_tpart = nullptr;                                          // [layers x column blocks][cap B] partial t
-  float *sr_u = nullptr, *sr_x = nullptr, *sr_r = nullptr, *sr_p = nullptr, *sr_q = nullptr;
-  double *sr_partial = nullptr, *sr_sc = nullptr;
+  DevBuf<float> sr_ws, sr_t, sr_ones;        // [slices][(max(N,H)+1) H], [cap B] x2
+  DevBuf<float> sr_tpart;                                          // [layers x column blocks][cap B] partial t
+  DevBuf<float> sr_u, sr_x, sr_r, sr_p, sr_q;
+  DevBuf<double> sr_partial, sr_sc;
   bool sr_begun = false;
   // collectives over sharded chains: host hook for non-RCCL transports + its staging
   vmc_host_allreduce_fn host_reduce = nullptr;
@@ -282,20 +294,19 @@ struct vmc_ctx {
   int host_reduce_caps = 0;                       // VMC_HOST_REDUCE_CAP_*: what the registered host hook has declared
   vmc_device_allreduce_fn dev_reduce = nullptr;   // in-stream transport of the host's own collective library
   void* dev_reduce_user = nullptr;
-  double* d_eval = nullptr;      // vmc_evaluate: batch sums / means of the samples
-  int d_eval_n = 0;
+  DevBuf<double> d_eval;      // vmc_evaluate: batch sums / means of the samples (grow-only)
   float* h_stage = nullptr;      // pinned
-  float* d_stage = nullptr;      // vmc_debug_allreduce only
-  long long h_stage_n = 0, d_stage_n = 0;
+  DevBuf<float> d_stage;      // vmc_debug_allreduce only
+  long long h_stage_n = 0;
   // scratch
-  unsigned long long* d_accepted = nullptr;
-  double* d_sum = nullptr;
-  float* d_max = nullptr;
-  float *tmp_cfg = nullptr, *tmp_z1 = nullptr, *tmp_out = nullptr, *tmp_on = nullptr;
+  DevBuf<unsigned long long> d_accepted;
+  DevBuf<double> d_sum;
+  DevBuf<float> d_max;
+  DevBuf<float> tmp_cfg, tmp_z1, tmp_out, tmp_on;
   long long tmp_rows = 0;
-  int *inj_up = nullptr, *inj_dn = nullptr;
-  float* inj_u = nullptr;
-  unsigned char* acc_mask = nullptr;
+  DevBuf<int> inj_up, inj_dn;
+  DevBuf<float> inj_u;
+  DevBuf<unsigned char> acc_mask;
   unsigned long long step = 0;
   // timing
   int timing = 0;            // 0 off, 1 every region, 2 the two roofline kernels only
@@ -396,11 +407,6 @@ inline void swap_chain_buffers(vmc_ctx* c) {
   std::swap(c->cnt, c->cnt_alt); std::swap(c->diag, c->diag_alt);
   for (size_t l = 0; l < c->act.size(); ++l) c->act[l] = c->act_all + (long long)l * c->B * c->Hp;
   c->parity ^= 1;
-}
-
-template <typename T>
-hipError_t dalloc(T** p, long long n) {
-  return hipMalloc((void**)p, (size_t)(n > 0 ? n : 1) * sizeof(T));
 }
 
 // Per-kernel timing: event pairs come from a pool (creating two events per region costs more
@@ -529,19 +535,26 @@ int refresh_cache_by_sampler(vmc_ctx* c, int which);
 }  // namespace vmcapi
 
 template <class T>
+int DevBuf<T>::alloc(vmc_ctx* c, long long n, const char* name) {
+  using vmcapi::fail;
+  if (p) HIPCHK(c, hipStreamSynchronize(c->stream));
+  release();
+  if (n < 1) n = 1;
+  const hipError_t e = hipMalloc((void**)&p, (size_t)n * sizeof(T));
+  if (e != hipSuccess) {
+    p = nullptr;
+    return fail(c, VMC_ERR_HIP, std::string("hipMalloc(") + name + "): " + hipGetErrorString(e));
+  }
+  cap = n;
+  return VMC_OK;
+}
+
+template <class T>
 int DevBuf<T>::reserve(vmc_ctx* c, long long n, const char* name, bool* grew) {
   if (grew) *grew = false;
   if (n < 1) n = 1;
   if (n <= cap) return VMC_OK;
-  using vmcapi::fail;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  release();
-  const hipError_t e = vmcapi::dalloc(&p, n);
-  if (e != hipSuccess) {
-    p = nullptr;
-    return fail(c, VMC_ERR_HIP, std::string("dalloc(&c->") + name + "): " + hipGetErrorString(e));
-  }
-  cap = n;
+  PROPAGATE(alloc(c, n, name));
   if (grew) *grew = true;
   return VMC_OK;
 }
