@@ -53,10 +53,15 @@ __device__ bool pb_lists(PbChain& s, int N, int n, int lane) {
 // magnitude, the lowest index among equals); `scale` is this lane's max |M| over the entries it wrote.  Returns
 // sign(det M) (0 when singular -- a pivot below n eps32 max|M| --, s.A is then garbage) and *logit = ln|det M| (-inf
 // when singular).  Every lane returns the same values.
+// Two equal rows of M (two equal rows of F, both sites up) stay equal bit for bit until one of them is the pivot row;
+// the other is then cancelled exactly (its multiplier is 1: `twin` below), so a later pivot search meets a zero column
+// and psi = 0 comes out exactly, as from the oracle's LU.  Through the scaled pivot row the cancellation would leave
+// eps32 |M| per entry, which the remaining steps amplify by about kappa of the other rows: at n = 65 that residue
+// reached the last pivot at 2.5 times the threshold.
 __device__ float pb_eliminate(int n, int ld, PbChain& s, int lane, float scale, float* logit) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) scale = fmaxf(scale, __shfl_xor(scale, m));
-  // a pivot below n eps32 max|M| is rounding noise (two equal rows of F leave residues of about eps32 |F|): singular
+  // a pivot below n eps32 max|M| is rounding noise: singular
   const float tiny = scale * (float)n * 1.1920929e-7f;
   double lsum = 0.0;
   float sg = 1.f;
@@ -87,25 +92,45 @@ __device__ float pb_eliminate(int n, int ld, PbChain& s, int lane, float scale, 
     if (piv < 0.f) sg = -sg;
     lsum += log((double)fabsf(piv));
     const float ip = 1.f / piv;
-    float rk[2];
+    float rk[2], ru[2];                      // the pivot row, scaled by 1 / pivot and as it was
+    unsigned long long twin[2];              // rows whose multiplier is exactly 1 (almost always none)
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int j = lane + 64 * t;
-      rk[t] = 0.f;
+      rk[t] = ru[t] = 0.f;
+      twin[t] = __ballot(j < n && j != k && s.A[j * ld + k] == piv);
       if (j < n) {
-        const float v = (j == k ? 1.f : s.A[k * ld + j]) * ip;
+        ru[t] = j == k ? 1.f : s.A[k * ld + j];
+        const float v = ru[t] * ip;
         s.A[k * ld + j] = v;
         rk[t] = v;
       }
     }
-    for (int i = 0; i < n; ++i) {
-      if (i == k) continue;
-      const float f = s.A[i * ld + k];       // read by every lane before the owner of column k overwrites it
-      __builtin_amdgcn_wave_barrier();
+    if ((twin[0] | twin[1]) == 0ull) {
+      for (int i = 0; i < n; ++i) {
+        if (i == k) continue;
+        const float f = s.A[i * ld + k];     // read by every lane before the owner of column k overwrites it
+        __builtin_amdgcn_wave_barrier();
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int j = lane + 64 * t;
-        if (j < n) s.A[i * ld + j] = fmaf(-f, rk[t], j == k ? 0.f : s.A[i * ld + j]);
+        for (int t = 0; t < 2; ++t) {
+          const int j = lane + 64 * t;
+          if (j < n) s.A[i * ld + j] = fmaf(-f, rk[t], j == k ? 0.f : s.A[i * ld + j]);
+        }
+      }
+    } else {
+      for (int i = 0; i < n; ++i) {
+        if (i == k) continue;
+        const float f = s.A[i * ld + k];
+        const bool same = ((i < 64 ? twin[0] : twin[1]) >> (i & 63)) & 1ull;   // subtract the pivot row as it was
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const int j = lane + 64 * t;
+          if (j < n) {
+            const float v = j == k ? 0.f : s.A[i * ld + j];
+            s.A[i * ld + j] = same ? v - ru[t] : fmaf(-f, rk[t], v);
+          }
+        }
       }
     }
   }

@@ -130,6 +130,32 @@ def local_energy(theta, configs, bonds, j_x, j_z, num_layers, h):
                         dtype=np.float64)
 
 
+def exchange_terms(theta, configs, bonds, j_x, num_layers, h, dtype=np.float64):
+  """terms[b, k] = 0.5 jx_k psi(x_b with bond k exchanged) / psi(x_b) for the antiparallel bonds of row b (zero for the
+  others) as k_nnb_rows forms them: sign' sign exp(logit' - logit) from the two (logit, sign) pairs.  dtype float32: the
+  trunk, the pairing layer, the elimination (pbdg_oracle.eliminate_fp32), the logits and their difference in float32."""
+  x = np.asarray(configs, np.float32)
+  jx = np.broadcast_to(np.asarray(j_x, dtype), (len(bonds),))
+
+  def amplitudes(rows):
+    if dtype is not np.float32:
+      return logit_sign(theta, rows, num_layers, h, dtype)
+    from tests import pbdg_oracle as po
+    res = [po.eliminate_fp32(m)[1:] for m in matrices(theta, rows, num_layers, h, np.float32)]
+    return np.array([r[1] for r in res], np.float32), np.array([r[0] for r in res], np.float32)
+
+  l0, s0 = amplitudes(x)
+  out = np.zeros((x.shape[0], len(bonds)), dtype)
+  for k, (i, j) in enumerate(bonds):
+    live = np.flatnonzero(x[:, i] * x[:, j] < 0)
+    if live.size:
+      new = x[live].copy()
+      new[:, [i, j]] = new[:, [j, i]]
+      l1, s1 = amplitudes(new)
+      out[live, k] = dtype(0.5) * jx[k] * (s1 * s0[live]).astype(dtype) * np.exp((l1 - l0[live]).astype(dtype))
+  return out
+
+
 def energy_gradient_accumulate(acc, theta, configs, bonds, j_x, j_z, num_layers, h):
   """vo.energy_gradient_accumulate (training.py:539-558) on the nnb ansatz, in fp64."""
   e_loc = local_energy(theta, configs, bonds, j_x, j_z, num_layers, h)

@@ -179,3 +179,29 @@ def test_nnb_planner_hostcheck_cases():
   r = subprocess.run(['make', '-s', '-C', os.path.join(ROOT, 'cgs_vmc_amd', 'csrc'), 'hostcheck'],
                      capture_output=True, text=True)
   assert r.returncode == 0, r.stdout + r.stderr
+
+
+@pytest.mark.parametrize('n_sites', [130, 160])
+def test_large_nnb_local_energy_bound_is_measured_and_sharp(n_sites):
+  """The local-energy bound of tests/test_gpu_det_large.py's nnb rows: the stored c is the float32 emulation's
+  (no.exchange_terms: trunk, pairing layer, elimination and logit difference in float32), the fp64 terms sum to
+  no.local_energy, and one term of the wrong sign moves E_loc by more than the bound for at least 90 % of the terms of
+  every row."""
+  from tests import det_large_cases as dc
+  from tests import pbdg_oracle as po
+  l, h = dc.NNB_LAYERS, dc.NNB_UNITS
+  theta, cfg, bonds, jx, jz = dc.nnb_inputs(n_sites)
+  eps = np.finfo(np.float32).eps
+  terms = no.exchange_terms(theta, cfg, bonds, jx, l, h)
+  diag = po.diagonal_energy(cfg, bonds, jz)
+  np.testing.assert_allclose(diag + terms.sum(1), no.local_energy(theta, cfg, bonds, jx, jz, l, h), rtol=1e-9)
+  t32 = no.exchange_terms(theta, cfg, bonds, jx, l, h, np.float32)
+  e32 = po.diagonal_energy(cfg, bonds, jz, np.float32) + t32.sum(1, dtype=np.float32)
+  ratio = (np.abs(e32 - (diag + terms.sum(1))) / (eps * np.abs(terms).sum(1))).max()
+  stored = dc.EMULATED_NNB_ELOC_RATIO[n_sites]
+  assert stored / 2 <= ratio <= 2 * stored, (ratio, stored)
+  bound = dc.nnb_eloc_bound(n_sites, terms, diag)
+  shares = [(2 * np.abs(t[t != 0]) > b).mean() for t, b in zip(terms, bound)]
+  print('nnb N = %d: err / (eps32 sum|terms|) %.3g (stored %.3g); share of terms whose flip exceeds the bound: %s'
+        % (n_sites, ratio, stored, np.round(shares, 3)))
+  assert min(shares) >= 0.9
