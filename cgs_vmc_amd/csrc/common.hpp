@@ -366,7 +366,17 @@ hipError_t launch_symm_rows(hipStream_t s, const float* configs, const int* perm
 hipError_t launch_symm_fold(hipStream_t s, const float* logit, const float* sign, const float* row_logit,
                             const float* row_sign, int B, int n_ops, double* ratio_sum);
 
-// device helpers and the grid rule the Renyi-2, dimer and symmetry kernels share
+// symmetry-projected energies (proj.hip): ops [k0, k0 + n) of a launch (n <= PLAN_PROJ_LAUNCH_OPS; row_logit / row_sign
+// [n][B] their rows) added into the per-chain accumulator acc [n_sectors][B] with the characters chi [n_sectors][n_ops_all],
+// sequential fp64 fmas in ascending k; then the fold over the chains in launch_symm_fold's order into
+// out = [n_sectors] w sums, [n_sectors] w E_loc sums, the E_loc sum, the chains alive.  signs null: unsigned
+hipError_t launch_proj_accum(hipStream_t s, const float* logit, const float* sign, const float* row_logit,
+                             const float* row_sign, const double* chi, int B, int n_sectors, int n_ops_all, int k0, int n,
+                             double* acc);
+hipError_t launch_proj_fold(hipStream_t s, const float* sign, const float* eloc, const double* acc, int B, int n_sectors,
+                            double* out);
+
+// device helpers and the grid rule the Renyi-2, dimer, symmetry and projection kernels share
 // sign of a stored sign / amplitude: +-1, 0 for a vanishing amplitude
 __device__ inline int sgn_of(float v) { return (v > 0.f) - (v < 0.f); }
 // psi(row) / psi(x) from ln|psi| and, signed types, the signs (own_sgn = +-1: the caller has dropped a chain whose own

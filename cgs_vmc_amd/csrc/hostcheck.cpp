@@ -886,10 +886,87 @@ static void symm_ops() {
   CHECK(plan_measure_per_pass(4096, 200, 0, plan_measure_row_limit(100, 256)) == 200);
 }
 
+// vmc_projected_energy: plan_symm_check_hamiltonian on tori with and without next-nearest bonds (the 2-wide torus names
+// its bonds across the short direction twice), the sector tile and the accumulator budget
+static void proj_grid() {
+  char msg[256];
+  struct Lattice { int sx, sy; bool j2; };
+  for (const Lattice& l : {Lattice{4, 4, true}, Lattice{4, 4, false}, Lattice{2, 4, false}, Lattice{8, 1, false}, Lattice{3, 5, true}}) {
+    const int sx = l.sx, sy = l.sy, N = sx * sy;
+    auto site = [&](int x, int y) { return (int32_t)(((x % sx) + sx) % sx + sx * (((y % sy) + sy) % sy)); };
+    std::vector<int32_t> ij;
+    std::vector<float> jx, jz;
+    auto bond = [&](int a, int b, float x, float z) { ij.push_back(a); ij.push_back(b); jx.push_back(x); jz.push_back(z); };
+    for (int y = 0; y < sy; ++y)
+      for (int x = 0; x < sx; ++x) {
+        bond(site(x, y), site(x + 1, y), 1.f, 1.f);
+        if (sy > 1) bond(site(x, y), site(x, y + 1), 1.f, 1.f);
+        if (l.j2) { bond(site(x, y), site(x + 1, y + 1), 0.5f, 0.25f); bond(site(x, y), site(x + 1, y - 1), 0.5f, 0.25f); }
+      }
+    const int nb = (int)jx.size();
+    // the translations, the mirror x -> -x, the inversion; on a square also the rotation and the diagonal mirror
+    std::vector<int32_t> perm;
+    auto op = [&](int a, int b, int c, int d, int tx, int ty) {     // (x, y) -> (a x + b y + tx, c x + d y + ty)
+      for (int y = 0; y < sy; ++y) for (int x = 0; x < sx; ++x) perm.push_back(site(a * x + b * y + tx, c * x + d * y + ty));
+    };
+    for (int ty = 0; ty < sy; ++ty) for (int tx = 0; tx < sx; ++tx) op(1, 0, 0, 1, tx, ty);
+    op(-1, 0, 0, 1, 0, 0); op(-1, 0, 0, -1, 1, 2);
+    if (sx == sy) { op(0, -1, 1, 0, 0, 0); op(0, 1, 1, 0, 3, 1); }
+    const int n_ops = (int)perm.size() / N;
+    CHECK(plan_symm_check_ops(N, n_ops, perm.data(), nullptr, msg, sizeof(msg)) == VMC_OK);
+    CHECK(plan_symm_check_hamiltonian(N, nb, ij.data(), jx.data(), jz.data(), n_ops, perm.data(), msg, sizeof(msg)) == VMC_OK && msg[0] == 0);
+    // one bond's j_x changed: the last translation (it moves both coordinates) is no symmetry any more, the identity is
+    const int hit = nb / 2;
+    const float kept = jx[(size_t)hit];
+    jx[(size_t)hit] = 0.75f;
+    CHECK(plan_symm_check_hamiltonian(N, nb, ij.data(), jx.data(), jz.data(), 1, perm.data(), msg, sizeof(msg)) == VMC_OK);
+    CHECK(plan_symm_check_hamiltonian(N, nb, ij.data(), jx.data(), jz.data(), n_ops, perm.data(), msg, sizeof(msg)) == VMC_ERR_INVALID);
+    CHECK(plan_symm_check_hamiltonian(N, nb, ij.data(), jx.data(), jz.data(), 1, perm.data() + (size_t)(N - 1) * N, msg, sizeof(msg)) == VMC_ERR_INVALID);
+    CHECK(strstr(msg, "op 0 ") == msg && strstr(msg, " bond "));
+    jx[(size_t)hit] = kept;
+    // the exchange of two sites that are no images of each other under the lattice's symmetries
+    if (N > 4) {
+      std::vector<int32_t> two(perm.begin(), perm.begin() + 2 * N);
+      std::swap(two[(size_t)N + 0], two[(size_t)N + 1]);
+      CHECK(plan_symm_check_ops(N, 2, two.data(), nullptr, msg, sizeof(msg)) == VMC_OK);
+      CHECK(plan_symm_check_hamiltonian(N, nb, ij.data(), jx.data(), jz.data(), 2, two.data(), msg, sizeof(msg)) == VMC_ERR_INVALID);
+      CHECK(strstr(msg, "op 1 ") == msg);
+    }
+    // the multiset: one of a doubled pair of bonds dropped is noticed where a set would not
+    if (sx == 2) {
+      std::vector<int32_t> ij1(ij.begin() + 2, ij.end());
+      CHECK(plan_symm_check_hamiltonian(N, nb - 1, ij1.data(), jx.data() + 1, jz.data() + 1, n_ops, perm.data(), msg, sizeof(msg)) == VMC_ERR_INVALID);
+    }
+    CHECK(plan_symm_check_hamiltonian(N, 0, ij.data(), jx.data(), jz.data(), n_ops, perm.data(), msg, sizeof(msg)) == VMC_ERR_INVALID);
+    CHECK(plan_symm_check_hamiltonian(N, nb, ij.data(), jx.data(), jz.data(), n_ops, nullptr, msg, sizeof(msg)) == VMC_ERR_INVALID);
+    ij[1] = N;
+    CHECK(plan_symm_check_hamiltonian(N, nb, ij.data(), jx.data(), jz.data(), n_ops, perm.data(), msg, sizeof(msg)) == VMC_ERR_INVALID);
+  }
+  for (long long n_sectors : {1LL, 2LL, 15LL, 16LL, 17LL, 104LL, 1LL << 20})
+    for (long long ops : {1LL, 7LL, 200LL, (long long)PLAN_PROJ_LAUNCH_OPS}) {
+      const int tile = plan_measure_sector_tile(n_sectors, ops);
+      CHECK(tile >= 1 && tile <= PLAN_PROJ_MAX_TILE && tile <= n_sectors);
+      CHECK(plan_proj_accum_lds_bytes(tile, (int)ops) <= PLAN_PROJ_LDS_BYTES);
+      const long long tiles = plan_proj_sector_tiles(n_sectors, tile);
+      CHECK(tiles * tile >= n_sectors && (tiles - 1) * tile < n_sectors);
+      for (long long B : {1LL, 40LL, 200LL, 256LL, 257LL, 4096LL})
+        if (plan_proj_acc_ok(B, n_sectors)) {
+          const long long blocks = plan_proj_chain_blocks(B);
+          CHECK(blocks * PLAN_PROJ_THREADS >= B && (blocks - 1) * PLAN_PROJ_THREADS < B);
+          CHECK(blocks * tiles <= 0x7fffffffLL);                         // the one-dimensional grid
+          CHECK(n_sectors * B <= PLAN_PROJ_MAX_ACC);
+        }
+    }
+  CHECK(plan_measure_sector_tile(0, 1) == 0 && plan_measure_sector_tile(1, 0) == 0);
+  CHECK(plan_measure_sector_tile(104, 200) == 16 && plan_measure_sector_tile(3, 200) == 3);
+  CHECK(plan_proj_acc_ok(4096, 104) && plan_proj_acc_ok(1, 1LL << 26) && !plan_proj_acc_ok(2, 1LL << 26) && !plan_proj_acc_ok(4096, 0) && !plan_proj_acc_ok(0, 1));
+}
+
 int main() {
   check_block_maps();
   measure_grid();
   symm_ops();
+  proj_grid();
   prod_grid();
   edvec_grid();
   nnb_grid();

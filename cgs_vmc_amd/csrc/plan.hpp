@@ -12,6 +12,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "../../include/cgsvmc.h"
@@ -637,7 +638,7 @@ inline int plan_prod_child_check(int ansatz, int output_activation, bool is_prod
   return VMC_ERR_UNSUPPORTED;
 }
 
-// ------------------------------------------------------------------------------- the measurements (vmc_api_measure.hip; corr.hip, renyi.hip, dimer.hip, symm.hip)
+// ------------------------------------------------------------------------------- the measurements (vmc_api_measure.hip; corr.hip, renyi.hip, dimer.hip, symm.hip, proj.hip)
 // A measurement runs its items -- pairs of sites, regions, bonds, pairs of bonds -- in passes; a pass is B rows per item
 // (row = item x B + chain): for the spin correlations a bond set of its own (bonds, couplings, rowinfo / val) plus the
 // dense [B][pairs] scatter target, for the others rows handed to the family's full forward.  Rows of a pass: the budget
@@ -709,6 +710,93 @@ inline int plan_symm_check_ops(int N, int n_ops, const int32_t* perm, const uint
         return VMC_ERR_INVALID;
       }
       seen[(size_t)g[i]] = 1;
+    }
+  }
+  return VMC_OK;
+}
+
+// Symmetry-projected energies (vmc_projected_energy; proj.hip).  The per-chain accumulator acc [n_sectors][B] (fp64,
+// sector major) is bounded by PLAN_PROJ_MAX_ACC doubles (512 MiB).  k_proj_accum takes the ops of a pass in launches of
+// at most PLAN_PROJ_LAUNCH_OPS ops; a workgroup stages the characters of its sector tile for the launch's ops in LDS
+// ([ops][tile] doubles) and a thread keeps the tile's accumulators of its chain in registers, hence at most
+// PLAN_PROJ_MAX_TILE sectors per tile, fewer where the launch's ops would not fit PLAN_PROJ_LDS_BYTES (several
+// workgroups per CU).  0: an argument out of range, or not even one sector fits.
+#define PLAN_PROJ_MAX_ACC (1LL << 26)
+#define PLAN_PROJ_MAX_TILE 16
+#define PLAN_PROJ_LAUNCH_OPS 256
+#define PLAN_PROJ_LDS_BYTES ((size_t)32 * 1024)
+#define PLAN_PROJ_THREADS 256             // chains per workgroup of k_proj_accum
+inline bool plan_proj_acc_ok(long long B, long long n_sectors) {
+  return B >= 1 && n_sectors >= 1 && n_sectors <= PLAN_PROJ_MAX_ACC / B;
+}
+inline int plan_measure_sector_tile(long long n_sectors, long long ops_per_launch) {
+  if (n_sectors < 1 || ops_per_launch < 1) return 0;
+  long long tile = (long long)(PLAN_PROJ_LDS_BYTES / sizeof(double)) / ops_per_launch;
+  if (tile > PLAN_PROJ_MAX_TILE) tile = PLAN_PROJ_MAX_TILE;
+  if (tile > n_sectors) tile = n_sectors;
+  return (int)tile;
+}
+inline size_t plan_proj_accum_lds_bytes(int tile, int ops) { return (size_t)tile * (size_t)ops * sizeof(double); }
+inline unsigned plan_proj_chain_blocks(long long B) { return (unsigned)((B + PLAN_PROJ_THREADS - 1) / PLAN_PROJ_THREADS); }
+inline unsigned plan_proj_sector_tiles(long long n_sectors, int tile) { return tile < 1 ? 0u : (unsigned)((n_sectors + tile - 1) / tile); }
+
+// Are the ops symmetries of the Hamiltonian sum_b j_x[b] (S+S- + S-S+) / 2 + j_z[b] SzSz over the bonds ij [n_bonds][2]?
+// Op k maps bond (i, j) to (perm_k[i], perm_k[j]); it is a symmetry when the multiset of (unordered pair, bits of j_x, bits
+// of j_z) over the bonds is the one it started as (a multiset: the 2-wide torus names a bond twice).  Invariance under
+// perm_k and under its inverse are the same statement, so the row convention of the ops does not matter; the global flip
+// is a symmetry of every XXZ bond and is not asked about.  perm: bijections (plan_symm_check_ops first).  VMC_OK, or
+// VMC_ERR_INVALID with the op and the first bond whose image is missing named in msg.
+struct PlanBondKey {
+  int32_t lo, hi; uint32_t jx, jz; int32_t bond;
+  bool same(const PlanBondKey& o) const { return lo == o.lo && hi == o.hi && jx == o.jx && jz == o.jz; }
+  bool before(const PlanBondKey& o) const {
+    if (lo != o.lo) return lo < o.lo;
+    if (hi != o.hi) return hi < o.hi;
+    if (jx != o.jx) return jx < o.jx;
+    if (jz != o.jz) return jz < o.jz;
+    return bond < o.bond;
+  }
+};
+inline void plan_bond_key_sort(std::vector<PlanBondKey>& v) {
+  std::sort(v.begin(), v.end(), [](const PlanBondKey& a, const PlanBondKey& b) { return a.before(b); });
+}
+inline int plan_symm_check_hamiltonian(int N, int n_bonds, const int32_t* ij, const float* jx, const float* jz, int n_ops,
+                                       const int32_t* perm, char* msg, size_t msg_len) {
+  if (msg_len) msg[0] = 0;
+  if (N < 1 || n_bonds < 1 || n_ops < 1 || !ij || !jx || !jz || !perm) {
+    snprintf(msg, msg_len, "bad Hamiltonian symmetry arguments");
+    return VMC_ERR_INVALID;
+  }
+  auto key = [&](int b, int32_t i, int32_t j) {
+    PlanBondKey k;
+    k.lo = i < j ? i : j; k.hi = i < j ? j : i; k.bond = b;
+    memcpy(&k.jx, jx + b, sizeof(uint32_t)); memcpy(&k.jz, jz + b, sizeof(uint32_t));
+    return k;
+  };
+  std::vector<PlanBondKey> base((size_t)n_bonds), image((size_t)n_bonds);
+  for (int b = 0; b < n_bonds; ++b) {
+    if (ij[2 * b] < 0 || ij[2 * b] >= N || ij[2 * b + 1] < 0 || ij[2 * b + 1] >= N) {
+      snprintf(msg, msg_len, "bond %d = (%d, %d) names no two sites in 0 .. %d", b, (int)ij[2 * b], (int)ij[2 * b + 1], N - 1);
+      return VMC_ERR_INVALID;
+    }
+    base[(size_t)b] = key(b, ij[2 * b], ij[2 * b + 1]);
+  }
+  plan_bond_key_sort(base);
+  for (int k = 0; k < n_ops; ++k) {
+    const int32_t* g = perm + (size_t)k * (size_t)N;
+    for (int b = 0; b < n_bonds; ++b) image[(size_t)b] = key(b, g[ij[2 * b]], g[ij[2 * b + 1]]);
+    plan_bond_key_sort(image);
+    int bad = -1;                         // the lowest bond whose image has no partner left in the original multiset
+    size_t p = 0;
+    for (size_t q = 0; q < image.size(); ++q) {
+      while (p < base.size() && !image[q].same(base[p]) && base[p].before(image[q])) ++p;
+      if (p < base.size() && image[q].same(base[p])) { ++p; continue; }
+      if (bad < 0 || image[q].bond < bad) bad = image[q].bond;
+    }
+    if (bad >= 0) {
+      snprintf(msg, msg_len, "op %d is no symmetry of the Hamiltonian: bond %d = (%d, %d) goes to (%d, %d), which is no bond with its couplings",
+               k, bad, (int)ij[2 * bad], (int)ij[2 * bad + 1], (int)g[ij[2 * bad]], (int)g[ij[2 * bad + 1]]);
+      return VMC_ERR_INVALID;
     }
   }
   return VMC_OK;

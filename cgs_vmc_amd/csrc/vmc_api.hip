@@ -2,7 +2,7 @@
 // work on ctx->stream.  This file: ctx life cycle, parameters, chains, amplitudes, local energies, timing; the other
 // entry points live in vmc_api_sweep.hip (samplers), vmc_api_train.hip (accumulators, Adam, epochs, evaluation),
 // vmc_api_coll.hip (collectives), vmc_api_sr.hip (stochastic reconfiguration), vmc_api_measure.hip (the measurements
-// beside the energy: spin correlations, Renyi-2 entropy, dimer-dimer correlations, symmetry expectation values), vmc_api_prod.hip (product ctxs);
+// beside the energy: spin correlations, Renyi-2 entropy, dimer-dimer correlations, symmetry expectation values, symmetry-projected energies), vmc_api_prod.hip (product ctxs);
 // vmc_api_cgen.hip is the general convolution path's machinery.  Shared state and helpers: vmc_ctx.hpp.
 #include "vmc_ctx.hpp"
 
@@ -758,6 +758,8 @@ int vmc_set_bonds(vmc_ctx* c, int32_t n_bonds, const int32_t* ij, const float* j
   // allocation and copy have succeeded
   c->n_bonds = 0;
   c->bonds = nullptr; c->half_jx = c->quarter_jz = c->val = nullptr; c->rowinfo = nullptr;
+  c->ham_ij.assign(ij, ij + 2 * (size_t)n_bonds);
+  c->ham_jx.assign(j_x, j_x + n_bonds); c->ham_jz.assign(j_z, j_z + n_bonds);
   c->bonds_epoch += 1;
   c->list_valid = false;
   c->cnt_valid = false;

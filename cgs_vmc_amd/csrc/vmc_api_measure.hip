@@ -1,8 +1,8 @@
 // The measurements over the ctx's current chains (extensions, no reference counterpart): vmc_pair_correlations,
-// vmc_renyi2_swap, vmc_dimer_correlations and vmc_symmetry_expectations.  Each is a pure measurement: chains, step counter, accumulators, the
+// vmc_renyi2_swap, vmc_dimer_correlations, vmc_symmetry_expectations and vmc_projected_energy.  Each is a pure measurement: chains, step counter, accumulators, the
 // Hamiltonian's bond set and the validity of the amplitude and activation caches are as before when it returns.
 //
-// One scaffold serves the four.  MEASURE_GATE is the shared front of the refusals; PureMeasurement records which caches
+// One scaffold serves the five.  MEASURE_GATE is the shared front of the refusals; PureMeasurement records which caches
 // were valid and un-vouches on every way out for those that were not; upload copies a host list into its device buffer;
 // for_passes walks the items in passes of plan_measure_per_pass (plan.hpp); read_back brings the fp64 sums down and
 // synchronises, on a failed call too.  The device buffers are the grow-only DevBufs of vmc_ctx.hpp.  What differs per
@@ -35,6 +35,15 @@
 // pass of ops is B rows per op in the row buffer of vmc_amplitude (symm.hip: k_symm_rows), evaluated by the family's own
 // full forward and folded per op (k_symm_fold) against the chains' cached ln|psi| and signs.  Every perm_k is checked
 // to be a bijection before anything is launched (plan_symm_check_ops): the rows must stay at Sz = 0.
+//
+// Symmetry-projected energies.  The ops of the symmetry expectation values and, per sector s, real characters chi[s][k]:
+// w_s(c) = sum_k chi[s][k] psi(row_{k,c}) / psi(x_c), and the host forms E_s = sum_c w_s(c) E_loc(c) / sum_c w_s(c), the
+// energy of P_s psi.  One local-energy call first (it uses the row buffers the passes then take), then the passes of the
+// symmetry expectation values with k_proj_accum (proj.hip) in the fold's place: it adds a pass's ops into the per-chain
+// fp64 accumulator [n_sectors][B]; k_proj_fold folds the chains at the end.  Beside the bijection check every perm_k is
+// checked to map the Hamiltonian's bonds onto themselves, couplings included (plan_symm_check_hamiltonian): the
+// estimator means nothing otherwise.  What a vmc_local_energy call leaves behind (the chains' local energies of `which`,
+// vmc_last_connected_rows) is the one thing this measurement changes.
 #include "vmc_ctx.hpp"
 
 using namespace vmcapi;
@@ -243,6 +252,41 @@ int symm_pass(vmc_ctx* c, int which, long long k0, int n) {
   return VMC_OK;
 }
 
+// ---- symmetry-projected energies (the ops are the symmetry expectation values': c->symm.perm / flip)
+
+int proj_reserve(vmc_ctx* c, long long n_ops, long long n_sectors) {
+  PROPAGATE(c->symm.perm.reserve(c, n_ops * c->N, "symm.perm"));
+  PROPAGATE(c->symm.flip.reserve(c, n_ops, "symm.flip"));
+  PROPAGATE(c->proj.chi.reserve(c, n_sectors * n_ops, "proj.chi"));
+  PROPAGATE(c->proj.acc.reserve(c, n_sectors * c->B, "proj.acc"));
+  return c->proj.out.reserve(c, 2 * n_sectors + 2, "proj.out");
+}
+
+// ops [k0, k0 + n): rows, forward, then their terms into the per-chain accumulator, PLAN_PROJ_LAUNCH_OPS ops a launch
+int proj_pass(vmc_ctx* c, int which, long long k0, int n, int n_ops, int n_sectors) {
+  const ParamSet& p = c->ps[which];
+  const SymmBufs& m = c->symm;
+  const long long rows = (long long)n * c->B;
+  {
+    Timer t(c, "proj_rows");
+    HIPCHK(c, launch_symm_rows(c->stream, c->configs, m.perm + k0 * c->N, m.flip + k0, c->B, c->N, n, c->num_cus,
+                               c->tmp_cfg));
+  }
+  {
+    Timer t(c, "proj_forward");
+    PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, rows, c->tmp_out, c->tmp_sign));
+  }
+  Timer t(c, "proj_accum");
+  for (int j0 = 0; j0 < n; j0 += PLAN_PROJ_LAUNCH_OPS) {
+    const int nj = n - j0 < PLAN_PROJ_LAUNCH_OPS ? n - j0 : PLAN_PROJ_LAUNCH_OPS;
+    const long long at = (long long)j0 * c->B;
+    HIPCHK(c, launch_proj_accum(c->stream, p.logit, c->sgn ? p.sign : nullptr, c->tmp_out + at,
+                                c->sgn ? c->tmp_sign + at : nullptr, c->proj.chi, c->B, n_sectors, n_ops, (int)k0 + j0, nj,
+                                c->proj.acc));
+  }
+  return VMC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -392,6 +436,73 @@ int vmc_symmetry_expectations(vmc_ctx* c, int which, int32_t n_ops, const int32_
   rc = read_back(c, rc, "vmc_symmetry_expectations", c->symm.out, (size_t)n_ops, &out);
   if (rc != VMC_OK) return rc;
   for (int k = 0; k < n_ops && ratio_sum; ++k) ratio_sum[k] = out[(size_t)k];
+  return VMC_OK;
+}
+
+int vmc_projected_energy(vmc_ctx* c, int which, int32_t n_ops, const int32_t* perm, const uint8_t* flip,
+                         int32_t n_sectors, const double* chi, int32_t ops_per_pass, double* w_sum, double* we_sum,
+                         double* e_sum, int64_t* n_alive) {
+  MEASURE_GATE(c, which, "vmc_projected_energy");
+  if (n_ops < 1 || !perm || ops_per_pass < 0) return fail(c, VMC_ERR_INVALID, "bad symmetry op arguments");
+  char msg[256];
+  if (plan_symm_check_ops(c->N, n_ops, perm, flip, msg, sizeof(msg)) != VMC_OK) return fail(c, VMC_ERR_INVALID, msg);
+  if (n_sectors < 1 || !chi) return fail(c, VMC_ERR_INVALID, "bad sector arguments: n_sectors >= 1 and the characters chi [n_sectors][n_ops] required");
+  if (!plan_proj_acc_ok(c->B, n_sectors)) {
+    snprintf(msg, sizeof(msg), "n_sectors x batch_size = %lld beyond the accumulator budget of 2^26 doubles", (long long)n_sectors * c->B);
+    return fail(c, VMC_ERR_UNSUPPORTED, msg);
+  }
+  for (size_t e = 0; e < (size_t)n_sectors * (size_t)n_ops; ++e)
+    if (!std::isfinite(chi[e])) {
+      snprintf(msg, sizeof(msg), "sector %d: the character of op %d is not finite", (int)(e / (size_t)n_ops), (int)(e % (size_t)n_ops));
+      return fail(c, VMC_ERR_INVALID, msg);
+    }
+  if (!c->sgn && c->oact != VMC_ACT_EXP_)
+    return fail(c, VMC_ERR_UNSUPPORTED, "vmc_projected_energy needs the exp output activation (the logit is ln psi only then)");
+  const int per = plan_measure_per_pass(c->B, n_ops, ops_per_pass, plan_measure_row_limit(c->N, c->Hp));
+  if (per < 1) return fail(c, VMC_ERR_UNSUPPORTED, "batch_size does not leave room for one op in the 32-bit row index");
+  if (c->n_bonds <= 0) return fail(c, VMC_ERR_STATE, "bonds not set (vmc_set_bonds)");
+  if (plan_symm_check_hamiltonian(c->N, c->n_bonds, c->ham_ij.data(), c->ham_jx.data(), c->ham_jz.data(), n_ops, perm, msg,
+                                  sizeof(msg)) != VMC_OK)
+    return fail(c, VMC_ERR_INVALID, msg);
+  const std::vector<int> hperm(perm, perm + (size_t)n_ops * (size_t)c->N);
+  std::vector<unsigned char> hflip((size_t)n_ops, 0);
+  if (flip) hflip.assign(flip, flip + n_ops);
+  const std::vector<double> hchi(chi, chi + (size_t)n_sectors * (size_t)n_ops);
+  PureMeasurement pure(c);
+  ProjBufs& m = c->proj;
+  int rc = ensure_cache(c, which);           // ln|psi(x_c)| and the signs, as the local energies take them
+  if (rc == VMC_OK) {
+    Timer t(c, "proj_eloc");                 // first: its rows go through the buffers the passes then take
+    rc = local_energy_device(c, which);
+  }
+  if (rc == VMC_OK) rc = proj_reserve(c, n_ops, n_sectors);
+  if (rc == VMC_OK) rc = grow_tmp(c, (long long)per * c->B);
+  if (rc == VMC_OK) rc = upload(c, c->symm.perm.p, hperm);
+  if (rc == VMC_OK) rc = upload(c, c->symm.flip.p, hflip);
+  if (rc == VMC_OK) rc = upload(c, m.chi.p, hchi);
+  if (rc == VMC_OK) {
+    hipError_t e = hipMemsetAsync(m.acc, 0, (size_t)n_sectors * (size_t)c->B * sizeof(double), c->stream);
+    if (e != hipSuccess) rc = fail(c, VMC_ERR_HIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
+  }
+  rc = for_passes(n_ops, per, rc, [&](long long k0, int n) { return proj_pass(c, which, k0, n, n_ops, n_sectors); });
+  int cnt_total = 0;
+  if (rc == VMC_OK) {
+    const ParamSet& p = c->ps[which];
+    Timer t(c, "proj_fold");
+    hipError_t e = launch_proj_fold(c->stream, c->sgn ? p.sign : nullptr, p.eloc, m.acc, c->B, n_sectors, m.out);
+    if (e == hipSuccess) e = hipMemcpyAsync(&cnt_total, c->off + c->B, sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) rc = fail(c, VMC_ERR_HIP, std::string("k_proj_fold: ") + hipGetErrorString(e));
+  }
+  std::vector<double> out;
+  rc = read_back(c, rc, "vmc_projected_energy", m.out, 2 * (size_t)n_sectors + 2, &out);
+  if (rc != VMC_OK) return rc;
+  c->last_rows = cnt_total;                  // (as vmc_local_energy leaves it)
+  for (int s = 0; s < n_sectors; ++s) {
+    if (w_sum) w_sum[s] = out[(size_t)s];
+    if (we_sum) we_sum[s] = out[(size_t)n_sectors + (size_t)s];
+  }
+  if (e_sum) *e_sum = out[2 * (size_t)n_sectors];
+  if (n_alive) *n_alive = (int64_t)out[2 * (size_t)n_sectors + 1];
   return VMC_OK;
 }
 

@@ -102,6 +102,12 @@ struct SymmBufs {
   DevBuf<unsigned char> flip;    // [n_ops] 0/1
   DevBuf<double> out;            // [n_ops] ratio sums
 };
+// symmetry-projected energies: the characters of a call, the per-chain accumulator and the sums (the ops live in SymmBufs)
+struct ProjBufs {
+  DevBuf<double> chi;            // [n_sectors][n_ops]
+  DevBuf<double> acc;            // [n_sectors][B] w_s(c), sector major
+  DevBuf<double> out;            // [n_sectors] w sums, [n_sectors] w E_loc sums, the E_loc sum, the chains alive
+};
 // dimer-dimer correlations: the two lists of a call, ln|psi| (and, signed types, the sign) of every single exchange,
 // and the sums
 struct DimerBufs {
@@ -250,6 +256,10 @@ struct vmc_ctx {
   RenyiBufs renyi;
   DimerBufs dimer;
   SymmBufs symm;
+  ProjBufs proj;
+  // the Hamiltonian as vmc_set_bonds was given it (vmc_projected_energy asks whether its ops are symmetries of it)
+  std::vector<int32_t> ham_ij;
+  std::vector<float> ham_jx, ham_jz;
   // gradient path
   std::vector<float*> act;   // L views [B][Hp] into act_all
   DevBuf<float> act_all;  // [L][B][Hp]

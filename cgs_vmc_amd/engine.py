@@ -390,6 +390,29 @@ class VmcEngine:
                                                     out.ctypes.data_as(C.POINTER(C.c_double))))
     return out
 
+  def projected_energy(self, perms, flips, characters, which: int = _hip.VMC_PSI, ops_per_pass: int = 0):
+    """Symmetry-projected energies over the current chains (extension, vmc_projected_energy).  `perms`, `flips`: the ops of
+    symmetry_expectations; `characters`: [n_sectors][n_ops] real characters (lattice.sector_characters).  Returns a dict:
+    'w_sum', 'we_sum' float64 [n_sectors] -- the sums over the chains of w_s(c) = sum_k chi[s][k] psi(row_k) / psi(x_c)
+    and of w_s(c) E_loc(c) -- 'e_sum' = sum_c E_loc(c) and 'n_alive', the chains whose own amplitude does not vanish (the
+    others add nothing to any sum), so that E_s ~ we_sum / w_sum is the energy of the projected state and
+    w_sum / n_alive its weight in psi.  Needs set_bonds; every permutation must map the bonds onto themselves, couplings
+    included (the library refuses anything else and names the op and the bond).  Permutations that are no bijections and
+    characters of the wrong shape or not finite are a ValueError before the library is called.  Moves no chain, touches
+    neither the step counter nor the accumulators nor the Hamiltonian, but leaves what local_energy(which) leaves;
+    ops_per_pass = 0 leaves the pass size to the library (the sums are the same bits either way)."""
+    from . import lattice
+    perm, flip = lattice.check_symmetry_ops(perms, flips, self.n_sites)
+    chi = lattice.check_characters(characters, perm.shape[0])
+    dp = C.POINTER(C.c_double)
+    w_sum, we_sum = np.empty(chi.shape[0], np.float64), np.empty(chi.shape[0], np.float64)
+    e_sum, n_alive = C.c_double(), C.c_int64()
+    self._check(self._lib.vmc_projected_energy(self._ctx, int(which), perm.shape[0], _iptr(perm),
+                                               flip.ctypes.data_as(C.POINTER(C.c_uint8)), chi.shape[0],
+                                               chi.ctypes.data_as(dp), int(ops_per_pass), w_sum.ctypes.data_as(dp),
+                                               we_sum.ctypes.data_as(dp), C.byref(e_sum), C.byref(n_alive)))
+    return {'w_sum': w_sum, 'we_sum': we_sum, 'e_sum': float(e_sum.value), 'n_alive': int(n_alive.value)}
+
   def last_connected_rows(self) -> int:
     v = C.c_int64()
     self._check(self._lib.vmc_last_connected_rows(self._ctx, C.byref(v)))

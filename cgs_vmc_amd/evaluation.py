@@ -125,7 +125,7 @@ def _sampling_eval_ops(wavefunction, hparams, shared_resources, make_value) -> E
 
 
 def _sampled(eval_ops, session, hparams, stack, per_sample) -> int:
-  """The sample loop of the four measurement evaluators, on the same schedule as MonteCarloOperatorEvaluator's (which
+  """The sample loop of the five measurement evaluators, on the same schedule as MonteCarloOperatorEvaluator's (which
   keeps its own loop: no all-reduce, and a fused path): thermalises for num_equilibration_sweeps sweeps, then takes
   num_evaluation_samples measurements, num_monte_carlo_sweeps sweeps apart.
   stack(session.run(value)) is the fp64 array of this rank's sums; with sharded chains the ranks' arrays are added by one
@@ -379,6 +379,96 @@ class SymmetryEvaluator(WavefunctionEvaluator):
     self.acceptance_count = _sampled(eval_ops, session, hparams, lambda v: np.asarray(v, np.float64), per_sample)
     return {'perms': value.perms.copy(), 'flips': value.flips.copy(), 'value': samples.mean(axis=0),
             'value_err': _std_err(samples), 'samples': samples}
+
+
+class ProjectedEnergyTensor(session_lib.Tensor):
+  """The sums of VmcEngine.projected_energy over THIS rank's chains for the ops (`perms`, `flips`) and the sectors
+  `characters` [n_sectors][n_ops]; `ensure_hamiltonian()` (optional) runs before every measurement: it puts the bonds the
+  ops are symmetries of in place."""
+
+  def __init__(self, engine, perms, flips, characters, which: int, num_sites: int, ensure_hamiltonian=None):
+    from . import lattice
+    self.engine, self.which, self.ensure_hamiltonian = engine, which, ensure_hamiltonian
+    self.perms, self.flips = lattice.check_symmetry_ops(perms, flips, num_sites)
+    self.characters = lattice.check_characters(characters, self.perms.shape[0])
+    super(ProjectedEnergyTensor, self).__init__(self._value, 'projected_energy')
+
+  def _value(self):
+    if self.ensure_hamiltonian is not None:
+      self.ensure_hamiltonian()
+    return self.engine.projected_energy(self.perms, self.flips, self.characters, self.which)
+
+
+def _ratio_jackknife(num, den):
+  """(sum num / sum den, its delete-one-sample jackknife error) over axis 0 of [n_samples][...] arrays; nan where a
+  denominator vanishes, error 0 for a single sample (as _std_err)."""
+  n = num.shape[0]
+  with np.errstate(divide='ignore', invalid='ignore'):
+    total_n, total_d = num.sum(axis=0), den.sum(axis=0)
+    value = np.where(total_d != 0, total_n / total_d, np.nan)
+    if n < 2:
+      return value, np.where(np.isnan(value), np.nan, 0.0)
+    left_d = total_d - den
+    left = np.where(left_d != 0, (total_n - num) / left_d, np.nan)
+    err = np.sqrt((n - 1.0) / n * ((left - left.mean(axis=0)) ** 2).sum(axis=0))
+  return value, np.where(np.isnan(value), np.nan, err)
+
+
+class ProjectedEnergyEvaluator(WavefunctionEvaluator):
+  """Energies of the symmetry-projected states P_s psi by running MCMC on psi (extension; quantum-number projection as
+  post-processing): E_s = <E_loc w_s> / <w_s> with w_s(x) = sum_k chi_s(k) psi(g_k x) / psi(x).  The signatures are
+  MonteCarloOperatorEvaluator's; `operator` is (hamiltonian, perms, flips, characters): the HeisenbergHamiltonian whose
+  symmetries the ops are, the ops of SymmetryEvaluator and the characters [n_sectors][n_ops] (lattice.sector_characters).
+  perms None: the translations of the hparams.size_x x hparams.size_y torus and the characters of its momentum sectors."""
+
+  def build_eval_ops(self, wavefunction, operator, hparams,
+                     shared_resources: Dict[graph_builders.ResourceName, Any]) -> EvalOps:
+    from . import lattice
+    hamiltonian, perms, flips, characters = operator
+    if perms is None:
+      size_x, size_y = getattr(hparams, 'size_x', 0), getattr(hparams, 'size_y', 0)
+      if min(size_x, size_y) < 1 or size_x * size_y != hparams.num_sites:
+        raise ValueError('ProjectedEnergyEvaluator: no ops given and size_x * size_y = {} x {} is not num_sites = {}'.format(
+            size_x, size_y, hparams.num_sites))
+      perms, flips = lattice.translations(size_x, size_y), None
+      characters = lattice.sector_characters(size_x, size_y, False)[1]
+    configs = graph_builders.get_configs(shared_resources, hparams.batch_size, hparams.num_sites)
+    ensure = None if configs is None else (lambda: configs._ensure_hamiltonian(hamiltonian))
+    return _sampling_eval_ops(wavefunction, hparams, shared_resources, lambda engine: ProjectedEnergyTensor(
+        engine, perms, flips, characters, wavefunction._which, hparams.num_sites, ensure))
+
+  def run_evaluation(self, eval_ops: EvalOps, session, hparams, epoch_num: int) -> Dict[str, np.ndarray]:
+    """Thermalises for num_equilibration_sweeps sweeps, then takes num_evaluation_samples measurements,
+    num_monte_carlo_sweeps sweeps apart (the loop of MonteCarloOperatorEvaluator).  A measurement is the stacked sums
+    [w_sum (n_sectors), we_sum (n_sectors), e_sum, n_alive] over the chains of ALL ranks: with sharded chains the ranks'
+    fp64 arrays are added by one parallel.allreduce_array per sample.  With W_t, WE_t, E_t, A_t the sums of sample t,
+    returns a dict: 'energy' [n_sectors] = sum_t WE_t / sum_t W_t and 'energy_err', the delete-one-sample jackknife error
+    of that ratio; 'weight' = sum_t W_t / sum_t A_t and 'weight_err', the standard error of the per-sample weights
+    W_t / A_t; 'plain_energy' = sum_t E_t / sum_t A_t, the unprojected energy, and 'plain_energy_err', the standard error
+    of E_t / A_t; 'samples' [n_samples][2 n_sectors + 2], the stacked sums themselves; 'perms', 'flips', 'characters'.
+    A sector whose sum_t W_t is exactly 0 has energy nan (no exception); a single sample gives the errors 0."""
+    del epoch_num
+    value = eval_ops.value
+    n_s = value.characters.shape[0]
+    samples = np.empty((hparams.num_evaluation_samples, 2 * n_s + 2), np.float64)
+
+    def stack(v):
+      return np.concatenate([np.asarray(v['w_sum'], np.float64), np.asarray(v['we_sum'], np.float64),
+                             np.array([v['e_sum'], v['n_alive']], np.float64)])
+
+    def per_sample(s, sums):
+      samples[s] = sums
+    self.acceptance_count = _sampled(eval_ops, session, hparams, stack, per_sample)
+    w, we, e, alive = samples[:, :n_s], samples[:, n_s:2 * n_s], samples[:, 2 * n_s], samples[:, 2 * n_s + 1]
+    energy, energy_err = _ratio_jackknife(we, w)
+    with np.errstate(divide='ignore', invalid='ignore'):
+      weight = w.sum(axis=0) / alive.sum()
+      weight_err = _std_err(w / alive[:, None])
+      plain = e.sum() / alive.sum()
+      plain_err = _std_err((e / alive)[:, None])[0]
+    return {'perms': value.perms.copy(), 'flips': value.flips.copy(), 'characters': value.characters.copy(),
+            'energy': energy, 'energy_err': energy_err, 'weight': weight, 'weight_err': weight_err,
+            'plain_energy': float(plain), 'plain_energy_err': float(plain_err), 'samples': samples}
 
 
 class VectorWavefunctionEvaluator(WavefunctionEvaluator):

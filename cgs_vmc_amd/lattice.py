@@ -329,6 +329,118 @@ def momentum_weights(values, size_x, size_y=1):
   return values @ np.cos(coords @ qs.T) / n
 
 
+def sector_characters(size_x, size_y=1, spin_flip=False):
+  """(labels, chi [n_sectors][n_ops] float64): the real characters of the symmetry sectors of the size_x x size_y torus
+  (size_y = 1: the periodic chain) for the ops `translations(size_x, size_y)` -- with spin_flip followed by the same N
+  translations after the global flip (n_ops = 2 N) -- as VmcEngine.projected_energy takes them.  One row per momentum
+  class {k, -k} (psi is real: the two are not told apart), with spin_flip one per class and parity +-:
+    chi[s][r, f] = mult cos(k . r) (+-1)^f / |G|,   mult = 2 unless k = -k,   |G| = n_ops
+  so that P_s = sum_k chi[s][k] g_k are idempotent, mutually orthogonal projectors that sum to the identity: the rows of
+  chi sum to the indicator of op 0.  Labels: `q<m>` on a chain, `q<m_x>,<m_y>` on a torus (k = 2 pi m / size, the class
+  named by the smaller of the two momenta in torus_momenta's order), then `+` / `-` with spin_flip."""
+  if size_x < 1 or size_y < 1:
+    raise ValueError('sector_characters: lattice sizes must be positive')
+  n = size_x * size_y
+  r = np.arange(n)
+  r_x, r_y = r % size_x, r // size_x
+  labels, rows = [], []
+  for m in range(n):
+    m_x, m_y = m % size_x, m // size_x
+    minus = (-m_x) % size_x + size_x * ((-m_y) % size_y)
+    if minus < m:
+      continue
+    phase = (m_x * r_x * size_y + m_y * r_y * size_x) % n           # k . r = 2 pi phase / n, reduced exactly
+    row = (1.0 if minus == m else 2.0) * np.cos(2.0 * np.pi * phase / n)
+    name = 'q{}'.format(m_x) if size_y == 1 else 'q{},{}'.format(m_x, m_y)
+    if not spin_flip:
+      labels.append(name); rows.append(row / n)
+    else:
+      for sign, parity in ((1.0, '+'), (-1.0, '-')):
+        labels.append(name + parity); rows.append(np.concatenate([row, sign * row]) / (2 * n))
+  return labels, np.ascontiguousarray(np.stack(rows))
+
+
+def write_characters(path, labels, chi):
+  """A text table of characters: one row per sector, the label (no blanks) first, then chi[s][0] chi[s][1] ... with 17
+  significant digits; `#` starts a comment."""
+  chi = np.asarray(chi, np.float64)
+  if chi.ndim != 2 or len(labels) != chi.shape[0] or any((not str(l)) or len(str(l).split()) != 1 or '#' in str(l) for l in labels):
+    raise ValueError('write_characters: one label without blanks per row of a [n_sectors][n_ops] table required')
+  with open(path, 'w') as f:
+    f.write('# label chi[0] chi[1] ...\n')
+    for label, row in zip(labels, chi):
+      f.write('{} {}\n'.format(label, ' '.join(repr(float(x)) for x in row)))
+
+
+def read_characters(path):
+  """(labels, chi [n_sectors][n_ops] float64) of the table write_characters writes; every row needs the same number of
+  finite characters."""
+  labels, rows = [], []
+  with open(path) as f:
+    for number, line in enumerate(f, 1):
+      fields = line.split('#', 1)[0].split()               # (blanks only: a torus label holds a comma)
+      if not fields:
+        continue
+      try:
+        row = [float(x) for x in fields[1:]]
+      except ValueError:
+        row = []
+      if not row or not np.isfinite(row).all() or (rows and len(row) != len(rows[0])):
+        raise ValueError('{}:{}: a sector is a label followed by one finite character per op, got {!r}'.format(
+            path, number, line.strip()))
+      labels.append(fields[0]); rows.append(row)
+  if not rows:
+    raise ValueError('{}: no sector'.format(path))
+  return labels, np.asarray(rows, np.float64)
+
+
+def check_characters(characters, n_ops):
+  """chi float64 [n_sectors][n_ops], contiguous, of the characters of VmcEngine.projected_energy (one row alone is one
+  sector); anything else, a non-finite character included, is a ValueError."""
+  try:
+    chi = np.asarray(characters, np.float64)
+  except (TypeError, ValueError):
+    raise ValueError('characters: a [n_sectors][{}] table of real numbers required'.format(n_ops))
+  if chi.ndim == 1 and chi.size:
+    chi = chi.reshape(1, -1)
+  if chi.ndim != 2 or chi.shape[0] < 1:
+    raise ValueError('characters: at least one sector of shape [{}] required'.format(n_ops))
+  if chi.shape[1] != n_ops:
+    raise ValueError('characters: {} characters per sector for {} ops'.format(chi.shape[1], n_ops))
+  if not np.isfinite(chi).all():
+    s, k = np.argwhere(~np.isfinite(chi))[0]
+    raise ValueError('characters: sector {}: the character of op {} is not finite'.format(int(s), int(k)))
+  return np.ascontiguousarray(chi)
+
+
+def check_hamiltonian_symmetry(bonds, j_x, j_z, perms):
+  """None when every site permutation of `perms` [n_ops][N] maps the Hamiltonian's bonds onto themselves -- the multiset
+  of (unordered pair, float32 j_x, float32 j_z) over `bonds` is unchanged (a multiset: the 2-wide torus of torus_bonds
+  names a bond twice); j_x / j_z: one value or one per bond -- else a ValueError that names the op and the first bond
+  whose image is missing.  The mirror of plan_symm_check_hamiltonian (the library checks by itself); invariance under a
+  permutation and under its inverse are the same statement; the global spin flip is always a symmetry of XXZ bonds."""
+  from collections import Counter
+  ij = np.asarray(bonds, np.int64).reshape(-1, 2)
+  nb = len(ij)
+  if nb < 1:
+    raise ValueError('check_hamiltonian_symmetry: at least one bond required')
+  bits = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32), (nb,))).view(np.uint32)   # one or one per bond
+  jx, jz = bits(j_x), bits(j_z)
+  perms = np.asarray(perms, np.int64)
+  if perms.ndim == 1:
+    perms = perms.reshape(1, -1)
+  key = lambda a, b, x, z: (int(min(a, b)), int(max(a, b)), int(x), int(z))
+  base = Counter(key(i, j, x, z) for (i, j), x, z in zip(ij, jx, jz))
+  for k, g in enumerate(perms):
+    left = base.copy()
+    for b, ((i, j), x, z) in enumerate(zip(ij, jx, jz)):
+      image = key(g[i], g[j], x, z)
+      if left[image] < 1:
+        raise ValueError('op {} is no symmetry of the Hamiltonian: bond {} = ({}, {}) goes to ({}, {}), which is no bond '
+                         'with its couplings'.format(k, b, int(i), int(j), int(g[i]), int(g[j])))
+      left[image] -= 1
+
+
 def load_bonds(checkpoint_dir, n_sites):
   """run_training.py:103-109 / run_energy_evaluation.py:51-57: `J.txt` of integer pairs
   (extra columns ignored), else the periodic chain."""

@@ -445,6 +445,38 @@ int vmc_symmetry_expectations(vmc_ctx* ctx, int which, int32_t n_ops, const int3
                               const uint8_t* flip /*[n_ops], 0/1; NULL: no flips*/,
                               int32_t ops_per_pass /*0: the library decides*/, double* ratio_sum /*[n_ops]*/);
 
+/* Symmetry-projected energies -- EXTENSION with no reference counterpart.  The ops are those of
+ * vmc_symmetry_expectations (same row convention, same bijection check); chi[s][k] are real characters of n_sectors
+ * sectors.  Over the ctx's current chains, with r_{k,c} = sigma exp(l(row_{k,c}) - l(x_c)) formed as there and E_loc(c)
+ * the local energy of chain c under the bonds of vmc_set_bonds (what vmc_local_energy gives):
+ *   w_s(c)    = sum_k chi[s][k] r_{k,c}
+ *   w_sum[s]  = sum_c w_s(c)          we_sum[s] = sum_c w_s(c) E_loc(c)          e_sum = sum_c E_loc(c)       (fp64)
+ *   n_alive   = the number of chains whose own amplitude does not vanish
+ * so that E_s ~ we_sum[s] / w_sum[s] is the energy of the projected state P_s psi, P_s = sum_k chi[s][k] g_k, its weight
+ * in psi is ~ w_sum[s] / n_alive, and e_sum / n_alive is the unprojected energy.  A chain whose own amplitude vanishes
+ * contributes exactly 0 to every sum; its E_loc is never read.
+ * Validity: every g_k is a symmetry of the Hamiltonian -- CHECKED: each perm_k must map the bonds of
+ * vmc_set_bonds onto themselves as a multiset, couplings compared by their bits; the global flip always is one -- the
+ * characters are real with chi(g^-1) = chi(g), and P_s is a projector only if the ops form a group (neither is checked).
+ * Determinism: w_s(c) is built by sequential fp64 fused multiply-adds in ascending k, carried across the passes, and
+ * the chains are folded in vmc_symmetry_expectations' order (lane l the chains l, l + 64, ... ascending, then a butterfly).
+ * Every output therefore depends on the chains, the ops and that sector's characters alone: not on ops_per_pass, not on
+ * the other sectors of the call, not on how the sectors are tiled over workgroups, not on the grid.
+ * A pure measurement like its four siblings: chains, step counter, accumulators, the Hamiltonian's bonds and the validity
+ * of the amplitude and activation caches are as before on return, on a failed call too -- with one exception: it runs
+ * one local-energy evaluation first, which leaves what vmc_local_energy(ctx, which, ...) leaves (the chains' local
+ * energies of `which` on the device, vmc_last_connected_rows).
+ * Refusals, all before anything touches the device, vmc_last_error naming the offender: everything
+ * vmc_symmetry_expectations refuses, with its codes; n_sectors < 1, a NULL chi or a character that is not finite:
+ * VMC_ERR_INVALID; n_sectors x batch_size beyond 2^26 doubles of accumulator: VMC_ERR_UNSUPPORTED; no bonds set:
+ * VMC_ERR_STATE; an op that is no symmetry of the Hamiltonian: VMC_ERR_INVALID, the op and the first offending bond
+ * named.  Outputs may be NULL. */
+int vmc_projected_energy(vmc_ctx* ctx, int which, int32_t n_ops, const int32_t* perm /*[n_ops][N]*/,
+                         const uint8_t* flip /*[n_ops], 0/1; NULL: no flips*/, int32_t n_sectors,
+                         const double* chi /*[n_sectors][n_ops]*/, int32_t ops_per_pass /*0: the library decides*/,
+                         double* w_sum /*[n_sectors]*/, double* we_sum /*[n_sectors]*/, double* e_sum /*[1]*/,
+                         int64_t* n_alive /*[1]*/);
+
 /* Stochastic reconfiguration -- EXTENSION: named by the north star, absent from the reference
  * (training.py has only the plain energy gradient + Adam), so these entries replace no reference
  * interface; they sit where TrainOpsTraditional.apply_gradients (training.py:560-567) sits.
