@@ -130,7 +130,7 @@ static void check_wgrad(long long N, long long H, int n_hh, bool rbm, long long 
 }
 
 static void check_sweep(const vmc_desc& d, const DescPlan& p) {
-  if (p.conv || (p.wide && !p.wide_fast)) return;
+  if (path_conv(p.path) || path_general_dense(p.path)) return;
   const int NT = p.Hp / 16;
   CHECK(NT == 4 || NT == 8 || NT == 12 || NT == 16 || NT == 24 || NT == 32);   // the instantiated tile counts
   const int NW = (NT == 16 || NT >= 24) ? 8 : 4;
@@ -149,7 +149,7 @@ static void check_sweep(const vmc_desc& d, const DescPlan& p) {
         if (sp.fast == 4) CHECK((d.n_sites + 3) / 4 <= 64);
         if (sp.w1l) CHECK(sp.lds == plan_sweep_lds_bytes(d.n_sites, p.Hp, p.n_hh, true, p.rbm != 0));
       }
-  if (p.wide_fast && p.n_hh >= 1) {
+  if (p.path == PATH_FUSED_LDS && p.n_hh >= 1) {
     CHECK(plan_tail_lds_supported(p.Hp, p.n_hh));
     CHECK(plan_tail_lds_bytes(p.Hp, p.n_hh) <= PLAN_LDS_PER_CU);
   }
@@ -178,6 +178,65 @@ static void check_sweep(const vmc_desc& d, const DescPlan& p) {
   }
 }
 
+// The nine flags (and the product pointer) vmc_ctx held before KernelPath, per path, exactly as the ternary of the old
+// vmc_debug_kernel_path related them.  Every predicate of plan.hpp, and every single-path test that replaced a flag, must
+// equal the boolean expression over the flags it replaced.
+struct OldFlags { int path; bool conv, conv_general, wide, wide_fast, split, split_sweep, pbdg, nnb, edvec, prod; };
+static const OldFlags kOldFlags[11] = {
+    //    conv cgen wide fast split ssweep pbdg nnb edvec prod
+    {0,   0,   0,   0,   0,   0,    0,     0,   0,  0,    0},
+    {1,   0,   0,   1,   1,   0,    0,     0,   0,  0,    0},
+    {2,   0,   0,   1,   0,   0,    0,     0,   0,  0,    0},
+    {3,   1,   0,   0,   0,   0,    0,     0,   0,  0,    0},
+    {4,   0,   0,   0,   0,   1,    0,     0,   0,  0,    0},
+    {5,   0,   0,   0,   0,   1,    1,     0,   0,  0,    0},
+    {6,   1,   1,   0,   0,   0,    0,     0,   0,  0,    0},
+    {7,   0,   0,   0,   0,   0,    0,     1,   0,  0,    0},
+    {8,   0,   0,   1,   0,   0,    0,     0,   1,  0,    0},      // nnb: the general dense path (wide, never wide_fast)
+    {9,   0,   0,   0,   0,   0,    0,     0,   0,  1,    0},
+    {10,  0,   0,   0,   0,   0,    0,     0,   0,  0,    1},      // a product starts from a minimal fully_connected ctx
+};
+
+static void path_truth_table() {
+  for (const OldFlags& f : kOldFlags) {
+    // the row is what the old ternary said
+    const int old_path = f.prod ? 10 : f.edvec ? 9 : f.nnb ? 8 : f.pbdg ? 7 : f.conv ? (f.conv_general ? 6 : 3)
+                       : (f.wide ? (f.wide_fast ? 1 : 2) : (f.split ? (f.split_sweep ? 5 : 4) : 0));
+    CHECK(old_path == f.path);
+    const KernelPath p = (KernelPath)f.path;
+    CHECK(&f == &kOldFlags[p]);
+    // the named predicates (the fused-dense one was only ever asked where a product had been sent elsewhere)
+    CHECK(path_fused_dense(p) == (!f.prod && !f.conv && !f.pbdg && !f.edvec && !(f.wide && !f.wide_fast)));
+    CHECK(path_general_dense(p) == (f.wide && !f.wide_fast));
+    CHECK(path_wide(p) == f.wide);
+    CHECK(path_conv(p) == f.conv);
+    CHECK(path_no_network(p) == (f.pbdg || f.edvec));
+    CHECK(path_split(p) == f.split);
+    // the single paths that stand where a flag stood
+    CHECK((p == PATH_CONV_GENERAL) == f.conv_general && (p == PATH_CONV) == (f.conv && !f.conv_general));
+    CHECK((p == PATH_FUSED_LDS) == (f.wide && f.wide_fast) && (p == PATH_DENSE_GENERAL) == (f.wide && !f.wide_fast && !f.nnb));
+    CHECK((p == PATH_SPLIT_SWEEP) == f.split_sweep && (p == PATH_SPLIT_ROWS) == (f.split && !f.split_sweep));
+    CHECK((p == PATH_PBDG) == f.pbdg && (p == PATH_NNB) == f.nnb && (p == PATH_EDVEC) == f.edvec && (p == PATH_PRODUCT) == f.prod);
+    // vmc_create's compounds: the eight-chain sampler's families, the families CGS_VMC_OVERLAP may switch on
+    CHECK((p == PATH_FUSED || p == PATH_SPLIT_ROWS) == (!f.prod && !f.conv && !f.wide && !(f.pbdg || f.edvec) && !f.split_sweep));
+    CHECK((!path_conv(p) && !path_wide(p) && !path_no_network(p)) == (!f.conv && !f.wide && !(f.pbdg || f.edvec)));
+    // the sampler leaves an exact cache
+    CHECK(!path_general_dense(p) == (!f.wide || f.wide_fast));
+  }
+}
+
+// plan_split_path against its condition, written out: CGS_VMC_SPLIT_BF16 = 1 | 2 on fully_connected, relu, 256 padded units,
+// at least one H x H layer -- neither convolutional nor wide nor rbm; level 2 reaches the sampler only where it is supported
+static void check_split(const DescPlan& p, int ansatz, int h, int act) {
+  for (int level : {-1, 0, 1, 2, 3})
+    for (int sweep_ok = 0; sweep_ok < 2; ++sweep_ok) {
+      const bool split = (level == 1 || level == 2) && ansatz == VMC_ANSATZ_FULLY_CONNECTED && h <= 256 && p.Hp == 256 &&
+                         p.n_hh >= 1 && act == VMC_ACT_RELU;
+      const KernelPath want = !split ? p.path : (level == 2 && sweep_ok) ? PATH_SPLIT_SWEEP : PATH_SPLIT_ROWS;
+      CHECK(plan_split_path(p, act, level, sweep_ok != 0) == want);
+    }
+}
+
 static void dense_grid() {
   const int sites[] = {2, 4, 10, 16, 36, 100, 144, 256, 400, 1024};
   const int units[] = {1, 7, 32, 64, 80, 128, 200, 256, 257, 300, 384, 400, 512, 513, 1024, 4096, 4097};
@@ -202,15 +261,23 @@ static void dense_grid() {
               }
               CHECK(h <= 4096 && !(L == 0 && ansatz == VMC_ANSATZ_FULLY_CONNECTED));
               CHECK(p.Hp >= h && p.Hp % 64 == 0 && p.Hp - h < 128);
-              CHECK(p.wide == (h > 256));
-              CHECK(!p.wide_fast || (wf && h > 256 && h <= 512 && (p.Hp == 384 || p.Hp == 512)));
+              CHECK(path_wide(p.path) == (h > 256));
+              CHECK(p.path != PATH_FUSED_LDS || (wf && h > 256 && h <= 512 && (p.Hp == 384 || p.Hp == 512)));
+              {   // the path decision, written out: <= 256 units fused; 257 .. 512 the LDS-operand kernels where they are
+                  // allowed and fit; the general GEMM path otherwise
+                const int n_hh = ansatz == VMC_ANSATZ_RBM ? L : L - 1, hp = (h + 127) / 128 * 128;
+                const bool fast = wf && h > 256 && h <= 512 && (n_hh == 0 || plan_tail_lds_supported(hp, n_hh)) &&
+                                  plan_sweep_lds_required(n, hp, n_hh, ansatz == VMC_ANSATZ_RBM) <= PLAN_LDS_PER_CU;
+                CHECK(p.path == (h <= 256 ? PATH_FUSED : fast ? PATH_FUSED_LDS : PATH_DENSE_GENERAL));
+                check_split(p, ansatz, h, act);
+              }
               CHECK(p.n_hh == (ansatz == VMC_ANSATZ_RBM ? L : L - 1) && p.lay.n_hh == p.n_hh);
               CHECK(p.P == plan_num_params_dense(ansatz, n, h, L));
               check_layout(p, n, h);
               check_sweep(d, p);
               for (long long b : batches) {
                 check_wgrad(n, h, p.n_hh, p.rbm != 0, b);
-                if (!p.rbm && !(p.wide && !p.wide_fast)) check_wgrad(n, h, p.n_hh, false, b, false);
+                if (!p.rbm && !path_general_dense(p.path)) check_wgrad(n, h, p.n_hh, false, b, false);
               }
             }
           }
@@ -219,10 +286,10 @@ static void dense_grid() {
   vmc_desc d = dense_desc(VMC_ANSATZ_FULLY_CONNECTED, 100, 4096, 3, 4097, VMC_ACT_RELU, VMC_ACT_EXP);
   CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_UNSUPPORTED);
   d = dense_desc(VMC_ANSATZ_FULLY_CONNECTED, 100, 4096, 3, 513, VMC_ACT_COS, VMC_ACT_EXP);
-  CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_OK && p.wide && !p.wide_fast);     // the general path has every activation
+  CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_OK && p.path == PATH_DENSE_GENERAL);     // the general path has every activation
   d = dense_desc(VMC_ANSATZ_FULLY_CONNECTED, 100, 4096, 3, 512, VMC_ACT_COS, VMC_ACT_EXP);
-  CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_OK && p.wide_fast && p.Hp == 512);
-  CHECK(plan_desc(&d, false, &p, msg, sizeof(msg)) == VMC_OK && !p.wide_fast);
+  CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_OK && p.path == PATH_FUSED_LDS && p.Hp == 512);
+  CHECK(plan_desc(&d, false, &p, msg, sizeof(msg)) == VMC_OK && p.path == PATH_DENSE_GENERAL);
   d = dense_desc(VMC_ANSATZ_RBM, 100, 4096, 2, 256, VMC_ACT_RELU, VMC_ACT_TANH);
   CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_INVALID);
   d = dense_desc(VMC_ANSATZ_FULLY_CONNECTED, 100, 4096, 3, 256, 7, VMC_ACT_EXP);
@@ -233,7 +300,7 @@ static void dense_grid() {
   const int cfg[4][4] = {{16, 64, 2, 32}, {36, 1024, 3, 128}, {100, 4096, 3, 256}, {256, 1024, 6, 256}};
   for (auto& c : cfg) {
     d = dense_desc(VMC_ANSATZ_FULLY_CONNECTED, c[0], c[1], c[2], c[3], VMC_ACT_RELU, VMC_ACT_EXP);
-    CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_OK && !p.wide);
+    CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_OK && !path_wide(p.path));
   }
   d = dense_desc(VMC_ANSATZ_FULLY_CONNECTED, 100, 4096, 3, 256, VMC_ACT_RELU, VMC_ACT_EXP);
   CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_OK && p.P == 157697);
@@ -389,13 +456,21 @@ static void conv_grid() {
                 CHECK(msg[0] != 0);
                 continue;
               }
-              CHECK((resnet || L >= 1) && p.conv);
-              if (p.conv_general) {       // beyond the fused kernels for one of their four reasons -- or sent here because the patch kernels beat them
+              CHECK((resnet || L >= 1) && path_conv(p.path));
+              {   // the path decision under the three CGS_VMC_CONV_GENERAL preferences, written out
+                const bool refused = F > 64 || K > 9 || plan_conv_rows_lds(p.cg, 1) > PLAN_LDS_PER_CU || B * p.cg.CS >= (1LL << 31);
+                CHECK(p.path == (refused || plan_cgen_patch_routes(p.cg, B) ? PATH_CONV_GENERAL : PATH_CONV));
+                DescPlan q;
+                if (plan_desc(&d, true, &q, msg, sizeof(msg), 1) == VMC_OK) CHECK(q.path == PATH_CONV_GENERAL);
+                if (plan_desc(&d, true, &q, msg, sizeof(msg), -1) == VMC_OK) CHECK(q.path == (refused ? PATH_CONV_GENERAL : PATH_CONV));
+                check_split(p, ansatz, F, VMC_ACT_RELU);      // a convolutional ctx never splits
+              }
+              if (p.path == PATH_CONV_GENERAL) {       // beyond the fused kernels for one of their four reasons -- or sent here because the patch kernels beat them
                 const bool refused = F > 64 || K > 9 || plan_conv_rows_lds(p.cg, 1) > PLAN_LDS_PER_CU || B * p.cg.CS >= (1LL << 31);
                 CHECK(refused || plan_cgen_patch_routes(p.cg, B));
                 if (!refused) {           // ... by preference only: CGS_VMC_CONV_GENERAL=0 keeps the fused kernels
                   DescPlan pf;
-                  CHECK(plan_desc(&d, true, &pf, msg, sizeof(msg), -1) == VMC_OK && !pf.conv_general);
+                  CHECK(plan_desc(&d, true, &pf, msg, sizeof(msg), -1) == VMC_OK && pf.path == PATH_CONV);
                 }
                 if (plan_cgen_patch_ok(p.cg, B)) {      // the patch kernels' LDS plan: within a CU's, every piece inside it
                   const size_t lds = plan_cgen_patch_lds_bytes(p.cg);
@@ -448,22 +523,22 @@ static void conv_grid() {
   CHECK(plan_conv_dw_nco(p.cg) == 1 && plan_conv_dw_parts(9, 9, 4) == 2 && plan_conv_dw_grid_z(p.cg) == 8);
   CHECK(plan_conv_dw_nco(5, 5, 2) == 2 && plan_conv_dw_parts(5, 5, 2) == 1);      // the measured 32-filter kernels are unchanged
   CHECK(plan_conv_dw_nco(5, 5, 1) == 1 && plan_conv_dw_parts(5, 5, 1) == 1 && plan_conv_dw_parts(9, 9, 1) == 1);
-  CHECK(!p.conv_general);
+  CHECK(p.path == PATH_CONV);
   d.layer_size = 65;                                                           // beyond: the general path (conv_general.hip)
-  CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_OK && p.conv_general);
+  CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_OK && p.path == PATH_CONV_GENERAL);
   d.layer_size = 1025;
   CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_UNSUPPORTED);
   d.layer_size = 16; d.kernel_size = 10;
-  CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_OK && p.conv_general && p.P == plan_num_params_conv(5, 16, 100));
+  CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_OK && p.path == PATH_CONV_GENERAL && p.P == plan_num_params_conv(5, 16, 100));
   d.kernel_size = 32;
   CHECK(plan_desc(&d, true, &p, msg, sizeof(msg)) == VMC_ERR_UNSUPPORTED);
   d.kernel_size = 5;
-  CHECK(plan_desc(&d, true, &p, msg, sizeof(msg), true) == VMC_OK && p.conv_general);      // forced (CGS_VMC_CONV_GENERAL=1)
+  CHECK(plan_desc(&d, true, &p, msg, sizeof(msg), true) == VMC_OK && p.path == PATH_CONV_GENERAL);      // forced (CGS_VMC_CONV_GENERAL=1)
   CHECK(plan_cgen_band_ok(p.cg) && plan_cgen_band_rows(p.cg) == 10);           // 16 filters 5 x 5 on 10 x 10: the band kernel, one band
   {  // 36 x 36 x 16 filters, 5 x 5 (bench workload heisenberg36x36_conv3x16k5_b32): three bands of 12 lattice rows
     vmc_desc b = d; DescPlan q;
     b.layer_size = 16; b.num_layers = 3; b.size_x = b.size_y = 36; b.n_sites = 1296; b.batch_size = 32;
-    CHECK(plan_desc(&b, true, &q, msg, sizeof(msg)) == VMC_OK && q.conv_general && plan_cgen_band_ok(q.cg));
+    CHECK(plan_desc(&b, true, &q, msg, sizeof(msg)) == VMC_OK && q.path == PATH_CONV_GENERAL && plan_cgen_band_ok(q.cg));
     CHECK(plan_cgen_band_rows(q.cg) == 12 && plan_cgen_band_lds_bytes(q.cg, false) == 16u * 40u * 64u);
     // the patch sampler: boxes of 5, 9, 13 sites per axis; spins 1,296 + fragments 2 x 25 x 256 + biases 48 + boxes
     // 2 x 16 (25 + 81 + 169) + two windows of 17 x 17 x 16 floats + 1,296 16-bit marks + 1,296 uniforms
@@ -472,28 +547,28 @@ static void conv_grid() {
     {
       DescPlan t; vmc_desc s = b;
       s.size_x = s.size_y = 12; s.n_sites = 144;                       // the last box (13) would meet itself around the torus
-      CHECK(plan_desc(&s, true, &t, msg, sizeof(msg), true) == VMC_OK && t.conv_general && !plan_cgen_patch_ok(t.cg, 32));
+      CHECK(plan_desc(&s, true, &t, msg, sizeof(msg), true) == VMC_OK && t.path == PATH_CONV_GENERAL && !plan_cgen_patch_ok(t.cg, 32));
       s.size_x = s.size_y = 13; s.n_sites = 169;                       // fits exactly -- and covers the lattice: does not pay
       CHECK(plan_desc(&s, true, &t, msg, sizeof(msg), true) == VMC_OK && plan_cgen_patch_ok(t.cg, 32) && !plan_cgen_patch_pays(t.cg));
       s = b; s.num_layers = 1;                                         // one convolution: nothing to keep
       CHECK(plan_desc(&s, true, &t, msg, sizeof(msg)) == VMC_OK && !plan_cgen_patch_ok(t.cg, 32));
       // routing: a shape the fused kernels take goes to the general path where the boxes are at most a fifth of a forward
       s = b; s.size_x = s.size_y = 24; s.n_sites = 576; s.num_layers = 2; s.batch_size = 256;     // 2 (25 + 81) of 2 x 576: 18 %
-      CHECK(plan_desc(&s, true, &t, msg, sizeof(msg)) == VMC_OK && t.conv_general && plan_cgen_patch_routes(t.cg, 256));
-      CHECK(plan_desc(&s, true, &t, msg, sizeof(msg), -1) == VMC_OK && !t.conv_general);         // CGS_VMC_CONV_GENERAL=0
+      CHECK(plan_desc(&s, true, &t, msg, sizeof(msg)) == VMC_OK && t.path == PATH_CONV_GENERAL && plan_cgen_patch_routes(t.cg, 256));
+      CHECK(plan_desc(&s, true, &t, msg, sizeof(msg), -1) == VMC_OK && t.path == PATH_CONV);         // CGS_VMC_CONV_GENERAL=0
       s.size_x = s.size_y = 16; s.n_sites = 256;                                                  // 2 (25 + 81) of 2 x 256: 41 %
-      CHECK(plan_desc(&s, true, &t, msg, sizeof(msg)) == VMC_OK && !t.conv_general && plan_cgen_patch_ok(t.cg, 256) && !plan_cgen_patch_routes(t.cg, 256));
+      CHECK(plan_desc(&s, true, &t, msg, sizeof(msg)) == VMC_OK && t.path == PATH_CONV && plan_cgen_patch_ok(t.cg, 256) && !plan_cgen_patch_routes(t.cg, 256));
       s = b; s.layer_size = 32; s.kernel_size = 3;                     // two channel blocks
-      CHECK(plan_desc(&s, true, &t, msg, sizeof(msg)) == VMC_OK && t.conv_general && !plan_cgen_patch_ok(t.cg, 32));
+      CHECK(plan_desc(&s, true, &t, msg, sizeof(msg)) == VMC_OK && t.path == PATH_CONV_GENERAL && !plan_cgen_patch_ok(t.cg, 32));
     }
     // the sampler's chain groups: one where the launches are latency, two for the one-workgroup-per-CU band kernel
     CHECK(plan_cgen_sweep_groups(q.cg, 32, 256) == 1);
     b.layer_size = 64; b.kernel_size = 3;
-    CHECK(plan_desc(&b, true, &q, msg, sizeof(msg)) == VMC_OK && q.conv_general && plan_cgen_band_ok(q.cg));
+    CHECK(plan_desc(&b, true, &q, msg, sizeof(msg)) == VMC_OK && q.path == PATH_CONV_GENERAL && plan_cgen_band_ok(q.cg));
     CHECK(plan_cgen_sweep_groups(q.cg, 32, 256) == 2 && plan_cgen_sweep_groups(q.cg, 1, 256) == 1);
     // ... and for the GEMM form where the last round of row tiles is mostly empty (800 tiles: 3.125 rounds of 256 CUs)
     b.layer_size = 128; b.size_x = b.size_y = 10; b.n_sites = 100; b.batch_size = 1024;
-    CHECK(plan_desc(&b, true, &q, msg, sizeof(msg)) == VMC_OK && q.conv_general && !plan_cgen_band_ok(q.cg));
+    CHECK(plan_desc(&b, true, &q, msg, sizeof(msg)) == VMC_OK && q.path == PATH_CONV_GENERAL && !plan_cgen_band_ok(q.cg));
     CHECK(plan_cgen_sweep_groups(q.cg, 1024, 256) == 2);       // 800 tiles
     CHECK(plan_cgen_sweep_groups(q.cg, 4096, 256) == 1);       // 3,200 tiles: 12.5 rounds, 0.96 full
     CHECK(plan_cgen_sweep_groups(q.cg, 256, 256) == 1);        // 200 tiles: less than a round
@@ -553,7 +628,7 @@ static void gnn_grid() {
           const int rc = plan_desc(&d, true, &p, msg, sizeof(msg));
           ++g_shapes;
           if (k < 2 || k > 64 || F > 1024) { CHECK(rc == VMC_ERR_UNSUPPORTED && msg[0]); ++g_rejected; continue; }
-          CHECK(rc == VMC_OK && p.conv && p.conv_general && !p.resnet);
+          CHECK(rc == VMC_OK && p.path == PATH_CONV_GENERAL && !p.resnet);
           const ConvGeom& g = p.cg;
           CHECK(g.graph == 1 && g.K == 1 && g.KW == k && g.D1 == 1 && g.D2 == n && g.N == n && g.n_conv == L);
           CHECK(g.lo == 0 && g.lo2 == 0 && !plan_cgen_periodic(g));
@@ -600,7 +675,7 @@ static void pbdg_grid() {
     ++g_shapes;
     if (n_sites < 2 || (n_sites & 1)) { CHECK(rc == VMC_ERR_INVALID); ++g_rejected; continue; }
     if (n_sites > PLAN_PBDG_MAX_SITES) { CHECK(rc == VMC_ERR_UNSUPPORTED); ++g_rejected; continue; }
-    CHECK(rc == VMC_OK && p.pbdg == 1 && p.conv == 0 && p.P == (long long)n_sites * n_sites);
+    CHECK(rc == VMC_OK && p.path == PATH_PBDG && p.P == (long long)n_sites * n_sites);
     CHECK(plan_num_params_dense(VMC_ANSATZ_PBDG, n_sites, 0, 0) == p.P);
     const int n = n_sites / 2, ld = plan_pbdg_ld(n);
     CHECK(ld >= n && (ld & 1) == 1);
@@ -660,7 +735,7 @@ static void nnb_grid() {
               B * NN > PLAN_NNB_MAX_DELTA) {
             CHECK(rc == VMC_ERR_UNSUPPORTED); ++g_rejected; continue;
           }
-          CHECK(rc == VMC_OK && p.nnb == 1 && p.wide == 1 && p.wide_fast == 0 && p.pbdg == 0 && p.conv == 0);
+          CHECK(rc == VMC_OK && p.path == PATH_NNB && path_wide(p.path) && path_general_dense(p.path));
           CHECK(p.Hp >= H && p.Hp % 64 == 0 && p.Hp < H + 64 && p.n_hh == L - 1);
           const long long P = (long long)n_sites * H + H + (long long)(L - 1) * ((long long)H * H + H) + H * NN + NN;
           CHECK(p.P == P && plan_num_params_dense(VMC_ANSATZ_NNB, n_sites, H, L) == P);
@@ -715,7 +790,7 @@ static void edvec_grid() {
     ++g_shapes;
     if (n_sites < 2 || (n_sites & 1)) { CHECK(rc == VMC_ERR_INVALID); ++g_rejected; continue; }
     if (n_sites > PLAN_EDVEC_MAX_SITES) { CHECK(rc == VMC_ERR_UNSUPPORTED); ++g_rejected; continue; }
-    CHECK(rc == VMC_OK && p.edvec == 1 && p.pbdg == 0 && p.conv == 0 && p.P == len);
+    CHECK(rc == VMC_OK && p.path == PATH_EDVEC && p.P == len);
     CHECK(plan_num_params_dense(VMC_ANSATZ_ED_VECTOR, n_sites, len, 0) == len);
     CHECK(2 * p.P + 8 < 0x7fffffffLL);                    // the accumulator offsets Adam indexes with int
     const size_t tb = plan_edvec_tables_bytes(n_sites);
@@ -963,6 +1038,7 @@ static void proj_grid() {
 }
 
 int main() {
+  path_truth_table();
   check_block_maps();
   measure_grid();
   symm_ops();

@@ -1,5 +1,6 @@
 // plan.hpp -- every PURE-HOST decision of libcgsvmc_hip.so in one header with no HIP in it: parameter
-// layouts, vmc_create's shape / LDS validation, the convolution group / band / slice pickers, the
+// layouts, vmc_create's shape / LDS validation and the kernel path of the ctx (enum KernelPath with its
+// predicates; plan_desc and plan_split_path decide it), the convolution group / band / slice pickers, the
 // sampler's LDS plan and kernel-variant choice, split-K and the XCD-aware block order of the
 // weight-gradient GEMM, the stochastic-reconfiguration tile schedules, and the sizes of the buffers
 // they index.  The .hip files call these functions (there is no second copy of any formula); the same
@@ -802,14 +803,42 @@ inline int plan_symm_check_hamiltonian(int N, int n_bonds, const int32_t* ij, co
   return VMC_OK;
 }
 
+// ------------------------------------------------------------------------------- the kernel path of a ctx
+// Which family of kernels a ctx runs: decided once (plan_desc, plan_split_path; vmc_create_product sets PATH_PRODUCT),
+// kept in vmc_ctx::path, reported by vmc_debug_kernel_path -- the numbers are part of the test suite and of bench.py.
+// Code that differs by family is a `switch` over the path that names every enumerator and has no `default`
+// (-Werror=switch: a new path fails to compile at every such site until each names it); yes/no questions that more
+// than one site asks are the predicates below.
+enum KernelPath {
+  PATH_FUSED = 0,          // fused dense kernels, <= 256 padded units (k_sweep16 / k_sweep8, k_tail16, k_backprop16)
+  PATH_FUSED_LDS = 1,      // fused dense kernels, 257 .. 512 units: operands in LDS (k_sweep16<24|32>, k_tail_lds)
+  PATH_DENSE_GENERAL = 2,  // dense layers as GEMMs over row buffers (wide.hip): > 512 units, or CGS_VMC_WIDE_FAST=0
+  PATH_CONV = 3,           // fused convolutions (conv.hip)
+  PATH_SPLIT_ROWS = 4,     // PATH_FUSED with the row kernel on the bf16 matrix cores (CGS_VMC_SPLIT_BF16=1, EXPERIMENT)
+  PATH_SPLIT_SWEEP = 5,    // ... and the sampler's H x H layers too (CGS_VMC_SPLIT_BF16=2)
+  PATH_CONV_GENERAL = 6,   // convolutions as im2col + GEMM over maps in HBM (conv_general.hip); every gnn
+  PATH_PBDG = 7,           // ProjectedBDG (pbdg.hip): theta is the pairing matrix
+  PATH_NNB = 8,            // FullyConnectedNNB (nnb.hip): the general dense trunk into determinant rows
+  PATH_EDVEC = 9,          // FullVector (edvec.hip): theta is the state vector
+  PATH_PRODUCT = 10,       // a product ctx (vmc_create_product): its factors run their own paths
+};
+// the fused dense kernels run here: rows, sampler (and its refresh pass) and k_backprop16 with its folds
+constexpr bool path_fused_dense(KernelPath p) {
+  return p == PATH_FUSED || p == PATH_FUSED_LDS || p == PATH_SPLIT_ROWS || p == PATH_SPLIT_SWEEP;
+}
+// the dense layers run as GEMMs over the row buffers, the sampler's z1 cache is updated incrementally
+constexpr bool path_general_dense(KernelPath p) { return p == PATH_DENSE_GENERAL || p == PATH_NNB; }
+// more than 256 units (nnb: any width): the ctx has the general row buffers (wbuf, wide_*)
+constexpr bool path_wide(KernelPath p) { return p == PATH_FUSED_LDS || path_general_dense(p); }
+constexpr bool path_conv(KernelPath p) { return p == PATH_CONV || p == PATH_CONV_GENERAL; }
+// no network: the kernels read theta as it lies, the dense members keep minimal shapes
+constexpr bool path_no_network(KernelPath p) { return p == PATH_PBDG || p == PATH_EDVEC; }
+constexpr bool path_split(KernelPath p) { return p == PATH_SPLIT_ROWS || p == PATH_SPLIT_SWEEP; }
+
 // ------------------------------------------------------------------------------- vmc_create
 struct DescPlan {
-  int rbm, conv, resnet, one_d;
-  int edvec;                 // FullVector (edvec.hip): theta is the state vector; none of the network members below apply
-  int pbdg;                  // ProjectedBDG (pbdg.hip): none of the network members below apply
-  int nnb;                   // FullyConnectedNNB (nnb.hip): the general dense path (wide, never wide_fast) into determinant rows
-  int conv_general;          // conv beyond the fused kernels' limits (or forced): conv_general.hip
-  int wide, wide_fast;       // > 256 units; of those, the fused 384 / 512-unit kernels
+  KernelPath path;           // PATH_SPLIT_* and PATH_PRODUCT are never planned here (plan_split_path, vmc_create_product)
+  int rbm, resnet, one_d;
   int Hp;                    // padded units of the dense kernels (conv: 64, unused)
   int n_hh;                  // H x H layers
   long long P;               // parameters
@@ -835,7 +864,7 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
     const int rc = plan_edvec_check(d->n_sites, d->layer_size, msg, msg_len);
     if (rc != VMC_OK) return rc;
     if (d->batch_size < 1) PLAN_FAIL(VMC_ERR_INVALID, "batch_size >= 1 required");
-    out->edvec = 1;
+    out->path = PATH_EDVEC;
     out->Hp = 64; out->n_hh = 0;
     out->P = plan_num_params_dense(VMC_ANSATZ_ED_VECTOR, d->n_sites, d->layer_size, 0);
     out->lay = plan_layout(false, d->n_sites, 1, 1);
@@ -846,7 +875,7 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
     // FullyConnectedNNB (wavefunctions.py:931-998): the fully_connected layout with an output layer N^2 wide; always relu
     const int rc = plan_nnb_check(d->n_sites, d->num_layers, d->layer_size, d->batch_size, msg, msg_len);
     if (rc != VMC_OK) return rc;
-    out->nnb = 1; out->wide = 1; out->wide_fast = 0;
+    out->path = PATH_NNB;
     out->Hp = (d->layer_size + 63) / 64 * 64; out->n_hh = d->num_layers - 1;
     out->P = plan_num_params_dense(VMC_ANSATZ_NNB, d->n_sites, d->layer_size, d->num_layers);
     out->lay = plan_layout(false, d->n_sites, d->layer_size, d->num_layers);
@@ -859,7 +888,7 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
     const int rc = plan_pbdg_check(d->n_sites, msg, msg_len);
     if (rc != VMC_OK) return rc;
     if (d->batch_size < 1) PLAN_FAIL(VMC_ERR_INVALID, "batch_size >= 1 required");
-    out->pbdg = 1;
+    out->path = PATH_PBDG;
     out->Hp = 64; out->n_hh = 0;
     out->P = plan_num_params_dense(VMC_ANSATZ_PBDG, d->n_sites, 0, 0);
     out->lay = plan_layout(false, d->n_sites, 1, 1);
@@ -870,7 +899,8 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
   const bool conv = d->ansatz >= VMC_ANSATZ_CONV_2D && d->ansatz <= VMC_ANSATZ_GNN;
   const bool resnet = d->ansatz == VMC_ANSATZ_RES_NET_2D || d->ansatz == VMC_ANSATZ_RES_NET_1D;
   const bool one_d = d->ansatz == VMC_ANSATZ_CONV_1D || d->ansatz == VMC_ANSATZ_RES_NET_1D;
-  out->rbm = rbm; out->conv = conv; out->resnet = resnet; out->one_d = one_d;
+  out->rbm = rbm; out->resnet = resnet; out->one_d = one_d;
+  bool conv_general = false;
   if (d->n_sites < 2 || d->batch_size < 1 || d->num_layers < ((rbm || resnet) ? 0 : 1) || d->layer_size < 1)
     PLAN_FAIL(VMC_ERR_INVALID, "n_sites >= 2, batch_size, layer_size >= 1, num_layers >= 1 (rbm, res_net_2d: >= 0) required");
   ConvGeom& cg = out->cg;
@@ -894,7 +924,7 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
     cg.graph = 1;
     if ((long long)cg.N * plan_cgen_lda(cg) >= (1LL << 28))
       PLAN_FAIL(VMC_ERR_UNSUPPORTED, "num_sites x k x filters too large for the general convolution path (one sample's im2col rows beyond 1 GiB)");
-    out->conv_general = 1;
+    conv_general = true;
   } else if (conv) {
     // Conv2DNetwork reshapes its input to [-1, size_x, size_y, 1] (wavefunctions.py:596-597);
     // Conv1DNetwork expands [B, N] to [B, N, 1] (wavefunctions.py:511): an N x 1 lattice here
@@ -933,7 +963,7 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
     if (!general && conv_general_pref == 0 && plan_cgen_patch_routes(cg, d->batch_size)) general = true;   // a lattice much wider than the network's reach
     if (general && (long long)cg.N * plan_cgen_lda(cg) >= (1LL << 28))
       PLAN_FAIL(VMC_ERR_UNSUPPORTED, "lattice x kernel x filters too large for the general convolution path (one sample's im2col rows beyond 1 GiB)");
-    out->conv_general = general ? 1 : 0;
+    conv_general = general;
   }
   if (d->nonlinearity < 0 || d->nonlinearity > 6 || d->output_activation < 0 || d->output_activation > 6)
     PLAN_FAIL(VMC_ERR_INVALID, "unknown activation id (layers.NONLINEARITIES has 7 entries)");
@@ -961,7 +991,9 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
     }
   }
 #undef PLAN_FAIL
-  out->wide = wide; out->wide_fast = wide_fast; out->n_hh = n_hh;
+  out->path = conv ? (conv_general ? PATH_CONV_GENERAL : PATH_CONV)
+                   : wide ? (wide_fast ? PATH_FUSED_LDS : PATH_DENSE_GENERAL) : PATH_FUSED;
+  out->n_hh = n_hh;
   out->Hp = conv ? 64 : (wide_fast ? (d->layer_size + 127) / 128 * 128 : (d->layer_size + 63) / 64 * 64);
   if (conv) {
     out->P = plan_num_params_conv(cg.n_conv, cg.F, (long long)cg.K * cg.KW);
@@ -973,6 +1005,15 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
   }
   if (msg_len) msg[0] = 0;
   return VMC_OK;
+}
+
+// CGS_VMC_SPLIT_BF16 = `level` on a planned ctx (EXPERIMENT: fully_connected, relu, 256 padded units, >= 1 H x H layer):
+// 1 the row kernel, 2 the sampler too where sweep16_split_supported (`sweep_ok`) takes the shape; every other ctx keeps
+// its path.  hact: the ctx's hidden activation.
+inline KernelPath plan_split_path(const DescPlan& p, int hact, int level, bool sweep_ok) {
+  if ((level != 1 && level != 2) || p.path != PATH_FUSED || p.rbm || p.Hp != 256 || p.n_hh < 1 || hact != VMC_ACT_RELU)
+    return p.path;
+  return level == 2 && sweep_ok ? PATH_SPLIT_SWEEP : PATH_SPLIT_ROWS;
 }
 
 // ------------------------------------------------------------------------------- gnn adjacency list

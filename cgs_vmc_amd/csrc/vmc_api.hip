@@ -12,29 +12,33 @@ namespace vmcapi { std::string g_create_error; }
 
 namespace vmcapi {
 
-int gnn_ready(vmc_ctx* c) {
+int late_inputs_set(vmc_ctx* c) {
   if (c->cg.graph && !c->gnn_adj) return fail(c, VMC_ERR_INVALID, "gnn: no adjacency list (vmc_set_adjacency)");
-  if (c->edvec && !c->ed_top) return fail(c, VMC_ERR_INVALID, "ed_vector: no Lin tables (vmc_set_lin_tables)");
+  if (c->path == PATH_EDVEC && !c->ed_top) return fail(c, VMC_ERR_INVALID, "ed_vector: no Lin tables (vmc_set_lin_tables)");
   return VMC_OK;
 }
 
 int ensure_packed(vmc_ctx* c, int which) {
-  PROPAGATE(gnn_ready(c));
+  PROPAGATE(late_inputs_set(c));
   ParamSet& p = c->ps[which];
   if (!p.has_params) return fail(c, VMC_ERR_STATE, "parameters not set (vmc_set_params)");
   if (p.packed_valid) return VMC_OK;
-  if (c->pbdg || c->edvec) { p.packed_valid = true; return VMC_OK; }     // (the kernels read theta as it lies)
-  if (c->conv) {
-    // (general path: the parameter slices are the B matrices of its GEMMs as they lie in theta)
-    if (!c->conv_general) HIPCHK(c, launch_conv_pack(c->stream, p.theta, c->cg, p.cw0, p.cwf, p.cwb, p.cbias));
-    p.packed_valid = true;
-    return VMC_OK;
+  switch (c->path) {
+    case PATH_PBDG: case PATH_EDVEC:      // (the kernels read theta as it lies)
+    case PATH_CONV_GENERAL:               // (the parameter slices are the B matrices of its GEMMs as they lie in theta)
+      break;
+    case PATH_CONV:
+      HIPCHK(c, launch_conv_pack(c->stream, p.theta, c->cg, p.cw0, p.cwf, p.cwb, p.cbias));
+      break;
+    case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP: case PATH_NNB:
+      HIPCHK(c, launch_pack(c->stream, p.theta, c->N, c->H, c->Hp, c->lay, p.w1p, p.b1p, p.bh, p.p16,
+                            p.p16t, p.woutp, p.bout, p.won));
+      if (path_split(c->path)) HIPCHK(c, launch_pack_split(c->stream, p.theta, c->H, c->lay, p.p16s));
+      p.bdiff_valid = false;      // (differences of the image just replaced)
+      break;
+    case PATH_PRODUCT: return product_has_none(c, "parameter image");
   }
-  HIPCHK(c, launch_pack(c->stream, p.theta, c->N, c->H, c->Hp, c->lay, p.w1p, p.b1p, p.bh, p.p16,
-                        p.p16t, p.woutp, p.bout, p.won));
-  if (c->split) HIPCHK(c, launch_pack_split(c->stream, p.theta, c->H, c->lay, p.p16s));
   p.packed_valid = true;
-  p.bdiff_valid = false;      // (differences of the image just replaced)
   return VMC_OK;
 }
 
@@ -59,7 +63,7 @@ static hipError_t ensure_bond_diff(vmc_ctx* c, int which, const int2* bonds) {
 
 // rows through the fused row kernel of this ctx (the 3 x bf16 split experiment when it is switched on)
 hipError_t launch_rows(vmc_ctx* c, int which, const TailArgs& a, bool ratio) {
-  if (c->split) return launch_tail16_split(c->stream, a, c->ps[which].p16s, ratio);
+  if (path_split(c->path)) return launch_tail16_split(c->stream, a, c->ps[which].p16s, ratio);
   if (a.n_hidden == 0) return launch_tail(c->stream, a, c->Hp, ratio, c->rbm);     // k_tail0 reads w1p itself
   TailArgs t = a;
   hipError_t e = ensure_bond_diff(c, which, a.bonds);
@@ -94,7 +98,7 @@ ConvParams conv_params(const ParamSet& p) { return ConvParams{p.cw0, p.cwf, p.cw
 // iup / idn != nullptr: row r is chain r with that pair exchanged (the sampler's candidates).
 int conv_rows(vmc_ctx* c, int which, const float* configs, const int2* rowinfo, int rows,
               const int* rows_dev, bool ratio, float* out, bool with_tape) {
-  if (c->conv_general) {
+  if (c->path == PATH_CONV_GENERAL) {
     // (the gradient path of the general convolution re-runs its own taped forward, cgen_gradient: the row entry keeps none)
     if (with_tape) return fail(c, VMC_ERR_UNSUPPORTED, "conv_rows keeps no tape on the general convolution path (its gradient entries run their own taped forward)");
     int n_rows = rows;
@@ -158,7 +162,7 @@ int wide_forward(vmc_ctx* c, int which, const float* z1, const int2* rowinfo, lo
   const int H = c->H, Hp = c->Hp, NH = c->n_hh;
   const int2* bonds = c->bonds ? c->bonds : c->bond_dummy;
   const WideOnsite on{c->rbm ? onsite : nullptr, p.won, bonds, nullptr, nullptr};
-  if (c->wide_fast) {
+  if (c->path == PATH_FUSED_LDS) {
     TailArgs a = tail_args(c, which);
     a.z1 = z1; a.logit_base = p.logit; a.rowinfo = rowinfo; a.on_base = onsite;
     a.n_rows = (int)n_rows; a.out = out;
@@ -225,48 +229,67 @@ int nnb_forward(vmc_ctx* c, int which, const float* z1, const float* configs, co
   return VMC_OK;
 }
 
+// The full forward of parameter set `which` on n_rows rows of a device buffer of configurations, by the ctx's kernel
+// family: log|psi| (the logit) per row into `logit` and, for the signed types, the sign (ed_vector: the entry itself) into
+// `sign`.  z1 [n_rows][Hp], onsite [n_rows] and rowinfo (the identity list of n_rows rows) are the scratch of the dense
+// trunk.  tape: the fused convolutions leave the inputs of every convolution in c->ctape.  timed: the regions of a cache
+// refill, "z1" for the first layer and "tail_amp" for the rest (otherwise none: the caller times the call).
+static int full_forward(vmc_ctx* c, int which, const float* configs, int n_rows, float* z1, float* onsite,
+                        const int2* rowinfo, float* logit, float* sign, bool tape, bool timed) {
+  ParamSet& p = c->ps[which];
+  const char* tail_region = timed ? "tail_amp" : nullptr;
+  auto trunk_first_layer = [&]() -> int {
+    Timer t(c, timed ? "z1" : nullptr);
+    PROPAGATE(first_layer(c, p, configs, z1, n_rows));
+    if (c->rbm) HIPCHK(c, launch_onsite(c->stream, configs, p.won, n_rows, c->N, onsite));
+    return VMC_OK;
+  };
+  switch (c->path) {
+    case PATH_EDVEC: {
+      Timer t(c, tail_region);
+      HIPCHK(c, launch_edvec_rows(c->stream, p.theta, (int)c->P, c->ed_top, c->ed_bot, c->N, configs, n_rows, logit, sign));
+      return VMC_OK;
+    }
+    case PATH_PBDG: {
+      Timer t(c, tail_region);
+      HIPCHK(c, launch_pbdg_rows(c->stream, p.theta, c->N, configs, n_rows, logit, sign, nullptr, nullptr));
+      return VMC_OK;
+    }
+    case PATH_CONV: case PATH_CONV_GENERAL: {
+      Timer t(c, tail_region);
+      return conv_rows(c, which, configs, rowinfo, n_rows, nullptr, false, logit, tape);
+    }
+    case PATH_NNB: {
+      PROPAGATE(trunk_first_layer());
+      Timer t(c, tail_region);
+      return nnb_forward(c, which, z1, configs, rowinfo, n_rows, false, logit, sign);
+    }
+    case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: {
+      PROPAGATE(trunk_first_layer());
+      Timer t(c, tail_region);
+      return wide_forward(c, which, z1, rowinfo, n_rows, false, logit, onsite);
+    }
+    case PATH_FUSED: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP: {
+      PROPAGATE(trunk_first_layer());
+      Timer t(c, tail_region);
+      TailArgs a = tail_args(c, which);
+      a.z1 = z1; a.on_base = onsite; a.n_rows = n_rows; a.out = logit; a.rowinfo = rowinfo;
+      HIPCHK(c, launch_rows(c, which, a, false));
+      return VMC_OK;
+    }
+    case PATH_PRODUCT: return product_has_none(c, "forward");
+  }
+  return VMC_OK;
+}
+
 // z1 / logit cache of parameter set `which` for the ctx's chains
 int ensure_cache(vmc_ctx* c, int which) {
   PROPAGATE(ensure_packed(c, which));
   ParamSet& p = c->ps[which];
   if (p.cache_valid) return VMC_OK;
-  if (c->edvec) {
-    Timer t(c, "tail_amp");
-    HIPCHK(c, launch_edvec_rows(c->stream, p.theta, (int)c->P, c->ed_top, c->ed_bot, c->N, c->configs, c->B, p.logit, p.sign));
-    p.cache_valid = true;
-    return VMC_OK;
-  }
-  if (c->pbdg) {
-    Timer t(c, "tail_amp");
-    HIPCHK(c, launch_pbdg_rows(c->stream, p.theta, c->N, c->configs, c->B, p.logit, p.sign, nullptr, nullptr));
-    p.cache_valid = true;
-    return VMC_OK;
-  }
-  if (c->conv) {
-    Timer t(c, "tail_amp");
-    const bool tape = which == VMC_PSI && !c->conv_general;       // (the general path keeps no gradient tape)
-    PROPAGATE(conv_rows(c, which, c->configs, c->rowinfo_id, c->B, nullptr, false, p.logit, tape));
-    if (tape) c->acts_valid = true;
-    p.cache_valid = true;
-    return VMC_OK;
-  }
-  {
-    Timer t(c, "z1");
-    PROPAGATE(first_layer(c, p, c->configs, p.z1, c->B));
-    if (c->rbm) HIPCHK(c, launch_onsite(c->stream, c->configs, p.won, c->B, c->N, p.onsite));
-  }
-  if (c->nnb) {
-    Timer t(c, "tail_amp");
-    PROPAGATE(nnb_forward(c, which, p.z1, c->configs, c->rowinfo_id, c->B, false, p.logit, p.sign));
-  } else if (c->wide) {
-    Timer t(c, "tail_amp");
-    PROPAGATE(wide_forward(c, which, p.z1, c->rowinfo_id, c->B, false, p.logit, p.onsite));
-  } else {
-    Timer t(c, "tail_amp");
-    TailArgs a = tail_args(c, which);
-    a.z1 = p.z1; a.n_rows = c->B; a.out = p.logit; a.rowinfo = c->rowinfo_id;
-    HIPCHK(c, launch_rows(c, which, a, false));
-  }
+  const bool tape = which == VMC_PSI && c->path == PATH_CONV;       // (the general path keeps no gradient tape)
+  PROPAGATE(full_forward(c, which, c->configs, c->B, p.z1, p.onsite, c->rowinfo_id, p.logit, p.sign, tape, true));
+  if (tape) c->acts_valid = true;
   p.cache_valid = true;
   return VMC_OK;
 }
@@ -299,7 +322,7 @@ int local_energy_device(vmc_ctx* c, int which, bool defer_reduce, bool* deferred
   PROPAGATE(ensure_list(c));
   PROPAGATE(connected_rows_device(c, which, true));
   ParamSet& p = c->ps[which];
-  if (defer_reduce && deferred && !c->conv && !c->pbdg && !c->edvec && !(c->wide && !c->wide_fast)) {
+  if (defer_reduce && deferred && path_fused_dense(c->path)) {
     *deferred = true;              // the fused back-propagation launch folds val into eloc
     return VMC_OK;
   }
@@ -313,42 +336,39 @@ int local_energy_device(vmc_ctx* c, int which, bool defer_reduce, bool* deferred
 // val[row] of every row of the list, by the ctx's kernel family (the spin-correlation passes run it over their own bond set)
 int connected_rows_device(vmc_ctx* c, int which, bool share_cus) {
   ParamSet& p = c->ps[which];
-  if (c->edvec) {
-    Timer t(c, "tail_eloc");
+  Timer t(c, "tail_eloc");
+  switch (c->path) {
+  case PATH_EDVEC:
     HIPCHK(c, launch_edvec_eloc(c->stream, p.theta, (int)c->P, c->ed_top, c->ed_bot, c->N, c->configs, p.sign, c->B, c->off,
                                 c->rowinfo, c->bonds, c->half_jx, c->val));
-  } else if (c->pbdg) {
-    Timer t(c, "tail_eloc");      // (a fresh M^-1 per chain: never the sampler's incrementally updated one)
+    break;
+  case PATH_PBDG:      // (a fresh M^-1 per chain: never the sampler's incrementally updated one)
     HIPCHK(c, launch_pbdg_eloc(c->stream, p.theta, c->N, c->configs, c->B, c->off, c->rowinfo, c->bonds, c->half_jx,
                                c->val));
-  } else if (c->conv) {
-    Timer t(c, "tail_eloc");
+    break;
+  case PATH_CONV: case PATH_CONV_GENERAL:
     PROPAGATE(conv_rows(c, which, c->configs, c->rowinfo, (int)((long long)c->B * c->n_bonds), c->off + c->B,
                         true, c->val, false));
-  } else if (c->wide && c->wide_fast) {
-    Timer t(c, "tail_eloc");
+    break;
+  case PATH_DENSE_GENERAL: case PATH_NNB: {
+    int n_rows = 0;      // the GEMM grids need the row count on the host
+    HIPCHK(c, hipMemcpyAsync(&n_rows, c->off + c->B, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->path == PATH_NNB) PROPAGATE(nnb_forward(c, which, p.z1, c->configs, c->rowinfo, n_rows, true, c->val, nullptr));
+    else PROPAGATE(wide_forward(c, which, p.z1, c->rowinfo, n_rows, true, c->val, p.onsite));
+    break;
+  }
+  case PATH_FUSED: case PATH_FUSED_LDS: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP: {
     TailArgs a = tail_args(c, which);
     a.z1 = p.z1; a.logit_base = p.logit; a.rowinfo = c->rowinfo;
     a.n_rows_dev = c->off + c->B;                 // the row count stays on the device
     a.n_rows = (int)((long long)c->B * c->n_bonds);
     a.out = c->val;
-    if (c->n_hh == 0) HIPCHK(c, launch_tail(c->stream, a, c->Hp, true, c->rbm));
-    else HIPCHK(c, launch_tail_lds(c->stream, a, c->Hp, true, c->rbm));
-  } else if (c->wide) {
-    Timer t(c, "tail_eloc");
-    int n_rows = 0;      // the GEMM grids need the row count on the host
-    HIPCHK(c, hipMemcpyAsync(&n_rows, c->off + c->B, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->nnb) PROPAGATE(nnb_forward(c, which, p.z1, c->configs, c->rowinfo, n_rows, true, c->val, nullptr));
-    else
-    PROPAGATE(wide_forward(c, which, p.z1, c->rowinfo, n_rows, true, c->val, p.onsite));
-  } else {
-    Timer t(c, "tail_eloc");
-    TailArgs a = tail_args(c, which);
-    a.z1 = p.z1; a.logit_base = p.logit; a.rowinfo = c->rowinfo;
-    a.n_rows_dev = c->off + c->B;
-    a.n_rows = (int)((long long)c->B * c->n_bonds);
-    a.out = c->val;
+    if (c->path == PATH_FUSED_LDS) {              // the LDS-operand kernel (without an H x H layer: k_tail0, any Hp)
+      if (c->n_hh == 0) HIPCHK(c, launch_tail(c->stream, a, c->Hp, true, c->rbm));
+      else HIPCHK(c, launch_tail_lds(c->stream, a, c->Hp, true, c->rbm));
+      break;
+    }
     // a sampler launch is expected to overtake this accumulate: its workgroups need a whole
     // CU each, so the persistent grid leaves them free
     if (share_cus && c->expect_sweep && can_overlap(c) && c->num_cus - sweep_cus(c) >= c->num_cus / 4) {
@@ -359,7 +379,7 @@ int connected_rows_device(vmc_ctx* c, int which, bool share_cus) {
       // sweep_stream, takes the CUs the first workgroups free).  A persistent grid on the CUs the sampler leaves
       // cannot grow when the sampler ends before it (eight-chain tiles: 3.6 ms against 5.1 ms on 128 CUs).
       static const int chunk_us = getenv("CGS_VMC_TAIL_CHUNK_US") ? atoi(getenv("CGS_VMC_TAIL_CHUNK_US")) : 150;
-      if (chunk_us > 0 && !c->split && c->n_hh > 0) {
+      if (chunk_us > 0 && !path_split(c->path) && c->n_hh > 0) {
         const long long tiles = ((long long)a.n_rows + 127) / 128;
         const double tile_us = 128.0 * c->n_hh * 2.0 * c->Hp * c->Hp / 491520.0;   // 0.8 of a CU's 256 flops per clock at 2.4 GHz
         long long k = (long long)(chunk_us / tile_us);
@@ -369,6 +389,9 @@ int connected_rows_device(vmc_ctx* c, int which, bool share_cus) {
       }
     }
     HIPCHK(c, launch_rows(c, which, a, true));
+    break;
+  }
+  case PATH_PRODUCT: return product_has_none(c, "row kernel");
   }
   return VMC_OK;
 }
@@ -393,39 +416,32 @@ int grow_tmp(vmc_ctx* c, long long rows) {
 // the scratch; `configs`, `logit`, `sign` may be the tmp buffers of the same rows or any others.
 int rows_forward_device(vmc_ctx* c, int which, const float* configs, long long n_rows, float* logit, float* sign) {
   if (n_rows <= 0) return VMC_OK;
-  ParamSet& p = c->ps[which];
-  if (c->edvec) {
-    HIPCHK(c, launch_edvec_rows(c->stream, p.theta, (int)c->P, c->ed_top, c->ed_bot, c->N, configs, (int)n_rows, logit, sign));
-  } else if (c->pbdg) {
-    HIPCHK(c, launch_pbdg_rows(c->stream, p.theta, c->N, configs, (int)n_rows, logit, sign, nullptr, nullptr));
-  } else if (c->nnb) {
-    PROPAGATE(first_layer(c, p, configs, c->tmp_z1, (int)n_rows));
-    PROPAGATE(nnb_forward(c, which, c->tmp_z1, configs, c->tmp_rowinfo, n_rows, false, logit, sign));
-  } else if (c->conv) {
-    PROPAGATE(conv_rows(c, which, configs, c->tmp_rowinfo, (int)n_rows, nullptr, false, logit, false));
-  } else if (c->wide) {
-    PROPAGATE(first_layer(c, p, configs, c->tmp_z1, (int)n_rows));
-    if (c->rbm) HIPCHK(c, launch_onsite(c->stream, configs, p.won, (int)n_rows, c->N, c->tmp_on));
-    PROPAGATE(wide_forward(c, which, c->tmp_z1, c->tmp_rowinfo, n_rows, false, logit, c->tmp_on));
-  } else {
-    PROPAGATE(first_layer(c, p, configs, c->tmp_z1, (int)n_rows));
-    if (c->rbm) HIPCHK(c, launch_onsite(c->stream, configs, p.won, (int)n_rows, c->N, c->tmp_on));
-    TailArgs a = tail_args(c, which);
-    a.z1 = c->tmp_z1; a.on_base = c->tmp_on; a.n_rows = (int)n_rows; a.out = logit; a.rowinfo = c->tmp_rowinfo;
-    HIPCHK(c, launch_rows(c, which, a, false));
-  }
-  return VMC_OK;
+  return full_forward(c, which, configs, (int)n_rows, c->tmp_z1, c->tmp_on, c->tmp_rowinfo, logit, sign, false, false);
 }
 
-// pbdg: every row must hold as many up as down spins (the projected BCS state lives at Sz = 0); host rows
-int pbdg_check_sz(vmc_ctx* c, const float* configs, long long n_rows) {
+// the name a signed ctx's refusals go by (Sz = 0 rows, stochastic reconfiguration)
+const char* signed_family_name(KernelPath path) {
+  switch (path) {
+    case PATH_PRODUCT: return "prod (a signed factor)";
+    case PATH_EDVEC: return "ed_vector";
+    case PATH_NNB: return "fully_connected_nnb";
+    case PATH_PBDG: return "pbdg";
+    case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_CONV: case PATH_SPLIT_ROWS:
+    case PATH_SPLIT_SWEEP: case PATH_CONV_GENERAL: break;      // (unsigned amplitudes: never asked)
+  }
+  return "unsigned";
+}
+
+// signed amplitudes (pbdg, nnb, ed_vector, a product with such a factor): every row must hold as many up as down spins
+// (the determinants and the Lin tables live at Sz = 0); host rows
+int check_sz0_rows(vmc_ctx* c, const float* configs, long long n_rows) {
   if (!c->sgn) return VMC_OK;
   for (long long r = 0; r < n_rows; ++r) {
     double m = 0.0;
     for (int i = 0; i < c->N; ++i) m += configs[r * c->N + i];
     if (m != 0.0) {
       char msg[160];
-      snprintf(msg, sizeof(msg), "%s: configuration %lld has magnetisation %g; the ansatz needs as many up as down spins", c->prod ? "prod (a signed factor)" : c->edvec ? "ed_vector" : c->nnb ? "fully_connected_nnb" : "pbdg", r, m);
+      snprintf(msg, sizeof(msg), "%s: configuration %lld has magnetisation %g; the ansatz needs as many up as down spins", signed_family_name(c->path), r, m);
       return fail(c, VMC_ERR_INVALID, msg);
     }
   }
@@ -444,6 +460,244 @@ float host_activation(int act, float x) {
     default: return x;
   }
 }
+
+// ---- the device buffers of vmc_create: what every ctx has (the non-dense paths keep minimal dense-side shapes), then the
+// groups of the ctx's path.  A failure names itself in g_create_error and returns VMC_ERR_HIP; vmc_create destroys the ctx.
+#define CA(expr) do { hipError_t e2 = (expr); if (e2 != hipSuccess) { \
+    g_create_error = std::string(#expr) + ": " + hipGetErrorString(e2); return VMC_ERR_HIP; } } while (0)
+#define NEW(buf, n) do { if ((buf).alloc(c, (n), #buf) != VMC_OK) { g_create_error = c->err; return VMC_ERR_HIP; } } while (0)
+
+// path_wide: the two activation row buffers of c->wrows rows and the sampler's proposal buffers
+static int create_wide_rows(vmc_ctx* c) {
+  const long long B = c->B, Hp = c->Hp;
+  NEW(c->wbuf[0], c->wrows * Hp); NEW(c->wbuf[1], c->wrows * Hp);
+  NEW(c->wide_u, B);
+  NEW(c->wide_dot, (long long)gemm_rowdot_tiles(c->H) * c->wrows);
+  NEW(c->wide_iup, B); NEW(c->wide_idn, B); NEW(c->wide_zero, Hp);
+  CA(hipMemsetAsync(c->wide_zero, 0, Hp * sizeof(float), c->stream));
+  return VMC_OK;
+}
+
+// PATH_NNB: blocks of rows whose dense pairing layer takes CGS_VMC_NNB_BLOCK_MB (default 256) MiB; they size the row buffers
+static int create_nnb_blocks(vmc_ctx* c) {
+  const long long B = c->B, N = c->N;
+  long long mb = PLAN_NNB_BLOCK_MB_DEFAULT;
+  if (const char* e = getenv("CGS_VMC_NNB_BLOCK_MB")) mb = atoll(e);
+  c->nnb_rows = plan_nnb_block_rows((int)N, mb);
+  if (const char* e = getenv("CGS_VMC_NNB_BLOCK_ROWS")) { const long long r = atoll(e); if (r >= 1 && r < c->nnb_rows) c->nnb_rows = r; }   // tests: several blocks at small shapes
+  c->wrows = c->nnb_rows;
+  NEW(c->nnb_out, c->nnb_rows * N * N);
+  NEW(c->nnb_delta, B * N * N);
+  NEW(c->nnb_cl, B); NEW(c->nnb_cs, B);
+  return VMC_OK;
+}
+
+// signed amplitudes: the sign beside the logit of both parameter sets (alt: the set the next sampler launch writes)
+static int create_sign(vmc_ctx* c, bool alt) {
+  const long long B = c->B;
+  for (int w = 0; w < 2; ++w) {
+    NEW(c->ps[w].sign, B);
+    CA(hipMemsetAsync(c->ps[w].sign, 0, B * sizeof(float), c->stream));
+  }
+  if (alt) {
+    NEW(c->ps[0].sign_alt, B);
+    CA(hipMemsetAsync(c->ps[0].sign_alt, 0, B * sizeof(float), c->stream));
+  }
+  return VMC_OK;
+}
+
+static int create_edvec(vmc_ctx* c) {
+  const long long B = c->B;
+  NEW(c->ed_keys, B); NEW(c->ed_keys_sorted, B);
+  CA(edvec_sort_bytes((int)B, (int)c->P, &c->ed_sort_bytes));
+  NEW(c->ed_sort_tmp, (long long)c->ed_sort_bytes);
+  c->ed_tables_lds = plan_edvec_tables_in_lds(c->N) && !(getenv("CGS_VMC_EDVEC_TABLES_LDS") && atoi(getenv("CGS_VMC_EDVEC_TABLES_LDS")) == 0);
+  if (c->ed_tables_lds) CA(edvec_sweep_reserve_lds(c->N));
+  return VMC_OK;
+}
+
+static int create_pbdg(vmc_ctx* c) {
+  const long long B = c->B, N = c->N, n = N / 2;
+  NEW(c->pbdg_inv, B * n * n); NEW(c->pbdg_pos, B * N);
+  c->pbdg_slices = plan_pbdg_grad_slices(c->P, B, c->num_cus);
+  NEW(c->pbdg_ws, plan_pbdg_grad_ws_doubles(c->P, c->pbdg_slices));
+  return VMC_OK;
+}
+
+static int create_conv_general(vmc_ctx* c) {
+  const ConvGeom& cg = c->cg;
+  const long long B = c->B;
+  // blocks of at most ~768 MB of im2col rows (one row configuration at least), at least B rows when that fits
+  const long long per_row = (long long)cg.N * plan_cgen_lda(cg) * (long long)sizeof(float);
+  long long block_mb = 768;
+  if (const char* e = getenv("CGS_VMC_CONV_GENERAL_BLOCK_MB")) { block_mb = atoll(e); if (block_mb < 1) block_mb = 1; if (block_mb > 16384) block_mb = 16384; }
+  long long rows = (block_mb << 20) / per_row;
+  if (rows < 1) rows = 1;
+  if (rows > (1LL << 30) / cg.N) rows = (1LL << 30) / cg.N;          // rows * N: the M of a GEMM (int)
+  if (rows > (B > 65536 ? B : 65536)) rows = B > 65536 ? B : 65536;  // (small shapes: no point in hundreds of MB of maps)
+  // whole rounds of the chip for the 128-row tiles of a block's products (the local energies run many full blocks:
+  // 5.09 rounds of 256 CUs are paid as 6)
+  if (rows * cg.N / 128 >= 2LL * c->num_cus) {
+    const long long rounds = rows * cg.N / (128LL * c->num_cus);
+    rows = rounds * 128LL * c->num_cus / cg.N;
+  }
+  if (const char* e = getenv("CGS_VMC_CONV_GENERAL_BLOCK_ROWS")) { const long long r = atoll(e); if (r >= 1 && r < rows) rows = r; }   // tests: several blocks at small shapes
+  c->cg_rows = rows;
+  // (cg_A, the im2col matrix: allocated by the first launch that writes one -- cgen_need_A, vmc_api_cgen.hip)
+  // the band kernel (conv_band.hip) needs no im2col matrix: an untaped forward on it runs blocks sized by the two
+  // maps alone, up to 2 GB of them (36 x 36 x 16 filters: 370 rows per im2col block against 12,900 -- the local
+  // energies' 58 k rows were 110 blocks of partly filled launches)
+  long long rows_fwd = rows;
+  if (plan_cgen_band_ok(cg)) {
+    const long long per_row_maps = 2LL * cg.N * cgen_fp(cg) * (long long)sizeof(float);
+    rows_fwd = (2048LL << 20) / per_row_maps;
+    if (rows_fwd > (1LL << 30) / cg.N) rows_fwd = (1LL << 30) / cg.N;
+    if (rows_fwd > 131072) rows_fwd = 131072;
+    if (rows_fwd < rows) rows_fwd = rows;
+    if (getenv("CGS_VMC_CONV_GENERAL_BLOCK_ROWS")) rows_fwd = rows;      // tests: several blocks at small shapes
+  }
+  c->cg_rows_fwd = rows_fwd;
+  for (int i = 0; i < 2; ++i) NEW(c->cg_fm[i], rows_fwd * cg.N * cgen_fp(cg));
+  NEW(c->cg_sum, rows_fwd); NEW(c->cg_zero, 1); NEW(c->cg_lnew, B);
+  CA(hipMemsetAsync(c->cg_zero, 0, sizeof(float), c->stream));
+  NEW(c->wide_u, B); NEW(c->wide_iup, B); NEW(c->wide_idn, B);
+  return VMC_OK;
+}
+
+static int create_conv_fused(vmc_ctx* c) {
+  const ConvGeom& cg = c->cg;
+  const long long B = c->B;
+  const long long nl = cg.n_conv > 1 ? cg.n_conv - 1 : 1;
+  for (int w = 0; w < 2; ++w) {
+    ParamSet& p = c->ps[w];
+    NEW(p.cw0, plan_conv_w0_floats(cg)); NEW(p.cwf, plan_conv_wf_floats(cg));
+    NEW(p.cwb, plan_conv_wf_floats(cg));
+    NEW(p.cbias, plan_conv_bias_floats(cg));
+  }
+  const int nw = conv_waves(cg);
+  c->cG = conv_pick_group(cg, nw);
+  if (c->cG > B) c->cG = (int)B;
+  c->cGs = conv_pick_sweep_group(cg, B, c->num_cus, nw);     // chains per sampler workgroup (plan.hpp)
+  if (const char* e = getenv("CGS_VMC_CONV_SWEEP_G")) {     // measurement knob: chains per sampler workgroup
+    const int G = atoi(e);
+    if (G >= 1 && G <= 64 && conv_rows_lds(cg, G) <= conv_lds_cap(cg)) c->cGs = G < B ? G : (int)B;
+  }
+  c->ctape_stride = B * cg.CS; c->cdelta_stride = B * cg.CS;
+  NEW(c->ctape, nl * c->ctape_stride); NEW(c->cdelta, (long long)cg.n_conv * c->cdelta_stride);
+  c->c_slices = plan_conv_dw_slices(cg, B, c->num_cus);
+  NEW(c->cws, plan_conv_dw_ws_floats(cg, c->c_slices));
+  return VMC_OK;
+}
+
+static int create_buffers(vmc_ctx* c) {
+  const long long B = c->B, N = c->N, Hp = c->Hp, P = c->P, L = c->A, NH = c->n_hh;   // L: activation buffers
+  const bool nnb = c->path == PATH_NNB;
+  for (int w = 0; w < 2; ++w) {
+    ParamSet& p = c->ps[w];
+    NEW(p.theta, P);
+    NEW(p.w1p, N * Hp); NEW(p.b1p, Hp); NEW(p.bh, NH * Hp);
+    NEW(p.p16, (NH > 0 ? NH : 1) * Hp * Hp);
+    NEW(p.p16t, (NH > 0 ? NH : 1) * Hp * Hp);
+    CA(hipMemsetAsync(p.p16t, 0, (size_t)(NH > 0 ? NH : 1) * Hp * Hp * sizeof(float), c->stream));
+    CA(hipMemsetAsync(p.p16, 0, (size_t)(NH > 0 ? NH : 1) * Hp * Hp * sizeof(float), c->stream));
+    NEW(p.won, N); NEW(p.onsite, B);
+    CA(hipMemsetAsync(p.won, 0, N * sizeof(float), c->stream));
+    CA(hipMemsetAsync(p.onsite, 0, B * sizeof(float), c->stream));
+    NEW(p.woutp, Hp); NEW(p.bout, 1);
+    if (path_split(c->path)) NEW(p.p16s, pack_split_dwords((int)NH));
+    NEW(p.z1, B * Hp); NEW(p.logit, B); NEW(p.eloc, B);
+    if (w == 0) {
+      NEW(p.z1_alt, B * Hp); NEW(p.logit_alt, B); NEW(p.onsite_alt, B);
+      CA(hipMemsetAsync(p.onsite_alt, 0, B * sizeof(float), c->stream));
+    }
+  }
+  NEW(c->configs, B * N); NEW(c->configs_alt, B * N);
+  CA(hipMemsetAsync(c->configs, 0, B * N * sizeof(float), c->stream));
+  CA(hipMemsetAsync(c->configs_alt, 0, B * N * sizeof(float), c->stream));
+  c->act.resize(L, nullptr);
+  NEW(c->act_all, L * B * Hp); NEW(c->act_alt, L * B * Hp);
+  CA(hipMemsetAsync(c->act_all, 0, L * B * Hp * sizeof(float), c->stream));
+  CA(hipMemsetAsync(c->act_alt, 0, L * B * Hp * sizeof(float), c->stream));
+  {  // the sampler's stream outranks `stream`: where both have workgroups waiting for a CU, the sampler's go first
+    int least = 0, greatest = 0;
+    CA(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    CA(hipStreamCreateWithPriority(&c->sweep_stream, hipStreamNonBlocking, greatest));
+  }
+  CA(hipEventCreateWithFlags(&c->ev_mark, hipEventDisableTiming));
+  CA(hipEventCreateWithFlags(&c->ev_now, hipEventDisableTiming));
+  CA(hipEventCreateWithFlags(&c->ev_sweep_done, hipEventDisableTiming));
+  for (int l = 0; l < L; ++l) c->act[l] = c->act_all + l * B * Hp;
+  c->delta.resize(L, nullptr);
+  NEW(c->delta_all, L * B * Hp);
+  CA(hipMemsetAsync(c->delta_all, 0, L * B * Hp * sizeof(float), c->stream));
+  for (int l = 0; l < L; ++l) c->delta[l] = c->delta_all + l * B * Hp;
+  for (int i = 0; i < 4; ++i) NEW(c->d_batch[i / 2][i % 2], (L + 1) * (long long)wgrad_problem_bytes());
+  {  // weight-gradient launch: the tiles of all layers
+    // fully_connected on the kernels that run k_backprop16: the N = 1 output layer leaves the MFMA tile grid
+    // (CGS_VMC_WGRAD_OUT_TILES=1 keeps it there: A/B measurements)
+    const char* e_out = getenv("CGS_VMC_WGRAD_OUT_TILES");
+    c->wg_out_partials = !c->rbm && path_fused_dense(c->path) && !(e_out && atoi(e_out) == 1);
+    c->wg_tiles = nnb ? plan_nnb_wgrad_total_tiles((int)N, c->H, (int)NH)
+                      : plan_wgrad_total_tiles((int)N, c->H, (int)NH, c->rbm, !c->wg_out_partials);
+    // (nnb: hundreds of tiles and more -- the workspace follows the planned slices, not the bound)
+    if (nnb) c->nnb_wg_slices = plan_wgrad_slices(c->wg_tiles, B, c->num_cus, 1, 0);
+    if (c->wg_out_partials) NEW(c->wg_outpart, ((B + 15) / 16) * 2 * (Hp + 4));
+    NEW(c->wg_tickets, c->wg_tiles > 0 ? c->wg_tiles : 1);
+    CA(hipMemsetAsync(c->wg_tickets, 0, (size_t)(c->wg_tiles > 0 ? c->wg_tiles : 1) * sizeof(int), c->stream));
+  }
+  NEW(c->ratio, B); NEW(c->ones, B); NEW(c->oscale, B);
+  CA(launch_fill(c->stream, c->ones, 1.f, B));
+  CA(launch_fill(c->stream, c->oscale, 1.f, B));
+  if (c->hact == VMC_ACT_COS_) {
+    NEW(c->dact_all, L * B * Hp); NEW(c->dact_alt, L * B * Hp);
+    CA(hipMemsetAsync(c->dact_all, 0, L * B * Hp * sizeof(float), c->stream));
+    CA(hipMemsetAsync(c->dact_alt, 0, L * B * Hp * sizeof(float), c->stream));
+  }
+  // (vmc_create_product allocates the members sized by P -- theta of both sets, acc, adam_m, adam_v, grad_tmp -- anew
+  // at P_a + P_b: alloc frees what vmc_create put there)
+  NEW(c->acc, 2 * P + 8); NEW(c->adam_m, P); NEW(c->adam_v, P);
+  NEW(c->grad_tmp, P);
+  CA(hipMemsetAsync(c->acc, 0, (2 * P + 8) * sizeof(float), c->stream));
+  CA(hipMemsetAsync(c->adam_m, 0, P * sizeof(float), c->stream));
+  CA(hipMemsetAsync(c->adam_v, 0, P * sizeof(float), c->stream));
+  NEW(c->gemm_ws, plan_wgrad_ws_floats(c->wg_tiles, nnb ? c->nnb_wg_slices : WG_MAX_SPLIT));
+  NEW(c->d_accepted, 1); NEW(c->d_sum, 1); NEW(c->d_max, 1);
+  NEW(c->inj_up, B); NEW(c->inj_dn, B); NEW(c->inj_u, B);
+  NEW(c->acc_mask, B);
+  NEW(c->cnt, B); NEW(c->off, B + 1); NEW(c->diag, B);
+  NEW(c->cnt_alt, B); NEW(c->diag_alt, B);
+  NEW(c->rowinfo_id, B); CA(launch_iota_rows(c->stream, c->rowinfo_id, (int)B));
+  NEW(c->bond_dummy, 1); CA(hipMemsetAsync(c->bond_dummy, 0, sizeof(int2), c->stream));
+  NEW(c->offdiag, B);
+  switch (c->path) {
+    case PATH_FUSED: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP:
+    case PATH_PRODUCT:      // (vmc_create_product starts from a minimal PATH_FUSED ctx and adds its own)
+      break;
+    case PATH_FUSED_LDS: case PATH_DENSE_GENERAL:
+      c->wrows = B > 131072 ? B : 131072;
+      PROPAGATE(create_wide_rows(c));
+      break;
+    case PATH_NNB:
+      PROPAGATE(create_nnb_blocks(c));
+      PROPAGATE(create_wide_rows(c));
+      PROPAGATE(create_sign(c, false));
+      break;
+    case PATH_EDVEC:
+      PROPAGATE(create_sign(c, true));
+      PROPAGATE(create_edvec(c));
+      break;
+    case PATH_PBDG:
+      PROPAGATE(create_sign(c, true));
+      PROPAGATE(create_pbdg(c));
+      break;
+    case PATH_CONV_GENERAL: PROPAGATE(create_conv_general(c)); break;
+    case PATH_CONV: PROPAGATE(create_conv_fused(c)); break;
+  }
+  CA(hipStreamSynchronize(c->stream));
+  return VMC_OK;
+}
+#undef NEW
+#undef CA
 
 
 }  // namespace vmcapi
@@ -482,11 +736,6 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
     const int rc = plan_desc(d, !(wf && atoi(wf) == 0), &dp, msg, sizeof(msg), fg ? (atoi(fg) != 0 ? 1 : -1) : 0);
     if (rc != VMC_OK) return fail(nullptr, rc, msg);
   }
-  const bool rbm = dp.rbm != 0, conv = dp.conv != 0, wide = dp.wide != 0, wide_fast_ok = dp.wide_fast != 0;
-  const bool nnb = dp.nnb != 0, edvec = dp.edvec != 0;
-  const bool pbdg = dp.pbdg != 0;
-  const bool no_network = pbdg || edvec;     // theta is read as it lies: minimal dense-side shapes, no network buffers in use
-  const ConvGeom cg = dp.cg;
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev <= 0)
@@ -495,227 +744,48 @@ int vmc_create(const vmc_desc* d, vmc_ctx** out) {
   if ((e = hipSetDevice(d->device)) != hipSuccess)
     return fail(nullptr, VMC_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
 
+  const bool no_network = path_no_network(dp.path);     // minimal dense-side shapes, no network buffers in use
   vmc_ctx* c = new vmc_ctx();
   c->d = *d;
   c->N = d->n_sites; c->B = d->batch_size; c->L = d->num_layers; c->H = d->layer_size;
-  c->rbm = rbm;
-  c->conv = conv; c->cg = cg; c->conv_general = conv && dp.conv_general != 0;
-  if (conv) { c->L = 1; c->overlap = false; }   // minimal dense-side shapes (unused)
-  c->pbdg = pbdg; c->edvec = edvec;
+  c->rbm = dp.rbm != 0;
+  c->path = dp.path; c->cg = dp.cg;
+  if (path_conv(dp.path)) { c->L = 1; c->overlap = false; }   // minimal dense-side shapes (unused)
   if (no_network) { c->L = 1; c->H = 1; c->overlap = false; c->hact = VMC_ACT_RELU_; }
-  c->nnb = nnb; c->sgn = no_network || nnb;
-  if (nnb || edvec) c->ps[0].shift = c->ps[1].shift = 0.f;     // no exponent shift: psi = det M itself
-  c->wide = wide;
-  if (wide) c->overlap = false;
+  c->sgn = no_network || dp.path == PATH_NNB;
+  if (dp.path == PATH_NNB || dp.path == PATH_EDVEC) c->ps[0].shift = c->ps[1].shift = 0.f;     // no exponent shift: psi = det M itself
+  // more than 256 units: no overtaking sampler.  Of those, 257 .. 512 units (PATH_FUSED_LDS) run the fused sampler padded
+  // to 384 / 512 units (k_sweep16<24|32>), rows on the LDS-operand kernel (k_tail_lds; without an H x H layer: k_tail0)
+  // and the fused back-propagation (k_backprop16<24|32>); both dense ansatz types, every hidden activation
+  if (path_wide(dp.path)) c->overlap = false;
   // (pbdg, nnb: the activations of the desc are ignored -- relu trunk, amplitudes kept as (logit, sign))
   c->hact = c->sgn ? VMC_ACT_RELU_ : d->nonlinearity; c->oact = c->sgn ? VMC_ACT_EXP_ : d->output_activation;
   c->lay = dp.lay;
-  // 257 .. 512 units (wide_fast): the fused sampler padded to 384 / 512 units (k_sweep16<24|32>), rows on
-  // the LDS-operand kernel (k_tail_lds; without an H x H layer: k_tail0) and the fused back-propagation
-  // (k_backprop16<24|32>); both dense ansatz types, every hidden activation
-  c->wide_fast = wide_fast_ok;
   c->Hp = dp.Hp;
   c->n_hh = c->lay.n_hh; c->A = c->n_hh + 1;
   c->P = dp.P;
   c->stream = (hipStream_t)d->stream;
   if (const char* e = getenv("CGS_VMC_SWEEP_W1L")) c->sweep_no_w1l = atoi(e) == 0 ? 1 : 0;
-  if (const char* e = getenv("CGS_VMC_SPLIT_BF16")) {
-    c->split = (atoi(e) == 1 || atoi(e) == 2) && !conv && !wide && !rbm && c->Hp == 256 && c->n_hh >= 1 && c->hact == VMC_ACT_RELU_;
-    c->split_sweep = c->split && atoi(e) == 2 && sweep16_split_supported(c->N, c->Hp, c->n_hh);
+  if (const char* e = getenv("CGS_VMC_SPLIT_BF16"))
+    c->path = plan_split_path(dp, c->hact, atoi(e), sweep16_split_supported(c->N, c->Hp, c->n_hh));
+  if (const char* e = getenv("CGS_VMC_OVERLAP")) {
+    c->overlap = !path_conv(c->path) && !path_wide(c->path) && !no_network && atoi(e) != 0;
+    c->overlap_full = atoi(e) == 2;
   }
-  if (const char* e = getenv("CGS_VMC_OVERLAP")) { c->overlap = !conv && !wide && !no_network && atoi(e) != 0; c->overlap_full = atoi(e) == 2; }
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, d->device) == hipSuccess && prop.multiProcessorCount > 0)
       c->num_cus = prop.multiProcessorCount;
   }
   // eight-chain sampler tiles where sixteen-chain tiles would leave half of the chip idle (sweep8.hip)
-  c->sweep8_ok = !conv && !wide && !rbm && !no_network && c->hact == VMC_ACT_RELU_ && !c->split_sweep &&
+  c->sweep8_ok = (c->path == PATH_FUSED || c->path == PATH_SPLIT_ROWS) && !c->rbm && c->hact == VMC_ACT_RELU_ &&
                  plan_sweep8(c->N, c->Hp, c->n_hh, c->sweep_no_w1l != 0).ok;
   {
     int forced = 0;
     if (const char* e = getenv("CGS_VMC_SWEEP_TILE")) forced = atoi(e);
     c->sweep_tile = plan_sweep_tile(c->B, c->num_cus, c->sweep8_ok, forced);
   }
-  const long long B = c->B, N = c->N, Hp = c->Hp, P = c->P, L = c->A, NH = c->n_hh;   // L: activation buffers
-#define CA(expr) do { hipError_t e2 = (expr); if (e2 != hipSuccess) { \
-    g_create_error = std::string(#expr) + ": " + hipGetErrorString(e2); vmc_destroy(c); return VMC_ERR_HIP; } } while (0)
-#define NEW(buf, n) do { if ((buf).alloc(c, (n), #buf) != VMC_OK) { g_create_error = c->err; vmc_destroy(c); return VMC_ERR_HIP; } } while (0)
-  for (int w = 0; w < 2; ++w) {
-    ParamSet& p = c->ps[w];
-    NEW(p.theta, P);
-    NEW(p.w1p, N * Hp); NEW(p.b1p, Hp); NEW(p.bh, NH * Hp);
-    NEW(p.p16, (NH > 0 ? NH : 1) * Hp * Hp);
-    NEW(p.p16t, (NH > 0 ? NH : 1) * Hp * Hp);
-    CA(hipMemsetAsync(p.p16t, 0, (size_t)(NH > 0 ? NH : 1) * Hp * Hp * sizeof(float), c->stream));
-    CA(hipMemsetAsync(p.p16, 0, (size_t)(NH > 0 ? NH : 1) * Hp * Hp * sizeof(float), c->stream));
-    NEW(p.won, N); NEW(p.onsite, B);
-    CA(hipMemsetAsync(p.won, 0, N * sizeof(float), c->stream));
-    CA(hipMemsetAsync(p.onsite, 0, B * sizeof(float), c->stream));
-    NEW(p.woutp, Hp); NEW(p.bout, 1);
-    if (c->split) NEW(p.p16s, pack_split_dwords((int)NH));
-    NEW(p.z1, B * Hp); NEW(p.logit, B); NEW(p.eloc, B);
-    if (w == 0) {
-      NEW(p.z1_alt, B * Hp); NEW(p.logit_alt, B); NEW(p.onsite_alt, B);
-      CA(hipMemsetAsync(p.onsite_alt, 0, B * sizeof(float), c->stream));
-    }
-  }
-  NEW(c->configs, B * N); NEW(c->configs_alt, B * N);
-  CA(hipMemsetAsync(c->configs, 0, B * N * sizeof(float), c->stream));
-  CA(hipMemsetAsync(c->configs_alt, 0, B * N * sizeof(float), c->stream));
-  c->act.resize(L, nullptr);
-  NEW(c->act_all, L * B * Hp); NEW(c->act_alt, L * B * Hp);
-  CA(hipMemsetAsync(c->act_all, 0, L * B * Hp * sizeof(float), c->stream));
-  CA(hipMemsetAsync(c->act_alt, 0, L * B * Hp * sizeof(float), c->stream));
-  {  // the sampler's stream outranks `stream`: where both have workgroups waiting for a CU, the sampler's go first
-    int least = 0, greatest = 0;
-    CA(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    CA(hipStreamCreateWithPriority(&c->sweep_stream, hipStreamNonBlocking, greatest));
-  }
-  CA(hipEventCreateWithFlags(&c->ev_mark, hipEventDisableTiming));
-  CA(hipEventCreateWithFlags(&c->ev_now, hipEventDisableTiming));
-  CA(hipEventCreateWithFlags(&c->ev_sweep_done, hipEventDisableTiming));
-  for (int l = 0; l < L; ++l) c->act[l] = c->act_all + l * B * Hp;
-  c->delta.resize(L, nullptr);
-  NEW(c->delta_all, L * B * Hp);
-  CA(hipMemsetAsync(c->delta_all, 0, L * B * Hp * sizeof(float), c->stream));
-  for (int l = 0; l < L; ++l) c->delta[l] = c->delta_all + l * B * Hp;
-  for (int i = 0; i < 4; ++i) NEW(c->d_batch[i / 2][i % 2], (L + 1) * (long long)wgrad_problem_bytes());
-  {  // weight-gradient launch: the tiles of all layers
-    // fully_connected on the kernels that run k_backprop16: the N = 1 output layer leaves the MFMA tile grid
-    // (CGS_VMC_WGRAD_OUT_TILES=1 keeps it there: A/B measurements)
-    const char* e_out = getenv("CGS_VMC_WGRAD_OUT_TILES");
-    c->wg_out_partials = !rbm && !conv && !no_network && !(wide && !c->wide_fast) && !(e_out && atoi(e_out) == 1);
-    c->wg_tiles = nnb ? plan_nnb_wgrad_total_tiles((int)N, c->H, (int)NH)
-                      : plan_wgrad_total_tiles((int)N, c->H, (int)NH, rbm, !c->wg_out_partials);
-    // (nnb: hundreds of tiles and more -- the workspace follows the planned slices, not the bound)
-    if (nnb) c->nnb_wg_slices = plan_wgrad_slices(c->wg_tiles, B, c->num_cus, 1, 0);
-    if (c->wg_out_partials) NEW(c->wg_outpart, ((B + 15) / 16) * 2 * (Hp + 4));
-    NEW(c->wg_tickets, c->wg_tiles > 0 ? c->wg_tiles : 1);
-    CA(hipMemsetAsync(c->wg_tickets, 0, (size_t)(c->wg_tiles > 0 ? c->wg_tiles : 1) * sizeof(int), c->stream));
-  }
-  NEW(c->ratio, B); NEW(c->ones, B); NEW(c->oscale, B);
-  CA(launch_fill(c->stream, c->ones, 1.f, B));
-  CA(launch_fill(c->stream, c->oscale, 1.f, B));
-  if (c->hact == VMC_ACT_COS_) {
-    NEW(c->dact_all, L * B * Hp); NEW(c->dact_alt, L * B * Hp);
-    CA(hipMemsetAsync(c->dact_all, 0, L * B * Hp * sizeof(float), c->stream));
-    CA(hipMemsetAsync(c->dact_alt, 0, L * B * Hp * sizeof(float), c->stream));
-  }
-  // (vmc_create_product allocates the members sized by P -- theta of both sets, acc, adam_m, adam_v, grad_tmp -- anew
-  // at P_a + P_b: alloc frees what vmc_create put there)
-  NEW(c->acc, 2 * P + 8); NEW(c->adam_m, P); NEW(c->adam_v, P);
-  NEW(c->grad_tmp, P);
-  CA(hipMemsetAsync(c->acc, 0, (2 * P + 8) * sizeof(float), c->stream));
-  CA(hipMemsetAsync(c->adam_m, 0, P * sizeof(float), c->stream));
-  CA(hipMemsetAsync(c->adam_v, 0, P * sizeof(float), c->stream));
-  NEW(c->gemm_ws, plan_wgrad_ws_floats(c->wg_tiles, nnb ? c->nnb_wg_slices : WG_MAX_SPLIT));
-  NEW(c->d_accepted, 1); NEW(c->d_sum, 1); NEW(c->d_max, 1);
-  NEW(c->inj_up, B); NEW(c->inj_dn, B); NEW(c->inj_u, B);
-  NEW(c->acc_mask, B);
-  NEW(c->cnt, B); NEW(c->off, B + 1); NEW(c->diag, B);
-  NEW(c->cnt_alt, B); NEW(c->diag_alt, B);
-  NEW(c->rowinfo_id, B); CA(launch_iota_rows(c->stream, c->rowinfo_id, (int)B));
-  NEW(c->bond_dummy, 1); CA(hipMemsetAsync(c->bond_dummy, 0, sizeof(int2), c->stream));
-  NEW(c->offdiag, B);
-  if (wide) {
-    c->wrows = B > 131072 ? B : 131072;
-    if (nnb) {   // blocks of rows whose dense pairing layer takes CGS_VMC_NNB_BLOCK_MB (default 256) MiB
-      long long mb = PLAN_NNB_BLOCK_MB_DEFAULT;
-      if (const char* e = getenv("CGS_VMC_NNB_BLOCK_MB")) mb = atoll(e);
-      c->nnb_rows = plan_nnb_block_rows((int)N, mb);
-      if (const char* e = getenv("CGS_VMC_NNB_BLOCK_ROWS")) { const long long r = atoll(e); if (r >= 1 && r < c->nnb_rows) c->nnb_rows = r; }   // tests: several blocks at small shapes
-      c->wrows = c->nnb_rows;
-      NEW(c->nnb_out, c->nnb_rows * N * N);
-      NEW(c->nnb_delta, B * N * N);
-      NEW(c->nnb_cl, B); NEW(c->nnb_cs, B);
-    }
-    NEW(c->wbuf[0], c->wrows * Hp); NEW(c->wbuf[1], c->wrows * Hp);
-    NEW(c->wide_u, B);
-    NEW(c->wide_dot, (long long)gemm_rowdot_tiles(c->H) * c->wrows);
-    NEW(c->wide_iup, B); NEW(c->wide_idn, B); NEW(c->wide_zero, Hp);
-    CA(hipMemsetAsync(c->wide_zero, 0, Hp * sizeof(float), c->stream));
-  }
-  if (c->sgn)
-    for (int w = 0; w < 2; ++w) {
-      NEW(c->ps[w].sign, B);
-      CA(hipMemsetAsync(c->ps[w].sign, 0, B * sizeof(float), c->stream));
-    }
-  if (edvec) {
-    NEW(c->ps[0].sign_alt, B);
-    CA(hipMemsetAsync(c->ps[0].sign_alt, 0, B * sizeof(float), c->stream));
-    NEW(c->ed_keys, B); NEW(c->ed_keys_sorted, B);
-    CA(edvec_sort_bytes((int)B, (int)P, &c->ed_sort_bytes));
-    NEW(c->ed_sort_tmp, (long long)c->ed_sort_bytes);
-    c->ed_tables_lds = plan_edvec_tables_in_lds((int)N) && !(getenv("CGS_VMC_EDVEC_TABLES_LDS") && atoi(getenv("CGS_VMC_EDVEC_TABLES_LDS")) == 0);
-    if (c->ed_tables_lds) CA(edvec_sweep_reserve_lds((int)N));
-  } else if (pbdg) {
-    const long long n = N / 2;
-    NEW(c->ps[0].sign_alt, B);
-    CA(hipMemsetAsync(c->ps[0].sign_alt, 0, B * sizeof(float), c->stream));
-    NEW(c->pbdg_inv, B * n * n); NEW(c->pbdg_pos, B * N);
-    c->pbdg_slices = plan_pbdg_grad_slices(P, B, c->num_cus);
-    NEW(c->pbdg_ws, plan_pbdg_grad_ws_doubles(P, c->pbdg_slices));
-  }
-  if (conv && c->conv_general) {
-    // blocks of at most ~768 MB of im2col rows (one row configuration at least), at least B rows when that fits
-    const long long per_row = (long long)cg.N * plan_cgen_lda(cg) * (long long)sizeof(float);
-    long long block_mb = 768;
-    if (const char* e = getenv("CGS_VMC_CONV_GENERAL_BLOCK_MB")) { block_mb = atoll(e); if (block_mb < 1) block_mb = 1; if (block_mb > 16384) block_mb = 16384; }
-    long long rows = (block_mb << 20) / per_row;
-    if (rows < 1) rows = 1;
-    if (rows > (1LL << 30) / cg.N) rows = (1LL << 30) / cg.N;          // rows * N: the M of a GEMM (int)
-    if (rows > (B > 65536 ? B : 65536)) rows = B > 65536 ? B : 65536;  // (small shapes: no point in hundreds of MB of maps)
-    // whole rounds of the chip for the 128-row tiles of a block's products (the local energies run many full blocks:
-    // 5.09 rounds of 256 CUs are paid as 6)
-    if (rows * cg.N / 128 >= 2LL * c->num_cus) {
-      const long long rounds = rows * cg.N / (128LL * c->num_cus);
-      rows = rounds * 128LL * c->num_cus / cg.N;
-    }
-    if (const char* e = getenv("CGS_VMC_CONV_GENERAL_BLOCK_ROWS")) { const long long r = atoll(e); if (r >= 1 && r < rows) rows = r; }   // tests: several blocks at small shapes
-    c->cg_rows = rows;
-    // (cg_A, the im2col matrix: allocated by the first launch that writes one -- cgen_need_A, vmc_api_cgen.hip)
-    // the band kernel (conv_band.hip) needs no im2col matrix: an untaped forward on it runs blocks sized by the two
-    // maps alone, up to 2 GB of them (36 x 36 x 16 filters: 370 rows per im2col block against 12,900 -- the local
-    // energies' 58 k rows were 110 blocks of partly filled launches)
-    long long rows_fwd = rows;
-    if (plan_cgen_band_ok(cg)) {
-      const long long per_row_maps = 2LL * cg.N * cgen_fp(cg) * (long long)sizeof(float);
-      rows_fwd = (2048LL << 20) / per_row_maps;
-      if (rows_fwd > (1LL << 30) / cg.N) rows_fwd = (1LL << 30) / cg.N;
-      if (rows_fwd > 131072) rows_fwd = 131072;
-      if (rows_fwd < rows) rows_fwd = rows;
-      if (getenv("CGS_VMC_CONV_GENERAL_BLOCK_ROWS")) rows_fwd = rows;      // tests: several blocks at small shapes
-    }
-    c->cg_rows_fwd = rows_fwd;
-    for (int i = 0; i < 2; ++i) NEW(c->cg_fm[i], rows_fwd * cg.N * cgen_fp(cg));
-    NEW(c->cg_sum, rows_fwd); NEW(c->cg_zero, 1); NEW(c->cg_lnew, B);
-    CA(hipMemsetAsync(c->cg_zero, 0, sizeof(float), c->stream));
-    NEW(c->wide_u, B); NEW(c->wide_iup, B); NEW(c->wide_idn, B);
-  } else if (conv) {
-    const long long nl = cg.n_conv > 1 ? cg.n_conv - 1 : 1;
-    for (int w = 0; w < 2; ++w) {
-      ParamSet& p = c->ps[w];
-      NEW(p.cw0, plan_conv_w0_floats(cg)); NEW(p.cwf, plan_conv_wf_floats(cg));
-      NEW(p.cwb, plan_conv_wf_floats(cg));
-      NEW(p.cbias, plan_conv_bias_floats(cg));
-    }
-    const int nw = conv_waves(cg);
-    c->cG = conv_pick_group(cg, nw);
-    if (c->cG > B) c->cG = (int)B;
-    c->cGs = conv_pick_sweep_group(cg, B, c->num_cus, nw);     // chains per sampler workgroup (plan.hpp)
-    if (const char* e = getenv("CGS_VMC_CONV_SWEEP_G")) {     // measurement knob: chains per sampler workgroup
-      const int G = atoi(e);
-      if (G >= 1 && G <= 64 && conv_rows_lds(cg, G) <= conv_lds_cap(cg)) c->cGs = G < B ? G : (int)B;
-    }
-    c->ctape_stride = B * cg.CS; c->cdelta_stride = B * cg.CS;
-    NEW(c->ctape, nl * c->ctape_stride); NEW(c->cdelta, (long long)cg.n_conv * c->cdelta_stride);
-    c->c_slices = plan_conv_dw_slices(cg, B, c->num_cus);
-    NEW(c->cws, plan_conv_dw_ws_floats(cg, c->c_slices));
-  }
-  CA(hipStreamSynchronize(c->stream));
-#undef NEW
-#undef CA
+  if (create_buffers(c) != VMC_OK) { vmc_destroy(c); return VMC_ERR_HIP; }     // (g_create_error names the failure)
   *out = c;
   return VMC_OK;
 }
@@ -803,7 +873,7 @@ int vmc_set_adjacency(vmc_ctx* c, int32_t n_sites, int32_t k, const int32_t* adj
 
 int vmc_set_lin_tables(vmc_ctx* c, int32_t n_half, const int32_t* top, const int32_t* bot) {
   ENTER(c);
-  if (!c->edvec) return fail(c, VMC_ERR_INVALID, "vmc_set_lin_tables: not an ed_vector ctx");
+  if (c->path != PATH_EDVEC) return fail(c, VMC_ERR_INVALID, "vmc_set_lin_tables: not an ed_vector ctx");
   {
     char msg[256];
     const int rc = plan_edvec_check_tables(c->N, n_half, top, bot, c->P, msg, sizeof(msg));
@@ -812,7 +882,7 @@ int vmc_set_lin_tables(vmc_ctx* c, int32_t n_half, const int32_t* top, const int
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (!c->ed_bot) PROPAGATE(c->ed_bot.alloc(c, n_half, "ed_bot"));
   HIPCHK(c, hipMemcpy(c->ed_bot, bot, (size_t)n_half * sizeof(int32_t), hipMemcpyHostToDevice));
-  if (!c->ed_top) PROPAGATE(c->ed_top.alloc(c, n_half, "ed_top"));      // (set last: gnn_ready takes it as "tables present")
+  if (!c->ed_top) PROPAGATE(c->ed_top.alloc(c, n_half, "ed_top"));      // (set last: late_inputs_set takes it as "tables present")
   HIPCHK(c, hipMemcpy(c->ed_top, top, (size_t)n_half * sizeof(int32_t), hipMemcpyHostToDevice));
   c->ps[0].cache_valid = c->ps[1].cache_valid = false;     // (the amplitudes of the chains belong to the previous tables)
   return VMC_OK;
@@ -856,7 +926,7 @@ int vmc_set_configs(vmc_ctx* c, const float* configs) {
   ENTER(c);
   REFUSE_COMPOSED(c);
   if (!configs) return fail(c, VMC_ERR_INVALID, "null configs");
-  PROPAGATE(pbdg_check_sz(c, configs, c->B));
+  PROPAGATE(check_sz0_rows(c, configs, c->B));
   const long long n = (long long)c->B * c->N;
   // staged in the alternate chain buffer (free between sampler launches), validated on the
   // device, and only then made current: a rejected batch leaves the chains untouched
@@ -883,8 +953,14 @@ int vmc_get_configs(vmc_ctx* c, float* configs) {
 int vmc_set_shift(vmc_ctx* c, int which, float shift) {
   CHECK_CTX(c);
   if (which != 0 && which != 1) return fail(c, VMC_ERR_INVALID, "bad which");
-  if (c->prod) return fail(c, VMC_ERR_INVALID, "prod: the product has no exponent shift of its own (set the factors')");
-  if (!c->nnb && !c->edvec) c->ps[which].shift = shift;     // (neural-network backflow, ed_vector: no exponent shift, it stays 0)
+  switch (c->path) {
+    case PATH_PRODUCT: return fail(c, VMC_ERR_INVALID, "prod: the product has no exponent shift of its own (set the factors')");
+    case PATH_NNB: case PATH_EDVEC: break;     // (neural-network backflow, ed_vector: no exponent shift, it stays 0)
+    case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_CONV: case PATH_SPLIT_ROWS:
+    case PATH_SPLIT_SWEEP: case PATH_CONV_GENERAL: case PATH_PBDG:
+      c->ps[which].shift = shift;
+      break;
+  }
   return VMC_OK;
 }
 
@@ -910,7 +986,7 @@ int vmc_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, f
       HIPCHK(c, hipMemcpyAsync(hsign.data(), c->ps[which].sign, n_rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   } else if (n_rows > 0) {
     PROPAGATE(ensure_packed(c, which));
-    PROPAGATE(pbdg_check_sz(c, configs, n_rows));
+    PROPAGATE(check_sz0_rows(c, configs, n_rows));
     PROPAGATE(grow_tmp(c, n_rows));
     HIPCHK(c, hipMemcpyAsync(c->tmp_cfg, configs, n_rows * c->N * sizeof(float), hipMemcpyHostToDevice, c->stream));
     PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, n_rows, c->tmp_out, c->tmp_sign));
@@ -922,10 +998,17 @@ int vmc_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, f
   const float shift = c->ps[which].shift;
   for (int64_t i = 0; i < n_rows; ++i) {
     if (logit) logit[i] = host[i];
-    // wavefunctions.py:350-353: exp(x - shift) (232), or the output activation itself, no shift
-    if (psi) psi[i] = c->edvec ? hsign[i]                               // the gathered entry itself
-                              : c->sgn ? hsign[i] * expf(host[i] - shift)      // signed: sign(det M) exp(logit - shift)
-                              : c->oact == VMC_ACT_EXP_ ? expf(host[i] - shift) : host_activation(c->oact, host[i]);
+    if (!psi) continue;
+    switch (c->path) {
+      case PATH_EDVEC: psi[i] = hsign[i]; break;                                   // the gathered entry itself
+      case PATH_PBDG: case PATH_NNB: psi[i] = hsign[i] * expf(host[i] - shift); break;     // sign(det M) exp(logit - shift)
+      case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_CONV: case PATH_SPLIT_ROWS:
+      case PATH_SPLIT_SWEEP: case PATH_CONV_GENERAL:
+        // wavefunctions.py:350-353: exp(x - shift) (232), or the output activation itself, no shift
+        psi[i] = c->oact == VMC_ACT_EXP_ ? expf(host[i] - shift) : host_activation(c->oact, host[i]);
+        break;
+      case PATH_PRODUCT: break;                                                    // (prod_amplitude, above)
+    }
   }
   return VMC_OK;
 }
@@ -961,7 +1044,7 @@ int vmc_local_energy_terms(vmc_ctx* c, int which, float* diag, float* offdiag_ov
 int vmc_debug_kernel_path(vmc_ctx* c, int32_t* path) {
   CHECK_CTX(c);
   if (!path) return fail(c, VMC_ERR_INVALID, "null");
-  *path = c->prod ? 10 : c->edvec ? 9 : c->nnb ? 8 : c->pbdg ? 7 : c->conv ? (c->conv_general ? 6 : 3) : (c->wide ? (c->wide_fast ? 1 : 2) : (c->split ? (c->split_sweep ? 5 : 4) : 0));
+  *path = c->path;
   return VMC_OK;
 }
 

@@ -98,7 +98,7 @@ const float* cgen_last_map(const vmc_ctx* c) {
 // CGS_VMC_CONV_PATCH=0 | 2, read per call (tests compare the two forms in one process); a box has the BAND kernel's bits, so not
 // with CGS_VMC_CONV_BAND=0.
 int cgen_patch_mode(const vmc_ctx* c) {
-  if (!c->conv_general) return 0;
+  if (c->path != PATH_CONV_GENERAL) return 0;
   const char* pe = getenv("CGS_VMC_CONV_PATCH");
   const int mode = pe ? atoi(pe) : 1;
   if (mode == 0 || !cgen_band_on() || !cgen_patch_ok(c->cg, c->B)) return 0;
@@ -139,7 +139,7 @@ int cgen_forward(vmc_ctx* c, int which, const float* configs, const int2* rowinf
   const long long moff = c->cg_map_row0 * g.N * Fp;      // (a sampler group's slice of the maps; 0 elsewhere)
   auto map = [&](int l) { return tape ? tape + (long long)l * tape_stride : c->cg_fm[g.resnet ? (l & 1 ? 1 : 0) : (l & 1)] + moff; };
   if (tape && n_rows > c->cg_rows) return fail(c, VMC_ERR_STATE, "taped forward beyond one block");
-  PROPAGATE(gnn_ready(c));
+  PROPAGATE(late_inputs_set(c));
   // The rows of a row list over the ctx's chains -- the local energies' connected configurations (operators.py:162-169:
   // the chain with one antiparallel bond exchanged) -- through the patch kernel: the chains' maps once (B forwards), then
   // per row the boxes around the bond's two sites and the last map's sum with them overlaid; the sums are k_cgen_rowsum's
@@ -310,7 +310,7 @@ int cgen_gradient_sums(vmc_ctx* c, const float* w) {
   c->cg_sr_tape_rows = 0;                  // (this path overwrites the tapes an SR solve may have left)
   const ConvGeom& g = c->cg;
   ParamSet& p = c->ps[0];
-  PROPAGATE(gnn_ready(c));
+  PROPAGATE(late_inputs_set(c));
   PROPAGATE(cgen_grad_buffers(c));
   const long long map_floats = c->cg_rows * g.N * cgen_fp(g);
   for (int l = 1; l < g.n_conv && plan_cgen_periodic(g); ++l)      // (gnn: the products read theta transposed)
@@ -356,7 +356,7 @@ static int cgen_sr_fwd_bwd(vmc_ctx* c, long long row0, int rows, long long n_row
 int cgen_sr_phase1(vmc_ctx* c, const float* v, int n_rows) {        // sr_t[b] = O_b . v
   const ConvGeom& g = c->cg;
   ParamSet& p = c->ps[0];
-  PROPAGATE(gnn_ready(c));
+  PROPAGATE(late_inputs_set(c));
   PROPAGATE(cgen_grad_buffers(c));
   if (!c->cg_centre) { PROPAGATE(c->cg_td.alloc(c, c->cg_rows, "cg_td")); PROPAGATE(c->cg_centre.alloc(c, 1, "cg_centre")); }
   const int Fp = cgen_fp(g), lda = plan_cgen_lda(g);

@@ -299,7 +299,7 @@ int prod_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, 
     finish(0, B);
     return VMC_OK;
   }
-  PROPAGATE(pbdg_check_sz(c, configs, n_rows));
+  PROPAGATE(check_sz0_rows(c, configs, n_rows));
   vmc_ctx *a = st->child[0], *b = st->child[1];
   std::vector<float> blk((size_t)B * N);
   for (int64_t row0 = 0; row0 < n_rows; row0 += B) {
@@ -350,9 +350,10 @@ int vmc_create_product(vmc_ctx* a, vmc_ctx* b, vmc_ctx** out) {
   PROPAGATE(vmc_create(&d, &c));
   DeviceGuard device_guard_(c->d.device);
   c->d.ansatz = VMC_ANSATZ_PRODUCT;
+  c->path = PATH_PRODUCT;
   c->overlap = false;
   c->sweep8_ok = false; c->sweep_tile = 16;
-  c->sgn = a->sgn || b->sgn;                  // Sz = 0 rows only, as for the signed factor alone (pbdg_check_sz)
+  c->sgn = a->sgn || b->sgn;                  // Sz = 0 rows only, as for the signed factor alone (check_sz0_rows)
   c->ps[0].shift = c->ps[1].shift = 0.f;
   ProdState* st = new ProdState();
   c->prod = st;

@@ -22,12 +22,14 @@ extern "C" {
 int vmc_sr_reserve(vmc_ctx* c, int32_t n_batches) {
   ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_reserve)");
   if (n_batches < 0) return fail(c, VMC_ERR_INVALID, "n_batches < 0");
-  if (n_batches > 0 && c->nnb)
-    return fail(c, VMC_ERR_UNSUPPORTED, "stochastic reconfiguration is not implemented for the fully_connected_nnb ansatz (use EnergyGradient or LogOverlapITSWO)");
-  if (n_batches > 0 && c->edvec)
-    return fail(c, VMC_ERR_UNSUPPORTED, "stochastic reconfiguration is not implemented for the ed_vector ansatz (use EnergyGradient or LogOverlapITSWO)");
-  if (n_batches > 0 && c->pbdg)
-    return fail(c, VMC_ERR_UNSUPPORTED, "stochastic reconfiguration is not implemented for the pbdg ansatz (use EnergyGradient or LogOverlapITSWO)");
+  if (n_batches > 0)
+    switch (c->path) {
+      case PATH_NNB: case PATH_EDVEC: case PATH_PBDG:
+        return fail(c, VMC_ERR_UNSUPPORTED, std::string("stochastic reconfiguration is not implemented for the ") + signed_family_name(c->path) +
+                                            " ansatz (use EnergyGradient or LogOverlapITSWO)");
+      case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_CONV: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP:
+      case PATH_CONV_GENERAL: case PATH_PRODUCT: break;      // (a product: REFUSE_PRODUCT, above)
+    }
   if (n_batches > 0 && c->oact != VMC_ACT_EXP_)
     return fail(c, VMC_ERR_UNSUPPORTED, "stochastic reconfiguration (an extension) covers the exp output activation (every hidden activation)");
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -36,15 +38,13 @@ int vmc_sr_reserve(vmc_ctx* c, int32_t n_batches) {
                            &c->sr_cws, &c->sr_tpart}) q->release();
   if (n_batches == 0) return VMC_OK;
   const long long B = c->B, N = c->N, Hp = c->Hp, L = c->A, R = (long long)n_batches * B;
-  if (c->conv_general) {       // the chains are all that is stored (cgen_sr_matvec; single-rank solves only)
+  switch (c->path) {
+  case PATH_CONV_GENERAL:      // the chains are all that is stored (cgen_sr_matvec; single-rank solves only)
     if (R * N >= (1LL << 31)) return fail(c, VMC_ERR_UNSUPPORTED, "SR sample store too large (rows * sites >= 2^31)");
     PROPAGATE(c->sr_cfg.alloc(c, R * N, "sr_cfg"));
     PROPAGATE(c->sr_t.alloc(c, R, "sr_t"));
-    PROPAGATE(sr_cg_vectors(c));
-    c->sr_cap = n_batches;
-    return VMC_OK;
-  }
-  if (c->conv) {
+    break;
+  case PATH_CONV: {
     const ConvGeom& cg = c->cg;
     const long long CS = cg.CS, nc = cg.n_conv, nl = nc > 1 ? nc - 1 : 1;
     if (R * CS >= (1LL << 31)) return fail(c, VMC_ERR_UNSUPPORTED, "SR sample store too large (rows * feature-map size >= 2^31)");
@@ -57,18 +57,20 @@ int vmc_sr_reserve(vmc_ctx* c, int32_t n_batches) {
       PROPAGATE(c->sr_cw0.alloc(c, plan_conv_w0_floats(cg), "sr_cw0")); PROPAGATE(c->sr_cwf.alloc(c, plan_conv_wf_floats(cg), "sr_cwf"));
       PROPAGATE(c->sr_cwb.alloc(c, plan_conv_wf_floats(cg), "sr_cwb")); PROPAGATE(c->sr_cbias.alloc(c, plan_conv_bias_floats(cg), "sr_cbias"));
     }
-    PROPAGATE(sr_cg_vectors(c));
-    c->sr_cap = n_batches;
-    return VMC_OK;
+    break;
   }
-  if (R > 0x7fffffffLL / Hp) return fail(c, VMC_ERR_UNSUPPORTED, "SR sample store too large (rows * Hp >= 2^31)");
-  PROPAGATE(c->sr_cfg.alloc(c, R * N, "sr_cfg"));
-  PROPAGATE(c->sr_act.alloc(c, L * R * Hp, "sr_act"));
-  PROPAGATE(c->sr_delta.alloc(c, L * R * Hp, "sr_delta"));
-  PROPAGATE(c->sr_ws.alloc(c, (long long)sr_wsum_slices((int)R, c->num_cus) * ((N > c->H ? N : c->H) + 1) * c->H, "sr_ws"));
-  PROPAGATE(c->sr_t.alloc(c, R, "sr_t")); PROPAGATE(c->sr_ones.alloc(c, R, "sr_ones"));
-  PROPAGATE(c->sr_tpart.alloc(c, L * ((c->H + 255) / 256) * R, "sr_tpart"));
-  HIPCHK(c, launch_fill(c->stream, c->sr_ones, 1.f, R));
+  case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP:
+  case PATH_PBDG: case PATH_NNB: case PATH_EDVEC: case PATH_PRODUCT:     // (the last four were refused above)
+    if (R > 0x7fffffffLL / Hp) return fail(c, VMC_ERR_UNSUPPORTED, "SR sample store too large (rows * Hp >= 2^31)");
+    PROPAGATE(c->sr_cfg.alloc(c, R * N, "sr_cfg"));
+    PROPAGATE(c->sr_act.alloc(c, L * R * Hp, "sr_act"));
+    PROPAGATE(c->sr_delta.alloc(c, L * R * Hp, "sr_delta"));
+    PROPAGATE(c->sr_ws.alloc(c, (long long)sr_wsum_slices((int)R, c->num_cus) * ((N > c->H ? N : c->H) + 1) * c->H, "sr_ws"));
+    PROPAGATE(c->sr_t.alloc(c, R, "sr_t")); PROPAGATE(c->sr_ones.alloc(c, R, "sr_ones"));
+    PROPAGATE(c->sr_tpart.alloc(c, L * ((c->H + 255) / 256) * R, "sr_tpart"));
+    HIPCHK(c, launch_fill(c->stream, c->sr_ones, 1.f, R));
+    break;
+  }
   PROPAGATE(sr_cg_vectors(c));
   c->sr_cap = n_batches;
   return VMC_OK;
@@ -99,24 +101,23 @@ int vmc_sr_begin(vmc_ctx* c, double* rr0) {
   return sr_read_rr(c, 0, rr0);
 }
 
-// u[0..P) = sum over this rank's stored samples of (O_b . p) O_b,  u[P] = sum (O_b . p)
-int vmc_sr_matvec_partial(vmc_ctx* c) {
-  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_matvec_partial)");
-  if (!c->sr_begun) return fail(c, VMC_ERR_STATE, "vmc_sr_begin first");
+// u[0..P) = sum over this rank's stored samples of (O_b . p) O_b,  u[P] = sum (O_b . p): the body of
+// vmc_sr_matvec_partial and, off the general convolution path, of vmc_sr_matvec_phase2 (the entry has been entered)
+static int sr_matvec(vmc_ctx* c) {
   const int B = c->B, N = c->N, H = c->H, Hp = c->Hp, L = c->A;
   const long long R = (long long)c->sr_cap * B;   // row stride between layers of the store
   const int rows = c->sr_n * B;                   // all recorded samples in one pass
   const float* v = c->sr_p;
   Timer t(c, "sr_matvec");
   HIPCHK(c, hipMemsetAsync(c->sr_u, 0, (c->P + 1) * sizeof(float), c->stream));
-  if (c->conv_general) {
+  switch (c->path) {
+  case PATH_CONV_GENERAL:
     if (!c->sr_centre)
       return fail(c, VMC_ERR_UNSUPPORTED, "on the general convolution path the op-by-op matvec is vmc_sr_matvec_phase1 -> all-reduce of the buffer's "
                                           "last float -> vmc_sr_matvec_phase2 (its per-sample weights are centred on the mean over ALL ranks, which "
                                           "vmc_sr_matvec_partial cannot know); or vmc_sr_solve / vmc_sr_solve_dist");
     return cgen_sr_matvec(c, v, rows);
-  }
-  if (c->conv) {
+  case PATH_CONV: {
     // t_b = O_b . p: the CG direction packed like a parameter set, convolved with the taped inputs and
     // dotted with the stored deltas (k_conv_sr_rowdot); u = sum_b t_b O_b: the weight-gradient kernel
     // over the stored samples with per-sample weight t_b (the unweighted sum is skipped)
@@ -136,6 +137,10 @@ int vmc_sr_matvec_partial(vmc_ctx* c) {
     HIPCHK(c, launch_conv_dw(c->stream, dw));
     HIPCHK(c, launch_sr_tsum(c->stream, c->sr_t, rows, c->sr_u + c->P));
     return VMC_OK;
+  }
+  case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP:
+  case PATH_PBDG: case PATH_NNB: case PATH_EDVEC: case PATH_PRODUCT:     // (the last four have no store: never begun)
+    break;      // the dense store, below
   }
   // t_b = O_b . p = sum_l delta_l[b] . (a_{l-1}[b] V_l + v_l) + (output / onsite layer term);
   // the row-dot kernel takes <= 256 output units at a time (257 .. 512 units: two column blocks)
@@ -186,6 +191,12 @@ int vmc_sr_matvec_partial(vmc_ctx* c) {
     HIPCHK(c, launch_sr_colsum(c->stream, c->sr_act + (long long)(L - 1) * R * Hp, Hp, c->sr_t, rows, H,
                                c->sr_ws, slices, c->sr_u + off_wout(c), c->sr_u + c->P));
   return VMC_OK;
+}
+
+int vmc_sr_matvec_partial(vmc_ctx* c) {
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_matvec_partial)");
+  if (!c->sr_begun) return fail(c, VMC_ERR_STATE, "vmc_sr_begin first");
+  return sr_matvec(c);
 }
 
 int vmc_sr_buffer_devptr(vmc_ctx* c, void** dev_ptr, int64_t* n_floats) {
@@ -243,7 +254,7 @@ struct SrCentreScope {
 int vmc_sr_matvec_phase1(vmc_ctx* c) {
   ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_matvec_phase1)");
   if (!c->sr_begun) return fail(c, VMC_ERR_STATE, "vmc_sr_begin first");
-  if (!c->conv_general) return VMC_OK;
+  if (c->path != PATH_CONV_GENERAL) return VMC_OK;
   const int rows = c->sr_n * c->B;
   Timer t(c, "sr_matvec");
   HIPCHK(c, hipMemsetAsync(c->sr_u, 0, (c->P + 1) * sizeof(float), c->stream));
@@ -256,7 +267,7 @@ int vmc_sr_matvec_phase1(vmc_ctx* c) {
 int vmc_sr_matvec_phase2(vmc_ctx* c) {
   ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_matvec_phase2)");
   if (!c->sr_begun) return fail(c, VMC_ERR_STATE, "vmc_sr_begin first");
-  if (!c->conv_general) return vmc_sr_matvec_partial(c);
+  if (c->path != PATH_CONV_GENERAL) return sr_matvec(c);
   if (!c->sr_phase1_done) return fail(c, VMC_ERR_STATE, "vmc_sr_matvec_phase1 first");
   c->sr_phase1_done = false;
   const int rows = c->sr_n * c->B;
@@ -276,7 +287,7 @@ static int sr_solve_impl(vmc_ctx* c, void* comm, int world, float diag_shift, fl
   int it = 0;
   SrCentreScope centre(c, !sharded(comm, world));   // (general convolution path: see cgen_sr_matvec)
   while (it < max_iter && rr > (double)tol * (double)tol * rr0 && rr0 > 0.0) {
-    if (c->conv_general && sharded(comm, world)) {
+    if (c->path == PATH_CONV_GENERAL && sharded(comm, world)) {
       // the general convolution path centres its weights on the mean of O_b . p over ALL ranks (cgen_sr_matvec): one more
       // all-reduce, of sum_b O_b . p alone, between its two phases
       const int rows = c->sr_n * c->B;

@@ -13,22 +13,16 @@ namespace vmcapi {
 // accept -- a handful of launches per step, chain state updated in place
 // the sampler launch of this ctx (the 3 x bf16 split sampler when it is switched on)
 static hipError_t launch_sampler(vmc_ctx* c, hipStream_t st, SweepArgs& a, int which) {
-  if (c->split_sweep) { a.p16s = c->ps[which].p16s; return launch_sweep16_split(st, a); }
+  if (c->path == PATH_SPLIT_SWEEP) { a.p16s = c->ps[which].p16s; return launch_sweep16_split(st, a); }
   // (injected proposals, the proposal dump and the diagnostic stamps stay on k_sweep16: the same chains, bit for bit)
   if (c->sweep_tile == 8 && !a.inj_up && !a.dbg_up && !a.acc_mask) return launch_sweep8(st, a, c->Hp);
   return launch_sweep16(st, a, c->Hp);
 }
 
-static int run_sweep_wide(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn,
-                          float* dbg_u, unsigned long long step0, bool count_accepted) {
+static int run_sweep_wide(vmc_ctx* c, long long n_steps, bool injected, unsigned long long step0, bool count_accepted) {
   ParamSet& p = c->ps[0];
   const int B = c->B, N = c->N, H = c->H, Hp = c->Hp, NH = c->n_hh;
   const uint32_t seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull), seed_hi = (uint32_t)(c->d.seed >> 32);
-  if (dbg) {
-    HIPCHK(c, launch_wide_propose(c->stream, c->configs, B, N, seed_lo, seed_hi, c->d.chain_offset, step0, nullptr,
-                                  nullptr, nullptr, dbg_up, dbg_dn, dbg_u));
-    return VMC_OK;
-  }
   PROPAGATE(ensure_cache(c, VMC_PSI));
   if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), c->stream));
   Timer t(c, "sweep");
@@ -81,7 +75,7 @@ static int run_sweep_wide(vmc_ctx* c, long long n_steps, bool injected, bool dbg
 // goes to the buffer the next sampler launch overwrites anyway); nothing is swapped.
 bool sampler_refresh_ok(const vmc_ctx* c) {
   static const bool on = !(getenv("CGS_VMC_SAMPLER_REFRESH") && atoi(getenv("CGS_VMC_SAMPLER_REFRESH")) == 0);
-  return on && !c->conv && !c->pbdg && !c->edvec && !(c->wide && !c->wide_fast);
+  return on && path_fused_dense(c->path);
 }
 int refresh_cache_by_sampler(vmc_ctx* c, int which) {
   PROPAGATE(ensure_packed(c, which));
@@ -125,16 +119,10 @@ static int cgen_sweep_groups(const vmc_ctx* c) {
 // The sampler of the general convolution path: per mc_step the proposals (k_wide_propose: the Philox streams and the
 // arg-max / arg-min rule of every sampler here), a full forward of the B candidates (the exchanged pair negated as the
 // first convolution gathers its operand), the Metropolis test and commit.  In place on configs / logit.
-static int run_sweep_cgen(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn,
-                          float* dbg_u, unsigned long long step0, bool count_accepted) {
+static int run_sweep_cgen(vmc_ctx* c, long long n_steps, bool injected, unsigned long long step0, bool count_accepted) {
   ParamSet& p = c->ps[0];
   const int B = c->B, N = c->N;
   const uint32_t seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull), seed_hi = (uint32_t)(c->d.seed >> 32);
-  if (dbg) {
-    HIPCHK(c, launch_wide_propose(c->stream, c->configs, B, N, seed_lo, seed_hi, c->d.chain_offset, step0, nullptr,
-                                  nullptr, nullptr, dbg_up, dbg_dn, dbg_u));
-    return VMC_OK;
-  }
   PROPAGATE(ensure_cache(c, VMC_PSI));
   if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), c->stream));
   Timer t(c, "sweep");
@@ -239,15 +227,9 @@ static int run_sweep_cgen(vmc_ctx* c, long long n_steps, bool injected, bool dbg
 // set, then the rows kernel writes the logits and signs of the final chains from a fresh factorisation (no drift from the
 // sampler's rank-2 updates: the cache equals vmc_amplitude's bit for bit).  Proposal dumps: k_wide_propose, the rule the
 // sampler follows.
-static int run_sweep_pbdg(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn,
-                          float* dbg_u, unsigned long long step0, bool count_accepted) {
+static int run_sweep_pbdg(vmc_ctx* c, long long n_steps, bool injected, unsigned long long step0, bool count_accepted) {
   ParamSet& p = c->ps[0];
   const uint32_t seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull), seed_hi = (uint32_t)(c->d.seed >> 32);
-  if (dbg) {
-    HIPCHK(c, launch_wide_propose(c->stream, c->configs, c->B, c->N, seed_lo, seed_hi, c->d.chain_offset, step0, nullptr,
-                                  nullptr, nullptr, dbg_up, dbg_dn, dbg_u));
-    return VMC_OK;
-  }
   if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), c->stream));
   PbdgSweepArgs a;
   memset(&a, 0, sizeof(a));
@@ -269,15 +251,9 @@ static int run_sweep_pbdg(vmc_ctx* c, long long n_steps, bool injected, bool dbg
 
 // The ed_vector sampler (edvec.hip): one persistent launch of n_steps steps, one thread per chain; it leaves the final
 // chains in the alternate set together with their amplitudes -- the last accepted gathers, hence vmc_amplitude's bits.
-static int run_sweep_edvec(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn,
-                           float* dbg_u, unsigned long long step0, bool count_accepted) {
+static int run_sweep_edvec(vmc_ctx* c, long long n_steps, bool injected, unsigned long long step0, bool count_accepted) {
   ParamSet& p = c->ps[0];
   const uint32_t seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull), seed_hi = (uint32_t)(c->d.seed >> 32);
-  if (dbg) {
-    HIPCHK(c, launch_wide_propose(c->stream, c->configs, c->B, c->N, seed_lo, seed_hi, c->d.chain_offset, step0, nullptr,
-                                  nullptr, nullptr, dbg_up, dbg_dn, dbg_u));
-    return VMC_OK;
-  }
   if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), c->stream));
   EdvecSweepArgs a;
   memset(&a, 0, sizeof(a));
@@ -301,16 +277,10 @@ static int run_sweep_edvec(vmc_ctx* c, long long n_steps, bool injected, bool db
 // sampler), the candidates as configurations in the alternate chain buffer, their amplitudes by the route vmc_amplitude
 // takes (first-layer GEMM off the spins, trunk, pairing layer, determinant rows: no incrementally updated state, nothing
 // to refresh), and the accept launch, which updates chains, logits and signs in place.
-static int run_sweep_nnb(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn,
-                         float* dbg_u, unsigned long long step0, bool count_accepted) {
+static int run_sweep_nnb(vmc_ctx* c, long long n_steps, bool injected, unsigned long long step0, bool count_accepted) {
   ParamSet& p = c->ps[0];
   const int B = c->B, N = c->N;
   const uint32_t seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull), seed_hi = (uint32_t)(c->d.seed >> 32);
-  if (dbg) {
-    HIPCHK(c, launch_wide_propose(c->stream, c->configs, B, N, seed_lo, seed_hi, c->d.chain_offset, step0, nullptr,
-                                  nullptr, nullptr, dbg_up, dbg_dn, dbg_u));
-    return VMC_OK;
-  }
   PROPAGATE(ensure_cache(c, VMC_PSI));
   if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), c->stream));
   Timer t(c, "sweep");
@@ -330,22 +300,31 @@ static int run_sweep_nnb(vmc_ctx* c, long long n_steps, bool injected, bool dbg,
   return VMC_OK;
 }
 
+// the proposal dump of the samplers whose proposals are k_wide_propose launches: that kernel, the rule they follow
+static int dump_proposals(vmc_ctx* c, unsigned long long step0, int* dbg_up, int* dbg_dn, float* dbg_u) {
+  HIPCHK(c, launch_wide_propose(c->stream, c->configs, c->B, c->N, (uint32_t)(c->d.seed & 0xFFFFFFFFull), (uint32_t)(c->d.seed >> 32),
+                                c->d.chain_offset, step0, nullptr, nullptr, nullptr, dbg_up, dbg_dn, dbg_u));
+  return VMC_OK;
+}
+
 static int run_sweep(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn,
                      float* dbg_u, unsigned long long step0, bool count_accepted = false,
                      bool overtake = false, hipEvent_t dep = nullptr) {
-  if (c->prod) return prod_run_sweep(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
-  PROPAGATE(ensure_packed(c, 0));
-  if (!dbg) c->cnt_valid = false;   // the chains change (set again below when this launch leaves their census)
-  if (c->edvec)
-    return run_sweep_edvec(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
-  if (c->nnb)
-    return run_sweep_nnb(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
-  if (c->wide && !c->wide_fast)
-    return run_sweep_wide(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
-  if (c->pbdg)
-    return run_sweep_pbdg(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
-  if (c->conv_general)
-    return run_sweep_cgen(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
+  if (c->path != PATH_PRODUCT) {      // (a product's factors pack their own parameters and keep their own census)
+    PROPAGATE(ensure_packed(c, 0));
+    if (!dbg) c->cnt_valid = false;   // the chains change (set again below when this launch leaves their census)
+  }
+  switch (c->path) {
+    case PATH_PRODUCT: return prod_run_sweep(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
+    case PATH_EDVEC: return dbg ? dump_proposals(c, step0, dbg_up, dbg_dn, dbg_u) : run_sweep_edvec(c, n_steps, injected, step0, count_accepted);
+    case PATH_NNB: return dbg ? dump_proposals(c, step0, dbg_up, dbg_dn, dbg_u) : run_sweep_nnb(c, n_steps, injected, step0, count_accepted);
+    case PATH_DENSE_GENERAL: return dbg ? dump_proposals(c, step0, dbg_up, dbg_dn, dbg_u) : run_sweep_wide(c, n_steps, injected, step0, count_accepted);
+    case PATH_PBDG: return dbg ? dump_proposals(c, step0, dbg_up, dbg_dn, dbg_u) : run_sweep_pbdg(c, n_steps, injected, step0, count_accepted);
+    case PATH_CONV_GENERAL: return dbg ? dump_proposals(c, step0, dbg_up, dbg_dn, dbg_u) : run_sweep_cgen(c, n_steps, injected, step0, count_accepted);
+    case PATH_FUSED: case PATH_FUSED_LDS: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP: case PATH_CONV:
+      break;      // one persistent launch from the current chain buffers into the alternate set, below
+  }
+  const bool conv = path_conv(c->path);
   ParamSet& p = c->ps[0];
   SweepArgs a;
   memset(&a, 0, sizeof(a));
@@ -365,13 +344,13 @@ static int run_sweep(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int
   // the activations of the final chains are handed to the gradient path only when a gradient
   // accumulate has been seen since the previous launch (equilibration / evaluation sweeps skip
   // the [L][B][Hp] write-back; gradient_sums then recomputes them)
-  const bool hand_over = !c->conv && !dbg && (injected || c->acc_since_sweep || c->sr_cap > 0);
+  const bool hand_over = !conv && !dbg && (injected || c->acc_since_sweep || c->sr_cap > 0);
   a.act_out = hand_over ? c->act_alt : nullptr;
   a.dact_out = hand_over ? c->dact_alt : nullptr;
   a.cache_in_valid = (!dbg && !injected && p.cache_valid) ? 1 : 0;
   // the census of the chains this launch leaves behind (k_bond_count's job; CGS_VMC_SWEEP_CENSUS=0: a launch of its own)
   static const bool census_on = !(getenv("CGS_VMC_SWEEP_CENSUS") && atoi(getenv("CGS_VMC_SWEEP_CENSUS")) == 0);
-  const bool census = census_on && !c->conv && !dbg && !injected && c->n_bonds > 0 && c->bonds && c->cnt_alt;
+  const bool census = census_on && !conv && !dbg && !injected && c->n_bonds > 0 && c->bonds && c->cnt_alt;
   if (census) {
     a.bonds = c->bonds; a.quarter_jz = c->quarter_jz; a.n_bonds = c->n_bonds;
     a.cnt_out = c->cnt_alt; a.diag_out = c->diag_alt;
@@ -380,7 +359,7 @@ static int run_sweep(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int
   if (overtake) HIPCHK(c, hipStreamWaitEvent(st, dep, 0));
   // the device counter is only zeroed when the caller will read it back
   if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), st));
-  if (c->conv) {
+  if (conv) {
     ConvSweepArgs s;
     memset(&s, 0, sizeof(s));
     s.g = c->cg; s.p = conv_params(p);
@@ -454,7 +433,7 @@ int vmc_mc_steps(vmc_ctx* c, int64_t n_steps, int64_t* accepted) {
   PROPAGATE(run_sweep(c, n_steps, false, false, nullptr, nullptr, nullptr, c->step, accepted != nullptr,
                       overtake, dep));
   c->step += (unsigned long long)n_steps;
-  c->ps[0].cache_valid = !c->wide || c->wide_fast;   // the sweep kernel writes back an exact z1/logit cache (the general
+  c->ps[0].cache_valid = !path_general_dense(c->path);   // the sweep kernel writes back an exact z1/logit cache (the general
                                      // wide path keeps an incrementally updated one: recomputed on demand)
   c->ps[1].cache_valid = false;
   c->list_valid = false;
@@ -479,7 +458,7 @@ int vmc_mc_step_injected(vmc_ctx* c, const int32_t* i_up, const int32_t* i_dn, c
   HIPCHK(c, hipMemcpyAsync(c->inj_dn, i_dn, c->B * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->inj_u, u, c->B * sizeof(float), hipMemcpyHostToDevice, c->stream));
   PROPAGATE(run_sweep(c, 1, true, false, nullptr, nullptr, nullptr, c->step));
-  c->ps[0].cache_valid = !c->wide || c->wide_fast; c->ps[1].cache_valid = false; c->list_valid = false;
+  c->ps[0].cache_valid = !path_general_dense(c->path); c->ps[1].cache_valid = false; c->list_valid = false;
   c->cnt_valid = false;
   if (accept_mask)
     HIPCHK(c, hipMemcpyAsync(accept_mask, c->acc_mask, c->B, hipMemcpyDeviceToHost, c->stream));
@@ -503,7 +482,13 @@ int vmc_debug_sweep_profile(vmc_ctx* c, int64_t n_steps, double* phase_cycles) {
   REFUSE_COMPOSED(c);
   REFUSE_PRODUCT(c, "vmc_debug_sweep_profile");
   if (n_steps < 1 || !phase_cycles) return fail(c, VMC_ERR_INVALID, "bad arguments");
-  if (c->rbm || c->conv || c->wide || c->pbdg || c->edvec) return fail(c, VMC_ERR_UNSUPPORTED, "the diagnostic sweep build exists for fully_connected (<= 256 units) only");
+  bool stamped = false;      // k_sweep16 / k_sweep8 have the stamped instantiation
+  switch (c->path) {
+    case PATH_FUSED: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP: stamped = !c->rbm; break;
+    case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_CONV: case PATH_CONV_GENERAL: case PATH_PBDG: case PATH_NNB:
+    case PATH_EDVEC: case PATH_PRODUCT: break;
+  }
+  if (!stamped) return fail(c, VMC_ERR_UNSUPPORTED, "the diagnostic sweep build exists for fully_connected (<= 256 units) only");
   PROPAGATE(ensure_packed(c, 0));
   const bool tile8 = c->sweep_tile == 8;      // k_sweep8's stamped instantiation (phases: sweep8.hip)
   const int wpg = tile8 ? c->Hp / 32 : c->sweep_waves;

@@ -19,22 +19,21 @@ static int gradient_sums(vmc_ctx* c, const float* w, bool fresh, const float* e,
   float* g1 = g1_ext ? g1_ext : c->acc;
   float* g2 = g1_ext ? g2_ext : c->acc + c->P;
   Timer t(c, "grad");
-  if (c->edvec) {
+  switch (c->path) {
+  case PATH_EDVEC:
     // O_k(b) = delta(k, idx_b) / psi_b: a scatter of 1 / psi_b and w_b / psi_b, every entry summed in chain order (edvec.hip)
     HIPCHK(c, launch_edvec_grad(c->stream, c->ed_top, c->ed_bot, N, (int)c->P, c->configs, p.sign, w, B, c->ed_keys,
                                 c->ed_keys_sorted, c->ed_sort_tmp, c->ed_sort_bytes, g1, g2));
     return VMC_OK;
-  }
-  if (c->pbdg) {
+  case PATH_PBDG:
     // O_ik = M^-1[pos k][pos i] of psi on the chains, from a fresh factorisation (pbdg.hip)
     // (the logits / signs land in the rows' scratch buffers, which the cache of `p` does not share)
     PROPAGATE(grow_tmp(c, B));
     HIPCHK(c, launch_pbdg_rows(c->stream, p.theta, N, c->configs, B, c->tmp_out, c->tmp_sign, c->pbdg_inv, c->pbdg_pos));
     HIPCHK(c, launch_pbdg_grad(c->stream, c->configs, c->pbdg_pos, c->pbdg_inv, w, B, N, c->pbdg_slices, c->pbdg_ws, g1, g2));
     return VMC_OK;
-  }
-  if (c->conv_general) return cgen_gradient_sums(c, w);
-  if (c->conv) {
+  case PATH_CONV_GENERAL: return cgen_gradient_sums(c, w);
+  case PATH_CONV: {
     // forward tapes (the inputs of every convolution), d logit / d (output of every convolution)
     // back through the transposed convolutions, then the weight-gradient correlations
     if (!c->acts_valid) {
@@ -55,6 +54,11 @@ static int gradient_sums(vmc_ctx* c, const float* w, bool fresh, const float* e,
     HIPCHK(c, launch_conv_dw(c->stream, dw));
     return VMC_OK;
   }
+  case PATH_PRODUCT: return product_has_none(c, "gradient path");
+  case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP: case PATH_NNB:
+    break;      // the dense trunk, below
+  }
+  const bool nnb = c->path == PATH_NNB;
   // forward with saved activations (wavefunctions.py:345-349 / 418-420); after a sweep launch
   // the kernel has already left them in act[] (exact refresh of the final chains).
   // act[l] = relu(z_{l+1}); RBM: the last one is tanh(z_last) = d sum log cosh / d z_last
@@ -77,9 +81,9 @@ static int gradient_sums(vmc_ctx* c, const float* w, bool fresh, const float* e,
   // back-propagation of d logit / d z_l: FC delta[NH] = w_out (.) relu'; RBM delta[NH] = tanh(z)
   // (which IS act[NH]); then the W_l^T chain through the relu masks -- one launch, 16 chains per
   // workgroup, transposed weight fragments on 16x16x4 MFMA (k_backprop16)
-  if (c->wide && !c->wide_fast) {
+  if (path_general_dense(c->path)) {
     // delta_NH = w_out (.) f'(z_NH); delta_{l-1} = f'(z_{l-1}) (.) (delta_l W_l^T) on the generic GEMM
-    if (c->nnb) {
+    if (nnb) {
       // the pairing layer of psi on the chains, dense [B][N^2]; the rows kernel factorises every M and overwrites the row
       // by d ln|psi| / d out = (M^-1)^T at the (up, down) entries; delta_NH = relu' (.) (d_out W_out^T)
       const long long NN = (long long)N * N;
@@ -140,7 +144,7 @@ static int gradient_sums(vmc_ctx* c, const float* w, bool fresh, const float* e,
       wgrad_fill_problem(tab.data(), n++, a, a_ld, delta, ldd, off, k_in, n_out, tile0);
       tile0 += plan_wgrad_tiles(k_in, n_out);
     };
-    if (c->nnb)   // pairing layer: d ln|psi| / d w_out = a_L^T d_out, d ln|psi| / d b_out = d_out
+    if (nnb)   // pairing layer: d ln|psi| / d w_out = a_L^T d_out, d ln|psi| / d b_out = d_out
       add(c->act[NH], Hp, H, c->nnb_delta, (long long)N * N, N * N, off_wout(c));
     else if (c->rbm)   // onsite layer: d logit / d w_on = x, d logit / d b_on = 1
       add(c->configs, N, N, c->ones, 1, 1, c->lay.off_won);
@@ -162,7 +166,7 @@ static int gradient_sums(vmc_ctx* c, const float* w, bool fresh, const float* e,
       L.out_part = c->wg_outpart; L.out_nwg = (B + 15) / 16; L.out_H = H; L.out_ld = Hp + 4; L.out_off = off_wout(c);
     }
     L.tiles = c->wg_tiles;
-    L.slices = c->nnb ? c->nnb_wg_slices
+    L.slices = nnb ? c->nnb_wg_slices
                       : plan_wgrad_slices(c->wg_tiles, B, c->num_cus, 1 + (c->wg_out_partials ? plan_wgrad_fold_blocks(H) : 0), forced);
     L.K = B; L.w = w; L.g1 = g1; L.g2 = g2; L.ws = c->gemm_ws; L.tickets = c->wg_tickets; L.fresh = fresh;
     L.sc_eloc = e; L.sc_ratio = mode == 1 ? c->ratio : nullptr; L.sc_out = g1_ext ? nullptr : c->acc + 2 * c->P; L.sc_B = B; L.sc_mode = mode;
@@ -178,7 +182,12 @@ namespace vmcapi {
 // The gradient path of a factor of a product ctx: sum_b O_k(b) -> g1 +=, sum_b w_b O_k(b) -> g2 += for psi on the ctx's
 // `configs` (whose cache the caller has made valid), with the caller's weights and accumulators
 int child_gradient_sums(vmc_ctx* c, const float* w, float* g1, float* g2) {
-  if (c->conv || c->nnb) return fail(c, VMC_ERR_UNSUPPORTED, "prod: this ansatz type cannot be a factor");
+  switch (c->path) {
+    case PATH_CONV: case PATH_CONV_GENERAL: case PATH_NNB: case PATH_PRODUCT:     // (plan_prod_child_check refuses them)
+      return fail(c, VMC_ERR_UNSUPPORTED, "prod: this ansatz type cannot be a factor");
+    case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP:
+    case PATH_PBDG: case PATH_EDVEC: break;
+  }
   bool scalars_done = false;
   return gradient_sums(c, w, false, nullptr, VMC_MODE_ENERGY_GRADIENT, &scalars_done, false, 0.f, g1, g2);
 }
@@ -193,23 +202,27 @@ static int sr_record(vmc_ctx* c) {
     return fail(c, VMC_ERR_STATE, "SR sample store full: vmc_sr_reserve fewer batches than accumulate calls");
   const long long B = c->B, N = c->N, Hp = c->Hp, L = c->A, k = c->sr_n, R = (long long)c->sr_cap * B;
   HIPCHK(c, hipMemcpyAsync(c->sr_cfg + k * B * N, c->configs, B * N * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-  if (c->conv_general) { c->sr_n += 1; return VMC_OK; }     // (its matvec re-derives everything from the chains)
-  if (c->conv) {   // the taped inputs of every convolution and d logit / d (their outputs) of this batch
+  switch (c->path) {
+  case PATH_CONV_GENERAL: break;     // (its matvec re-derives everything from the chains)
+  case PATH_CONV: {   // the taped inputs of every convolution and d logit / d (their outputs) of this batch
     const long long CS = c->cg.CS, nc = c->cg.n_conv;
     if (nc > 1)
       HIPCHK(c, hipMemcpy2DAsync(c->sr_ctape + k * B * CS, R * CS * sizeof(float), c->ctape, c->ctape_stride * sizeof(float),
                                  B * CS * sizeof(float), nc - 1, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpy2DAsync(c->sr_cdelta + k * B * CS, R * CS * sizeof(float), c->cdelta, c->cdelta_stride * sizeof(float),
                                B * CS * sizeof(float), nc, hipMemcpyDeviceToDevice, c->stream));
-    c->sr_n += 1;
-    return VMC_OK;
+    break;
   }
-  // layer-major store [L][cap * B][Hp]: every layer's rows of ALL stored batches are contiguous,
-  // so the CG matrix-vector product runs each GEMM once over all samples
-  HIPCHK(c, hipMemcpy2DAsync(c->sr_act + k * B * Hp, R * Hp * sizeof(float), c->act_all, B * Hp * sizeof(float),
-                             B * Hp * sizeof(float), L, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipMemcpy2DAsync(c->sr_delta + k * B * Hp, R * Hp * sizeof(float), c->delta_all, B * Hp * sizeof(float),
-                             B * Hp * sizeof(float), L, hipMemcpyDeviceToDevice, c->stream));
+  case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP:
+  case PATH_PBDG: case PATH_NNB: case PATH_EDVEC: case PATH_PRODUCT:     // (the last four: vmc_sr_reserve gives them no store)
+    // layer-major store [L][cap * B][Hp]: every layer's rows of ALL stored batches are contiguous,
+    // so the CG matrix-vector product runs each GEMM once over all samples
+    HIPCHK(c, hipMemcpy2DAsync(c->sr_act + k * B * Hp, R * Hp * sizeof(float), c->act_all, B * Hp * sizeof(float),
+                               B * Hp * sizeof(float), L, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(c->sr_delta + k * B * Hp, R * Hp * sizeof(float), c->delta_all, B * Hp * sizeof(float),
+                               B * Hp * sizeof(float), L, hipMemcpyDeviceToDevice, c->stream));
+    break;
+  }
   c->sr_n += 1;
   return VMC_OK;
 }
@@ -242,20 +255,32 @@ int vmc_accumulate(vmc_ctx* c, int mode, float beta) {
     }
     PROPAGATE(local_energy_device(c, VMC_OMEGA, true, &fold_eloc));   // training.py:664, 667
     PROPAGATE(ensure_cache(c, VMC_PSI));
-    if (c->edvec)     // the amplitudes themselves: psi_w / psi (1 - beta E_loc^w)
-      HIPCHK(c, launch_edvec_itswo_ratio(c->stream, c->ps[0].sign, c->ps[1].sign, c->ps[1].eloc, beta, c->B, c->ratio));
-    else if (c->sgn)       // signed amplitudes: sign_w sign_psi exp(...)
-      HIPCHK(c, launch_pbdg_itswo_ratio(c->stream, c->ps[0].logit, c->ps[0].sign, c->ps[1].logit, c->ps[1].sign,
-                                        c->ps[1].eloc, c->ps[0].shift - c->ps[1].shift, beta, c->B, c->ratio));
-    else if (!fold_eloc)   // (otherwise the back-propagation launch folds E_loc^w and forms the ratio: two launches less)
-      HIPCHK(c, launch_itswo_ratio(c->stream, c->ps[0].logit, c->ps[1].logit, c->ps[1].eloc,
-                                   c->ps[0].shift - c->ps[1].shift, beta, c->B, c->ratio, c->oact));
+    switch (c->path) {
+      case PATH_EDVEC:     // the amplitudes themselves: psi_w / psi (1 - beta E_loc^w)
+        HIPCHK(c, launch_edvec_itswo_ratio(c->stream, c->ps[0].sign, c->ps[1].sign, c->ps[1].eloc, beta, c->B, c->ratio));
+        break;
+      case PATH_PBDG: case PATH_NNB:       // signed amplitudes: sign_w sign_psi exp(...)
+        HIPCHK(c, launch_pbdg_itswo_ratio(c->stream, c->ps[0].logit, c->ps[0].sign, c->ps[1].logit, c->ps[1].sign,
+                                          c->ps[1].eloc, c->ps[0].shift - c->ps[1].shift, beta, c->B, c->ratio));
+        break;
+      case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_CONV: case PATH_SPLIT_ROWS:
+      case PATH_SPLIT_SWEEP: case PATH_CONV_GENERAL:
+        if (!fold_eloc)    // (otherwise the back-propagation launch folds E_loc^w and forms the ratio: two launches less)
+          HIPCHK(c, launch_itswo_ratio(c->stream, c->ps[0].logit, c->ps[1].logit, c->ps[1].eloc,
+                                       c->ps[0].shift - c->ps[1].shift, beta, c->B, c->ratio, c->oact));
+        break;
+      case PATH_PRODUCT: break;            // (prod_accumulate, above)
+    }
     w = c->ratio; e = c->ps[1].eloc;
   }
   PROPAGATE(ensure_cache(c, VMC_PSI));
   // the batched weight-gradient GEMMs of the dense ansatz types cover every parameter, so a pending
   // reset is absorbed: their reduction stores instead of adding (conv: zero first)
-  if (c->conv || c->pbdg || c->edvec) PROPAGATE(acc_zeros(c));
+  switch (c->path) {
+    case PATH_CONV: case PATH_CONV_GENERAL: case PATH_PBDG: case PATH_EDVEC: PROPAGATE(acc_zeros(c)); break;
+    case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP: case PATH_NNB:
+    case PATH_PRODUCT: break;
+  }
   const bool fresh = c->acc_fresh;
   bool scalars_done = false;
   PROPAGATE(gradient_sums(c, w, fresh, e, mode, &scalars_done, fold_eloc, beta));
@@ -355,18 +380,24 @@ int vmc_set_adam_state(vmc_ctx* c, const float* m, const float* v, int64_t t) {
 
 // Wavefunction.update_norm (wavefunctions.py:261-288); max_b psi over the chains of all ranks
 static int update_norm_impl(vmc_ctx* c, void* comm, int world, float max_value) {
-  if (c->prod) return VMC_OK;      // the product has no shift of its own; the factors' stay where they are (log domain)
-  if (c->oact != VMC_ACT_EXP_ || c->nnb || c->edvec) return VMC_OK;   // wavefunctions.py:276-277: no exp_norm_shift, nothing to do
+  const bool pbdg = c->path == PATH_PBDG;
+  switch (c->path) {
+    case PATH_PRODUCT: return VMC_OK;      // the product has no shift of its own; the factors' stay where they are (log domain)
+    case PATH_NNB: case PATH_EDVEC: return VMC_OK;     // no exponent shift
+    case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_CONV: case PATH_SPLIT_ROWS:
+    case PATH_SPLIT_SWEEP: case PATH_CONV_GENERAL: case PATH_PBDG: break;
+  }
+  if (c->oact != VMC_ACT_EXP_) return VMC_OK;   // wavefunctions.py:276-277: no exp_norm_shift, nothing to do
   PROPAGATE(ensure_cache(c, VMC_PSI));
   // pbdg: max_b psi_b of the SIGNED amplitudes (wavefunctions.py:283): the largest logit among the chains with psi > 0
-  if (c->pbdg) HIPCHK(c, launch_pbdg_signed_max(c->stream, c->ps[0].logit, c->ps[0].sign, c->B, c->d_max));
+  if (pbdg) HIPCHK(c, launch_pbdg_signed_max(c->stream, c->ps[0].logit, c->ps[0].sign, c->B, c->d_max));
   else HIPCHK(c, launch_max(c->stream, c->ps[0].logit, c->B, c->d_max));
   PROPAGATE(reduce_buffer(c, comm, world, c->d_max, 1, VMC_REDUCE_MAX));
   float mx = 0.f;
   HIPCHK(c, hipMemcpyAsync(&mx, c->d_max, sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   // no chain with psi > 0: the reference writes log(max psi) = NaN into the shift; the shift is kept
-  if (c->pbdg && !(mx > -INFINITY)) return VMC_OK;
+  if (pbdg && !(mx > -INFINITY)) return VMC_OK;
   // wavefunctions.py:280-288: log_max = log(reduce_max(psi)); where psi overflows float32 the
   // reference yields inf; the logit-domain value is used there instead.
   const float shift = c->ps[0].shift;

@@ -1,6 +1,9 @@
 // Internal header of the host side of libcgsvmc_hip.so (round 6: vmc_api.hip split by kernel path behind the same
 // include/cgsvmc.h): the ctx, the entry-point macros, the small inline helpers and the prototypes of what the
 // translation units vmc_api*.hip share.  Not installed; nothing outside csrc/ includes it.
+// Which family of kernels a ctx runs is ONE member, vmc_ctx::path (enum KernelPath, plan.hpp): code that differs by
+// family switches over it without a `default`, yes/no questions go through plan.hpp's path_* predicates.  The ctx holds
+// no per-family flag beside it; rbm (orthogonal to the path) and sgn (on a product: the OR of its factors) stay.
 #pragma once
 #include "../../include/cgsvmc.h"
 #include "common.hpp"
@@ -125,54 +128,45 @@ struct vmc_ctx {
   // the owner's caches.  The dense members of a product ctx keep minimal shapes (unused); P = P_a + P_b.
   ProdState* prod = nullptr;
   vmc_ctx* owner = nullptr;
+  KernelPath path = PATH_FUSED;   // the kernel family (plan.hpp); vmc_debug_kernel_path reports it
   int N = 0, B = 0, L = 0, H = 0, Hp = 0;
   bool rbm = false;        // RestrictedBoltzmannNetwork instead of FullyConnectedNetwork
-  // ProjectedBDG (pbdg.hip): theta is the pairing matrix; the network members keep minimal shapes (unused).  The
+  // PATH_PBDG (pbdg.hip): theta is the pairing matrix; the network members keep minimal shapes (unused).  The
   // gradient path factorises psi on the chains into pbdg_inv [B][n][n] / pbdg_pos [B][N] and folds the partial sums
   // of pbdg_slices chain slices (pbdg_ws, double) in slice order
-  bool pbdg = false;
   DevBuf<float> pbdg_inv; DevBuf<int> pbdg_pos; DevBuf<double> pbdg_ws; int pbdg_slices = 1;
   DevBuf<float> tmp_sign;   // [tmp_rows] signs of vmc_amplitude's rows
-  // FullyConnectedNNB (nnb.hip): the general dense path (wide && !wide_fast) whose output stage is the pairing layer of a
+  // PATH_NNB (nnb.hip): the general dense path whose output stage is the pairing layer of a
   // block of nnb_rows rows (nnb_out [nnb_rows][N^2], wbuf[] [nnb_rows][Hp]) and the determinant rows kernel.  sgn: signed
-  // amplitudes (pbdg || nnb: sign buffers, the signed ITSWO ratio, Sz = 0 configurations only).  nnb_delta [B][N^2]: the
-  // pairing layer of psi on the chains, overwritten by d ln|psi| / d out (gradient path); nnb_cl / nnb_cs [B]: logits and
-  // signs of the sampler's candidates; nnb_wg_slices: K slices of the weight-gradient launch
-  bool nnb = false, sgn = false;
+  // amplitudes (pbdg, nnb, ed_vector, a product with such a factor: sign buffers, Sz = 0 configurations only).  nnb_delta
+  // [B][N^2]: the pairing layer of psi on the chains, overwritten by d ln|psi| / d out (gradient path); nnb_cl / nnb_cs [B]:
+  // logits and signs of the sampler's candidates; nnb_wg_slices: K slices of the weight-gradient launch
+  bool sgn = false;
   long long nnb_rows = 0;
   DevBuf<float> nnb_out, nnb_delta, nnb_cl, nnb_cs;
   int nnb_wg_slices = 1;
-  // FullVector (edvec.hip): theta is the state vector, ed_top / ed_bot the Lin tables [2^(N/2)] (null until
+  // PATH_EDVEC (edvec.hip): theta is the state vector, ed_top / ed_bot the Lin tables [2^(N/2)] (null until
   // vmc_set_lin_tables).  ParamSet::sign holds the chains' amplitudes themselves (psi, not a sign), logit = ln|psi|,
   // the shift stays 0.  ed_keys / ed_keys_sorted [B], ed_sort_tmp: the gradient scatter's sort (launch_edvec_grad)
-  bool edvec = false, ed_tables_lds = false;
+  bool ed_tables_lds = false;
   DevBuf<int> ed_top, ed_bot;
   DevBuf<unsigned long long> ed_keys, ed_keys_sorted;
   DevBuf<unsigned char> ed_sort_tmp; size_t ed_sort_bytes = 0;
-  // Conv2DNetwork / ResNet2D (conv.hip).  The dense-ansatz members below keep harmless minimal
+  // PATH_CONV / PATH_CONV_GENERAL (conv.hip, conv_general.hip).  The dense-ansatz members below keep harmless minimal
   // shapes (H = filters, Hp = 64, no H x H layer); acts_valid tells whether the forward tapes
   // hold the inputs of every convolution for psi on the current chains.
-  bool conv = false;
   ConvGeom cg;
   int cG = 1, cGs = 1;     // samples per workgroup pass of the row / backward kernels, of the sampler
   DevBuf<float> ctape, cdelta, cws;
   long long ctape_stride = 0, cdelta_stride = 0;
   int c_slices = 64;       // sample slices of the weight-gradient kernel
-  // fully_connected with more than 256 hidden units: general path (wide.hip)
-  bool wide = false;
-  // ... except relu networks of at most 512 units with an H x H layer: their sampler and row kernel
-  // are instantiations of the fused kernels (k_sweep16<24|32>, k_tail_lds); only the gradient path
-  // stays on the general GEMMs.  CGS_VMC_WIDE_FAST=0 forces the general path.
-  bool wide_fast = false;
-  // EXPERIMENT (CGS_VMC_SPLIT_BF16=1; fully_connected, relu, 193 .. 256 units, >= 1 H x H layer): the row
-  // kernel computes its fp32 results on the bf16 matrix cores from three-term splits (tail_split.hip)
-  bool split = false;             // CGS_VMC_SPLIT_BF16 >= 1: the row kernel on the BF16 matrix cores (3 x bf16 split, EXPERIMENT)
-  bool split_sweep = false;       // CGS_VMC_SPLIT_BF16 == 2: the sampler's H x H layers too (k_sweep16s)
+  // more than 256 hidden units (path_wide): the general path's row buffers (wide.hip).  PATH_FUSED_LDS (at most 512
+  // units) keeps them for its gradient path only: its sampler and row kernel are instantiations of the fused kernels
+  // (k_sweep16<24|32>, k_tail_lds).  CGS_VMC_WIDE_FAST=0 forces PATH_DENSE_GENERAL.
   long long wrows = 0;     // rows of the two activation row buffers
   DevBuf<float> wbuf[2], wide_u, wide_zero;
   DevBuf<double> wide_dot;          // [ceil(H / 128)][wrows] row-dot partials of the last H x H layer (GemmArgs epilogue 10)
-  // general convolution path (conv_general.hip; plan.hpp: conv beyond the fused kernels' limits): block buffers
-  bool conv_general = false;
+  // PATH_CONV_GENERAL (conv_general.hip; plan.hpp: conv beyond the fused kernels' limits): block buffers
   long long cg_rows = 0;                   // row configurations per block (sized by the im2col matrix: the GEMM form, the gradient path)
   long long cg_rows_fwd = 0;               // ... of an untaped forward whose convolutions all run on the band kernel (sized by the two maps)
   DevBuf<float> cg_A;                   // im2col rows [cg_rows * N][plan_cgen_lda]
@@ -196,7 +190,7 @@ struct vmc_ctx {
                                            // at the parameters of the running solve (one block: kept across its CG iterations)
   DevBuf<float> cg_centre;              // [1] mean of O_b . v over the stored samples (SR)
   // gnn (cg.graph): the adjacency list [N][k] and its inverse lists (plan_gnn_inverse: [N + 1] offsets, [N k] entries m k + t),
-  // set by vmc_set_adjacency; every compute entry of a gnn ctx refuses to run without them (gnn_ready)
+  // set by vmc_set_adjacency; every compute entry of a gnn ctx refuses to run without them (late_inputs_set)
   DevBuf<int> gnn_adj, gnn_inv_ptr, gnn_inv;
   bool sr_centre = false;                  // the SR matvec may centre its weights: a single-rank solve is running
   bool sr_phase1_done = false;             // vmc_sr_matvec_phase1 has run for the current CG direction (general convolution path)
@@ -377,6 +371,10 @@ struct DeviceGuard {
 // entries a product ctx does not have
 #define REFUSE_PRODUCT(c, what) \
   do { if ((c)->prod) return fail((c), VMC_ERR_UNSUPPORTED, what " is not available on a product ctx ('prod')"); } while (0)
+// the PATH_PRODUCT arm of a switch no product ctx reaches (its entries go to the factors, which run their own paths)
+inline int product_has_none(vmc_ctx* c, const char* what) {
+  return fail(c, VMC_ERR_STATE, std::string("prod: a product ctx has no ") + what + " of its own (its factors run theirs)");
+}
 
 // CUs a sampler launch occupies (8 waves at 255 registers, or LDS, fill a CU per workgroup)
 inline int sweep_cus(const vmc_ctx* c) { return c->sweep_tile == 8 ? (c->B + 7) / 8 : (c->B + 15) / 16; }
@@ -442,7 +440,8 @@ inline void harvest_finished(vmc_ctx* c) {
 struct Timer {
   vmc_ctx* c; hipStream_t st; bool on; TimedRegion r;
   Timer(vmc_ctx* ctx, const char* name, hipStream_t stream = nullptr, bool own_stream = false)
-      : c(ctx), st(own_stream ? stream : ctx->stream), on(ctx->timing == 1 || (ctx->timing == 2 && (!strcmp(name, "sweep") || !strcmp(name, "tail_eloc")))) {
+      : c(ctx), st(own_stream ? stream : ctx->stream),      // (a null name: no region -- the caller times the call itself)
+        on(name && (ctx->timing == 1 || (ctx->timing == 2 && (!strcmp(name, "sweep") || !strcmp(name, "tail_eloc"))))) {
     if (on) {
       r.name = name;
       if (c->event_pool.empty()) harvest_finished(c);
@@ -495,7 +494,9 @@ int local_energy_device(vmc_ctx* c, int which, bool defer_reduce = false, bool* 
 // ensure_list have run); share_cus: leave CUs to a sampler launch that is expected to overtake (expect_sweep)
 int connected_rows_device(vmc_ctx* c, int which, bool share_cus);
 int grow_tmp(vmc_ctx* c, long long rows);
-int pbdg_check_sz(vmc_ctx* c, const float* configs, long long n_rows);
+// VMC_ERR_INVALID (with the message) when `c` holds signed amplitudes and a row of `configs` (host) is not at Sz = 0
+int check_sz0_rows(vmc_ctx* c, const float* configs, long long n_rows);
+const char* signed_family_name(KernelPath path);     // "pbdg", "fully_connected_nnb", "ed_vector", "prod (a signed factor)"
 // the full forward on n_rows rows of a device buffer of configurations -> log|psi| and, for the signed types, the sign per
 // row (vmc_amplitude, vmc_renyi2_swap); ensure_packed and grow_tmp(n_rows) have run
 int rows_forward_device(vmc_ctx* c, int which, const float* configs, long long n_rows, float* logit, float* sign);
@@ -507,8 +508,9 @@ int nnb_forward(vmc_ctx* c, int which, const float* z1, const float* configs, co
 int cgen_forward(vmc_ctx* c, int which, const float* configs, const int2* rowinfo, long long n_rows,
                  const int* iup, const int* idn, bool ratio, float* out, float* tape = nullptr,
                  long long tape_stride = 0, long long first_row = 0);
-// VMC_ERR_INVALID (with the message) when `c` is a gnn ctx whose adjacency list has not been set
-int gnn_ready(vmc_ctx* c);
+// VMC_ERR_INVALID (with the message) while an input the ctx takes after vmc_create is missing: a gnn ctx's adjacency
+// list (vmc_set_adjacency), an ed_vector ctx's Lin tables (vmc_set_lin_tables)
+int late_inputs_set(vmc_ctx* c);
 int cgen_patch_mode(const vmc_ctx* c);
 int cgen_patch_maps(vmc_ctx* c, int which);
 void cgen_patch_args(const vmc_ctx* c, int which, CgenPatchArgs* a);
