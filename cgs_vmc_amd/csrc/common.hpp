@@ -376,7 +376,28 @@ hipError_t launch_proj_accum(hipStream_t s, const float* logit, const float* sig
 hipError_t launch_proj_fold(hipStream_t s, const float* sign, const float* eloc, const double* acc, int B, int n_sectors,
                             double* out);
 
-// device helpers and the grid rule the Renyi-2, dimer, symmetry and projection kernels share
+// Lanczos-step energies (moments.hip; its header states the list rules and every summation order).  rowinfo / off / val /
+// eloc: what a local-energy call leaves, n1_dev = off + B its row count on the device, n1 the same on the host (grids).
+// count: cnt2 / diag1 / self1 [n1] per first-order row and the exclusive prefix off2 [n1 + 1].  fill: descriptors and
+// coefficients of the second-order rows [q0, q0 + n) of a pass; rows: their configurations; accum: their coef r into
+// lanes [B][64]; fold: chain [2][B] = e, g per chain and out [6] = sum e, e^2, g, e g, g^2, the chains alive
+hipError_t launch_mom_count(hipStream_t s, const float* configs, const int2* bonds, const float* half_jx,
+                            const float* quarter_jz, const int2* rowinfo, const int* n1_dev, int n1, int N, int n_bonds,
+                            int num_cus, int* cnt2, int* off2, double* diag1, double* self1);
+hipError_t launch_mom_fill(hipStream_t s, const float* configs, const int2* bonds, const float* half_jx,
+                           const float* quarter_jz, const int2* rowinfo, const int* n1_dev, int n1, const int* off2, int N,
+                           int n_bonds, long long q0, int n, int num_cus, int2* desc, double* coef);
+hipError_t launch_mom_rows(hipStream_t s, const float* configs, const int2* bonds, const int2* rowinfo, const int2* desc,
+                           int N, int n, int num_cus, float* rows);
+hipError_t launch_mom_accum(hipStream_t s, const float* logit, const float* sign, const float* row_logit,
+                            const float* row_sign, const double* coef, const int* off, const int* off2, int B, long long q0,
+                            int n, double* lanes);
+hipError_t launch_mom_fold(hipStream_t s, const float* configs, const int2* bonds, const float* half_jx,
+                           const float* quarter_jz, const int2* rowinfo, const int* off, const float* val, const float* eloc,
+                           const float* sign, const double* diag1, const double* self1, const double* lanes, int B, int N,
+                           int n_bonds, double* chain, double* out);
+
+// device helpers and the grid rule the Renyi-2, dimer, symmetry, projection and moment kernels share
 // sign of a stored sign / amplitude: +-1, 0 for a vanishing amplitude
 __device__ inline int sgn_of(float v) { return (v > 0.f) - (v < 0.f); }
 // psi(row) / psi(x) from ln|psi| and, signed types, the signs (own_sgn = +-1: the caller has dropped a chain whose own

@@ -803,6 +803,35 @@ inline int plan_symm_check_hamiltonian(int N, int n_bonds, const int32_t* ij, co
   return VMC_OK;
 }
 
+// Lanczos-step energies (vmc_energy_moments; moments.hip).  The second-order list -- the rows x^{ab} over (chain,
+// antiparallel bond a, bond b antiparallel on x^a) -- is indexed with 32-bit integers like the first-order list; a chain
+// has at most n_bonds first-order rows of at most n_bonds second-order rows each, so B n_bonds^2 <= 2^31 - 1 keeps every
+// index and the prefix off2 in range whatever the configurations are.  The list goes through the forward in passes of
+// ROWS (not of items x B as its siblings): the budget of 2^24 rows, never more than row_limit (plan_measure_row_limit; 0:
+// none), requested > 0: at most that many; at least one row.  0 passes for an empty list; -1: an argument out of range.
+// Within a chain the row at place p = q - s (s: the chain's first row) belongs to lane p mod 64 of the chain's
+// accumulator: plan_moment_first_row is the first row >= lo that lane `lane` owns, plan_moment_rows_of_lane how many
+// of [lo, hi) it owns -- together they state that the lanes' walks partition every pass's slice of a chain.
+inline bool plan_moment_index_ok(long long B, long long n_bonds) {
+  return B >= 1 && n_bonds >= 1 && n_bonds <= 0x7fffffffLL && n_bonds * n_bonds <= 0x7fffffffLL / B;
+}
+inline long long plan_moment_per_pass(long long n_rows2, long long requested, long long row_limit) {
+  if (n_rows2 < 0 || requested < 0 || row_limit < 0) return -1;
+  long long per = PLAN_MEASURE_ROW_BUDGET;
+  if (row_limit > 0 && row_limit < per) per = row_limit;
+  if (requested > 0 && requested < per) per = requested;
+  if (per > n_rows2) per = n_rows2;
+  if (per < 1) per = 1;
+  return per;
+}
+PLAN_HD inline long long plan_moment_first_row(long long s, long long lo, int lane) {
+  return lo + ((lane - (int)((lo - s) & 63)) & 63);
+}
+inline long long plan_moment_rows_of_lane(long long s, long long lo, long long hi, int lane) {
+  const long long q = plan_moment_first_row(s, lo, lane);
+  return q >= hi ? 0 : (hi - q + 63) / 64;
+}
+
 // ------------------------------------------------------------------------------- the kernel path of a ctx
 // Which family of kernels a ctx runs: decided once (plan_desc, plan_split_path; vmc_create_product sets PATH_PRODUCT),
 // kept in vmc_ctx::path, reported by vmc_debug_kernel_path -- the numbers are part of the test suite and of bench.py.

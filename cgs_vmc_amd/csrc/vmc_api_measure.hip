@@ -1,8 +1,8 @@
 // The measurements over the ctx's current chains (extensions, no reference counterpart): vmc_pair_correlations,
-// vmc_renyi2_swap, vmc_dimer_correlations, vmc_symmetry_expectations and vmc_projected_energy.  Each is a pure measurement: chains, step counter, accumulators, the
+// vmc_renyi2_swap, vmc_dimer_correlations, vmc_symmetry_expectations, vmc_projected_energy and vmc_energy_moments.  Each is a pure measurement: chains, step counter, accumulators, the
 // Hamiltonian's bond set and the validity of the amplitude and activation caches are as before when it returns.
 //
-// One scaffold serves the five.  MEASURE_GATE is the shared front of the refusals; PureMeasurement records which caches
+// One scaffold serves the six.  MEASURE_GATE is the shared front of the refusals; PureMeasurement records which caches
 // were valid and un-vouches on every way out for those that were not; upload copies a host list into its device buffer;
 // for_passes walks the items in passes of plan_measure_per_pass (plan.hpp); read_back brings the fp64 sums down and
 // synchronises, on a failed call too.  The device buffers are the grow-only DevBufs of vmc_ctx.hpp.  What differs per
@@ -44,6 +44,13 @@
 // checked to map the Hamiltonian's bonds onto themselves, couplings included (plan_symm_check_hamiltonian): the
 // estimator means nothing otherwise.  What a vmc_local_energy call leaves behind (the chains' local energies of `which`,
 // vmc_last_connected_rows) is the one thing this measurement changes.
+//
+// Lanczos-step energies.  Per chain e = (H psi)(x) / psi(x) and g = (H^2 psi)(x) / psi(x) (moments.hip states the estimator,
+// the list rules and every summation order).  One local-energy call first; its row list, val and eloc are the first
+// order.  Then the second-order list: counted per first-order row and prefixed (k_mom_count, k_mom_scan), its length read
+// back, and walked in passes of ROWS (plan_moment_per_pass): k_mom_fill writes the descriptors of the pass alone,
+// k_mom_rows the configurations, the family's full forward evaluates them and k_mom_accum adds coef r into the chains'
+// lanes.  k_mom_chain / k_mom_sums fold at the end.  Like the projected energies it leaves what vmc_local_energy leaves.
 #include "vmc_ctx.hpp"
 
 using namespace vmcapi;
@@ -287,6 +294,49 @@ int proj_pass(vmc_ctx* c, int which, long long k0, int n, int n_ops, int n_secto
   return VMC_OK;
 }
 
+// ---- Lanczos-step energies
+
+int mom_reserve_list(vmc_ctx* c, long long n1) {
+  MomentBufs& m = c->mom;
+  PROPAGATE(m.cnt2.reserve(c, n1, "mom.cnt2"));
+  PROPAGATE(m.off2.reserve(c, n1 + 1, "mom.off2"));
+  PROPAGATE(m.diag1.reserve(c, n1, "mom.diag1"));
+  PROPAGATE(m.self1.reserve(c, n1, "mom.self1"));
+  PROPAGATE(m.lanes.reserve(c, 64LL * c->B, "mom.lanes"));
+  PROPAGATE(m.chain.reserve(c, 2LL * c->B, "mom.chain"));
+  return m.out.reserve(c, 6, "mom.out");
+}
+
+// rows [q0, q0 + n) of the second-order list: descriptors, configurations, forward, into the chains' lanes
+int mom_pass(vmc_ctx* c, int which, long long q0, int n, int n1) {
+  const ParamSet& p = c->ps[which];
+  const MomentBufs& m = c->mom;
+  {
+    Timer t(c, "mom_list");
+    HIPCHK(c, launch_mom_fill(c->stream, c->configs, c->bonds, c->half_jx, c->quarter_jz, c->rowinfo, c->off + c->B, n1,
+                              m.off2, c->N, c->n_bonds, q0, n, c->num_cus, m.desc, m.coef));
+  }
+  {
+    Timer t(c, "mom_rows");
+    HIPCHK(c, launch_mom_rows(c->stream, c->configs, c->bonds, c->rowinfo, m.desc, c->N, n, c->num_cus, c->tmp_cfg));
+  }
+  {
+    Timer t(c, "mom_forward");
+    PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, n, c->tmp_out, c->tmp_sign));
+  }
+  Timer t(c, "mom_fold");
+  HIPCHK(c, launch_mom_accum(c->stream, p.logit, c->sgn ? p.sign : nullptr, c->tmp_out, c->sgn ? c->tmp_sign : nullptr,
+                             m.coef, c->off, m.off2, c->B, q0, n, m.lanes));
+  return VMC_OK;
+}
+
+// an int the device holds, on the host (the stream is synchronised)
+int read_int(vmc_ctx* c, const int* dev, int* host) {
+  HIPCHK(c, hipMemcpyAsync(host, dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VMC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -503,6 +553,63 @@ int vmc_projected_energy(vmc_ctx* c, int which, int32_t n_ops, const int32_t* pe
   }
   if (e_sum) *e_sum = out[2 * (size_t)n_sectors];
   if (n_alive) *n_alive = (int64_t)out[2 * (size_t)n_sectors + 1];
+  return VMC_OK;
+}
+
+int vmc_energy_moments(vmc_ctx* c, int which, int64_t rows_per_pass, double sums[6], double* e_loc, double* h2_loc,
+                       int64_t* n_rows2) {
+  MEASURE_GATE(c, which, "vmc_energy_moments");
+  if (rows_per_pass < 0) return fail(c, VMC_ERR_INVALID, "bad rows_per_pass (0: the library decides)");
+  if (!c->sgn && c->oact != VMC_ACT_EXP_)
+    return fail(c, VMC_ERR_UNSUPPORTED, "vmc_energy_moments needs the exp output activation (the logit is ln psi only then)");
+  if (c->n_bonds <= 0) return fail(c, VMC_ERR_STATE, "bonds not set (vmc_set_bonds)");
+  if (!plan_moment_index_ok(c->B, c->n_bonds))
+    return fail(c, VMC_ERR_UNSUPPORTED, "batch_size x n_bonds^2 does not fit the 32-bit row index of the second-order list");
+  PureMeasurement pure(c);
+  MomentBufs& m = c->mom;
+  const ParamSet& p = c->ps[which];
+  int rc = ensure_cache(c, which);           // ln|psi(x_c)| and the signs, as the local energies take them
+  if (rc == VMC_OK) {
+    Timer t(c, "mom_eloc");                  // first: its rows go through the buffers the passes then take
+    rc = local_energy_device(c, which);
+  }
+  int n1 = 0, n2 = 0;
+  if (rc == VMC_OK) rc = read_int(c, c->off + c->B, &n1);
+  if (rc == VMC_OK) rc = mom_reserve_list(c, n1);
+  if (rc == VMC_OK) {
+    Timer t(c, "mom_list");
+    hipError_t e = launch_mom_count(c->stream, c->configs, c->bonds, c->half_jx, c->quarter_jz, c->rowinfo, c->off + c->B, n1,
+                                    c->N, c->n_bonds, c->num_cus, m.cnt2, m.off2, m.diag1, m.self1);
+    if (e == hipSuccess) e = hipMemsetAsync(m.lanes, 0, 64 * (size_t)c->B * sizeof(double), c->stream);
+    if (e != hipSuccess) rc = fail(c, VMC_ERR_HIP, std::string("k_mom_count: ") + hipGetErrorString(e));
+  }
+  if (rc == VMC_OK) rc = read_int(c, m.off2 + n1, &n2);
+  const long long per = plan_moment_per_pass(n2, rows_per_pass, plan_measure_row_limit(c->N, c->Hp));
+  if (rc == VMC_OK && per < 1) rc = fail(c, VMC_ERR_HIP, "the second-order list has a negative length");
+  if (rc == VMC_OK) rc = m.desc.reserve(c, per, "mom.desc");
+  if (rc == VMC_OK) rc = m.coef.reserve(c, per, "mom.coef");
+  if (rc == VMC_OK) rc = grow_tmp(c, per);
+  rc = for_passes(n2, (int)per, rc, [&](long long q0, int n) { return mom_pass(c, which, q0, n, n1); });
+  std::vector<double> chain;
+  if (rc == VMC_OK) {
+    Timer t(c, "mom_fold");
+    hipError_t e = launch_mom_fold(c->stream, c->configs, c->bonds, c->half_jx, c->quarter_jz, c->rowinfo, c->off, c->val,
+                                   p.eloc, c->sgn ? p.sign : nullptr, m.diag1, m.self1, m.lanes, c->B, c->N, c->n_bonds,
+                                   m.chain, m.out);
+    if (e == hipSuccess && (e_loc || h2_loc)) {
+      chain.resize(2 * (size_t)c->B);
+      e = hipMemcpyAsync(chain.data(), m.chain, chain.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    }
+    if (e != hipSuccess) rc = fail(c, VMC_ERR_HIP, std::string("k_mom_chain: ") + hipGetErrorString(e));
+  }
+  std::vector<double> out;
+  rc = read_back(c, rc, "vmc_energy_moments", m.out, 6, &out);
+  if (rc != VMC_OK) return rc;
+  c->last_rows = n1;                         // (as vmc_local_energy leaves it)
+  for (int k = 0; k < 6 && sums; ++k) sums[k] = out[(size_t)k];
+  for (int k = 0; k < c->B && e_loc; ++k) e_loc[k] = chain[(size_t)k];
+  for (int k = 0; k < c->B && h2_loc; ++k) h2_loc[k] = chain[(size_t)c->B + (size_t)k];
+  if (n_rows2) *n_rows2 = n2;
   return VMC_OK;
 }
 

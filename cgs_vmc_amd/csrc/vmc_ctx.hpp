@@ -111,6 +111,17 @@ struct ProjBufs {
   DevBuf<double> acc;            // [n_sectors][B] w_s(c), sector major
   DevBuf<double> out;            // [n_sectors] w sums, [n_sectors] w E_loc sums, the E_loc sum, the chains alive
 };
+// Lanczos-step energies (moments.hip): per first-order row the count, prefix, diag(x^a) and rule 1's sum; the descriptors
+// and coefficients of one pass of second-order rows; the per-chain lanes, e and g; the sums
+struct MomentBufs {
+  DevBuf<int> cnt2, off2;        // [n1], [n1 + 1]
+  DevBuf<double> diag1, self1;   // [n1]
+  DevBuf<int2> desc;             // [rows per pass] {first-order row, b}
+  DevBuf<double> coef;           // [rows per pass]
+  DevBuf<double> lanes;          // [B][64]
+  DevBuf<double> chain;          // [2][B] e, g
+  DevBuf<double> out;            // [6]
+};
 // dimer-dimer correlations: the two lists of a call, ln|psi| (and, signed types, the sign) of every single exchange,
 // and the sums
 struct DimerBufs {
@@ -251,6 +262,7 @@ struct vmc_ctx {
   DimerBufs dimer;
   SymmBufs symm;
   ProjBufs proj;
+  MomentBufs mom;
   // the Hamiltonian as vmc_set_bonds was given it (vmc_projected_energy asks whether its ops are symmetries of it)
   std::vector<int32_t> ham_ij;
   std::vector<float> ham_jx, ham_jz;

@@ -413,6 +413,31 @@ class VmcEngine:
                                                we_sum.ctypes.data_as(dp), C.byref(e_sum), C.byref(n_alive)))
     return {'w_sum': w_sum, 'we_sum': we_sum, 'e_sum': float(e_sum.value), 'n_alive': int(n_alive.value)}
 
+  def energy_moments(self, which: int = _hip.VMC_PSI, rows_per_pass: int = 0, per_chain: bool = False):
+    """Lanczos-step energies over the current chains (extension, vmc_energy_moments): the local energy e(c) =
+    (H psi)(x_c) / psi(x_c) and the local value of H^2, g(c) = (H^2 psi)(x_c) / psi(x_c), under the bonds of set_bonds.
+    Returns a dict: 'e_sum', 'e2_sum', 'g_sum', 'eg_sum', 'g2_sum' -- the fp64 sums over the chains of e, e^2, g, e g and
+    g^2, so that h1 .. h4 = e_sum, e2_sum (or g_sum), eg_sum, g2_sum over n_alive estimate <H^n> -- 'n_alive', the chains
+    whose own amplitude does not vanish (the others add nothing), 'n_rows2', the length of the compacted list of doubly
+    exchanged configurations the ansatz evaluated, and with per_chain also 'e_loc' and 'h2_loc', float64 [batch_size].
+    Moves no chain, touches neither the step counter nor the accumulators nor the Hamiltonian, but leaves what
+    local_energy(which) leaves; rows_per_pass = 0 leaves the pass size to the library (every output is the same bits
+    either way)."""
+    dp = C.POINTER(C.c_double)
+    sums = np.empty(6, np.float64)
+    e_loc = np.empty(self.batch_size, np.float64) if per_chain else None
+    h2_loc = np.empty(self.batch_size, np.float64) if per_chain else None
+    n_rows2 = C.c_int64()
+    self._check(self._lib.vmc_energy_moments(
+        self._ctx, int(which), int(rows_per_pass), sums.ctypes.data_as(dp),
+        e_loc.ctypes.data_as(dp) if per_chain else None, h2_loc.ctypes.data_as(dp) if per_chain else None,
+        C.byref(n_rows2)))
+    out = {'e_sum': float(sums[0]), 'e2_sum': float(sums[1]), 'g_sum': float(sums[2]), 'eg_sum': float(sums[3]),
+           'g2_sum': float(sums[4]), 'n_alive': int(sums[5]), 'n_rows2': int(n_rows2.value)}
+    if per_chain:
+      out['e_loc'], out['h2_loc'] = e_loc, h2_loc
+    return out
+
   def last_connected_rows(self) -> int:
     v = C.c_int64()
     self._check(self._lib.vmc_last_connected_rows(self._ctx, C.byref(v)))

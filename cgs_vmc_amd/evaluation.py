@@ -125,7 +125,7 @@ def _sampling_eval_ops(wavefunction, hparams, shared_resources, make_value) -> E
 
 
 def _sampled(eval_ops, session, hparams, stack, per_sample) -> int:
-  """The sample loop of the five measurement evaluators, on the same schedule as MonteCarloOperatorEvaluator's (which
+  """The sample loop of the six measurement evaluators, on the same schedule as MonteCarloOperatorEvaluator's (which
   keeps its own loop: no all-reduce, and a fused path): thermalises for num_equilibration_sweeps sweeps, then takes
   num_evaluation_samples measurements, num_monte_carlo_sweeps sweeps apart.
   stack(session.run(value)) is the fp64 array of this rank's sums; with sharded chains the ranks' arrays are added by one
@@ -469,6 +469,116 @@ class ProjectedEnergyEvaluator(WavefunctionEvaluator):
     return {'perms': value.perms.copy(), 'flips': value.flips.copy(), 'characters': value.characters.copy(),
             'energy': energy, 'energy_err': energy_err, 'weight': weight, 'weight_err': weight_err,
             'plain_energy': float(plain), 'plain_energy_err': float(plain_err), 'samples': samples}
+
+
+class EnergyMomentsTensor(session_lib.Tensor):
+  """The six sums of VmcEngine.energy_moments over THIS rank's chains, float64 [6]: e, e^2, g, e g, g^2, chains alive;
+  `ensure_hamiltonian()` (optional) runs before every measurement: it puts the Hamiltonian's bonds in place."""
+
+  def __init__(self, engine, which: int, ensure_hamiltonian=None):
+    self.engine, self.which, self.ensure_hamiltonian = engine, which, ensure_hamiltonian
+    self.last_rows2 = 0
+    super(EnergyMomentsTensor, self).__init__(self._value, 'energy_moments')
+
+  def _value(self):
+    if self.ensure_hamiltonian is not None:
+      self.ensure_hamiltonian()
+    v = self.engine.energy_moments(self.which)
+    self.last_rows2 = v['n_rows2']
+    return np.array([v['e_sum'], v['e2_sum'], v['g_sum'], v['eg_sum'], v['g2_sum'], v['n_alive']], np.float64)
+
+
+LANCZOS_QUANTITIES = ('energy', 'variance', 'lanczos_energy', 'alpha', 'lanczos_variance', 'extrapolated_energy',
+                      'h2_check', 'h1', 'h2', 'h3', 'h4')
+# The local energies are fp32: a variance below this share of <e^2> is below what they resolve (eps32^2 ~ 1.4e-14 times the
+# conditioning of a sum of ratios), and the overlap matrix of the Lanczos step counts as degenerate.
+LANCZOS_DEGENERATE = 1e-10
+
+
+def lanczos_step(sums) -> Dict[str, float]:
+  """The quantities of LANCZOS_QUANTITIES from summed sums [6] = (sum e, sum e^2, sum g, sum e g, sum g^2, chains alive).
+  h1 .. h4 = <e>, <e^2>, <e g>, <g^2>; h2 = <e^2> serves both matrices of
+    [[h1, h2], [h2, h3]] v = E [[1, h1], [h1, h2]] v,
+  so the overlap matrix is a Gram matrix of the samples; lanczos_energy is the lowest E -- the lower root of
+  var E^2 - (h3 - h1 h2) E + (h1 h3 - h2^2) = 0, var = h2 - h1^2, taken in its cancellation-free form -- alpha = v1 / v0,
+  lanczos_variance = (h2 + 2 alpha h3 + alpha^2 h4) / (1 + 2 alpha h1 + alpha^2 h2) - E1^2, and extrapolated_energy the
+  line through (var, h1) and (lanczos_variance, E1) at variance 0.  A degenerate overlap matrix (var <= LANCZOS_DEGENERATE
+  h2: an eigenstate) gives lanczos_energy = extrapolated_energy = energy, alpha = 0, lanczos_variance = variance; no
+  chain alive gives nan throughout."""
+  s = np.asarray(sums, np.float64)
+  if not s[5] > 0:
+    return {k: float('nan') for k in LANCZOS_QUANTITIES}
+  h1, h2, hg, h3, h4 = (float(v) for v in s[:5] / s[5])
+  var = h2 - h1 * h1
+  out = {'energy': h1, 'variance': var, 'h2_check': hg, 'h1': h1, 'h2': h2, 'h3': h3, 'h4': h4}
+  e1, alpha, var1 = h1, 0.0, var
+  if var > LANCZOS_DEGENERATE * h2:
+    p, q = h3 - h1 * h2, h1 * h3 - h2 * h2
+    t = p + np.copysign(np.sqrt(max(p * p - 4.0 * var * q, 0.0)), p)
+    roots = [t / (2.0 * var)] + ([2.0 * q / t] if t != 0 else [])
+    e1 = float(min(roots))
+    d0 = h2 - e1 * h1                                   # the first row of (A - E B) v = 0
+    alpha = float((e1 - h1) / d0) if d0 != 0 else float('inf')
+    norm = 1.0 + 2.0 * alpha * h1 + alpha * alpha * h2
+    if np.isfinite(alpha) and norm > 0:
+      var1 = (h2 + 2.0 * alpha * h3 + alpha * alpha * h4) / norm - e1 * e1
+    else:
+      e1, alpha, var1 = h1, 0.0, var
+  out['lanczos_energy'], out['alpha'], out['lanczos_variance'] = e1, alpha, var1
+  out['extrapolated_energy'] = e1 if var1 == var else h1 - var * (e1 - h1) / (var1 - var)
+  return out
+
+
+def _jackknife(samples, fn, names):
+  """({name: fn(sum of the samples)[name]}, {name: delete-one-sample jackknife error}); errors 0 for a single sample.
+  The deviations are taken against the first leave-one-out value, so identical samples give exactly 0."""
+  n = samples.shape[0]
+  total = samples.sum(axis=0)
+  value = fn(total)
+  err = {k: 0.0 for k in names}
+  if n > 1:
+    left = [fn(total - samples[i]) for i in range(n)]
+    for k in names:
+      d = np.array([l[k] - left[0][k] for l in left], np.float64)
+      err[k] = float(np.sqrt((n - 1.0) / n * ((d - d.mean()) ** 2).sum()))
+  return value, err
+
+
+class LanczosStepEvaluator(WavefunctionEvaluator):
+  """One Lanczos step and the variance extrapolation by running MCMC on psi (extension): from the local values e of H and
+  g of H^2 per chain, the moments <H^n>, n = 1 .. 4, the best energy of psi + alpha H psi, its variance, and the energy
+  extrapolated to zero variance through the two points.  The signatures are MonteCarloOperatorEvaluator's; `operator` is
+  the HeisenbergHamiltonian."""
+
+  def build_eval_ops(self, wavefunction, operator, hparams,
+                     shared_resources: Dict[graph_builders.ResourceName, Any]) -> EvalOps:
+    configs = graph_builders.get_configs(shared_resources, hparams.batch_size, hparams.num_sites)
+    ensure = None if configs is None else (lambda: configs._ensure_hamiltonian(operator))
+    return _sampling_eval_ops(wavefunction, hparams, shared_resources, lambda engine: EnergyMomentsTensor(
+        engine, wavefunction._which, ensure))
+
+  def run_evaluation(self, eval_ops: EvalOps, session, hparams, epoch_num: int) -> Dict[str, Any]:
+    """Thermalises for num_equilibration_sweeps sweeps, then takes num_evaluation_samples measurements,
+    num_monte_carlo_sweeps sweeps apart (the loop of MonteCarloOperatorEvaluator).  A measurement is the six sums of
+    VmcEngine.energy_moments over the chains of ALL ranks: with sharded chains the ranks' fp64 arrays are added by one
+    parallel.allreduce_array per sample.  Returns a dict: every name of LANCZOS_QUANTITIES, formed by lanczos_step from the
+    sums of all samples, and under name + '_err' its delete-one-sample jackknife error (0 for a single sample);
+    'n_rows2', the length of the last measurement's second-order list on this rank; 'samples' [n_samples][6], the
+    stacked sums."""
+    del epoch_num
+    value = eval_ops.value
+    samples = np.empty((hparams.num_evaluation_samples, 6), np.float64)
+
+    def per_sample(s, sums):
+      samples[s] = sums
+    self.acceptance_count = _sampled(eval_ops, session, hparams, lambda v: np.asarray(v, np.float64), per_sample)
+    out, err = _jackknife(samples, lanczos_step, LANCZOS_QUANTITIES)
+    out = dict(out)
+    for k in LANCZOS_QUANTITIES:
+      out[k + '_err'] = err[k] if np.isfinite(out[k]) else float('nan')
+    out['samples'] = samples
+    out['n_rows2'] = int(getattr(value, 'last_rows2', 0))
+    return out
 
 
 class VectorWavefunctionEvaluator(WavefunctionEvaluator):

@@ -477,6 +477,34 @@ int vmc_projected_energy(vmc_ctx* ctx, int which, int32_t n_ops, const int32_t* 
                          double* w_sum /*[n_sectors]*/, double* we_sum /*[n_sectors]*/, double* e_sum /*[1]*/,
                          int64_t* n_alive /*[1]*/);
 
+/* Lanczos-step energies: the local values of H and H^2 -- EXTENSION with no reference counterpart.  Over the ctx's
+ * current chains x_c and the bonds of vmc_set_bonds, H = sum_b j_x[b] (S+S- + S-S+) / 2 + j_z[b] SzSz:
+ *   e(c) = (H psi)(x_c) / psi(x_c)      what vmc_local_energy gives (fp32, widened)
+ *   g(c) = (H^2 psi)(x_c) / psi(x_c)    = diag(x) e(x) + sum_{a anti on x} hx_a [ r(x^a) diag(x^a) + sum_{b anti on x^a} hx_b r(x^{ab}) ]
+ * with hx_b = j_x[b] / 2, diag(y) = sum_b (j_z[b] / 4) y_i y_j, y^a = y with the sites of bond a exchanged and
+ * r(y) = psi(y) / psi(x_c), always against the chain's own amplitude.  e(c) and the products hx_a r(x^a) are those of the
+ * local-energy call this entry runs first (fp32); everything added on top is fp64.
+ *   sums = { sum_c e, sum_c e^2, sum_c g, sum_c e g, sum_c g^2, the number of chains alive }            (fp64)
+ * so that under |psi|^2 sampling h1 = <e>, h2 = <e^2> (= <g>), h3 = <e g>, h4 = <g^2> are the moments <H^n> a Lanczos
+ * step psi + alpha H psi and the variance extrapolation need.  e_loc / h2_loc [batch_size] (optional) are e and g per
+ * chain.  A chain whose own amplitude vanishes has e = g = 0, adds to no sum and is not alive.
+ * The rows x^{ab} are a compacted list, chain-major, then a, then b ascending: b naming the site pair of a (a itself, a
+ * twin bond) gives the term hx_a hx_b without a row; b disjoint from a gives one row for a < b alone, counted twice; b
+ * sharing one site with a gives one row.  *n_rows2 is the length of that list; it goes through the ansatz type's own
+ * full forward in passes of at most rows_per_pass rows (0: the library decides).
+ * Determinism: every output is the same bits for every rows_per_pass -- a pass may end inside a chain's rows; row p of a
+ * chain is added into lane p mod 64 of the chain's accumulator in ascending p, the lanes are folded by a fixed butterfly
+ * and the chains are summed in strictly ascending order (csrc/moments.hip states every order).
+ * A pure measurement like its siblings: chains, step counter, accumulators, the Hamiltonian's bonds and the validity of
+ * the amplitude and activation caches are as before on return -- except what vmc_local_energy(ctx, which, ...) leaves
+ * (the chains' local energies of `which` on the device, vmc_last_connected_rows).
+ * Refusals, before anything is launched: a bad `which` or rows_per_pass < 0: VMC_ERR_INVALID; no bonds set:
+ * VMC_ERR_STATE; an output activation other than exp on an unsigned type, a product ctx, or batch_size x n_bonds^2 beyond
+ * the 32-bit row index: VMC_ERR_UNSUPPORTED; a factor of a product ctx: VMC_ERR_STATE.  Outputs may be NULL. */
+int vmc_energy_moments(vmc_ctx* ctx, int which, int64_t rows_per_pass /*0: the library decides*/, double sums[6],
+                       double* e_loc /*[batch_size] or NULL*/, double* h2_loc /*[batch_size] or NULL*/,
+                       int64_t* n_rows2 /*[1]*/);
+
 /* Stochastic reconfiguration -- EXTENSION: named by the north star, absent from the reference
  * (training.py has only the plain energy gradient + Adam), so these entries replace no reference
  * interface; they sit where TrainOpsTraditional.apply_gradients (training.py:560-567) sits.
