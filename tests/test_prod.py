@@ -189,3 +189,105 @@ def test_product_oracle_with_signed_factors():
   from tests import pbdg_oracle as po
   np.testing.assert_allclose(prod.psi(cfg), po.psi(th, cfg, 0.0) * vec[eo.index(cfg, top, bot)], rtol=1e-12)
   assert (np.sign(prod.psi(cfg)) == np.sign(po.psi(th, cfg, 0.0)) * np.sign(vec[eo.index(cfg, top, bot)])).all()
+
+
+# ---- the inputs of tests/test_gpu_prod_shapes.py (tests/prod_shape_cases.py): the conditions its checks lean on, proved
+# on the oracle alone
+from tests import prod_shape_cases as psc     # noqa: E402
+
+
+@pytest.mark.parametrize('cid', psc.IDS)
+def test_shape_case_replay_stays_inside_the_caps(cid):
+  """Banded verdicts over the whole replay: at most 2 chains (S5: none, so mc_steps' count is compared exactly);
+  acceptance share in [0.2, 0.8] on S1-S5, so k_prod_accept's patched-spin path runs both ways; S6, one chain: at least
+  one accept and one reject."""
+  c, r = psc.CASES[cid], psc.replay(cid)
+  assert c['steps'] == {'S4': 40, 'S5': 20}.get(cid, 3 * c['n'])
+  print('%s: share %.3f, accepted %d of %d, banded chains %d' % (cid, r.share, r.accepted, r.accepts.size, r.band.sum()))
+  assert r.band.sum() <= (0 if cid == 'S5' else 2)
+  assert r.accepts.shape == (c['steps'], c['b_chains']) and (r.configs.sum(1) == 0).all()
+  if cid == 'S6':
+    assert r.accepts.any() and not r.accepts.all()
+  else:
+    assert 0.2 <= r.share <= 0.8
+  assert (r.configs != psc.start(cid)).any()
+
+
+def test_shape_case_evaluation_replay_has_no_banded_verdict():
+  eq, samples = psc.eval_replay()
+  assert not eq.band.any() and not any(s.band.any() for s in samples)
+  assert all(0 < s.accepted < s.accepts.size for s in samples)
+
+
+@pytest.mark.parametrize('cid', psc.IDS)
+def test_shape_case_inputs(cid):
+  """The bond list is irregular (N + 5 bonds, some i > j, one jx = 0, one jx < 0), the offsets and tails are the ones
+  the table names, and the pbdg logit bound 64 (N/2) eps32 kappa stays below 0.5 on every test row, so every sign is
+  checked."""
+  c = psc.CASES[cid]
+  bonds, jx, jz = psc.bonds(cid)
+  n = c['n']
+  assert len(bonds) == n + 5 and all(i != j and 0 <= i < n and 0 <= j < n for i, j in bonds)
+  assert any(i > j for i, j in bonds) and any(i < j for i, j in bonds) and any(abs(i - j) > 2 for i, j in bonds)
+  assert (jx == 0).sum() == 1 and (jx < 0).sum() == 1 and jx[(jx != 0) & (jx > 0)].min() >= 0.3 and jx.max() <= 1.7
+  assert jz.min() >= -1.0 and jz.max() <= 1.5
+  prod = psc.product_of(cid)
+  rows = psc.compared_rows(cid)
+  assert (rows.sum(1) == 0).all()
+  bound = psc.pbdg_logit_bound(prod, rows)
+  print('%s: largest pbdg logit bound %.3g over %d rows' % (cid, bound.max(), len(rows)))
+  assert bound.max() < 0.5
+  assert np.isfinite(np.log(np.abs(prod.psi(rows)))).all()
+  if psc.signed(cid) and c['b_chains'] > 4:
+    ref = prod.psi(psc.start(cid))
+    assert (ref > 0).any() and (ref < 0).any()        # both signs among the start chains
+  for th in psc.thetas(cid):
+    assert th.dtype == np.float32
+  if cid == 'S4':
+    assert (n + 3) // 4 == 65 and n % 4 == 2         # block 64: lane 0's second trip, two valid sites
+  if cid == 'S5':
+    assert c['b_chains'] > 1024 and c['b_chains'] % 4 == 1
+
+
+def test_shape_case_sampler_proposals_reach_the_last_philox_block():
+  """S4: over the replay some proposal names a site of Philox block 64 (sites 256, 257), and some accepted move has
+  changed a spin there before a later proposal -- the second trip of k_prod_accept's loop with patched spins decides."""
+  cid = 'S4'
+  prod, cur = psc.product_of(cid), psc.start(cid)
+  hit = 0
+  for k in range(psc.CASES[cid]['steps']):
+    i_up, i_dn, u = psc.proposals(cid, cur, k)
+    hit += int(((i_up >= 256) | (i_dn >= 256)).sum())
+    cur, _, _ = pro.mc_step(prod, cur, i_up, i_dn, u)
+  assert hit >= 1
+
+
+@pytest.mark.parametrize('name', sorted(psc.SCRIPTS))
+def test_shape_case_injected_scripts_hold_every_group(name):
+  """At least two chains start on psi = 0 and leave on their first non-zero candidate, at least two candidates land on
+  a zero and are rejected, at least two proposals name sites with the wrong spins; no verdict is banded."""
+  s = psc.SCRIPTS[name]()
+  print('%s: zero starts %d (left on a non-zero candidate %d), zero candidates %d, bad proposals %d' % (
+      name, s.zero_start, s.first_nonzero_accepts, s.zero_cand, s.bad))
+  assert s.zero_start >= 2 and s.first_nonzero_accepts >= 2 and s.zero_cand >= 2 and s.bad >= 2
+  assert not s.band.any()
+  assert (s.prod.psi(s.start) == 0).sum() >= 2
+  for after in s.after:
+    assert (after.sum(1) == 0).all()
+  before = [s.start] + s.after[:-1]
+  for cur, new, mask, bad in zip(before, s.after, s.masks, s.bads):       # a bad proposal: mask false, the chain stays
+    assert not mask[bad].any() and (new[bad] == cur[bad]).all()
+    assert ((new != cur).sum(1) == 2 * mask).all()
+  assert s.bads[2].sum() >= 5 and not any(b.any() for k, b in enumerate(s.bads) if k != 2)
+
+
+def test_shape_case_zero_supervisor_entries_sit_under_two_chains():
+  top, bot, _ = eo.lin_tables(psc.CASES['S3']['n'])
+  idx = eo.index(psc.start('S3'), top, bot)
+  assert len(set(idx[:2].tolist())) == 2 and not np.isin(idx[2:], idx[:2]).any()
+
+
+@pytest.mark.parametrize('cid', ['S1', 'S2', 'S3'])
+def test_shape_case_supervisor_gives_ratios_of_both_signs(cid):
+  _, e_w, ratio, _ = psc.itswo_reference(cid)
+  assert np.isfinite(ratio).all() and np.isfinite(e_w).all() and (ratio > 0).any() and (ratio < 0).any()
