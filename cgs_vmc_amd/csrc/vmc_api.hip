@@ -139,6 +139,27 @@ int wide_stage_act(const vmc_ctx* c, int l) {
   return (c->rbm && l == c->n_hh) ? VMC_ACT_LOGCOSH_ : c->hact;
 }
 
+// Hidden layer l of the dense trunk as a GEMM: the weights [H][H] and biases of theta, row buffers of pitch Hp
+GemmArgs trunk_gemm(const vmc_ctx* c, const ParamSet& p, int l, const float* A, int rows, float* C, int act) {
+  GemmArgs g; memset(&g, 0, sizeof(g));
+  g.A = A; g.sam = c->Hp; g.sak = 1;
+  g.B = p.theta + off_w(c, l); g.sbk = c->H; g.sbn = 1;
+  g.M = rows; g.N = c->H; g.K = c->H; g.C = C; g.ldc = c->Hp;
+  g.bias = p.theta + off_b(c, l); g.epilogue = 1; g.splitk = 1; g.act = act;
+  return g;
+}
+
+// nnb's pairing layer: out[rows][N^2] = a_L W_out + b_out
+GemmArgs nnb_pairing_gemm(const vmc_ctx* c, const ParamSet& p, const float* A, int rows, float* C) {
+  const long long NN = (long long)c->N * c->N;
+  GemmArgs g; memset(&g, 0, sizeof(g));
+  g.A = A; g.sam = c->Hp; g.sak = 1;
+  g.B = p.theta + off_wout(c); g.sbk = NN; g.sbn = 1;
+  g.M = rows; g.N = (int)NN; g.K = c->H; g.C = C; g.ldc = NN;
+  g.bias = p.theta + off_bout(c); g.epilogue = 4; g.splitk = 1;
+  return g;
+}
+
 // The last H x H layer of a forward whose activations nobody reads: turn its GEMM into the row-dot form (the output
 // layer's dot product as column-tile partials in c->wide_dot, nothing stored to C) where a tile kernel takes the
 // shape.  CGS_VMC_ROWDOT=0: never (A/B measurements, tests).  Returns whether `g` was changed.
@@ -176,11 +197,7 @@ int wide_forward(vmc_ctx* c, int which, const float* z1, const int2* rowinfo, lo
                                    Hp, wide_stage_act(c, 0), c->wbuf[0]));
     bool dot_fused = false;          // the output dot rode in the last layer's GEMM (row-dot epilogue)
     for (int l = 1; l <= NH; ++l) {
-      GemmArgs g; memset(&g, 0, sizeof(g));
-      g.A = c->wbuf[(l - 1) & 1]; g.sam = Hp; g.sak = 1;
-      g.B = p.theta + off_w(c, l); g.sbk = H; g.sbn = 1;
-      g.M = rows; g.N = H; g.K = H; g.C = c->wbuf[l & 1]; g.ldc = Hp;
-      g.bias = p.theta + off_b(c, l); g.epilogue = 1; g.splitk = 1; g.act = wide_stage_act(c, l);
+      GemmArgs g = trunk_gemm(c, p, l, c->wbuf[(l - 1) & 1], rows, c->wbuf[l & 1], wide_stage_act(c, l));
       if (l == NH) dot_fused = wide_rowdot(c, p, g);
       HIPCHK(c, launch_gemm(c->stream, g));
     }
@@ -197,28 +214,16 @@ int wide_forward(vmc_ctx* c, int which, const float* z1, const int2* rowinfo, lo
 int nnb_forward(vmc_ctx* c, int which, const float* z1, const float* configs, const int2* rowinfo, long long n_rows,
                 bool ratio, float* out, float* out_sign) {
   ParamSet& p = c->ps[which];
-  const int H = c->H, Hp = c->Hp, NH = c->n_hh;
+  const int Hp = c->Hp, NH = c->n_hh;
   const long long NN = (long long)c->N * c->N;
   const int2* bonds = c->bonds ? c->bonds : c->bond_dummy;
   for (long long row0 = 0; row0 < n_rows; row0 += c->nnb_rows) {
     const int rows = (int)(n_rows - row0 < c->nnb_rows ? n_rows - row0 : c->nnb_rows);
     HIPCHK(c, launch_wide_rows_act(c->stream, z1, p.w1p, rowinfo, bonds, row0, rows, Hp, VMC_ACT_RELU_, c->wbuf[0]));
-    for (int l = 1; l <= NH; ++l) {
-      GemmArgs g; memset(&g, 0, sizeof(g));
-      g.A = c->wbuf[(l - 1) & 1]; g.sam = Hp; g.sak = 1;
-      g.B = p.theta + off_w(c, l); g.sbk = H; g.sbn = 1;
-      g.M = rows; g.N = H; g.K = H; g.C = c->wbuf[l & 1]; g.ldc = Hp;
-      g.bias = p.theta + off_b(c, l); g.epilogue = 1; g.splitk = 1; g.act = VMC_ACT_RELU_;
-      HIPCHK(c, launch_gemm(c->stream, g));
-    }
-    {   // the pairing layer of the block: out[rows][N^2] = a_L W_out + b_out
-      GemmArgs g; memset(&g, 0, sizeof(g));
-      g.A = c->wbuf[NH & 1]; g.sam = Hp; g.sak = 1;
-      g.B = p.theta + off_wout(c); g.sbk = NN; g.sbn = 1;
-      g.M = rows; g.N = (int)NN; g.K = H; g.C = c->nnb_out; g.ldc = NN;
-      g.bias = p.theta + off_bout(c); g.epilogue = 4; g.splitk = 1;
-      HIPCHK(c, launch_gemm(c->stream, g));
-    }
+    for (int l = 1; l <= NH; ++l)
+      HIPCHK(c, launch_gemm(c->stream, trunk_gemm(c, p, l, c->wbuf[(l - 1) & 1], rows, c->wbuf[l & 1], VMC_ACT_RELU_)));
+    // the pairing layer of the block
+    HIPCHK(c, launch_gemm(c->stream, nnb_pairing_gemm(c, p, c->wbuf[NH & 1], rows, c->nnb_out)));
     NnbRowsArgs a; memset((void*)&a, 0, sizeof(a));
     a.out = c->nnb_out; a.ldo = NN; a.N = c->N; a.configs = configs; a.rowinfo = rowinfo + row0; a.bonds = bonds;
     a.n_rows = rows;
@@ -467,13 +472,14 @@ float host_activation(int act, float x) {
     g_create_error = std::string(#expr) + ": " + hipGetErrorString(e2); return VMC_ERR_HIP; } } while (0)
 #define NEW(buf, n) do { if ((buf).alloc(c, (n), #buf) != VMC_OK) { g_create_error = c->err; return VMC_ERR_HIP; } } while (0)
 
-// path_wide: the two activation row buffers of c->wrows rows and the sampler's proposal buffers
+// path_wide: the two activation row buffers of c->wrows rows, and the proposal buffers of a step-at-a-time sampler (the
+// general dense sampler and nnb's; PATH_FUSED_LDS allocates them too and never reads them)
 static int create_wide_rows(vmc_ctx* c) {
   const long long B = c->B, Hp = c->Hp;
   NEW(c->wbuf[0], c->wrows * Hp); NEW(c->wbuf[1], c->wrows * Hp);
-  NEW(c->wide_u, B);
+  NEW(c->prop_u, B);
   NEW(c->wide_dot, (long long)gemm_rowdot_tiles(c->H) * c->wrows);
-  NEW(c->wide_iup, B); NEW(c->wide_idn, B); NEW(c->wide_zero, Hp);
+  NEW(c->prop_iup, B); NEW(c->prop_idn, B); NEW(c->wide_zero, Hp);
   CA(hipMemsetAsync(c->wide_zero, 0, Hp * sizeof(float), c->stream));
   return VMC_OK;
 }
@@ -560,7 +566,7 @@ static int create_conv_general(vmc_ctx* c) {
   for (int i = 0; i < 2; ++i) NEW(c->cg_fm[i], rows_fwd * cg.N * cgen_fp(cg));
   NEW(c->cg_sum, rows_fwd); NEW(c->cg_zero, 1); NEW(c->cg_lnew, B);
   CA(hipMemsetAsync(c->cg_zero, 0, sizeof(float), c->stream));
-  NEW(c->wide_u, B); NEW(c->wide_iup, B); NEW(c->wide_idn, B);
+  NEW(c->prop_u, B); NEW(c->prop_iup, B); NEW(c->prop_idn, B);
   return VMC_OK;
 }
 

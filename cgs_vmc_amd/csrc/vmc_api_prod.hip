@@ -32,7 +32,7 @@ struct ProdState {
 
 namespace vmcapi {
 
-static int prod_alive(vmc_ctx* c) {
+int prod_alive(vmc_ctx* c) {
   if (c->prod->dead) return fail(c, VMC_ERR_STATE, "prod: a factor of this product ctx has been destroyed");
   return VMC_OK;
 }
@@ -128,26 +128,19 @@ int prod_local_energy(vmc_ctx* c, int which) {
 // n_steps x mc_step (graph_builders.py:38-89): per step the candidates (written straight into the factors' `configs`), a
 // full forward of both factors on them -- the route vmc_amplitude takes, so the cached logits of the final chains are
 // vmc_amplitude's bit for bit --, and one accept kernel that also draws the next proposal
-int prod_run_sweep(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn, float* dbg_u,
-                   unsigned long long step0, bool count_accepted) {
+int prod_run_sweep(vmc_ctx* c, const SweepCall& call) {
   ProdState* st = c->prod;
   PROPAGATE(prod_alive(c));
   const int B = c->B, N = c->N;
-  const uint32_t seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull), seed_hi = (uint32_t)(c->d.seed >> 32);
-  if (dbg) {
-    HIPCHK(c, launch_wide_propose(c->stream, c->configs, B, N, seed_lo, seed_hi, c->d.chain_offset, step0, nullptr,
-                                  nullptr, nullptr, dbg_up, dbg_dn, dbg_u));
-    return VMC_OK;
-  }
+  const long long n_steps = call.n_steps;
+  const bool injected = call.injected;
   PROPAGATE(prod_ensure_cache(c, VMC_PSI));
-  if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), c->stream));
+  PROPAGATE(zero_accepted(c, call, c->stream));
   if (n_steps <= 0) return VMC_OK;
   vmc_ctx *a = st->child[0], *b = st->child[1];
   Timer t(c, "sweep");
   HIPCHK(c, hipMemsetAsync(st->acc_cnt, 0, (size_t)B * sizeof(unsigned), c->stream));
-  HIPCHK(c, launch_wide_propose(c->stream, c->configs, B, N, seed_lo, seed_hi, c->d.chain_offset, step0,
-                                injected ? c->inj_up : nullptr, injected ? c->inj_dn : nullptr,
-                                injected ? c->inj_u : nullptr, st->iup, st->idn, st->u));
+  HIPCHK(c, launch_proposals(c, c->stream, call.step0, injected, st->iup, st->idn, st->u));
   for (long long s = 0; s < n_steps; ++s) {
     HIPCHK(c, launch_prod_candidates(c->stream, c->configs, st->iup, st->idn, B, N, a->configs, b->configs));
     st->on_chains = false;
@@ -161,18 +154,16 @@ int prod_run_sweep(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* 
     x.la = st->l[0][0]; x.sa = st->s[0][0]; x.lb = st->l[0][1]; x.sb = st->s[0][1];
     x.ca_l = a->ps[0].logit; x.ca_s = a->sgn ? a->ps[0].sign : nullptr;
     x.cb_l = b->ps[0].logit; x.cb_s = b->sgn ? b->ps[0].sign : nullptr;
-    x.acc_mask = injected ? c->acc_mask : nullptr;
+    x.acc_mask = injected ? c->acc_mask : nullptr;      // (k_prod_accept never sees the injected proposals: only the mask)
     x.acc_cnt = st->acc_cnt;
     x.draw_next = (!injected && s + 1 < n_steps) ? 1 : 0;
-    x.next_step = step0 + (unsigned long long)s + 1;
-    x.seed_lo = seed_lo; x.seed_hi = seed_hi; x.chain_offset = c->d.chain_offset;
+    x.next_step = call.step0 + (unsigned long long)s + 1;
+    set_key(c, x);
     HIPCHK(c, launch_prod_accept(c->stream, x));
   }
   // (also when !count_accepted: vmc_evaluate zeroes d_accepted once and lets the sweeps of all its samples add to it)
   HIPCHK(c, launch_prod_count_fold(c->stream, st->acc_cnt, B, c->d_accepted));
-  c->acts_valid = false;
-  c->acc_since_sweep = false;
-  return VMC_OK;
+  return chains_moved(c, call);
 }
 
 // TrainOps.accumulate_gradients of the product: its E_loc (EnergyGradient) or its signed ITSWO ratio is the weight vector

@@ -7,11 +7,12 @@ using namespace vmcapi;
 
 namespace vmcapi {
 
-// One sampler launch: reads the current chain buffers, writes the alternate set, swaps.
-//   overtake: the launch goes to sweep_stream and only waits for `dep` (an event on `stream`)
-// fc_layer_size > 256: one mc_step = proposals, candidate first layer, H x H GEMMs, output dot,
-// accept -- a handful of launches per step, chain state updated in place
-// the sampler launch of this ctx (the 3 x bf16 split sampler when it is switched on)
+// Seven samplers share one host scaffold (vmc_ctx.hpp: SweepCall, philox_key / set_key, launch_proposals, set_injected,
+// zero_accepted, chains_moved, sampler_returned): run_sweep_wide / _cgen / _pbdg / _edvec / _nnb, prod_run_sweep
+// (vmc_api_prod.hip) and the fused arm at the bottom of run_sweep.  What one of them writes out beside the scaffold is
+// where it differs from the others.
+
+// the fused dense sampler launch of this ctx (the 3 x bf16 split sampler when it is switched on)
 static hipError_t launch_sampler(vmc_ctx* c, hipStream_t st, SweepArgs& a, int which) {
   if (c->path == PATH_SPLIT_SWEEP) { a.p16s = c->ps[which].p16s; return launch_sweep16_split(st, a); }
   // (injected proposals, the proposal dump and the diagnostic stamps stay on k_sweep16: the same chains, bit for bit)
@@ -19,26 +20,44 @@ static hipError_t launch_sampler(vmc_ctx* c, hipStream_t st, SweepArgs& a, int w
   return launch_sweep16(st, a, c->Hp);
 }
 
-static int run_sweep_wide(vmc_ctx* c, long long n_steps, bool injected, unsigned long long step0, bool count_accepted) {
+// What every launch of the fused dense sampler kernels is handed: parameter set `which`, the current chains with their
+// z1 / logit cache as the input, the alternate chain buffer as the output, the counter, the shape, the key, the steps and the
+// activations.  Everything else is zero: where z1 / logit (/ onsite) go, rbm, waves / no_w1l, the injected proposals, the
+// dump, the hand-over, the census and cache_in_valid are the caller's, because the three callers differ in them.
+static SweepArgs fused_sweep_args(vmc_ctx* c, int which, unsigned long long step0, long long n_steps) {
+  const ParamSet& p = c->ps[which];
+  SweepArgs a;
+  memset(&a, 0, sizeof(a));
+  a.pp = p.packed();
+  a.configs_in = c->configs; a.z1_in = p.z1; a.logit_in = p.logit;
+  a.configs = c->configs_alt;
+  a.accepted = c->d_accepted;
+  a.B = c->B; a.N = c->N; a.n_hidden = c->n_hh;
+  set_key(c, a);
+  a.step0 = step0; a.n_steps = n_steps;
+  a.act = c->hact; a.oact = c->oact;
+  return a;
+}
+
+static int run_sweep_wide(vmc_ctx* c, const SweepCall& s) {
   ParamSet& p = c->ps[0];
-  const int B = c->B, N = c->N, H = c->H, Hp = c->Hp, NH = c->n_hh;
-  const uint32_t seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull), seed_hi = (uint32_t)(c->d.seed >> 32);
+  const int B = c->B, NH = c->n_hh;
   PROPAGATE(ensure_cache(c, VMC_PSI));
-  if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), c->stream));
+  PROPAGATE(zero_accepted(c, s, c->stream));
   Timer t(c, "sweep");
   // Per step ONE k_wide_step launch (accept the move in flight, propose the next, candidate activations) and
   // the H x H layers as GEMMs; a segment of steps ends with an accept-only launch.
   WideStepArgs w; memset((void*)&w, 0, sizeof(w));
   w.configs = c->configs; w.z1 = p.z1; w.w1p = p.w1p; w.a_last = c->wbuf[NH & 1]; w.a0 = c->wbuf[0];
   w.wout = p.woutp; w.bout = p.bout; w.logit = p.logit;
-  w.iup = c->wide_iup; w.idn = c->wide_idn; w.u = c->wide_u;
-  if (injected) { w.inj_up = c->inj_up; w.inj_dn = c->inj_dn; w.inj_u = c->inj_u; w.acc_mask = c->acc_mask; }
+  w.iup = c->prop_iup; w.idn = c->prop_idn; w.u = c->prop_u;
+  if (s.injected) set_injected(c, w);
   w.accepted = c->d_accepted;
   if (c->rbm) { w.onsite = p.onsite; w.won = p.won; }
-  w.B = B; w.N = N; w.H = H; w.Hp = Hp; w.act = wide_stage_act(c, 0); w.oact = c->oact;
-  w.seed_lo = seed_lo; w.seed_hi = seed_hi; w.chain_offset = c->d.chain_offset;
+  w.B = B; w.N = c->N; w.H = c->H; w.Hp = c->Hp; w.act = wide_stage_act(c, 0); w.oact = c->oact;
+  set_key(c, w);
   bool in_flight = false;                          // a proposal whose last-layer activations are in a_last
-  for (long long st = 0; st < n_steps; ++st) {
+  for (long long st = 0; st < s.n_steps; ++st) {
     if (st > 0 && st % 128 == 0) {   // z1 is updated incrementally: re-derive it from the spins now and then
       w.do_accept = 1; w.do_propose = 0;
       HIPCHK(c, launch_wide_step(c->stream, w));
@@ -46,15 +65,11 @@ static int run_sweep_wide(vmc_ctx* c, long long n_steps, bool injected, unsigned
       p.cache_valid = false;
       PROPAGATE(ensure_cache(c, VMC_PSI));
     }
-    w.do_accept = in_flight ? 1 : 0; w.do_propose = 1; w.step = step0 + (unsigned long long)st;
+    w.do_accept = in_flight ? 1 : 0; w.do_propose = 1; w.step = s.step0 + (unsigned long long)st;
     HIPCHK(c, launch_wide_step(c->stream, w));
     for (int l = 1; l <= NH; ++l) {
-      GemmArgs g; memset(&g, 0, sizeof(g));
-      g.A = c->wbuf[(l - 1) & 1]; g.sam = Hp; g.sak = 1;
-      g.B = p.theta + off_w(c, l); g.sbk = H; g.sbn = 1;
-      g.M = B; g.N = H; g.K = H; g.C = c->wbuf[l & 1]; g.ldc = Hp;
-      g.bias = p.theta + off_b(c, l); g.epilogue = 1; g.splitk = 1; g.act = wide_stage_act(c, l);
-      if (l == NH && wide_rowdot(c, p, g)) { w.dot_part = c->wide_dot; w.n_part = gemm_rowdot_tiles(H); }
+      GemmArgs g = trunk_gemm(c, p, l, c->wbuf[(l - 1) & 1], B, c->wbuf[l & 1], wide_stage_act(c, l));
+      if (l == NH && wide_rowdot(c, p, g)) { w.dot_part = c->wide_dot; w.n_part = gemm_rowdot_tiles(c->H); }
       HIPCHK(c, launch_gemm(c->stream, g));
     }
     in_flight = true;
@@ -63,9 +78,7 @@ static int run_sweep_wide(vmc_ctx* c, long long n_steps, bool injected, unsigned
     w.do_accept = 1; w.do_propose = 0;
     HIPCHK(c, launch_wide_step(c->stream, w));
   }
-  c->acts_valid = false;
-  c->acc_since_sweep = false;
-  return VMC_OK;
+  return chains_moved(c, s);
 }
 
 // z1 / logit (/ onsite) cache of parameter set `which` for the current chains by ONE refresh pass of the sampler
@@ -80,20 +93,10 @@ bool sampler_refresh_ok(const vmc_ctx* c) {
 int refresh_cache_by_sampler(vmc_ctx* c, int which) {
   PROPAGATE(ensure_packed(c, which));
   ParamSet& p = c->ps[which];
-  SweepArgs a;
-  memset(&a, 0, sizeof(a));
-  a.pp = p.packed();
-  a.configs_in = c->configs; a.z1_in = p.z1; a.logit_in = p.logit;
-  a.configs = c->configs_alt; a.z1 = p.z1; a.logit = p.logit;
+  SweepArgs a = fused_sweep_args(c, which, c->step, 0);      // n_steps = 0, cache_in_valid = 0: the refresh pass
+  a.z1 = p.z1; a.logit = p.logit;                            // in place
   a.onsite = p.onsite; a.rbm = c->rbm ? 1 : 0;
-  a.accepted = c->d_accepted;
-  a.B = c->B; a.N = c->N; a.n_hidden = c->n_hh;
-  a.chain_offset = c->d.chain_offset;
-  a.seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull); a.seed_hi = (uint32_t)(c->d.seed >> 32);
-  a.step0 = c->step; a.n_steps = 0;
   a.waves = c->sweep_waves; a.no_w1l = c->sweep_no_w1l;
-  a.act = c->hact; a.oact = c->oact;
-  a.cache_in_valid = 0;
   Timer t(c, "refresh");
   HIPCHK(c, launch_sampler(c, c->stream, a, which));
   p.cache_valid = true;
@@ -119,12 +122,13 @@ static int cgen_sweep_groups(const vmc_ctx* c) {
 // The sampler of the general convolution path: per mc_step the proposals (k_wide_propose: the Philox streams and the
 // arg-max / arg-min rule of every sampler here), a full forward of the B candidates (the exchanged pair negated as the
 // first convolution gathers its operand), the Metropolis test and commit.  In place on configs / logit.
-static int run_sweep_cgen(vmc_ctx* c, long long n_steps, bool injected, unsigned long long step0, bool count_accepted) {
+static int run_sweep_cgen(vmc_ctx* c, const SweepCall& s) {
   ParamSet& p = c->ps[0];
   const int B = c->B, N = c->N;
-  const uint32_t seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull), seed_hi = (uint32_t)(c->d.seed >> 32);
+  const long long n_steps = s.n_steps;
+  const unsigned long long step0 = s.step0;
   PROPAGATE(ensure_cache(c, VMC_PSI));
-  if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), c->stream));
+  PROPAGATE(zero_accepted(c, s, c->stream));
   Timer t(c, "sweep");
   // One launch closes a step and opens the next (k_cgen_step_tail: map sum, candidate logit, accept, next proposal) where
   // the candidates are one block of rows whose last map cgen_forward leaves in place; injected proposals (test hook) and
@@ -133,39 +137,33 @@ static int run_sweep_cgen(vmc_ctx* c, long long n_steps, bool injected, unsigned
   // The patch sampler (conv_patch.hip): on a lattice much larger than the convolutions' reach a step recomputes the two boxes
   // the exchanged pair touches instead of the lattice, all steps of a chain in one launch -- the same chains bit for bit.
   // (cgen_patch_use: CGS_VMC_CONV_PATCH)
-  {
-    if (!injected && cgen_patch_use(c, n_steps)) {   // (mc_steps always samples psi: ps[0])
-      HIPCHK(c, launch_wide_propose(c->stream, c->configs, B, N, seed_lo, seed_hi, c->d.chain_offset, step0, nullptr, nullptr,
-                                    nullptr, c->wide_iup, c->wide_idn, c->wide_u));
-      PROPAGATE(cgen_patch_maps(c, VMC_PSI));       // the chains' maps as they stand: one taped full forward
-      CgenPatchArgs a;
-      cgen_patch_args(c, VMC_PSI, &a);
-      a.logit = p.logit; a.iup = c->wide_iup; a.idn = c->wide_idn; a.u = c->wide_u;
-      a.accepted = c->d_accepted; a.seed_lo = seed_lo; a.seed_hi = seed_hi; a.chain_offset = c->d.chain_offset;
-      a.step0 = step0; a.n_steps = n_steps;
-      DevBuf<unsigned long long> d_prof;            // diagnostic: the phase clocks of chain 0 to stderr (synchronises)
-      if (getenv("CGS_VMC_CONV_PATCH_PROF") && atoi(getenv("CGS_VMC_CONV_PATCH_PROF")) != 0) {
-        PROPAGATE(d_prof.alloc(c, 6, "d_prof"));
-        a.prof = d_prof;
-      }
-      HIPCHK(c, launch_cgen_patch_sweep(c->stream, a));
-      if (d_prof) {
-        unsigned long long h[6];
-        HIPCHK(c, hipMemcpyAsync(h, d_prof, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        fprintf(stderr, "k_cgen_patch_sweep, clocks per step of chain 0: first convolution %.0f, staging %.0f, tiles %.0f, map sum %.0f, "
-                "test + commit %.0f, proposal %.0f\n", (double)h[0] / n_steps, (double)h[1] / n_steps, (double)h[2] / n_steps,
-                (double)h[3] / n_steps, (double)h[4] / n_steps, (double)h[5] / n_steps);
-      }
-      c->acts_valid = false;
-      c->acc_since_sweep = false;
-      return VMC_OK;
+  if (!s.injected && cgen_patch_use(c, n_steps)) {   // (mc_steps always samples psi: ps[0])
+    HIPCHK(c, launch_proposals(c, c->stream, step0, false, c->prop_iup, c->prop_idn, c->prop_u));
+    PROPAGATE(cgen_patch_maps(c, VMC_PSI));       // the chains' maps as they stand: one taped full forward
+    CgenPatchArgs a;
+    cgen_patch_args(c, VMC_PSI, &a);
+    a.logit = p.logit; a.iup = c->prop_iup; a.idn = c->prop_idn; a.u = c->prop_u;
+    a.accepted = c->d_accepted;
+    set_key(c, a);
+    a.step0 = step0; a.n_steps = n_steps;
+    DevBuf<unsigned long long> d_prof;            // diagnostic: the phase clocks of chain 0 to stderr (synchronises)
+    if (getenv("CGS_VMC_CONV_PATCH_PROF") && atoi(getenv("CGS_VMC_CONV_PATCH_PROF")) != 0) {
+      PROPAGATE(d_prof.alloc(c, 6, "d_prof"));
+      a.prof = d_prof;
     }
-  }
-  if (!injected && !(tail_env && atoi(tail_env) == 0) && cgen_single_block(c, B)) {
+    HIPCHK(c, launch_cgen_patch_sweep(c->stream, a));
+    if (d_prof) {
+      unsigned long long h[6];
+      HIPCHK(c, hipMemcpyAsync(h, d_prof, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      fprintf(stderr, "k_cgen_patch_sweep, clocks per step of chain 0: first convolution %.0f, staging %.0f, tiles %.0f, map sum %.0f, "
+              "test + commit %.0f, proposal %.0f\n", (double)h[0] / n_steps, (double)h[1] / n_steps, (double)h[2] / n_steps,
+              (double)h[3] / n_steps, (double)h[4] / n_steps, (double)h[5] / n_steps);
+    }
+  } else if (!s.injected && !(tail_env && atoi(tail_env) == 0) && cgen_single_block(c, B)) {
     const ConvGeom& g = c->cg;
-    HIPCHK(c, launch_wide_propose(c->stream, c->configs, B, N, seed_lo, seed_hi, c->d.chain_offset, step0, nullptr, nullptr,
-                                  nullptr, c->wide_iup, c->wide_idn, c->wide_u));
+    const PhiloxKey key = philox_key(c);          // (k_cgen_step_tail takes it by position, offset by the group's first chain)
+    HIPCHK(c, launch_proposals(c, c->stream, step0, false, c->prop_iup, c->prop_idn, c->prop_u));
     // Chain groups: the chains are independent (graph_builders.py:57-88 maps one update over the batch), so the batch is
     // cut into G contiguous groups whose steps run on streams of their own.  A launch of one group that leaves CUs idle
     // (800 row tiles of 128 positions on 256 CUs: the fourth round is one eighth full) then runs beside the next launch
@@ -188,13 +186,13 @@ static int run_sweep_cgen(vmc_ctx* c, long long n_steps, bool injected, unsigned
         const int rows = (int)(r1 - r0);
         hipStream_t s = gi ? c->cg_grp_stream[gi - 1] : c->stream;
         c->cg_stream_cur = s; c->cg_map_row0 = r0;
-        rc = cgen_forward(c, VMC_PSI, c->configs, nullptr, rows, c->wide_iup, c->wide_idn, false, nullptr, nullptr, 0, r0);
+        rc = cgen_forward(c, VMC_PSI, c->configs, nullptr, rows, c->prop_iup, c->prop_idn, false, nullptr, nullptr, 0, r0);
         const float* last = cgen_last_map(c);
         c->cg_stream_cur = nullptr; c->cg_map_row0 = 0;
         if (rc != VMC_OK) break;
         if (launch_cgen_step_tail(s, last, N, g.F, cgen_fp(g), c->configs + r0 * N, p.logit + r0, rows, c->oact,
-                                  c->wide_iup + r0, c->wide_idn + r0, c->wide_u + r0, c->d_accepted, seed_lo, seed_hi,
-                                  c->d.chain_offset + (int)r0, step0 + (unsigned long long)st + 1,
+                                  c->prop_iup + r0, c->prop_idn + r0, c->prop_u + r0, c->d_accepted, key.seed_lo, key.seed_hi,
+                                  key.chain_offset + (int)r0, step0 + (unsigned long long)st + 1,
                                   st + 1 < n_steps) != hipSuccess)
           rc = fail(c, VMC_ERR_HIP, "k_cgen_step_tail launch");
       }
@@ -205,38 +203,33 @@ static int run_sweep_cgen(vmc_ctx* c, long long n_steps, bool injected, unsigned
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->cg_grp_ev[i], 0));
     }
     if (rc != VMC_OK) return rc;
-    c->acts_valid = false;
-    c->acc_since_sweep = false;
-    return VMC_OK;
+  } else {
+    for (long long st = 0; st < n_steps; ++st) {
+      HIPCHK(c, launch_proposals(c, c->stream, step0 + (unsigned long long)st, s.injected, c->prop_iup, c->prop_idn,
+                                 c->prop_u));
+      PROPAGATE(cgen_forward(c, VMC_PSI, c->configs, nullptr, B, c->prop_iup, c->prop_idn, false, c->cg_lnew));
+      // (k_cgen_accept has no argument struct: the accept mask by position)
+      HIPCHK(c, launch_cgen_accept(c->stream, c->configs, p.logit, c->cg_lnew, c->prop_iup, c->prop_idn, c->prop_u, B, N,
+                                   c->oact, c->d_accepted, s.injected ? c->acc_mask.p : nullptr));
+    }
   }
-  for (long long st = 0; st < n_steps; ++st) {
-    HIPCHK(c, launch_wide_propose(c->stream, c->configs, B, N, seed_lo, seed_hi, c->d.chain_offset,
-                                  step0 + (unsigned long long)st, injected ? c->inj_up : nullptr,
-                                  injected ? c->inj_dn : nullptr, injected ? c->inj_u : nullptr, c->wide_iup,
-                                  c->wide_idn, c->wide_u));
-    PROPAGATE(cgen_forward(c, VMC_PSI, c->configs, nullptr, B, c->wide_iup, c->wide_idn, false, c->cg_lnew));
-    HIPCHK(c, launch_cgen_accept(c->stream, c->configs, p.logit, c->cg_lnew, c->wide_iup, c->wide_idn, c->wide_u, B, N,
-                                 c->oact, c->d_accepted, injected ? c->acc_mask : nullptr));
-  }
-  c->acts_valid = false;
-  c->acc_since_sweep = false;
-  return VMC_OK;
+  return chains_moved(c, s);
 }
 
 // The pbdg sampler (pbdg.hip): one persistent launch of n_steps steps reads the current chains and writes the alternate
 // set, then the rows kernel writes the logits and signs of the final chains from a fresh factorisation (no drift from the
 // sampler's rank-2 updates: the cache equals vmc_amplitude's bit for bit).  Proposal dumps: k_wide_propose, the rule the
 // sampler follows.
-static int run_sweep_pbdg(vmc_ctx* c, long long n_steps, bool injected, unsigned long long step0, bool count_accepted) {
+static int run_sweep_pbdg(vmc_ctx* c, const SweepCall& s) {
   ParamSet& p = c->ps[0];
-  const uint32_t seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull), seed_hi = (uint32_t)(c->d.seed >> 32);
-  if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), c->stream));
+  PROPAGATE(zero_accepted(c, s, c->stream));
   PbdgSweepArgs a;
   memset(&a, 0, sizeof(a));
   a.F = p.theta; a.N = c->N; a.B = c->B;
   a.configs_in = c->configs; a.configs_out = c->configs_alt;
-  a.n_steps = n_steps; a.step0 = step0; a.seed_lo = seed_lo; a.seed_hi = seed_hi; a.chain_offset = c->d.chain_offset;
-  if (injected) { a.inj_up = c->inj_up; a.inj_dn = c->inj_dn; a.inj_u = c->inj_u; a.acc_mask = c->acc_mask; }
+  a.n_steps = s.n_steps; a.step0 = s.step0;
+  set_key(c, a);
+  if (s.injected) set_injected(c, a);
   a.accepted = c->d_accepted;
   {
     Timer t(c, "sweep");
@@ -244,148 +237,127 @@ static int run_sweep_pbdg(vmc_ctx* c, long long n_steps, bool injected, unsigned
     HIPCHK(c, launch_pbdg_rows(c->stream, p.theta, c->N, c->configs_alt, c->B, p.logit_alt, p.sign_alt, nullptr, nullptr));
   }
   swap_chain_buffers(c);
-  c->acts_valid = false;
-  c->acc_since_sweep = false;
-  return VMC_OK;
+  return chains_moved(c, s);
 }
 
 // The ed_vector sampler (edvec.hip): one persistent launch of n_steps steps, one thread per chain; it leaves the final
 // chains in the alternate set together with their amplitudes -- the last accepted gathers, hence vmc_amplitude's bits.
-static int run_sweep_edvec(vmc_ctx* c, long long n_steps, bool injected, unsigned long long step0, bool count_accepted) {
+static int run_sweep_edvec(vmc_ctx* c, const SweepCall& s) {
   ParamSet& p = c->ps[0];
-  const uint32_t seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull), seed_hi = (uint32_t)(c->d.seed >> 32);
-  if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), c->stream));
+  PROPAGATE(zero_accepted(c, s, c->stream));
   EdvecSweepArgs a;
   memset(&a, 0, sizeof(a));
   a.vec = p.theta; a.len = (int)c->P; a.top = c->ed_top; a.bot = c->ed_bot; a.N = c->N; a.B = c->B;
   a.tables_lds = c->ed_tables_lds ? 1 : 0;
   a.configs_in = c->configs; a.configs_out = c->configs_alt; a.psi_out = p.sign_alt; a.logit_out = p.logit_alt;
-  a.n_steps = n_steps; a.step0 = step0; a.seed_lo = seed_lo; a.seed_hi = seed_hi; a.chain_offset = c->d.chain_offset;
-  if (injected) { a.inj_up = c->inj_up; a.inj_dn = c->inj_dn; a.inj_u = c->inj_u; a.acc_mask = c->acc_mask; }
+  a.n_steps = s.n_steps; a.step0 = s.step0;
+  set_key(c, a);
+  if (s.injected) set_injected(c, a);
   a.accepted = c->d_accepted;
   {
     Timer t(c, "sweep");
     HIPCHK(c, launch_edvec_sweep(c->stream, a, c->num_cus));
   }
   swap_chain_buffers(c);
-  c->acts_valid = false;
-  c->acc_since_sweep = false;
-  return VMC_OK;
+  return chains_moved(c, s);
 }
 
 // The neural-network-backflow sampler (nnb.hip): per mc_step the proposals (k_wide_propose: the Philox streams of every
 // sampler), the candidates as configurations in the alternate chain buffer, their amplitudes by the route vmc_amplitude
 // takes (first-layer GEMM off the spins, trunk, pairing layer, determinant rows: no incrementally updated state, nothing
 // to refresh), and the accept launch, which updates chains, logits and signs in place.
-static int run_sweep_nnb(vmc_ctx* c, long long n_steps, bool injected, unsigned long long step0, bool count_accepted) {
+static int run_sweep_nnb(vmc_ctx* c, const SweepCall& s) {
   ParamSet& p = c->ps[0];
   const int B = c->B, N = c->N;
-  const uint32_t seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull), seed_hi = (uint32_t)(c->d.seed >> 32);
   PROPAGATE(ensure_cache(c, VMC_PSI));
-  if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), c->stream));
+  PROPAGATE(zero_accepted(c, s, c->stream));
   Timer t(c, "sweep");
-  for (long long st = 0; st < n_steps; ++st) {
-    HIPCHK(c, launch_wide_propose(c->stream, c->configs, B, N, seed_lo, seed_hi, c->d.chain_offset,
-                                  step0 + (unsigned long long)st, injected ? c->inj_up : nullptr,
-                                  injected ? c->inj_dn : nullptr, injected ? c->inj_u : nullptr, c->wide_iup,
-                                  c->wide_idn, c->wide_u));
-    HIPCHK(c, launch_nnb_candidates(c->stream, c->configs, c->wide_iup, c->wide_idn, B, N, c->configs_alt));
+  for (long long st = 0; st < s.n_steps; ++st) {
+    HIPCHK(c, launch_proposals(c, c->stream, s.step0 + (unsigned long long)st, s.injected, c->prop_iup, c->prop_idn,
+                               c->prop_u));
+    HIPCHK(c, launch_nnb_candidates(c->stream, c->configs, c->prop_iup, c->prop_idn, B, N, c->configs_alt));
     PROPAGATE(first_layer(c, p, c->configs_alt, p.z1_alt, B));
     PROPAGATE(nnb_forward(c, VMC_PSI, p.z1_alt, c->configs_alt, c->rowinfo_id, B, false, c->nnb_cl, c->nnb_cs));
-    HIPCHK(c, launch_nnb_accept(c->stream, c->configs, c->configs_alt, c->wide_iup, c->wide_idn, c->wide_u, p.logit,
-                                p.sign, c->nnb_cl, c->nnb_cs, B, N, injected ? c->acc_mask : nullptr, c->d_accepted));
+    HIPCHK(c, launch_nnb_accept(c->stream, c->configs, c->configs_alt, c->prop_iup, c->prop_idn, c->prop_u, p.logit,
+                                p.sign, c->nnb_cl, c->nnb_cs, B, N, s.injected ? c->acc_mask : nullptr, c->d_accepted));
   }
-  c->acts_valid = false;
-  c->acc_since_sweep = false;
+  return chains_moved(c, s);
+}
+
+// The proposal dump of every path but the fused arm (whose kernels write their own): k_wide_propose, the rule those
+// samplers follow.  Nothing is sampled, nothing written back.
+static int dump_proposals(vmc_ctx* c, const SweepCall& s) {
+  HIPCHK(c, launch_proposals(c, c->stream, s.step0, false, s.dump_up, s.dump_dn, s.dump_u));
   return VMC_OK;
 }
 
-// the proposal dump of the samplers whose proposals are k_wide_propose launches: that kernel, the rule they follow
-static int dump_proposals(vmc_ctx* c, unsigned long long step0, int* dbg_up, int* dbg_dn, float* dbg_u) {
-  HIPCHK(c, launch_wide_propose(c->stream, c->configs, c->B, c->N, (uint32_t)(c->d.seed & 0xFFFFFFFFull), (uint32_t)(c->d.seed >> 32),
-                                c->d.chain_offset, step0, nullptr, nullptr, nullptr, dbg_up, dbg_dn, dbg_u));
-  return VMC_OK;
-}
-
-static int run_sweep(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn,
-                     float* dbg_u, unsigned long long step0, bool count_accepted = false,
-                     bool overtake = false, hipEvent_t dep = nullptr) {
+static int run_sweep(vmc_ctx* c, const SweepCall& s) {
+  const bool dbg = s.dump(), injected = s.injected;
+  const bool fused_arm = path_fused_dense(c->path) || c->path == PATH_CONV;   // one persistent launch into the alternate set
   if (c->path != PATH_PRODUCT) {      // (a product's factors pack their own parameters and keep their own census)
     PROPAGATE(ensure_packed(c, 0));
     if (!dbg) c->cnt_valid = false;   // the chains change (set again below when this launch leaves their census)
   }
+  if (dbg && !fused_arm) {
+    if (c->path == PATH_PRODUCT) PROPAGATE(prod_alive(c));      // (a product whose factor is gone refuses every entry)
+    return dump_proposals(c, s);
+  }
   switch (c->path) {
-    case PATH_PRODUCT: return prod_run_sweep(c, n_steps, injected, dbg, dbg_up, dbg_dn, dbg_u, step0, count_accepted);
-    case PATH_EDVEC: return dbg ? dump_proposals(c, step0, dbg_up, dbg_dn, dbg_u) : run_sweep_edvec(c, n_steps, injected, step0, count_accepted);
-    case PATH_NNB: return dbg ? dump_proposals(c, step0, dbg_up, dbg_dn, dbg_u) : run_sweep_nnb(c, n_steps, injected, step0, count_accepted);
-    case PATH_DENSE_GENERAL: return dbg ? dump_proposals(c, step0, dbg_up, dbg_dn, dbg_u) : run_sweep_wide(c, n_steps, injected, step0, count_accepted);
-    case PATH_PBDG: return dbg ? dump_proposals(c, step0, dbg_up, dbg_dn, dbg_u) : run_sweep_pbdg(c, n_steps, injected, step0, count_accepted);
-    case PATH_CONV_GENERAL: return dbg ? dump_proposals(c, step0, dbg_up, dbg_dn, dbg_u) : run_sweep_cgen(c, n_steps, injected, step0, count_accepted);
+    case PATH_PRODUCT: return prod_run_sweep(c, s);
+    case PATH_EDVEC: return run_sweep_edvec(c, s);
+    case PATH_NNB: return run_sweep_nnb(c, s);
+    case PATH_DENSE_GENERAL: return run_sweep_wide(c, s);
+    case PATH_PBDG: return run_sweep_pbdg(c, s);
+    case PATH_CONV_GENERAL: return run_sweep_cgen(c, s);
     case PATH_FUSED: case PATH_FUSED_LDS: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP: case PATH_CONV:
-      break;      // one persistent launch from the current chain buffers into the alternate set, below
+      break;      // the fused arm, below
   }
   const bool conv = path_conv(c->path);
   ParamSet& p = c->ps[0];
-  SweepArgs a;
-  memset(&a, 0, sizeof(a));
-  a.pp = p.packed();
-  a.configs_in = c->configs; a.z1_in = p.z1; a.logit_in = p.logit;
-  a.configs = c->configs_alt; a.z1 = p.z1_alt; a.logit = p.logit_alt;
-  a.onsite = p.onsite_alt; a.rbm = c->rbm ? 1 : 0;
-  a.accepted = c->d_accepted;
-  if (injected) { a.inj_up = c->inj_up; a.inj_dn = c->inj_dn; a.inj_u = c->inj_u; a.acc_mask = c->acc_mask; }
-  if (dbg) { a.dbg_up = dbg_up; a.dbg_dn = dbg_dn; a.dbg_u = dbg_u; }
-  a.B = c->B; a.N = c->N; a.n_hidden = c->n_hh;
-  a.chain_offset = c->d.chain_offset;
-  a.seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull); a.seed_hi = (uint32_t)(c->d.seed >> 32);
-  a.step0 = step0; a.n_steps = n_steps;
-  a.waves = c->sweep_waves; a.no_w1l = c->sweep_no_w1l;
-  a.act = c->hact; a.oact = c->oact;
   // the activations of the final chains are handed to the gradient path only when a gradient
   // accumulate has been seen since the previous launch (equilibration / evaluation sweeps skip
   // the [L][B][Hp] write-back; gradient_sums then recomputes them)
   const bool hand_over = !conv && !dbg && (injected || c->acc_since_sweep || c->sr_cap > 0);
-  a.act_out = hand_over ? c->act_alt : nullptr;
-  a.dact_out = hand_over ? c->dact_alt : nullptr;
-  a.cache_in_valid = (!dbg && !injected && p.cache_valid) ? 1 : 0;
+  const int cache_in_valid = (!dbg && !injected && p.cache_valid) ? 1 : 0;
   // the census of the chains this launch leaves behind (k_bond_count's job; CGS_VMC_SWEEP_CENSUS=0: a launch of its own)
   static const bool census_on = !(getenv("CGS_VMC_SWEEP_CENSUS") && atoi(getenv("CGS_VMC_SWEEP_CENSUS")) == 0);
   const bool census = census_on && !conv && !dbg && !injected && c->n_bonds > 0 && c->bonds && c->cnt_alt;
-  if (census) {
-    a.bonds = c->bonds; a.quarter_jz = c->quarter_jz; a.n_bonds = c->n_bonds;
-    a.cnt_out = c->cnt_alt; a.diag_out = c->diag_alt;
-  }
-  hipStream_t st = overtake ? c->sweep_stream : c->stream;
-  if (overtake) HIPCHK(c, hipStreamWaitEvent(st, dep, 0));
-  // the device counter is only zeroed when the caller will read it back
-  if (count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), st));
+  hipStream_t st = s.overtake ? c->sweep_stream : c->stream;
+  if (s.overtake) HIPCHK(c, hipStreamWaitEvent(st, s.dep, 0));
+  PROPAGATE(zero_accepted(c, s, st));
   if (conv) {
-    ConvSweepArgs s;
-    memset(&s, 0, sizeof(s));
-    s.g = c->cg; s.p = conv_params(p);
-    s.configs_in = c->configs; s.logit_in = p.logit; s.configs = c->configs_alt; s.logit = p.logit_alt;
-    s.accepted = c->d_accepted;
-    s.inj_up = a.inj_up; s.inj_dn = a.inj_dn; s.inj_u = a.inj_u; s.acc_mask = a.acc_mask;
-    s.dbg_up = a.dbg_up; s.dbg_dn = a.dbg_dn; s.dbg_u = a.dbg_u;
-    s.oact = c->oact; s.cache_in_valid = a.cache_in_valid; s.B = c->B; s.G = c->cGs;
-    s.chain_offset = a.chain_offset; s.seed_lo = a.seed_lo; s.seed_hi = a.seed_hi;
-    s.step0 = step0; s.n_steps = n_steps;
+    ConvSweepArgs v;
+    memset(&v, 0, sizeof(v));
+    v.g = c->cg; v.p = conv_params(p);
+    v.configs_in = c->configs; v.logit_in = p.logit; v.configs = c->configs_alt; v.logit = p.logit_alt;
+    v.accepted = c->d_accepted;
+    if (injected) set_injected(c, v);
+    if (dbg) { v.dbg_up = s.dump_up; v.dbg_dn = s.dump_dn; v.dbg_u = s.dump_u; }
+    v.oact = c->oact; v.cache_in_valid = cache_in_valid; v.B = c->B; v.G = c->cGs;
+    set_key(c, v);
+    v.step0 = s.step0; v.n_steps = s.n_steps;
     Timer t(c, "sweep", st, true);
-    HIPCHK(c, launch_conv_sweep(st, s));
+    HIPCHK(c, launch_conv_sweep(st, v));
   } else {
+    SweepArgs a = fused_sweep_args(c, 0, s.step0, s.n_steps);
+    a.z1 = p.z1_alt; a.logit = p.logit_alt;                     // the alternate set
+    a.onsite = p.onsite_alt; a.rbm = c->rbm ? 1 : 0;
+    a.waves = c->sweep_waves; a.no_w1l = c->sweep_no_w1l;
+    if (injected) set_injected(c, a);
+    if (dbg) { a.dbg_up = s.dump_up; a.dbg_dn = s.dump_dn; a.dbg_u = s.dump_u; }
+    a.act_out = hand_over ? c->act_alt : nullptr;
+    a.dact_out = hand_over ? c->dact_alt : nullptr;
+    a.cache_in_valid = cache_in_valid;
+    if (census) {
+      a.bonds = c->bonds; a.quarter_jz = c->quarter_jz; a.n_bonds = c->n_bonds;
+      a.cnt_out = c->cnt_alt; a.diag_out = c->diag_alt;
+    }
     Timer t(c, "sweep", st, true);
     HIPCHK(c, launch_sampler(c, st, a, 0));
   }
   if (dbg) return VMC_OK;               // the proposal dump writes nothing back
   swap_chain_buffers(c);
-  c->cnt_valid = census;
-  c->acts_valid = hand_over;
-  c->acc_since_sweep = false;
-  if (overtake) {
-    HIPCHK(c, hipEventRecord(c->ev_sweep_done, st));
-    c->sweep_pending = true;
-  }
-  return VMC_OK;
+  return chains_moved(c, s, hand_over, census);
 }
 
 }  // namespace vmcapi
@@ -430,13 +402,13 @@ int vmc_mc_steps(vmc_ctx* c, int64_t n_steps, int64_t* accepted) {
   }
   if (!overtake) PROPAGATE(join_sweep(c));
   c->expect_sweep = overtake && after_acc && !side;
-  PROPAGATE(run_sweep(c, n_steps, false, false, nullptr, nullptr, nullptr, c->step, accepted != nullptr,
-                      overtake, dep));
+  SweepCall s;
+  s.n_steps = n_steps; s.step0 = c->step; s.count_accepted = accepted != nullptr;
+  s.overtake = overtake; s.dep = dep;
+  PROPAGATE(run_sweep(c, s));
   c->step += (unsigned long long)n_steps;
-  c->ps[0].cache_valid = !path_general_dense(c->path);   // the sweep kernel writes back an exact z1/logit cache (the general
-                                     // wide path keeps an incrementally updated one: recomputed on demand)
-  c->ps[1].cache_valid = false;
-  c->list_valid = false;
+  // (the census is what run_sweep has just left: the fused arm's launch counts the bonds of its final chains)
+  sampler_returned(c, /*psi_cache=*/!path_general_dense(c->path), /*census_stays=*/true);
   if (accepted) {
     hipStream_t st = overtake ? c->sweep_stream : c->stream;
     unsigned long long h = 0;
@@ -457,9 +429,10 @@ int vmc_mc_step_injected(vmc_ctx* c, const int32_t* i_up, const int32_t* i_dn, c
   HIPCHK(c, hipMemcpyAsync(c->inj_up, i_up, c->B * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->inj_dn, i_dn, c->B * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->inj_u, u, c->B * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  PROPAGATE(run_sweep(c, 1, true, false, nullptr, nullptr, nullptr, c->step));
-  c->ps[0].cache_valid = !path_general_dense(c->path); c->ps[1].cache_valid = false; c->list_valid = false;
-  c->cnt_valid = false;
+  SweepCall s;
+  s.n_steps = 1; s.step0 = c->step; s.injected = true;
+  PROPAGATE(run_sweep(c, s));
+  sampler_returned(c, /*psi_cache=*/!path_general_dense(c->path), /*census_stays=*/false);
   if (accept_mask)
     HIPCHK(c, hipMemcpyAsync(accept_mask, c->acc_mask, c->B, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -469,7 +442,9 @@ int vmc_mc_step_injected(vmc_ctx* c, const int32_t* i_up, const int32_t* i_dn, c
 int vmc_debug_proposals(vmc_ctx* c, uint64_t step, int32_t* i_up, int32_t* i_dn, float* u) {
   ENTER(c);
   if (!i_up || !i_dn || !u) return fail(c, VMC_ERR_INVALID, "null outputs");
-  PROPAGATE(run_sweep(c, 0, false, true, c->inj_up, c->inj_dn, c->inj_u, step));
+  SweepCall s;
+  s.step0 = step; s.dump_up = c->inj_up; s.dump_dn = c->inj_dn; s.dump_u = c->inj_u;
+  PROPAGATE(run_sweep(c, s));
   HIPCHK(c, hipMemcpyAsync(i_up, c->inj_up, c->B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(i_dn, c->inj_dn, c->B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(u, c->inj_u, c->B * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -496,22 +471,17 @@ int vmc_debug_sweep_profile(vmc_ctx* c, int64_t n_steps, double* phase_cycles) {
   DevBuf<unsigned long long> d;
   PROPAGATE(d.alloc(c, (long long)grid * 128, "dbg_cycles"));
   HIPCHK(c, hipMemsetAsync(d, 0, (size_t)grid * 128 * sizeof(unsigned long long), c->stream));
-  SweepArgs a;
-  memset(&a, 0, sizeof(a));
-  a.pp = c->ps[0].packed();
-  a.configs_in = c->configs; a.z1_in = c->ps[0].z1; a.logit_in = c->ps[0].logit;
-  a.configs = c->configs_alt; a.z1 = c->ps[0].z1_alt; a.logit = c->ps[0].logit_alt;
-  a.accepted = c->d_accepted; a.dbg_cycles = d; a.waves = 8; a.act = c->hact; a.oact = c->oact;
-  a.B = c->B; a.N = c->N; a.n_hidden = c->n_hh; a.chain_offset = c->d.chain_offset;
-  a.seed_lo = (uint32_t)(c->d.seed & 0xFFFFFFFFull); a.seed_hi = (uint32_t)(c->d.seed >> 32);
-  a.step0 = c->step; a.n_steps = n_steps;
+  SweepArgs a = fused_sweep_args(c, 0, c->step, n_steps);
+  a.z1 = c->ps[0].z1_alt; a.logit = c->ps[0].logit_alt;      // the alternate set
+  a.dbg_cycles = d; a.waves = 8;      // (only !rbm ctxs come here: rbm, onsite and no_w1l stay zero)
   if (tile8) HIPCHK(c, launch_sweep8(c->stream, a, c->Hp));
   else HIPCHK(c, launch_sweep16(c->stream, a, c->Hp));
   swap_chain_buffers(c);
+  // not chains_moved: the diagnostic launch hands nothing over, but it leaves acc_since_sweep to the next sampler call
+  // (an accumulate seen before it still asks that call for the hand-over)
   c->acts_valid = false;
   c->step += (unsigned long long)n_steps;
-  c->ps[0].cache_valid = true; c->ps[1].cache_valid = false; c->list_valid = false;
-  c->cnt_valid = false;
+  sampler_returned(c, /*psi_cache=*/true, /*census_stays=*/false);
   std::vector<unsigned long long> h((size_t)grid * 128);
   HIPCHK(c, hipMemcpyAsync(h.data(), d, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -67,12 +67,8 @@ static int gradient_sums(vmc_ctx* c, const float* w, bool fresh, const float* e,
     else HIPCHK(c, launch_act_copy(c->stream, p.z1, c->act[0], c->dact_all, (long long)B * Hp, c->hact));
   }
   for (int l = 1; l <= NH && !c->acts_valid; ++l) {
-    GemmArgs g; memset(&g, 0, sizeof(g));
-    g.A = c->act[l - 1]; g.sam = Hp; g.sak = 1;
-    g.B = p.theta + off_w(c, l); g.sbk = H; g.sbn = 1;
-    g.M = B; g.N = H; g.K = H; g.C = c->act[l]; g.ldc = Hp;
-    g.bias = p.theta + off_b(c, l); g.epilogue = (c->rbm && l == NH) ? 7 : 1; g.splitk = 1;
-    g.act = c->hact;
+    GemmArgs g = trunk_gemm(c, p, l, c->act[l - 1], B, c->act[l], c->hact);
+    if (c->rbm && l == NH) g.epilogue = 7;      // the taped forward keeps tanh(z_last) = d sum log cosh / d z_last
     if (c->dact_all && g.epilogue == 1) g.dact_out = c->dact_all + (long long)l * B * Hp;
     HIPCHK(c, launch_gemm(c->stream, g));
   }
@@ -88,11 +84,7 @@ static int gradient_sums(vmc_ctx* c, const float* w, bool fresh, const float* e,
       // by d ln|psi| / d out = (M^-1)^T at the (up, down) entries; delta_NH = relu' (.) (d_out W_out^T)
       const long long NN = (long long)N * N;
       PROPAGATE(grow_tmp(c, B));
-      GemmArgs g; memset(&g, 0, sizeof(g));
-      g.A = c->act[NH]; g.sam = Hp; g.sak = 1;
-      g.B = p.theta + off_wout(c); g.sbk = NN; g.sbn = 1;
-      g.M = B; g.N = (int)NN; g.K = H; g.C = c->nnb_delta; g.ldc = NN;
-      g.bias = p.theta + off_bout(c); g.epilogue = 4; g.splitk = 1;
+      GemmArgs g = nnb_pairing_gemm(c, p, c->act[NH], B, c->nnb_delta);
       HIPCHK(c, launch_gemm(c->stream, g));
       NnbRowsArgs a; memset((void*)&a, 0, sizeof(a));
       a.out = c->nnb_delta; a.ldo = NN; a.N = N; a.configs = c->configs; a.rowinfo = c->rowinfo_id;

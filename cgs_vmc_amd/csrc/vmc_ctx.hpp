@@ -175,7 +175,7 @@ struct vmc_ctx {
   // units) keeps them for its gradient path only: its sampler and row kernel are instantiations of the fused kernels
   // (k_sweep16<24|32>, k_tail_lds).  CGS_VMC_WIDE_FAST=0 forces PATH_DENSE_GENERAL.
   long long wrows = 0;     // rows of the two activation row buffers
-  DevBuf<float> wbuf[2], wide_u, wide_zero;
+  DevBuf<float> wbuf[2], wide_zero;
   DevBuf<double> wide_dot;          // [ceil(H / 128)][wrows] row-dot partials of the last H x H layer (GemmArgs epilogue 10)
   // PATH_CONV_GENERAL (conv_general.hip; plan.hpp: conv beyond the fused kernels' limits): block buffers
   long long cg_rows = 0;                   // row configurations per block (sized by the im2col matrix: the GEMM form, the gradient path)
@@ -205,7 +205,9 @@ struct vmc_ctx {
   DevBuf<int> gnn_adj, gnn_inv_ptr, gnn_inv;
   bool sr_centre = false;                  // the SR matvec may centre its weights: a single-rank solve is running
   bool sr_phase1_done = false;             // vmc_sr_matvec_phase1 has run for the current CG direction (general convolution path)
-  DevBuf<int> wide_iup, wide_idn;
+  // the proposal in flight of the step-at-a-time samplers (dense general, general convolution, nnb): [B] sites, [B] uniforms
+  DevBuf<int> prop_iup, prop_idn;
+  DevBuf<float> prop_u;
   int hact = VMC_ACT_RELU_;  // hidden activation (layers.NONLINEARITIES id)
   int oact = VMC_ACT_EXP_;   // output activation; exp: psi = exp(x - shift), else psi = g(x), no shift
   DevBuf<float> oscale;   // [B] (1/psi) d psi / d x of a non-exp output activation
@@ -479,6 +481,80 @@ inline void drain_timings(vmc_ctx* c) {
   c->pending.clear();
 }
 
+// ---- the host scaffold of the samplers (run_sweep and the run_sweep_* of vmc_api_sweep.hip, prod_run_sweep): what a call
+// is, the Philox key, the proposal launch, the injected proposals, and what is declared before and after the launches.
+// Whatever a sampler writes out beside these is where it differs from the others.
+
+// One sampler call.  dump_*: a proposal dump of step `step0` into these three [B] buffers -- nothing is sampled, nothing
+// written back.  overtake / dep: the fused arm's launch goes to sweep_stream and only waits for `dep` (an event on `stream`)
+struct SweepCall {
+  long long n_steps = 0;
+  unsigned long long step0 = 0;
+  bool injected = false;          // the proposals are c->inj_up / inj_dn / inj_u, the accept mask goes to c->acc_mask
+  bool count_accepted = false;    // the caller reads c->d_accepted back: zero it first
+  bool overtake = false;
+  hipEvent_t dep = nullptr;
+  int *dump_up = nullptr, *dump_dn = nullptr;
+  float* dump_u = nullptr;
+  bool dump() const { return dump_up != nullptr; }
+};
+
+// The Philox key of a ctx's chains: the one place the seed is split.  set_key: onto any kernel argument struct
+struct PhiloxKey { uint32_t seed_lo, seed_hi; int chain_offset; };
+inline PhiloxKey philox_key(const vmc_ctx* c) {
+  return PhiloxKey{(uint32_t)(c->d.seed & 0xFFFFFFFFull), (uint32_t)(c->d.seed >> 32), c->d.chain_offset};
+}
+template <class Args>
+inline void set_key(const vmc_ctx* c, Args& a) {
+  const PhiloxKey k = philox_key(c);
+  a.seed_lo = k.seed_lo; a.seed_hi = k.seed_hi; a.chain_offset = k.chain_offset;
+}
+
+// injected proposals (vmc_mc_step_injected) onto any kernel argument struct
+template <class Args>
+inline void set_injected(const vmc_ctx* c, Args& a) {
+  a.inj_up = c->inj_up; a.inj_dn = c->inj_dn; a.inj_u = c->inj_u; a.acc_mask = c->acc_mask;
+}
+
+// k_wide_propose for the chains as they stand: the proposals of `step` (or the injected ones) into iup / idn / u
+inline hipError_t launch_proposals(const vmc_ctx* c, hipStream_t st, unsigned long long step, bool injected, int* iup,
+                                   int* idn, float* u) {
+  const PhiloxKey k = philox_key(c);
+  return launch_wide_propose(st, c->configs, c->B, c->N, k.seed_lo, k.seed_hi, k.chain_offset, step,
+                             injected ? c->inj_up.p : nullptr, injected ? c->inj_dn.p : nullptr,
+                             injected ? c->inj_u.p : nullptr, iup, idn, u);
+}
+
+// the device counter of acceptances is only zeroed when the caller will read it back
+inline int zero_accepted(vmc_ctx* c, const SweepCall& s, hipStream_t st) {
+  if (s.count_accepted) HIPCHK(c, hipMemsetAsync(c->d_accepted, 0, sizeof(unsigned long long), st));
+  return VMC_OK;
+}
+
+// The chains moved: what a sampler declares once its launches are enqueued.  acts / census: the launch left the final
+// chains' activations (the gradient hand-over) and their bond census -- only the fused arm's can; an overtaking launch
+// (the fused arm alone) leaves the event `stream` will wait for
+inline int chains_moved(vmc_ctx* c, const SweepCall& s, bool acts = false, bool census = false) {
+  c->cnt_valid = census;
+  c->acts_valid = acts;
+  c->acc_since_sweep = false;
+  if (s.overtake) {
+    HIPCHK(c, hipEventRecord(c->ev_sweep_done, c->sweep_stream));
+    c->sweep_pending = true;
+  }
+  return VMC_OK;
+}
+
+// What an entry point declares after its sampler call.  psi_cache: psi's z1 / logit cache is that of the new chains (every
+// sampler writes an exact one back but the general dense path's, which keeps an incrementally updated z1: recomputed on
+// demand).  census_stays: cnt_valid is left as the sampler set it (vmc_mc_steps); otherwise the census is dropped
+inline void sampler_returned(vmc_ctx* c, bool psi_cache, bool census_stays) {
+  c->ps[0].cache_valid = psi_cache;
+  c->ps[1].cache_valid = false;
+  c->list_valid = false;
+  if (!census_stays) c->cnt_valid = false;
+}
+
 inline long long off_w(const vmc_ctx* c, int l) { return plan_off_w(c->lay, c->H, l); }   // weight matrix of layer l (0 = first)
 inline long long off_b(const vmc_ctx* c, int l) { return plan_off_b(c->lay, c->H, l); }   // biases sit right behind their weights
 inline long long off_wout(const vmc_ctx* c) { return c->lay.off_wout; }
@@ -496,6 +572,10 @@ int conv_rows(vmc_ctx* c, int which, const float* configs, const int2* rowinfo, 
               const int* rows_dev, bool ratio, float* out, bool with_tape);
 int first_layer(vmc_ctx* c, const ParamSet& p, const float* configs, float* z1, int rows);
 int wide_stage_act(const vmc_ctx* c, int l);
+// hidden layer l (1 .. n_hh) of the dense trunk on `rows` rows: C = act(A W_l + b_l), A and C row buffers of pitch Hp
+GemmArgs trunk_gemm(const vmc_ctx* c, const ParamSet& p, int l, const float* A, int rows, float* C, int act);
+// nnb's pairing layer on `rows` rows: C [rows][N^2] = A W_out + b_out
+GemmArgs nnb_pairing_gemm(const vmc_ctx* c, const ParamSet& p, const float* A, int rows, float* C);
 bool wide_rowdot(vmc_ctx* c, const ParamSet& p, GemmArgs& g);
 int wide_forward(vmc_ctx* c, int which, const float* z1, const int2* rowinfo, long long n_rows, bool ratio,
                  float* out, const float* onsite);
@@ -541,8 +621,8 @@ int child_gradient_sums(vmc_ctx* c, const float* w, float* g1, float* g2);
 // vmc_api_prod.hip (the product ctx; every function takes the PRODUCT unless named child)
 int prod_ensure_cache(vmc_ctx* c, int which);
 int prod_local_energy(vmc_ctx* c, int which);
-int prod_run_sweep(vmc_ctx* c, long long n_steps, bool injected, bool dbg, int* dbg_up, int* dbg_dn, float* dbg_u,
-                   unsigned long long step0, bool count_accepted);
+int prod_alive(vmc_ctx* c);                         // VMC_ERR_STATE (with the message) once a factor has been destroyed
+int prod_run_sweep(vmc_ctx* c, const SweepCall& s);
 int prod_accumulate(vmc_ctx* c, int mode, float beta);
 int prod_set_bonds(vmc_ctx* c, int32_t n_bonds, const int32_t* ij, const float* j_x, const float* j_z);
 int prod_gather_params(vmc_ctx* c, int which);      // the factors' theta -> the product's [a | b]
