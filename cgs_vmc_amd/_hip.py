@@ -20,6 +20,7 @@ VMC_ERR_STATE = -4
 
 VMC_PSI, VMC_OMEGA = 0, 1
 VMC_MODE_ENERGY_GRADIENT, VMC_MODE_LOG_OVERLAP_ITSWO = 0, 1
+VMC_MODE_PENALIZED_ENERGY = 2     # extension: E + lambda F against the frozen set (cgsvmc.h)
 # wavefunctions.WAVEFUNCTION_TYPES with kernels (cgsvmc.h VMC_ANSATZ_*)
 ANSATZ_IDS = {'fully_connected': 0, 'rbm': 1, 'conv_2d': 2, 'res_net_2d': 3, 'conv_1d': 4, 'res_net_1d': 5,
               'gnn': 6, 'pbdg': 7, 'fully_connected_nnb': 9, 'ed_vector': 10}
@@ -101,6 +102,7 @@ SIGNATURES = {
                                        C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'vmc_energy_moments': (C.c_int, [_ctx, C.c_int, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    'vmc_overlap': (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     'vmc_accumulate': (C.c_int, [_ctx, C.c_int, C.c_float]),
     'vmc_reset_accumulators': (C.c_int, [_ctx]),
     'vmc_accumulators_devptr': (C.c_int, [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
@@ -117,6 +119,7 @@ SIGNATURES = {
     'vmc_epoch_log_overlap': (C.c_int, [_ctx, C.c_float, C.c_int64, C.c_int32, C.c_int64, C.c_float,
                                         C.c_float, C.c_float, C.c_float, C.c_float,
                                         C.POINTER(C.c_double)]),
+    'vmc_epoch_penalized_energy': (C.c_int, [_ctx, C.c_float, C.c_int64, C.c_int32, C.c_int64, C.c_float]),
     'vmc_set_host_allreduce': (C.c_int, [_ctx, HOST_ALLREDUCE_FN, C.c_void_p]),
     'vmc_set_host_allreduce_caps': (C.c_int, [_ctx, C.c_int32]),
     'vmc_set_device_allreduce': (C.c_int, [_ctx, DEVICE_ALLREDUCE_FN, C.c_void_p]),
@@ -170,7 +173,7 @@ _lib = None
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 _STAMP_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libcgsvmc_hip.stamp')
 # the files the library is built from, in the order csrc/Makefile hashes them
-_SOURCES = ('vmc_api.hip', 'vmc_api_cgen.hip', 'vmc_api_sweep.hip', 'vmc_api_train.hip', 'vmc_api_coll.hip', 'vmc_api_sr.hip', 'vmc_api_prod.hip', 'prod.hip', 'mlp.hip', 'eloc.hip', 'grad.hip', 'sr.hip', 'srmm.hip', 'conv.hip', 'conv32.hip', 'conv48.hip', 'conv64.hip', 'conv_general.hip', 'conv_band.hip', 'conv_patch.hip', 'wide.hip', 'tail_split.hip', 'sweep_split.hip', 'sweep8.hip', 'pbdg.hip', 'nnb.hip', 'edvec.hip', 'vmc_api_measure.hip', 'corr.hip', 'renyi.hip', 'dimer.hip', 'symm.hip', 'proj.hip', 'moments.hip', 'act_tail.hip',
+_SOURCES = ('vmc_api.hip', 'vmc_api_cgen.hip', 'vmc_api_sweep.hip', 'vmc_api_train.hip', 'vmc_api_coll.hip', 'vmc_api_sr.hip', 'vmc_api_prod.hip', 'prod.hip', 'mlp.hip', 'eloc.hip', 'grad.hip', 'sr.hip', 'srmm.hip', 'conv.hip', 'conv32.hip', 'conv48.hip', 'conv64.hip', 'conv_general.hip', 'conv_band.hip', 'conv_patch.hip', 'wide.hip', 'tail_split.hip', 'sweep_split.hip', 'sweep8.hip', 'pbdg.hip', 'nnb.hip', 'edvec.hip', 'vmc_api_measure.hip', 'corr.hip', 'renyi.hip', 'dimer.hip', 'symm.hip', 'proj.hip', 'moments.hip', 'overlap.hip', 'act_tail.hip',
             'act_sweep.hip', 'vmc_ctx.hpp', 'prod.hpp', 'plan.hpp', 'common.hpp', 'pb_det.hpp', 'tail16.hpp', 'tail_lds.hpp', 'sweep16.hpp', 'conv.hpp', 'conv_kernels.hpp',
             'conv_wide.hpp',
             os.path.join('..', '..', 'include', 'cgsvmc.h'), 'Makefile')

@@ -66,7 +66,7 @@ def graph_kwargs(**parts) -> Dict[str, object]:
 
 def measurement_flag_table(own_rows, outputs: str):
   """The flag table of a measurement driver (run_correlation_evaluation, run_entanglement_evaluation,
-  run_dimer_evaluation, run_symmetry_evaluation, run_projected_energy_evaluation, run_lanczos_evaluation): --checkpoint_dir, the driver's own rows, --output_dir for `outputs`, --hparams."""
+  run_dimer_evaluation, run_symmetry_evaluation, run_projected_energy_evaluation, run_lanczos_evaluation, run_overlap_evaluation): --checkpoint_dir, the driver's own rows, --output_dir for `outputs`, --hparams."""
   return (('checkpoint_dir', str, '', 'Full path to the checkpoint directory.'),) + tuple(own_rows) + (
       ('output_dir', str, '', 'Where {} (default: the checkpoint directory).'.format(outputs)),
       ('hparams', str, '', 'Comma-separated name=value overrides of the hyper-parameters.'),

@@ -418,6 +418,21 @@ inline unsigned measure_rows_grid(long long items, int num_cus) {
   return (unsigned)blocks;
 }
 
+// overlap with the frozen parameter set (overlap.hip; the estimator, the dead-chain rule and every summation order are
+// stated there).  ratio: d [B] = ln|omega / psi| per chain in fp64, code [B] = the combined sign (+-1, 0 where omega
+// vanishes, OVERLAP_DEAD where psi does) and bmax [plan_overlap_blocks(B)] the blocks' maxima of d; sign_* null: an
+// unsigned type.  fold: out [4] = S1, S2, alive, m.  weights: w [B] = eloc + lambda (S1 / S2) s exp(d - m), rounded once
+// to fp32 (null: not wanted), ratio [B] = s exp(d - m) in fp64 (null: not wanted).  tail: the accumulators' slots 5 and 6
+#define OVERLAP_DEAD 2
+inline int plan_overlap_blocks(int B) { return B > 0 ? (B + 255) / 256 : 1; }
+hipError_t launch_overlap_ratio(hipStream_t s, const float* logit_psi, const float* sign_psi, double shift_psi,
+                                const float* logit_omega, const float* sign_omega, double shift_omega, int B, double* d,
+                                int* code, double* bmax);
+hipError_t launch_overlap_fold(hipStream_t s, const double* d, const int* code, const double* bmax, int B, double* out);
+hipError_t launch_overlap_weights(hipStream_t s, const double* d, const int* code, const double* sums, const float* eloc,
+                                  float lambda, int B, float* w, double* ratio);
+hipError_t launch_overlap_tail(hipStream_t s, const double* sums, float* acc_scalars);
+
 // gradient path (grad.hip)
 struct GemmArgs {
   const float* A; long long sam, sak;   // A(m,k) = A[m*sam + k*sak]

@@ -1491,7 +1491,8 @@ __global__ void k_adam(float* __restrict__ theta, float* __restrict__ m, float* 
   const float mean_r = sc[2] / sc[3];
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < P; i += gridDim.x * blockDim.x) {
     const float g1 = acc[i] / gc, g2 = acc[P + i] / gc;
-    const float g = mode == 0 ? g2 - mean_e * g1 : g1 - g2 / mean_r;
+    // (mode 2, PENALIZED_ENERGY: the covariance with the weights w whose sum r_total holds)
+    const float g = mode == 0 ? g2 - mean_e * g1 : mode == 1 ? g1 - g2 / mean_r : g2 - mean_r * g1;
     if (grad_out) grad_out[i] = g;
     if (apply) {
       const float mi = m[i] + (g - m[i]) * (1.f - b1);

@@ -1,8 +1,8 @@
 // The measurements over the ctx's current chains (extensions, no reference counterpart): vmc_pair_correlations,
-// vmc_renyi2_swap, vmc_dimer_correlations, vmc_symmetry_expectations, vmc_projected_energy and vmc_energy_moments.  Each is a pure measurement: chains, step counter, accumulators, the
+// vmc_renyi2_swap, vmc_dimer_correlations, vmc_symmetry_expectations, vmc_projected_energy, vmc_energy_moments and vmc_overlap.  Each is a pure measurement: chains, step counter, accumulators, the
 // Hamiltonian's bond set and the validity of the amplitude and activation caches are as before when it returns.
 //
-// One scaffold serves the six.  MEASURE_GATE is the shared front of the refusals; PureMeasurement records which caches
+// One scaffold serves the seven.  MEASURE_GATE is the shared front of the refusals; PureMeasurement records which caches
 // were valid and un-vouches on every way out for those that were not; upload copies a host list into its device buffer;
 // for_passes walks the items in passes of plan_measure_per_pass (plan.hpp); read_back brings the fp64 sums down and
 // synchronises, on a failed call too.  The device buffers are the grow-only DevBufs of vmc_ctx.hpp.  What differs per
@@ -339,6 +339,35 @@ int read_int(vmc_ctx* c, const int* dev, int* host) {
 
 }  // namespace
 
+namespace vmcapi {
+
+// ---- overlap with the frozen set
+
+int overlap_refusals(vmc_ctx* c, const char* what) {
+  if (c->prod) return fail(c, VMC_ERR_UNSUPPORTED, std::string(what) + " is not available on a product ctx ('prod')");
+  if (!c->sgn && c->oact != VMC_ACT_EXP_)
+    return fail(c, VMC_ERR_UNSUPPORTED, std::string(what) + " needs the exp output activation (the logit is ln psi only then)");
+  if (!c->ps[1].has_params)
+    return fail(c, VMC_ERR_STATE, std::string(what) + ": the frozen parameters are not set (vmc_set_params(VMC_OMEGA) / vmc_transfer_params)");
+  return VMC_OK;
+}
+
+int overlap_sums_device(vmc_ctx* c) {
+  OverlapBufs& m = c->ovl;
+  PROPAGATE(m.d.reserve(c, c->B, "ovl.d"));
+  PROPAGATE(m.code.reserve(c, c->B, "ovl.code"));
+  PROPAGATE(m.bmax.reserve(c, plan_overlap_blocks(c->B), "ovl.bmax"));
+  PROPAGATE(m.out.reserve(c, 4, "ovl.out"));
+  const ParamSet &p = c->ps[0], &w = c->ps[1];
+  Timer t(c, "overlap_fold");
+  HIPCHK(c, launch_overlap_ratio(c->stream, p.logit, c->sgn ? p.sign.p : nullptr, (double)p.shift, w.logit,
+                                 c->sgn ? w.sign.p : nullptr, (double)w.shift, c->B, m.d, m.code, m.bmax));
+  HIPCHK(c, launch_overlap_fold(c->stream, m.d, m.code, m.bmax, c->B, m.out));
+  return VMC_OK;
+}
+
+}  // namespace vmcapi
+
 extern "C" {
 
 int vmc_pair_correlations(vmc_ctx* c, int which, int32_t n_pairs, const int32_t* ij, int32_t pairs_per_pass,
@@ -610,6 +639,33 @@ int vmc_energy_moments(vmc_ctx* c, int which, int64_t rows_per_pass, double sums
   for (int k = 0; k < c->B && e_loc; ++k) e_loc[k] = chain[(size_t)k];
   for (int k = 0; k < c->B && h2_loc; ++k) h2_loc[k] = chain[(size_t)c->B + (size_t)k];
   if (n_rows2) *n_rows2 = n2;
+  return VMC_OK;
+}
+
+int vmc_overlap(vmc_ctx* c, double sums[4], double* ratio) {
+  MEASURE_GATE(c, 0, "vmc_overlap");
+  PROPAGATE(overlap_refusals(c, "vmc_overlap"));
+  PureMeasurement pure(c);
+  OverlapBufs& m = c->ovl;
+  int rc = ensure_cache(c, VMC_OMEGA);
+  if (rc == VMC_OK) rc = ensure_cache(c, VMC_PSI);
+  if (rc == VMC_OK) rc = overlap_sums_device(c);
+  std::vector<double> chain;
+  if (rc == VMC_OK && ratio) {
+    rc = m.ratio.reserve(c, c->B, "ovl.ratio");
+    if (rc == VMC_OK) {
+      chain.resize((size_t)c->B);
+      hipError_t e = launch_overlap_weights(c->stream, m.d, m.code, m.out, nullptr, 0.f, c->B, nullptr, m.ratio);
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(chain.data(), m.ratio, chain.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+      if (e != hipSuccess) rc = fail(c, VMC_ERR_HIP, std::string("k_overlap_weights: ") + hipGetErrorString(e));
+    }
+  }
+  std::vector<double> out;
+  rc = read_back(c, rc, "vmc_overlap", m.out, 4, &out);
+  if (rc != VMC_OK) return rc;
+  for (int k = 0; k < 4 && sums; ++k) sums[k] = out[(size_t)k];
+  for (int k = 0; k < c->B && ratio; ++k) ratio[k] = chain[(size_t)k];
   return VMC_OK;
 }
 

@@ -219,12 +219,40 @@ static int sr_record(vmc_ctx* c) {
   return VMC_OK;
 }
 
+// Mode PENALIZED_ENERGY, E[psi] + lambda F(psi, omega): what vmc_accumulate and the fused epoch refuse before anything is
+// launched, and the weight vector.  The weights need the batch's S1 / S2 first, so psi's local energies are folded at once
+// (no fusion into k_backprop16); w goes to c->ratio, the gradient path's weight slot 1.
+static int penalized_refusals(vmc_ctx* c, float lambda, const char* what) {
+  PROPAGATE(overlap_refusals(c, what));
+  if (c->sr_cap > 0)
+    return fail(c, VMC_ERR_STATE, std::string(what) + " does not record SR samples: release the store (vmc_sr_reserve(0))");
+  if (!(lambda >= 0.f) || !std::isfinite(lambda))
+    return fail(c, VMC_ERR_INVALID, std::string(what) + ": the penalty lambda must be finite and >= 0");
+  if (c->n_bonds <= 0) return fail(c, VMC_ERR_STATE, "bonds not set (vmc_set_bonds)");
+  return VMC_OK;
+}
+
+static int penalized_weights(vmc_ctx* c, float lambda) {
+  PROPAGATE(local_energy_device(c, VMC_PSI, false));
+  PROPAGATE(ensure_cache(c, VMC_OMEGA));
+  PROPAGATE(ensure_cache(c, VMC_PSI));
+  PROPAGATE(overlap_sums_device(c));
+  Timer t(c, "overlap_weights");
+  HIPCHK(c, launch_overlap_weights(c->stream, c->ovl.d, c->ovl.code, c->ovl.out, c->ps[0].eloc, lambda, c->B, c->ratio,
+                                   nullptr));
+  return VMC_OK;
+}
+
 int vmc_accumulate(vmc_ctx* c, int mode, float beta) {
   ENTER(c);
   REFUSE_COMPOSED(c);
-  if (mode != VMC_MODE_ENERGY_GRADIENT && mode != VMC_MODE_LOG_OVERLAP_ITSWO)
+  if (mode != VMC_MODE_ENERGY_GRADIENT && mode != VMC_MODE_LOG_OVERLAP_ITSWO && mode != VMC_MODE_PENALIZED_ENERGY)
     return fail(c, VMC_ERR_INVALID, "bad mode");
+  const bool penalized = mode == VMC_MODE_PENALIZED_ENERGY;      // (beta carries lambda)
+  if (penalized) PROPAGATE(penalized_refusals(c, beta, "vmc_accumulate(VMC_MODE_PENALIZED_ENERGY)"));
   if (c->prod) return prod_accumulate(c, mode, beta);
+  // the scalar tail of mode PENALIZED_ENERGY is filled as LOG_OVERLAP_ITSWO fills it: e_total, r_total = sum w, the counts
+  const int sc_mode = penalized ? VMC_MODE_LOG_OVERLAP_ITSWO : mode;
   const float* w = nullptr;
   const float* e = nullptr;
   // everything this call enqueues comes after ev_mark; a sampler launch that follows directly
@@ -236,6 +264,9 @@ int vmc_accumulate(vmc_ctx* c, int mode, float beta) {
   if (mode == VMC_MODE_ENERGY_GRADIENT) {
     PROPAGATE(local_energy_device(c, VMC_PSI, true, &fold_eloc));   // training.py:542-543
     w = e = c->ps[0].eloc;
+  } else if (penalized) {
+    PROPAGATE(penalized_weights(c, beta));
+    w = c->ratio; e = c->ps[0].eloc;
   } else {
     if (!c->ps[1].has_params) return fail(c, VMC_ERR_STATE, "supervisor parameters not set (vmc_transfer_params)");
     if (!c->ps[1].cache_valid && sampler_refresh_ok(c)) {
@@ -275,13 +306,15 @@ int vmc_accumulate(vmc_ctx* c, int mode, float beta) {
   }
   const bool fresh = c->acc_fresh;
   bool scalars_done = false;
-  PROPAGATE(gradient_sums(c, w, fresh, e, mode, &scalars_done, fold_eloc, beta));
+  PROPAGATE(gradient_sums(c, w, fresh, e, sc_mode, &scalars_done, fold_eloc, beta));
   if (!scalars_done)
-    HIPCHK(c, launch_scalar_accum(c->stream, e, mode == 1 ? c->ratio : nullptr, c->B, c->acc + 2 * c->P, mode, fresh));
+    HIPCHK(c, launch_scalar_accum(c->stream, e, sc_mode == 1 ? c->ratio : nullptr, c->B, c->acc + 2 * c->P, sc_mode, fresh));
   c->acc_fresh = false;
+  if (penalized) HIPCHK(c, launch_overlap_tail(c->stream, c->ovl.out, c->acc + 2 * c->P));   // slots 5, 6: F^ and the calls
   if (c->sr_cap > 0 && mode == VMC_MODE_ENERGY_GRADIENT) PROPAGATE(sr_record(c));
   c->acc_since_sweep = true;
-  c->token = cache_was_valid && !refresh_ran;
+  // a sampler launch behind a penalised accumulate waits for all of it: the call reads both amplitude caches to its end
+  c->token = cache_was_valid && !refresh_ran && !penalized;
   return VMC_OK;
 }
 
@@ -323,7 +356,7 @@ int vmc_mean_energy(vmc_ctx* c, double* energy) {
 
 int vmc_get_gradient(vmc_ctx* c, int mode, float* grad) {
   CHECK_CTX(c);
-  if (!grad || (mode != 0 && mode != 1)) return fail(c, VMC_ERR_INVALID, "bad arguments");
+  if (!grad || (mode != 0 && mode != 1 && mode != VMC_MODE_PENALIZED_ENERGY)) return fail(c, VMC_ERR_INVALID, "bad arguments");
   PROPAGATE(acc_zeros(c));
   HIPCHK(c, launch_adam(c->stream, nullptr, nullptr, nullptr, c->acc, (int)c->P, mode, 0.f, 0.f, 0.f, 0.f, c->grad_tmp));
   HIPCHK(c, hipMemcpyAsync(grad, c->grad_tmp, c->P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -334,7 +367,7 @@ int vmc_get_gradient(vmc_ctx* c, int mode, float* grad) {
 int vmc_apply_adam(vmc_ctx* c, int mode, float lr, float beta1, float beta2, float eps, double* energy) {
   ENTER(c);
   REFUSE_COMPOSED(c);
-  if (mode != 0 && mode != 1) return fail(c, VMC_ERR_INVALID, "bad mode");
+  if (mode != 0 && mode != 1 && mode != VMC_MODE_PENALIZED_ENERGY) return fail(c, VMC_ERR_INVALID, "bad mode");
   if (c->prod) PROPAGATE(prod_gather_params(c, VMC_PSI));      // theta = [a | b] from the factors
   if (!c->ps[0].has_params) return fail(c, VMC_ERR_STATE, "parameters not set");
   PROPAGATE(acc_zeros(c));
@@ -416,7 +449,8 @@ int vmc_update_norm_dist(vmc_ctx* c, void* nccl_comm, int32_t world_size, float 
 static bool side_sweep_enabled() { const char* e = getenv("CGS_VMC_SIDE_SWEEP"); return !(e && atoi(e) == 0); }
 
 static int epoch_energy_gradient_impl(vmc_ctx* c, void* comm, int world, int64_t n_eq_steps, int32_t n_batches,
-                                      int64_t n_mc_steps, float max_value) {
+                                      int64_t n_mc_steps, float max_value, int mode = VMC_MODE_ENERGY_GRADIENT,
+                                      float lambda = 0.f) {
   if (n_eq_steps < 0 || n_batches < 0 || n_mc_steps < 0) return fail(c, VMC_ERR_INVALID, "negative count");
   PROPAGATE(vmc_mc_steps(c, n_eq_steps, nullptr));                       // training.py:608-609
   if (max_value > 0.f) {                                                  // training.py:611-612
@@ -425,8 +459,8 @@ static int epoch_energy_gradient_impl(vmc_ctx* c, void* comm, int world, int64_t
   }
   PROPAGATE(vmc_reset_accumulators(c));                                   // training.py:613
   for (int b = 0; b < n_batches; ++b) {                                   // training.py:614-617
-    c->expect_sweep = n_mc_steps > 0;
-    PROPAGATE(vmc_accumulate(c, VMC_MODE_ENERGY_GRADIENT, 0.f));
+    c->expect_sweep = n_mc_steps > 0 && mode == VMC_MODE_ENERGY_GRADIENT;    // (mode PENALIZED_ENERGY is not overtaken)
+    PROPAGATE(vmc_accumulate(c, mode, lambda));
     // sharded chains: the last sweep does not touch the accumulators -- on its own stream it runs beside the
     // all-reduce instead of in front of it (CGS_VMC_SIDE_SWEEP=0: in stream order, for A/B)
     if (b == n_batches - 1 && world > 1 && n_mc_steps > 0 && side_sweep_enabled()) c->side_sweep_once = true;
@@ -443,6 +477,16 @@ int vmc_epoch_energy_gradient(vmc_ctx* c, int64_t n_eq_steps, int32_t n_batches,
   ENTER(c);
   REFUSE_COMPOSED(c);
   return epoch_energy_gradient_impl(c, nullptr, 1, n_eq_steps, n_batches, n_mc_steps, max_value);
+}
+
+int vmc_epoch_penalized_energy(vmc_ctx* c, float lambda, int64_t n_eq_steps, int32_t n_batches, int64_t n_mc_steps,
+                               float max_value) {
+  ENTER(c);
+  REFUSE_COMPOSED(c);
+  // (before the equilibration sweeps move the chains: what the first accumulate would refuse)
+  PROPAGATE(penalized_refusals(c, lambda, "vmc_epoch_penalized_energy"));
+  return epoch_energy_gradient_impl(c, nullptr, 1, n_eq_steps, n_batches, n_mc_steps, max_value, VMC_MODE_PENALIZED_ENERGY,
+                                    lambda);
 }
 
 int vmc_epoch_energy_gradient_dist(vmc_ctx* c, void* nccl_comm, int32_t world_size, int64_t n_eq_steps,

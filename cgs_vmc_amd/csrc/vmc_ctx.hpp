@@ -122,6 +122,15 @@ struct MomentBufs {
   DevBuf<double> chain;          // [2][B] e, g
   DevBuf<double> out;            // [6]
 };
+// overlap with the frozen set (overlap.hip): per chain ln|omega / psi| and the sign code, the blocks' maxima, the four
+// sums and the scaled ratios
+struct OverlapBufs {
+  DevBuf<double> d;              // [B]
+  DevBuf<int> code;              // [B] +-1, 0, OVERLAP_DEAD
+  DevBuf<double> bmax;           // [plan_overlap_blocks(B)]
+  DevBuf<double> out;            // [4] S1, S2, alive, m
+  DevBuf<double> ratio;          // [B] s exp(d - m) (vmc_overlap's per-chain output)
+};
 // dimer-dimer correlations: the two lists of a call, ln|psi| (and, signed types, the sign) of every single exchange,
 // and the sums
 struct DimerBufs {
@@ -265,6 +274,7 @@ struct vmc_ctx {
   SymmBufs symm;
   ProjBufs proj;
   MomentBufs mom;
+  OverlapBufs ovl;
   // the Hamiltonian as vmc_set_bonds was given it (vmc_projected_energy asks whether its ops are symmetries of it)
   std::vector<int32_t> ham_ij;
   std::vector<float> ham_jx, ham_jz;
@@ -633,6 +643,10 @@ void prod_chains_changed(vmc_ctx* c);
 void prod_child_params_changed(vmc_ctx* child, int which);
 void prod_release(vmc_ctx* c);                       // vmc_destroy of a product: the factors are free again
 void prod_child_destroyed(vmc_ctx* child);           // vmc_destroy of a factor that is still composed
+// vmc_api_measure.hip: what vmc_overlap and mode PENALIZED_ENERGY share -- the front of their refusals, and the ratio pass
+// and the fold over the two amplitude caches (ensure_cache of both sets has run) into c->ovl.out
+int overlap_refusals(vmc_ctx* c, const char* what);
+int overlap_sums_device(vmc_ctx* c);
 // vmc_api_sweep.hip
 bool sampler_refresh_ok(const vmc_ctx* c);
 int refresh_cache_by_sampler(vmc_ctx* c, int which);

@@ -438,12 +438,30 @@ class VmcEngine:
       out['e_loc'], out['h2_loc'] = e_loc, h2_loc
     return out
 
+  def overlap(self, per_chain: bool = False):
+    """Overlap of psi with the frozen parameter set omega over the current chains (extension, vmc_overlap).  With
+    r_c = omega(x_c) / psi(x_c) = s_c exp(d_c) and log_scale = max_c d_c, returns a dict: 's1' = sum_c s_c exp(d_c -
+    log_scale), 's2' = sum_c exp(2 (d_c - log_scale)), 'alive', the chains whose own amplitude does not vanish (the
+    others add nothing), 'log_scale', and with per_chain 'ratio', float64 [batch_size] = s_c exp(d_c - log_scale).  The
+    fidelity |<omega|psi>|^2 / (<psi|psi><omega|omega>) ~ s1^2 / (alive s2) (evaluation.fidelity_from_sums).  Needs the
+    frozen set (set_params(theta, VMC_OMEGA) or transfer_params).  Moves no chain, touches neither the step counter nor
+    the accumulators nor the Hamiltonian; every output is the same bits from call to call."""
+    dp = C.POINTER(C.c_double)
+    sums = np.empty(4, np.float64)
+    ratio = np.empty(self.batch_size, np.float64) if per_chain else None
+    self._check(self._lib.vmc_overlap(self._ctx, sums.ctypes.data_as(dp), ratio.ctypes.data_as(dp) if per_chain else None))
+    out = {'s1': float(sums[0]), 's2': float(sums[1]), 'alive': int(sums[2]), 'log_scale': float(sums[3])}
+    if per_chain:
+      out['ratio'] = ratio
+    return out
+
   def last_connected_rows(self) -> int:
     v = C.c_int64()
     self._check(self._lib.vmc_last_connected_rows(self._ctx, C.byref(v)))
     return int(v.value)
 
   def accumulate(self, mode: int, beta: float = 0.0):
+    """mode VMC_MODE_PENALIZED_ENERGY (extension): `beta` carries the penalty lambda of E + lambda F(psi, omega)."""
     self._check(self._lib.vmc_accumulate(self._ctx, mode, float(beta)))
 
   def reset_accumulators(self):
@@ -503,6 +521,13 @@ class VmcEngine:
     """training.py:608-617 in one host call (everything before apply_gradients)."""
     self._check(self._lib.vmc_epoch_energy_gradient(self._ctx, int(n_eq_steps), int(n_batches),
                                                     int(n_mc_steps), float(max_value)))
+
+  def epoch_penalized_energy(self, penalty: float, n_eq_steps: int, n_batches: int, n_mc_steps: int,
+                             max_value: float = 1e10):
+    """epoch_energy_gradient with accumulate(VMC_MODE_PENALIZED_ENERGY, penalty) in its accumulate's place (extension,
+    vmc_epoch_penalized_energy; one rank)."""
+    self._check(self._lib.vmc_epoch_penalized_energy(self._ctx, float(penalty), int(n_eq_steps), int(n_batches),
+                                                     int(n_mc_steps), float(max_value)))
 
   def epoch_log_overlap(self, beta: float, n_eq_steps: int, n_batches: int, n_mc_steps: int,
                         max_value: float, lr: float, beta1: float, beta2: float,

@@ -125,7 +125,7 @@ def _sampling_eval_ops(wavefunction, hparams, shared_resources, make_value) -> E
 
 
 def _sampled(eval_ops, session, hparams, stack, per_sample) -> int:
-  """The sample loop of the six measurement evaluators, on the same schedule as MonteCarloOperatorEvaluator's (which
+  """The sample loop of the seven measurement evaluators, on the same schedule as MonteCarloOperatorEvaluator's (which
   keeps its own loop: no all-reduce, and a fused path): thermalises for num_equilibration_sweeps sweeps, then takes
   num_evaluation_samples measurements, num_monte_carlo_sweeps sweeps apart.
   stack(session.run(value)) is the fp64 array of this rank's sums; with sharded chains the ranks' arrays are added by one
@@ -579,6 +579,89 @@ class LanczosStepEvaluator(WavefunctionEvaluator):
     out['samples'] = samples
     out['n_rows2'] = int(getattr(value, 'last_rows2', 0))
     return out
+
+
+class OverlapTensor(session_lib.Tensor):
+  """The four sums of VmcEngine.overlap over THIS rank's chains, float64 [4]: s1, s2, chains alive, log_scale (s1 and s2
+  are in units of exp(log_scale) and exp(2 log_scale))."""
+
+  def __init__(self, engine):
+    self.engine = engine
+    super(OverlapTensor, self).__init__(self._value, 'overlap')
+
+  def _value(self):
+    v = self.engine.overlap()
+    return np.array([v['s1'], v['s2'], v['alive'], v['log_scale']], np.float64)
+
+
+def fidelity_from_sums(s1, s2, alive) -> float:
+  """s1^2 / (alive s2), the estimator of |<phi|psi>|^2 / (<psi|psi><phi|phi>) from sums at ONE scale; 0 -- never nan --
+  when s2 = 0 (phi vanishes on every chain) or no chain is alive."""
+  s1, s2, alive = float(s1), float(s2), float(alive)
+  if not s2 > 0 or not alive > 0:
+    return 0.0
+  return s1 * s1 / (alive * s2)
+
+
+def overlap_common_scale(samples):
+  """[n_samples][3] = s1, s2, alive of `samples` [n_samples][4] (s1, s2, alive, log_scale) at the largest log_scale among
+  the samples that hold a ratio (s2 > 0), in fp64: s1 exp(l - L), s2 exp(2 (l - L)).  A sample far below the common scale
+  underflows to 0, which is its share of the sums."""
+  samples = np.asarray(samples, np.float64).reshape(-1, 4)
+  out = samples[:, :3].copy()
+  live = samples[:, 1] > 0
+  if live.any():
+    shift = np.where(live, samples[:, 3] - samples[live, 3].max(), 0.0)
+    with np.errstate(under='ignore'):
+      out[:, 0] = samples[:, 0] * np.exp(shift)
+      out[:, 1] = samples[:, 1] * np.exp(2.0 * shift)
+  return out
+
+
+class OverlapEvaluator(WavefunctionEvaluator):
+  """Fidelity of psi with a second, frozen state phi of the same architecture by running MCMC on psi (extension):
+  F = |<phi|psi>|^2 / (<psi|psi><phi|phi>) = <r>^2 / <r^2>, r = phi / psi on chains drawn from |psi|^2.  The signatures are
+  MonteCarloOperatorEvaluator's; `operator` is phi, a wavefunction built like psi that holds its values (or receives them
+  before run_evaluation); it is bound to the chains' second parameter set.  One rank only."""
+
+  def build_eval_ops(self, wavefunction, operator, hparams,
+                     shared_resources: Dict[graph_builders.ResourceName, Any]) -> EvalOps:
+    if parallel.is_distributed():
+      raise NotImplementedError('OverlapEvaluator runs on one rank (the sums of two ranks have no common scale)')
+    if operator is None or operator is wavefunction:
+      raise ValueError('OverlapEvaluator: `operator` is the second wavefunction')
+
+    def make_value(engine):
+      configs = graph_builders.get_configs(shared_resources, hparams.batch_size, hparams.num_sites)
+      if operator._bind(configs) is not engine or operator._which != 1:
+        raise ValueError('OverlapEvaluator: the second wavefunction must take the frozen parameter set of psi\'s chains')
+      return OverlapTensor(engine)
+    return _sampling_eval_ops(wavefunction, hparams, shared_resources, make_value)
+
+  def run_evaluation(self, eval_ops: EvalOps, session, hparams, epoch_num: int) -> Dict[str, Any]:
+    """Thermalises for num_equilibration_sweeps sweeps, then takes num_evaluation_samples measurements,
+    num_monte_carlo_sweeps sweeps apart (the loop of MonteCarloOperatorEvaluator).  A measurement is the four sums of
+    VmcEngine.overlap; the samples are brought to one scale on the host in fp64 (overlap_common_scale).  With S1_t, S2_t,
+    A_t the scaled sums of sample t, returns a dict: 'fidelity' = (sum_t S1_t)^2 / (sum_t A_t sum_t S2_t) and
+    'fidelity_err', its delete-one-sample jackknife error (0 for a single sample); 'overlap_sign', the sign of sum_t S1_t;
+    'alive_fraction' = sum_t A_t / (n_samples batch_size); 'samples' [n_samples][4], the sums as measured.  A phi that
+    vanishes on every chain gives fidelity 0, never nan."""
+    del epoch_num
+    samples = np.empty((hparams.num_evaluation_samples, 4), np.float64)
+
+    def per_sample(s, sums):
+      samples[s] = sums
+    self.acceptance_count = _sampled(eval_ops, session, hparams, lambda v: np.asarray(v, np.float64), per_sample)
+    scaled = overlap_common_scale(samples)
+    n = scaled.shape[0]
+    total = scaled.sum(axis=0)
+    err = 0.0
+    if n > 1:
+      left = np.array([fidelity_from_sums(*(total - scaled[t])) for t in range(n)], np.float64)
+      err = float(np.sqrt((n - 1.0) / n * ((left - left.mean()) ** 2).sum()))
+    chains = float(n) * float(hparams.batch_size)
+    return {'fidelity': fidelity_from_sums(*total), 'fidelity_err': err, 'overlap_sign': float(np.sign(total[0])),
+            'alive_fraction': float(total[2] / chains) if chains > 0 else 0.0, 'samples': samples}
 
 
 class VectorWavefunctionEvaluator(WavefunctionEvaluator):

@@ -10,6 +10,7 @@ launch (`mc_step.run_many(n)`), which is the same Markov chain.
 from __future__ import annotations
 
 import copy
+import os
 from typing import Dict, NamedTuple
 
 import numpy as np
@@ -142,7 +143,7 @@ class _AccumulatorState:
     self.reduced = True
 
 
-def _common_ops(wavefunction, hamiltonian, hparams, shared_resources, mode, apply_fn=None):
+def _common_ops(wavefunction, hamiltonian, hparams, shared_resources, mode, apply_fn=None, beta=None):
   batch_size = hparams.batch_size
   n_sites = hparams.num_sites
   configs = graph_builders.get_configs(shared_resources, batch_size, n_sites)
@@ -154,7 +155,8 @@ def _common_ops(wavefunction, hamiltonian, hparams, shared_resources, mode, appl
   update_wf_norm = wavefunction.update_norm(psi)
   state = _AccumulatorState(engine)
   optimizer = create_sgd_optimizer(hparams)
-  beta = float(getattr(hparams, 'time_evolution_beta', 0.0))
+  if beta is None:       # (mode PENALIZED_ENERGY hands its penalty in here)
+    beta = float(getattr(hparams, 'time_evolution_beta', 0.0))
 
   def accumulate():
     configs._ensure_hamiltonian(hamiltonian)
@@ -282,6 +284,109 @@ class StochasticReconfigurationOptimizer(EnergyGradientOptimizer):
     return train_ops
 
 
+def check_lower_state(variables, directory: str):
+  """The arrays of the latest checkpoint of `directory`, checked against `variables` (names and shapes): a missing name
+  or another shape is a ValueError that names the first such variable."""
+  path = session_lib.latest_checkpoint(directory)
+  if path is None:
+    raise ValueError('lower_state_dir {!r} holds no checkpoint'.format(directory))
+  if os.path.exists(path + '.npz'):
+    data = dict(np.load(path + '.npz'))
+  else:
+    from . import tf_checkpoint
+    data = dict(tf_checkpoint.read_bundle(path))
+  for v in variables:
+    if v.name not in data:
+      raise ValueError('lower state {}: no variable {} (the two states must share one architecture)'.format(path, v.name))
+    if tuple(np.shape(data[v.name])) != tuple(v.shape):
+      raise ValueError('lower state {}: variable {} has shape {}, psi\'s has {}'.format(
+          path, v.name, tuple(np.shape(data[v.name])), tuple(v.shape)))
+  return data
+
+
+def load_frozen_state(wavefunction, frozen, directory: str):
+  """The latest checkpoint of `directory` -- written for a wavefunction built like `wavefunction` -- into `frozen`, its
+  twin: the variables pair up in creation order and are looked up under `wavefunction`'s names (check_lower_state)."""
+  data = check_lower_state(wavefunction.get_trainable_variables(), directory)
+  for own, twin in zip(wavefunction.get_trainable_variables(), frozen.get_trainable_variables()):
+    twin.load(data[own.name])
+
+
+class PenalizedEnergyGradientOptimizer(EnergyGradientOptimizer):
+  """EXTENSION (the reference finds ground states only): trains E[psi] + overlap_penalty F(psi, phi) against a frozen
+  lower state phi (Choo et al. 2018); above the gap the minimum is the first excited state of the sampled sector.  The
+  ops, op order and accumulators are EnergyGradientOptimizer's; the accumulate weights each chain by
+  w = E_loc + overlap_penalty (S1 / S2) phi / psi (csrc/overlap.hip), so that apply_gradients feeds mean(w O) - mean(w)
+  mean(O) to Adam.  phi = copy.deepcopy(wavefunction) is the engine's second parameter set, as LogOverlapITSWO's
+  supervisor; psi is never transferred into it.  hparams: overlap_penalty (required, > 0) and lower_state_dir (optional:
+  the run directory whose latest checkpoint phi is loaded from at build time; without it the caller fills
+  `frozen_wavefunction`).  `last_fidelity` is the mean over the epoch's accumulate calls of the batch estimate
+  S1^2 / (alive S2).  One rank only."""
+
+  def build_opt_ops(self, wavefunction, hamiltonian, hparams, shared_resources) -> NamedTuple:
+    penalty = getattr(hparams, 'overlap_penalty', None)
+    if penalty is None:
+      raise ValueError('PenalizedEnergyGradient needs hparams.overlap_penalty (> 0)')
+    penalty = float(penalty)
+    if not np.isfinite(penalty) or penalty <= 0:
+      raise ValueError('PenalizedEnergyGradient: overlap_penalty = {} is not a positive number'.format(penalty))
+    if parallel.is_distributed():
+      raise NotImplementedError('PenalizedEnergyGradient runs on one rank (the batch sums S1, S2 are per rank)')
+    configs = graph_builders.get_configs(shared_resources, hparams.batch_size, hparams.num_sites)
+    # bind psi first so that it owns the sampling slot, then the frozen copy
+    wavefunction._bind(configs)
+    frozen = copy.deepcopy(wavefunction)
+    frozen._bind(configs)
+    lower_state_dir = getattr(hparams, 'lower_state_dir', '') or ''
+    if lower_state_dir:
+      load_frozen_state(wavefunction, frozen, lower_state_dir)
+    self.frozen_wavefunction = frozen
+    self.overlap_penalty = penalty
+    self.last_fidelity = float('nan')
+    ops = _common_ops(wavefunction, hamiltonian, hparams, shared_resources, _hip.VMC_MODE_PENALIZED_ENERGY,
+                      beta=penalty)
+    self._fused = ops
+    self._train_ops = TrainOpsTraditional(
+        accumulate_gradients=ops['accumulate_gradients'],
+        apply_gradients=ops['apply_gradients'],
+        reset_gradients=ops['reset_gradients'],
+        mc_step=ops['mc_step'],
+        acc_rate=ops['acc_rate'],
+        metrics=ops['mean_energy'],
+        epoch_increment=ops['epoch_increment'],
+        update_wf_norm=ops['update_wf_norm'],
+    )
+    return self._train_ops
+
+  def run_optimization_epoch(self, train_ops, session, hparams, epoch_number: int = 0
+                             ) -> np.float32:
+    """EnergyGradientOptimizer's epoch.  Own handles: the sampling / accumulation part is ONE call into the library
+    (vmc_epoch_penalized_energy); foreign handles run op by op."""
+    n_eq = hparams.num_equilibration_sweeps * hparams.num_sites
+    n_mc = hparams.num_monte_carlo_sweeps * hparams.num_sites
+    if train_ops is getattr(self, '_train_ops', None):
+      fused = self._fused
+      fused['configs']._ensure_hamiltonian(fused['hamiltonian'])
+      max_value = 1e10 if train_ops.update_wf_norm is not None else 0.0
+      fused['engine'].epoch_penalized_energy(self.overlap_penalty, n_eq, hparams.num_batches_per_epoch, n_mc, max_value)
+      fused['state'].reduced = False
+      tail = fused['engine'].get_accumulators()[-8:]       # ... f_total f_count 0
+      self.last_fidelity = float(tail[5] / tail[6]) if tail[6] > 0 else float('nan')
+    else:
+      _run_mc_steps(session, train_ops.mc_step, n_eq)
+      if train_ops.update_wf_norm is not None:
+        session.run(train_ops.update_wf_norm)
+      session.run(train_ops.reset_gradients)
+      for _ in range(hparams.num_batches_per_epoch):
+        session.run(train_ops.accumulate_gradients)
+        _run_mc_steps(session, train_ops.mc_step, n_mc)
+    session.run(train_ops.apply_gradients)
+    energy = session.run(train_ops.metrics)
+    session.run(train_ops.reset_gradients)
+    session.run(train_ops.epoch_increment)
+    return energy
+
+
 class LogOverlapImaginaryTimeSWO(WavefunctionOptimizer):
   """Imaginary-time SWO based on the log-overlap gradient formula (training.py:626-778)."""
 
@@ -372,6 +477,11 @@ GROUND_STATE_OPTIMIZERS = {
     'LogOverlapITSWO': LogOverlapImaginaryTimeSWO,
     'ITSWO': ImaginaryTimeSWO,
     'StochasticReconfiguration': StochasticReconfigurationOptimizer,   # extension, see class
+}
+
+# run_excited_state_training's optimizers (extension)
+EXCITED_STATE_OPTIMIZERS = {
+    'PenalizedEnergyGradient': PenalizedEnergyGradientOptimizer,
 }
 
 # run_supervised_training's optimizers (SWO, LogOverlapSWO, DualSamplingSWO, BasisIterSWO)

@@ -88,8 +88,10 @@ typedef enum {
  * copy (copy.deepcopy(wavefunction), training.py:660). */
 enum { VMC_PSI = 0, VMC_OMEGA = 1 };
 
-/* accumulate / apply modes (training.GROUND_STATE_OPTIMIZERS, training.py:913-917) */
+/* accumulate / apply modes (training.GROUND_STATE_OPTIMIZERS, training.py:913-917); PENALIZED_ENERGY is an
+ * extension (see vmc_overlap) */
 enum { VMC_MODE_ENERGY_GRADIENT = 0, VMC_MODE_LOG_OVERLAP_ITSWO = 1 };
+#define VMC_MODE_PENALIZED_ENERGY 2
 
 /* wavefunctions.WAVEFUNCTION_TYPES with kernels (wavefunctions.py:1157-1170) */
 enum { VMC_ANSATZ_FULLY_CONNECTED = 0, VMC_ANSATZ_RBM = 1, VMC_ANSATZ_CONV_2D = 2,
@@ -236,12 +238,18 @@ int vmc_local_energy_terms(vmc_ctx* ctx, int which, float* diag, float* offdiag_
 
 /* TrainOps.accumulate_gradients: training.py:539-558 (mode ENERGY_GRADIENT) or
  * training.py:661-695 (mode LOG_OVERLAP_ITSWO, beta = hparams.time_evolution_beta). */
+/* Mode PENALIZED_ENERGY (extension, no reference counterpart): beta carries the penalty lambda of E[psi] + lambda F(psi,
+ * omega) against the frozen set omega; the weights of the second sum are w_c = E_loc(c) + lambda (S1 / S2) r_c (see
+ * vmc_overlap), the scalars get e_total += sum E_loc, r_total += sum w and the two counts as mode LOG_OVERLAP_ITSWO fills
+ * them, slot 5 += the call's fidelity estimate S1^2 / (alive S2) and slot 6 += 1.  One rank only.  Refusals, before
+ * anything is launched: a product ctx or an output activation other than exp on an unsigned type: VMC_ERR_UNSUPPORTED;
+ * omega unset, or an SR sample store reserved: VMC_ERR_STATE; lambda < 0 or not finite: VMC_ERR_INVALID. */
 int vmc_accumulate(vmc_ctx* ctx, int mode, float beta);
 /* TrainOps.reset_gradients: tf.variables_initializer(tf.local_variables()). */
 int vmc_reset_accumulators(vmc_ctx* ctx);
-/* Accumulator buffer: [g1 (P) | g2 (P) | e_total e_count r_total r_count g_count 0 0 0]
- * = 2P+8 floats.  The device pointer is exposed so the host can all-reduce it in place
- * (RCCL via torch.distributed); *n_floats = 2P+8. */
+/* Accumulator buffer: [g1 (P) | g2 (P) | e_total e_count r_total r_count g_count f_total f_count 0]
+ * = 2P+8 floats (f_total / f_count: mode PENALIZED_ENERGY only, 0 otherwise).  The device pointer is
+ * exposed so the host can all-reduce it in place (RCCL via torch.distributed); *n_floats = 2P+8. */
 int vmc_accumulators_devptr(vmc_ctx* ctx, void** dev_ptr, int64_t* n_floats);
 /* The same all-reduce for hosts without torch.distributed: nccl_comm is an existing ncclComm_t of
  * RCCL (NULL or world_size <= 1: no-op); stream-ordered on the ctx's stream, g_count corrected.
@@ -251,7 +259,8 @@ int vmc_get_accumulators(vmc_ctx* ctx, float* host /*[2P+8]*/);
 int vmc_set_accumulators(vmc_ctx* ctx, const float* host /*[2P+8]*/);
 
 /* TrainOps.apply_gradients: gradient formula (training.py:560-564 or 697-699) + TF1
- * Adam (training.py:84-91).  *energy (may be NULL) = TrainOps.metrics / .energy. */
+ * Adam (training.py:84-91).  *energy (may be NULL) = TrainOps.metrics / .energy.
+ * Mode PENALIZED_ENERGY: grad = g2 / n - (r_total / r_count) g1 / n, the energy still e_total / e_count. */
 int vmc_apply_adam(vmc_ctx* ctx, int mode, float lr, float beta1, float beta2, float eps,
                    double* energy);
 int vmc_get_gradient(vmc_ctx* ctx, int mode, float* grad /*[P]*/);
@@ -272,6 +281,10 @@ int vmc_epoch_energy_gradient(vmc_ctx* ctx, int64_t n_eq_steps, int32_t n_batche
 int vmc_epoch_log_overlap(vmc_ctx* ctx, float beta, int64_t n_eq_steps, int32_t n_batches,
                           int64_t n_mc_steps, float max_value, float lr, float beta1, float beta2,
                           float eps, double* energy);
+/* The EnergyGradient epoch with vmc_accumulate(ctx, VMC_MODE_PENALIZED_ENERGY, lambda) in its accumulate's place
+ * (extension; one rank only). */
+int vmc_epoch_penalized_energy(vmc_ctx* ctx, float lambda, int64_t n_eq_steps, int32_t n_batches,
+                               int64_t n_mc_steps, float max_value);
 
 /* ---- chains sharded over ranks (the reference is single-process) ----------------
  * Rank r owns chains [r B/G, (r+1) B/G) (vmc_desc.chain_offset); the only exchanges are a SUM
@@ -504,6 +517,25 @@ int vmc_projected_energy(vmc_ctx* ctx, int which, int32_t n_ops, const int32_t* 
 int vmc_energy_moments(vmc_ctx* ctx, int which, int64_t rows_per_pass /*0: the library decides*/, double sums[6],
                        double* e_loc /*[batch_size] or NULL*/, double* h2_loc /*[batch_size] or NULL*/,
                        int64_t* n_rows2 /*[1]*/);
+
+/* Overlap with the frozen parameter set -- EXTENSION with no reference counterpart.  Over the ctx's current chains x_c,
+ * drawn from |psi|^2, with r_c = omega(x_c) / psi(x_c):
+ *   d_c = (logit_omega(c) - shift_omega) - (logit_psi(c) - shift_psi)      fp64, from the two fp32 amplitude caches
+ *   s_c = sgn(omega(x_c)) sgn(psi(x_c))                                    1 on the unsigned types
+ *   m   = max of d_c over the chains with s_c != 0 (0 when there is none)
+ *   sums = { S1 = sum_c s_c exp(d_c - m), S2 = sum_c exp(2 (d_c - m)), alive, m }
+ * so that r_c = s_c exp(d_c), the fidelity |<omega|psi>|^2 / (<psi|psi><omega|omega>) ~ S1^2 / (alive S2) whatever m is,
+ * and sum_c r_c = exp(m) S1.  ratio [batch_size] (optional) receives s_c exp(d_c - m).  A chain whose own amplitude
+ * vanishes is dead: its ratio is 0, it adds to no sum and is not alive.  A vanishing omega(x_c) gives a ratio of 0
+ * exactly (its logarithm is never read); the chain stays alive.
+ * Determinism: thread t of one workgroup of 256 adds the chains t, t + 256, ... in ascending order, the 256 partial
+ * sums are folded by a fixed butterfly; the max is exact in any order.  The four outputs are the same bits from call to
+ * call and for every launch grid (csrc/overlap.hip).
+ * A pure measurement: chains, step counter, accumulators, the Hamiltonian's bonds and the validity of the amplitude and
+ * activation caches are as before on return.
+ * Refusals, before anything is launched: omega unset: VMC_ERR_STATE; an output activation other than exp on an
+ * unsigned type, or a product ctx: VMC_ERR_UNSUPPORTED; a factor of a product ctx: VMC_ERR_STATE.  Outputs may be NULL. */
+int vmc_overlap(vmc_ctx* ctx, double sums[4], double* ratio /*[batch_size] or NULL*/);
 
 /* Stochastic reconfiguration -- EXTENSION: named by the north star, absent from the reference
  * (training.py has only the plain energy gradient + Adam), so these entries replace no reference
