@@ -333,46 +333,45 @@ hipError_t launch_pair_fold(hipStream_t s, const float* configs, const int2* pai
                             const float* val, const int* n_rows_dev, int B, int N, int n_pairs, int num_cus,
                             float* dense, double* zz, double* ex);
 
+// ln|psi| and the signs of a set of rows, as the folds of the measurements take them: the chains' own cache or the rows of a
+// pass (vmc_ctx.hpp: own_amps, row_amps).  sign null: unsigned amplitudes
+struct AmpPair { const float* logit; const float* sign; };
+
 // Renyi-2 swap estimator (renyi.hip): the rows of a pass of regions (row = region x B + chain: the replica pair's swapped
 // configurations where the pair matches on the region, the chain's own elsewhere) and their fold per region over the pairs
-// in ascending order, fp64.  mask [n_regions][N] 0/1; sign / row_sign null: unsigned amplitudes
+// in ascending order, fp64.  mask [n_regions][N] 0/1 amplitudes
 hipError_t launch_swap_rows(hipStream_t s, const float* configs, const unsigned char* mask, int B, int N,
                             int n_regions, int num_cus, float* rows);
-hipError_t launch_swap_fold(hipStream_t s, const float* configs, const unsigned char* mask, const float* logit,
-                            const float* sign, const float* row_logit, const float* row_sign, int B, int N,
-                            int n_regions, double* swap_sum, double* match_count);
+hipError_t launch_swap_fold(hipStream_t s, const float* configs, const unsigned char* mask, AmpPair own, AmpPair rows, int B,
+                            int N, int n_regions, double* swap_sum, double* match_count);
 
 // dimer-dimer correlations (dimer.hip).  bonds [..] site pairs, pairs [..] (a, b) indices into bonds.  Rows of phase 1:
 // row = bond x B + chain, the exchanged configuration where the bond is antiparallel, the chain's own elsewhere; of a
 // pass of phase 2: row = pair x B + chain, swap_kl swap_ij x where both exchanges act, the chain's own elsewhere.  The
-// folds give one thread per bond / pair over the chains in ascending order, fp64.  logit / sign [B]: the chains' own;
-// one_logit / one_sign [n_bonds][B]: phase 1's rows; two_logit / two_sign [n_pairs][B]: the pass's; signs null: unsigned
+// folds give one thread per bond / pair over the chains in ascending order, fp64.  own [B]: the chains';
+// one [n_bonds][B]: phase 1's rows; two [n_pairs][B]: the pass's
 hipError_t launch_dimer_rows1(hipStream_t s, const float* configs, const int2* bonds, int B, int N, int n_bonds,
                               int num_cus, float* rows);
 hipError_t launch_dimer_rows2(hipStream_t s, const float* configs, const int2* bonds, const int2* pairs, int B, int N,
                               int n_pairs, int num_cus, float* rows);
-hipError_t launch_dimer_bond_fold(hipStream_t s, const float* configs, const int2* bonds, const float* logit,
-                                  const float* sign, const float* one_logit, const float* one_sign, int B, int N,
-                                  int n_bonds, double* bond_sum);
-hipError_t launch_dimer_fold(hipStream_t s, const float* configs, const int2* bonds, const int2* pairs,
-                             const float* logit, const float* sign, const float* one_logit, const float* one_sign,
-                             const float* two_logit, const float* two_sign, int B, int N, int n_pairs, double* dd_sum);
+hipError_t launch_dimer_bond_fold(hipStream_t s, const float* configs, const int2* bonds, AmpPair own, AmpPair one, int B,
+                                  int N, int n_bonds, double* bond_sum);
+hipError_t launch_dimer_fold(hipStream_t s, const float* configs, const int2* bonds, const int2* pairs, AmpPair own,
+                             AmpPair one, AmpPair two, int B, int N, int n_pairs, double* dd_sum);
 
 // symmetry expectation values (symm.hip): the rows of a pass of ops (row = op x B + chain: f_k x_c[perm_k[i]], f_k = -1
 // where flip[k]) and their fold per op over the chains -- one wavefront per op, lane l the chains l, l + 64, ...
-// ascending, then a fixed butterfly, fp64.  perm [n_ops][N] bijections (plan_symm_check_ops); signs null: unsigned
+// ascending, then a fixed butterfly, fp64.  perm [n_ops][N] bijections (plan_symm_check_ops)
 hipError_t launch_symm_rows(hipStream_t s, const float* configs, const int* perm, const unsigned char* flip, int B,
                             int N, int n_ops, int num_cus, float* rows);
-hipError_t launch_symm_fold(hipStream_t s, const float* logit, const float* sign, const float* row_logit,
-                            const float* row_sign, int B, int n_ops, double* ratio_sum);
+hipError_t launch_symm_fold(hipStream_t s, AmpPair own, AmpPair rows, int B, int n_ops, double* ratio_sum);
 
-// symmetry-projected energies (proj.hip): ops [k0, k0 + n) of a launch (n <= PLAN_PROJ_LAUNCH_OPS; row_logit / row_sign
-// [n][B] their rows) added into the per-chain accumulator acc [n_sectors][B] with the characters chi [n_sectors][n_ops_all],
+// symmetry-projected energies (proj.hip): ops [k0, k0 + n) of a launch (n <= PLAN_PROJ_LAUNCH_OPS; rows
+// [n][B] theirs) added into the per-chain accumulator acc [n_sectors][B] with the characters chi [n_sectors][n_ops_all],
 // sequential fp64 fmas in ascending k; then the fold over the chains in launch_symm_fold's order into
-// out = [n_sectors] w sums, [n_sectors] w E_loc sums, the E_loc sum, the chains alive.  signs null: unsigned
-hipError_t launch_proj_accum(hipStream_t s, const float* logit, const float* sign, const float* row_logit,
-                             const float* row_sign, const double* chi, int B, int n_sectors, int n_ops_all, int k0, int n,
-                             double* acc);
+// out = [n_sectors] w sums, [n_sectors] w E_loc sums, the E_loc sum, the chains alive.  sign null: unsigned
+hipError_t launch_proj_accum(hipStream_t s, AmpPair own, AmpPair rows, const double* chi, int B, int n_sectors, int n_ops_all,
+                             int k0, int n, double* acc);
 hipError_t launch_proj_fold(hipStream_t s, const float* sign, const float* eloc, const double* acc, int B, int n_sectors,
                             double* out);
 
@@ -389,9 +388,8 @@ hipError_t launch_mom_fill(hipStream_t s, const float* configs, const int2* bond
                            int n_bonds, long long q0, int n, int num_cus, int2* desc, double* coef);
 hipError_t launch_mom_rows(hipStream_t s, const float* configs, const int2* bonds, const int2* rowinfo, const int2* desc,
                            int N, int n, int num_cus, float* rows);
-hipError_t launch_mom_accum(hipStream_t s, const float* logit, const float* sign, const float* row_logit,
-                            const float* row_sign, const double* coef, const int* off, const int* off2, int B, long long q0,
-                            int n, double* lanes);
+hipError_t launch_mom_accum(hipStream_t s, AmpPair own, AmpPair rows, const double* coef, const int* off, const int* off2,
+                            int B, long long q0, int n, double* lanes);
 hipError_t launch_mom_fold(hipStream_t s, const float* configs, const int2* bonds, const float* half_jx,
                            const float* quarter_jz, const int2* rowinfo, const int* off, const float* val, const float* eloc,
                            const float* sign, const double* diag1, const double* self1, const double* lanes, int B, int N,
@@ -420,14 +418,12 @@ inline unsigned measure_rows_grid(long long items, int num_cus) {
 
 // overlap with the frozen parameter set (overlap.hip; the estimator, the dead-chain rule and every summation order are
 // stated there).  ratio: d [B] = ln|omega / psi| per chain in fp64, code [B] = the combined sign (+-1, 0 where omega
-// vanishes, OVERLAP_DEAD where psi does) and bmax [plan_overlap_blocks(B)] the blocks' maxima of d; sign_* null: an
-// unsigned type.  fold: out [4] = S1, S2, alive, m.  weights: w [B] = eloc + lambda (S1 / S2) s exp(d - m), rounded once
+// vanishes, OVERLAP_DEAD where psi does) and bmax [plan_overlap_blocks(B)] the blocks' maxima of d.  fold: out [4] = S1, S2, alive, m.  weights: w [B] = eloc + lambda (S1 / S2) s exp(d - m), rounded once
 // to fp32 (null: not wanted), ratio [B] = s exp(d - m) in fp64 (null: not wanted).  tail: the accumulators' slots 5 and 6
 #define OVERLAP_DEAD 2
 inline int plan_overlap_blocks(int B) { return B > 0 ? (B + 255) / 256 : 1; }
-hipError_t launch_overlap_ratio(hipStream_t s, const float* logit_psi, const float* sign_psi, double shift_psi,
-                                const float* logit_omega, const float* sign_omega, double shift_omega, int B, double* d,
-                                int* code, double* bmax);
+hipError_t launch_overlap_ratio(hipStream_t s, AmpPair psi, double shift_psi, AmpPair omega, double shift_omega, int B,
+                                double* d, int* code, double* bmax);
 hipError_t launch_overlap_fold(hipStream_t s, const double* d, const int* code, const double* bmax, int B, double* out);
 hipError_t launch_overlap_weights(hipStream_t s, const double* d, const int* code, const double* sums, const float* eloc,
                                   float lambda, int B, float* w, double* ratio);

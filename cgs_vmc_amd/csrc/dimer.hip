@@ -143,18 +143,16 @@ hipError_t launch_dimer_rows2(hipStream_t s, const float* configs, const int2* b
   return hipGetLastError();
 }
 
-hipError_t launch_dimer_bond_fold(hipStream_t s, const float* configs, const int2* bonds, const float* logit,
-                                  const float* sign, const float* one_logit, const float* one_sign, int B, int N,
-                                  int n_bonds, double* bond_sum) {
-  hipLaunchKernelGGL(k_dimer_bond_fold, dim3(plan_measure_fold_grid(n_bonds)), dim3(64), 0, s, configs, bonds, logit, sign,
-                     one_logit, one_sign, B, N, n_bonds, bond_sum);
+hipError_t launch_dimer_bond_fold(hipStream_t s, const float* configs, const int2* bonds, AmpPair own, AmpPair one, int B,
+                                  int N, int n_bonds, double* bond_sum) {
+  hipLaunchKernelGGL(k_dimer_bond_fold, dim3(plan_measure_fold_grid(n_bonds)), dim3(64), 0, s, configs, bonds, own.logit,
+                     own.sign, one.logit, one.sign, B, N, n_bonds, bond_sum);
   return hipGetLastError();
 }
 
-hipError_t launch_dimer_fold(hipStream_t s, const float* configs, const int2* bonds, const int2* pairs,
-                             const float* logit, const float* sign, const float* one_logit, const float* one_sign,
-                             const float* two_logit, const float* two_sign, int B, int N, int n_pairs, double* dd_sum) {
-  hipLaunchKernelGGL(k_dimer_fold, dim3(plan_measure_fold_grid(n_pairs)), dim3(64), 0, s, configs, bonds, pairs, logit, sign,
-                     one_logit, one_sign, two_logit, two_sign, B, N, n_pairs, dd_sum);
+hipError_t launch_dimer_fold(hipStream_t s, const float* configs, const int2* bonds, const int2* pairs, AmpPair own,
+                             AmpPair one, AmpPair two, int B, int N, int n_pairs, double* dd_sum) {
+  hipLaunchKernelGGL(k_dimer_fold, dim3(plan_measure_fold_grid(n_pairs)), dim3(64), 0, s, configs, bonds, pairs, own.logit,
+                     own.sign, one.logit, one.sign, two.logit, two.sign, B, N, n_pairs, dd_sum);
   return hipGetLastError();
 }

@@ -303,11 +303,10 @@ hipError_t launch_mom_rows(hipStream_t s, const float* configs, const int2* bond
   return hipGetLastError();
 }
 
-hipError_t launch_mom_accum(hipStream_t s, const float* logit, const float* sign, const float* row_logit,
-                            const float* row_sign, const double* coef, const int* off, const int* off2, int B, long long q0,
-                            int n, double* lanes) {
-  hipLaunchKernelGGL(k_mom_accum, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, logit, sign, row_logit, row_sign, coef, off,
-                     off2, B, q0, n, lanes);
+hipError_t launch_mom_accum(hipStream_t s, AmpPair own, AmpPair rows, const double* coef, const int* off, const int* off2,
+                            int B, long long q0, int n, double* lanes) {
+  hipLaunchKernelGGL(k_mom_accum, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, own.logit, own.sign, rows.logit, rows.sign,
+                     coef, off, off2, B, q0, n, lanes);
   return hipGetLastError();
 }
 

@@ -114,11 +114,10 @@ __global__ void k_overlap_tail(const double* __restrict__ sums, float* __restric
   sc[6] += 1.f;
 }
 
-hipError_t launch_overlap_ratio(hipStream_t s, const float* logit_psi, const float* sign_psi, double shift_psi,
-                                const float* logit_omega, const float* sign_omega, double shift_omega, int B, double* d,
-                                int* code, double* bmax) {
-  hipLaunchKernelGGL(k_overlap_ratio, dim3(plan_overlap_blocks(B)), dim3(256), 0, s, logit_psi, sign_psi, shift_psi,
-                     logit_omega, sign_omega, shift_omega, B, d, code, bmax);
+hipError_t launch_overlap_ratio(hipStream_t s, AmpPair psi, double shift_psi, AmpPair omega, double shift_omega, int B,
+                                double* d, int* code, double* bmax) {
+  hipLaunchKernelGGL(k_overlap_ratio, dim3(plan_overlap_blocks(B)), dim3(256), 0, s, psi.logit, psi.sign, shift_psi,
+                     omega.logit, omega.sign, shift_omega, B, d, code, bmax);
   return hipGetLastError();
 }
 

@@ -86,14 +86,13 @@ __global__ __launch_bounds__(64) void k_proj_fold(const float* __restrict__ sign
   else { out[2 * n_sectors] = u; out[2 * n_sectors + 1] = v; }
 }
 
-hipError_t launch_proj_accum(hipStream_t s, const float* logit, const float* sign, const float* row_logit,
-                             const float* row_sign, const double* chi, int B, int n_sectors, int n_ops_all, int k0, int n,
-                             double* acc) {
+hipError_t launch_proj_accum(hipStream_t s, AmpPair own, AmpPair rows, const double* chi, int B, int n_sectors, int n_ops_all,
+                             int k0, int n, double* acc) {
   const int tile = plan_measure_sector_tile(n_sectors, n);
   if (tile < 1 || n > PLAN_PROJ_LAUNCH_OPS) return hipErrorInvalidValue;
   const dim3 grid(plan_proj_chain_blocks(B) * plan_proj_sector_tiles(n_sectors, tile));
-  hipLaunchKernelGGL(k_proj_accum, grid, dim3(PLAN_PROJ_THREADS), plan_proj_accum_lds_bytes(tile, n), s, logit, sign,
-                     row_logit, row_sign, chi, B, n_sectors, n_ops_all, k0, n, tile, acc);
+  hipLaunchKernelGGL(k_proj_accum, grid, dim3(PLAN_PROJ_THREADS), plan_proj_accum_lds_bytes(tile, n), s, own.logit, own.sign,
+                     rows.logit, rows.sign, chi, B, n_sectors, n_ops_all, k0, n, tile, acc);
   return hipGetLastError();
 }
 

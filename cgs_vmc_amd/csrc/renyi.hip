@@ -85,10 +85,9 @@ hipError_t launch_swap_rows(hipStream_t s, const float* configs, const unsigned 
   return hipGetLastError();
 }
 
-hipError_t launch_swap_fold(hipStream_t s, const float* configs, const unsigned char* mask, const float* logit,
-                            const float* sign, const float* row_logit, const float* row_sign, int B, int N,
-                            int n_regions, double* swap_sum, double* match_count) {
-  hipLaunchKernelGGL(k_swap_fold, dim3(plan_measure_fold_grid(n_regions)), dim3(64), 0, s, configs, mask, logit, sign,
-                     row_logit, row_sign, B, N, n_regions, swap_sum, match_count);
+hipError_t launch_swap_fold(hipStream_t s, const float* configs, const unsigned char* mask, AmpPair own, AmpPair rows, int B,
+                            int N, int n_regions, double* swap_sum, double* match_count) {
+  hipLaunchKernelGGL(k_swap_fold, dim3(plan_measure_fold_grid(n_regions)), dim3(64), 0, s, configs, mask, own.logit, own.sign,
+                     rows.logit, rows.sign, B, N, n_regions, swap_sum, match_count);
   return hipGetLastError();
 }

@@ -56,9 +56,8 @@ hipError_t launch_symm_rows(hipStream_t s, const float* configs, const int* perm
   return hipGetLastError();
 }
 
-hipError_t launch_symm_fold(hipStream_t s, const float* logit, const float* sign, const float* row_logit,
-                            const float* row_sign, int B, int n_ops, double* ratio_sum) {
-  hipLaunchKernelGGL(k_symm_fold, dim3((unsigned)n_ops), dim3(64), 0, s, logit, sign, row_logit, row_sign, B, n_ops,
+hipError_t launch_symm_fold(hipStream_t s, AmpPair own, AmpPair rows, int B, int n_ops, double* ratio_sum) {
+  hipLaunchKernelGGL(k_symm_fold, dim3((unsigned)n_ops), dim3(64), 0, s, own.logit, own.sign, rows.logit, rows.sign, B, n_ops,
                      ratio_sum);
   return hipGetLastError();
 }

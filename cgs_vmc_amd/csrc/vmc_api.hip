@@ -2,7 +2,8 @@
 // work on ctx->stream.  This file: ctx life cycle, parameters, chains, amplitudes, local energies, timing; the other
 // entry points live in vmc_api_sweep.hip (samplers), vmc_api_train.hip (accumulators, Adam, epochs, evaluation),
 // vmc_api_coll.hip (collectives), vmc_api_sr.hip (stochastic reconfiguration), vmc_api_measure.hip (the measurements
-// beside the energy: spin correlations, Renyi-2 entropy, dimer-dimer correlations, symmetry expectation values, symmetry-projected energies), vmc_api_prod.hip (product ctxs);
+// beside the energy: spin correlations, Renyi-2 entropy, dimer-dimer correlations, symmetry expectation values,
+// symmetry-projected energies, Lanczos-step energies, the overlap with the frozen set), vmc_api_prod.hip (product ctxs);
 // vmc_api_cgen.hip is the general convolution path's machinery.  Shared state and helpers: vmc_ctx.hpp.
 #include "vmc_ctx.hpp"
 

@@ -1,12 +1,19 @@
 // The measurements over the ctx's current chains (extensions, no reference counterpart): vmc_pair_correlations,
-// vmc_renyi2_swap, vmc_dimer_correlations, vmc_symmetry_expectations, vmc_projected_energy, vmc_energy_moments and vmc_overlap.  Each is a pure measurement: chains, step counter, accumulators, the
-// Hamiltonian's bond set and the validity of the amplitude and activation caches are as before when it returns.
+// vmc_renyi2_swap, vmc_dimer_correlations, vmc_symmetry_expectations, vmc_projected_energy, vmc_energy_moments and
+// vmc_overlap.  Each is a pure measurement: chains, step counter, accumulators, the Hamiltonian's bond set and the
+// validity of the amplitude and activation caches are as before when it returns.
 //
-// One scaffold serves the seven.  MEASURE_GATE is the shared front of the refusals; PureMeasurement records which caches
-// were valid and un-vouches on every way out for those that were not; upload copies a host list into its device buffer;
-// for_passes walks the items in passes of plan_measure_per_pass (plan.hpp); read_back brings the fp64 sums down and
-// synchronises, on a failed call too.  The device buffers are the grow-only DevBufs of vmc_ctx.hpp.  What differs per
-// measurement is its own checks, what a pass launches and how the sums are handed out:
+// One scaffold serves the seven.  An entry is straight-line code: its refusals (MEASURE_GATE in front, needs_ln_psi where
+// the logit must be ln psi), then the host buffers of its asynchronous copies, then ONE guard, PureMeasurement, and behind
+// it plain PROPAGATE / HIPCHK steps that return as soon as one fails.  The guard makes that safe: on every way out it
+// synchronises the stream (unless read_back, the last step, already has) and un-vouches the caches that were not valid
+// before; its declaration rule is stated where it is defined.  HamiltonianSet is the same idea for the bond set the spin
+// correlations swap out.  upload copies a host list into its device buffer; for_passes walks the items in passes of
+// plan_measure_per_pass (plan.hpp); row_pass is a pass of all but the spin correlations: the measurement's rows kernel
+// into the row buffer of vmc_amplitude, then the family's own full forward; read_back brings the fp64 sums down.  The
+// amplitudes a fold compares travel as AmpPair (common.hpp): own_amps, the chains' cache, and row_amps, the rows of the
+// pass (vmc_ctx.hpp).  The device buffers are the grow-only DevBufs of vmc_ctx.hpp.  What differs per measurement is its
+// own checks, which rows kernel and which fold a pass launches, and how the sums are handed out:
 //
 // Spin correlations.  Per pair (i, j): zz = sum_c s_i s_j and ex = sum_c [s_i s_j < 0] psi(swap_ij x_c) / psi(x_c); the
 // host forms <S_i . S_j> = (zz / 4 + ex / 2) / B.  The ratios are the rows the local energies already evaluate: a pass of
@@ -17,9 +24,8 @@
 // Renyi-2 entanglement entropy, the replica swap estimator over the chains taken as the B / 2 pairs (c, c + B / 2).  Per
 // region A: swap_sum = sum over the pairs that hold the same sum of spins on A of psi(x~) psi(y~) / (psi(x) psi(y)), with
 // the spins of A exchanged between the two chains, and match_count = the number of such pairs; the host forms
-// Tr rho_A^2 ~ swap_sum / (B / 2) and S2 = -ln of it.  A pass of regions is B rows per region in the row buffer of
-// vmc_amplitude (renyi.hip: k_swap_rows), evaluated by the family's own full forward (rows_forward_device, vmc_api.hip)
-// and folded per region (k_swap_fold) against the chains' cached ln|psi| and signs.
+// Tr rho_A^2 ~ swap_sum / (B / 2) and S2 = -ln of it.  A pass of regions is B rows per region (renyi.hip: k_swap_rows),
+// folded per region (k_swap_fold) against the chains' cached ln|psi| and signs.
 //
 // Dimer-dimer correlations.  Per bond a = (i, j): bond_sum = sum_c bond(a; x_c); per ordered pair of bonds (a, b):
 // dd_sum = sum_c dd(a, b; x_c), the local value of (S_i . S_j)(S_k . S_l) (dimer.hip states both); the host forms
@@ -32,18 +38,18 @@
 //
 // Symmetry expectation values.  Per op k -- a site permutation perm_k, optionally followed by the global spin flip:
 // ratio_sum = sum_c psi(row_{k,c}) / psi(x_c) with row[i] = f_k x_c[perm_k[i]]; the host forms <P_k> ~ ratio_sum / B.  A
-// pass of ops is B rows per op in the row buffer of vmc_amplitude (symm.hip: k_symm_rows), evaluated by the family's own
-// full forward and folded per op (k_symm_fold) against the chains' cached ln|psi| and signs.  Every perm_k is checked
-// to be a bijection before anything is launched (plan_symm_check_ops): the rows must stay at Sz = 0.
+// pass of ops is B rows per op (symm.hip: k_symm_rows), folded per op (k_symm_fold) against the chains' cached ln|psi|
+// and signs.  Every perm_k is checked to be a bijection before anything is launched (symm_ops_check): the rows must stay
+// at Sz = 0.
 //
-// Symmetry-projected energies.  The ops of the symmetry expectation values and, per sector s, real characters chi[s][k]:
-// w_s(c) = sum_k chi[s][k] psi(row_{k,c}) / psi(x_c), and the host forms E_s = sum_c w_s(c) E_loc(c) / sum_c w_s(c), the
-// energy of P_s psi.  One local-energy call first (it uses the row buffers the passes then take), then the passes of the
-// symmetry expectation values with k_proj_accum (proj.hip) in the fold's place: it adds a pass's ops into the per-chain
-// fp64 accumulator [n_sectors][B]; k_proj_fold folds the chains at the end.  Beside the bijection check every perm_k is
-// checked to map the Hamiltonian's bonds onto themselves, couplings included (plan_symm_check_hamiltonian): the
-// estimator means nothing otherwise.  What a vmc_local_energy call leaves behind (the chains' local energies of `which`,
-// vmc_last_connected_rows) is the one thing this measurement changes.
+// Symmetry-projected energies.  The ops of the symmetry expectation values (symm_ops_check / symm_ops_upload serve both)
+// and, per sector s, real characters chi[s][k]: w_s(c) = sum_k chi[s][k] psi(row_{k,c}) / psi(x_c), and the host forms
+// E_s = sum_c w_s(c) E_loc(c) / sum_c w_s(c), the energy of P_s psi.  One local-energy call first (it uses the row
+// buffers the passes then take), then the passes of the symmetry expectation values with k_proj_accum (proj.hip) in the
+// fold's place: it adds a pass's ops into the per-chain fp64 accumulator [n_sectors][B]; k_proj_fold folds the chains at
+// the end.  Beside the bijection check every perm_k is checked to map the Hamiltonian's bonds onto themselves, couplings
+// included (plan_symm_check_hamiltonian): the estimator means nothing otherwise.  What a vmc_local_energy call leaves
+// behind (the chains' local energies of `which`, vmc_last_connected_rows) is the one thing this measurement changes.
 //
 // Lanczos-step energies.  Per chain e = (H psi)(x) / psi(x) and g = (H^2 psi)(x) / psi(x) (moments.hip states the estimator,
 // the list rules and every summation order).  One local-energy call first; its row list, val and eloc are the first
@@ -51,6 +57,9 @@
 // back, and walked in passes of ROWS (plan_moment_per_pass): k_mom_fill writes the descriptors of the pass alone,
 // k_mom_rows the configurations, the family's full forward evaluates them and k_mom_accum adds coef r into the chains'
 // lanes.  k_mom_chain / k_mom_sums fold at the end.  Like the projected energies it leaves what vmc_local_energy leaves.
+//
+// Overlap with the frozen set.  No rows: one ratio pass and one fold over the two amplitude caches (overlap.hip), shared
+// with the penalised-energy mode of the training entries (overlap_refusals, overlap_sums_device).
 #include "vmc_ctx.hpp"
 
 using namespace vmcapi;
@@ -64,14 +73,26 @@ namespace {
   REFUSE_COMPOSED(c);                                                                    \
   if ((which) != 0 && (which) != 1) return fail((c), VMC_ERR_INVALID, "bad which")
 
-// what was not valid before the measurement is not vouched for after it either: the next consumer fills it exactly as
-// it would have
+// the refusal of every entry that takes the logit for ln psi
+int needs_ln_psi(vmc_ctx* c, const std::string& entry) {
+  if (c->sgn || c->oact == VMC_ACT_EXP_) return VMC_OK;
+  return fail(c, VMC_ERR_UNSUPPORTED, entry + " needs the exp output activation (the logit is ln psi only then)");
+}
+
+// The scope guard of a measurement entry: behind it the entry may return wherever a step fails.  On every way out it
+// first synchronises the stream -- the entry's host buffers are sources and targets of asynchronous copies -- unless
+// read_back has (a call that succeeds synchronises once), then un-vouches: what was not valid before the measurement is
+// not vouched for after it either, the next consumer fills it exactly as it would have.
+// THE RULE: every host buffer that is the source or the target of an asynchronous copy of the entry is declared BEFORE
+// the guard, so that it outlives the guard's synchronisation.
 struct PureMeasurement {
   vmc_ctx* c;
   const bool cache_was[2], acts_were;
+  bool synchronised = false;
   explicit PureMeasurement(vmc_ctx* ctx)
       : c(ctx), cache_was{ctx->ps[0].cache_valid, ctx->ps[1].cache_valid}, acts_were(ctx->acts_valid) {}
   ~PureMeasurement() {
+    if (!synchronised) hipStreamSynchronize(c->stream);
     for (int w = 0; w < 2; ++w) if (!cache_was[w]) c->ps[w].cache_valid = false;
     if (!acts_were) c->acts_valid = false;
   }
@@ -81,30 +102,39 @@ struct PureMeasurement {
 
 template <class T>
 int upload(vmc_ctx* c, T* dst, const std::vector<T>& src) {
-  hipError_t e = hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, c->stream);
-  return e == hipSuccess ? VMC_OK : fail(c, VMC_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+  HIPCHK(c, hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
+  return VMC_OK;
 }
 
-// items [k0, k0 + n) per call of pass(k0, n), `per` at a time, until one fails; rc: the call so far
+// items [k0, k0 + n) per call of pass(k0, n), `per` at a time, until one fails
 template <class Pass>
-int for_passes(long long n_items, int per, int rc, Pass pass) {
-  for (long long k0 = 0; k0 < n_items && rc == VMC_OK; k0 += per)
-    rc = pass(k0, (int)(n_items - k0 < per ? n_items - k0 : per));
-  return rc;
+int for_passes(long long n_items, int per, Pass pass) {
+  for (long long k0 = 0; k0 < n_items; k0 += per) PROPAGATE(pass(k0, (int)(n_items - k0 < per ? n_items - k0 : per)));
+  return VMC_OK;
 }
 
-// the end of every measurement: n sums to the host.  The stream is synchronised on a failed call (rc) too -- the host
-// lists of the entry are the sources of asynchronous copies
-int read_back(vmc_ctx* c, int rc, const char* entry, const double* sums, size_t n, std::vector<double>* out) {
-  hipError_t e = hipSuccess;
-  if (rc == VMC_OK) {
-    out->resize(n);
-    e = hipMemcpyAsync(out->data(), sums, n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+// One pass of rows: rows_kernel() launches the measurement's rows kernel, which writes n_rows configurations into
+// tmp_cfg; the family's own full forward (rows_forward_device, vmc_api.hip) leaves their ln|psi| and signs in logit / sign
+template <class Rows>
+int row_pass(vmc_ctx* c, int which, const char* rows_region, const char* forward_region, long long n_rows, float* logit,
+             float* sign, Rows rows_kernel) {
+  {
+    Timer t(c, rows_region);
+    HIPCHK(c, rows_kernel());
   }
-  const hipError_t e_sync = hipStreamSynchronize(c->stream);
-  if (rc != VMC_OK) return rc;
-  if (e == hipSuccess) e = e_sync;
-  return e == hipSuccess ? VMC_OK : fail(c, VMC_ERR_HIP, std::string(entry) + " read-back: " + hipGetErrorString(e));
+  Timer t(c, forward_region);
+  return rows_forward_device(c, which, c->tmp_cfg, n_rows, logit, sign);
+}
+
+// the last step of every measurement: n sums to the host (out: declared before the guard), and the one synchronisation
+// of a call that succeeds
+int read_back(PureMeasurement& pure, const double* sums, size_t n, std::vector<double>* out) {
+  vmc_ctx* c = pure.c;
+  out->resize(n);
+  HIPCHK(c, hipMemcpyAsync(out->data(), sums, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  pure.synchronised = true;
+  return VMC_OK;
 }
 
 // ---- spin correlations
@@ -123,6 +153,16 @@ void install_set(vmc_ctx* c, const BondSet& s) {
   c->list_valid = false;
   c->cnt_valid = false;
 }
+
+// the set that is current where the guard is made -- the Hamiltonian's -- is installed again on every way out of the scope
+struct HamiltonianSet {
+  vmc_ctx* c;
+  const BondSet set;
+  explicit HamiltonianSet(vmc_ctx* ctx) : c(ctx), set(current_set(ctx)) {}
+  ~HamiltonianSet() { install_set(c, set); }
+  HamiltonianSet(const HamiltonianSet&) = delete;
+  HamiltonianSet& operator=(const HamiltonianSet&) = delete;
+};
 
 // the set of a pass for `per` pairs; hx and qz are (re)filled whenever one of the five grew
 int corr_reserve_pass(vmc_ctx* c, long long per) {
@@ -168,21 +208,14 @@ int renyi_reserve(vmc_ctx* c, long long n_regions) {
 
 // regions [k0, k0 + n): rows, forward, fold
 int renyi_pass(vmc_ctx* c, int which, long long k0, int n, long long n_regions) {
-  const ParamSet& p = c->ps[which];
   const unsigned char* mask = c->renyi.mask + k0 * c->N;
   double* out = c->renyi.out;
-  const long long rows = (long long)n * c->B;
-  {
-    Timer t(c, "renyi_rows");
-    HIPCHK(c, launch_swap_rows(c->stream, c->configs, mask, c->B, c->N, n, c->num_cus, c->tmp_cfg));
-  }
-  {
-    Timer t(c, "renyi_forward");
-    PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, rows, c->tmp_out, c->tmp_sign));
-  }
+  PROPAGATE(row_pass(c, which, "renyi_rows", "renyi_forward", (long long)n * c->B, c->tmp_out, c->tmp_sign, [&] {
+    return launch_swap_rows(c->stream, c->configs, mask, c->B, c->N, n, c->num_cus, c->tmp_cfg);
+  }));
   Timer t(c, "renyi_fold");
-  HIPCHK(c, launch_swap_fold(c->stream, c->configs, mask, p.logit, c->sgn ? p.sign : nullptr, c->tmp_out,
-                             c->sgn ? c->tmp_sign : nullptr, c->B, c->N, n, out + k0, out + n_regions + k0));
+  HIPCHK(c, launch_swap_fold(c->stream, c->configs, mask, own_amps(c, which), row_amps(c), c->B, c->N, n, out + k0,
+                             out + n_regions + k0));
   return VMC_OK;
 }
 
@@ -197,73 +230,76 @@ int dimer_reserve(vmc_ctx* c, long long n_bonds, long long n_pairs) {
   return m.out.reserve(c, n_bonds + n_pairs, "dimer.out");
 }
 
+// phase 1's rows [n_bonds][B]: dimer.sign is allocated on a signed ctx alone, so the sign is null on every other
+AmpPair dimer_single_amps(const vmc_ctx* c) { return AmpPair{c->dimer.logit, c->dimer.sign}; }
+
 // bonds [a0, a0 + n): rows, forward into the [n_bonds][B] buffers
 int dimer_single_pass(vmc_ctx* c, int which, long long a0, int n) {
   const DimerBufs& m = c->dimer;
-  const long long rows = (long long)n * c->B;
-  {
-    Timer t(c, "dimer_rows");
-    HIPCHK(c, launch_dimer_rows1(c->stream, c->configs, m.bonds + a0, c->B, c->N, n, c->num_cus, c->tmp_cfg));
-  }
-  Timer t(c, "dimer_forward");
-  PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, rows, m.logit + a0 * c->B,
-                                c->sgn ? m.sign + a0 * c->B : c->tmp_sign));
-  return VMC_OK;
+  float* sign = c->tmp_sign;                 // (an unsigned ctx keeps no sign per bond: the forward's goes to the scratch rows)
+  if (c->sgn) sign = m.sign + a0 * c->B;
+  return row_pass(c, which, "dimer_rows", "dimer_forward", (long long)n * c->B, m.logit + a0 * c->B, sign, [&] {
+    return launch_dimer_rows1(c->stream, c->configs, m.bonds + a0, c->B, c->N, n, c->num_cus, c->tmp_cfg);
+  });
 }
 
 // pairs [p0, p0 + n): rows, forward, fold
 int dimer_double_pass(vmc_ctx* c, int which, long long p0, int n, double* dd_out) {
-  const ParamSet& p = c->ps[which];
   const DimerBufs& m = c->dimer;
-  const long long rows = (long long)n * c->B;
-  {
-    Timer t(c, "dimer_rows");
-    HIPCHK(c, launch_dimer_rows2(c->stream, c->configs, m.bonds, m.pairs + p0, c->B, c->N, n, c->num_cus, c->tmp_cfg));
-  }
-  {
-    Timer t(c, "dimer_forward");
-    PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, rows, c->tmp_out, c->tmp_sign));
-  }
+  PROPAGATE(row_pass(c, which, "dimer_rows", "dimer_forward", (long long)n * c->B, c->tmp_out, c->tmp_sign, [&] {
+    return launch_dimer_rows2(c->stream, c->configs, m.bonds, m.pairs + p0, c->B, c->N, n, c->num_cus, c->tmp_cfg);
+  }));
   Timer t(c, "dimer_fold");
-  HIPCHK(c, launch_dimer_fold(c->stream, c->configs, m.bonds, m.pairs + p0, p.logit, c->sgn ? p.sign : nullptr,
-                              m.logit, c->sgn ? m.sign : nullptr, c->tmp_out, c->sgn ? c->tmp_sign : nullptr, c->B,
-                              c->N, n, dd_out + p0));
+  HIPCHK(c, launch_dimer_fold(c->stream, c->configs, m.bonds, m.pairs + p0, own_amps(c, which), dimer_single_amps(c),
+                              row_amps(c), c->B, c->N, n, dd_out + p0));
   return VMC_OK;
 }
 
-// ---- symmetry expectation values
+// ---- the ops of the symmetry expectation values and of the symmetry-projected energies (c->symm.perm / flip)
 
-int symm_reserve(vmc_ctx* c, long long n_ops) {
-  PROPAGATE(c->symm.perm.reserve(c, n_ops * c->N, "symm.perm"));
-  PROPAGATE(c->symm.flip.reserve(c, n_ops, "symm.flip"));
-  return c->symm.out.reserve(c, n_ops, "symm.out");
+struct SymmOps {
+  std::vector<int> perm;                 // [n_ops][N]
+  std::vector<unsigned char> flip;       // [n_ops]; a null flip of the caller: zeros
+};
+
+// the checking half: the arguments, every op a bijection with a 0 / 1 flip (plan_symm_check_ops), the host copies
+int symm_ops_check(vmc_ctx* c, int32_t n_ops, const int32_t* perm, const uint8_t* flip, int32_t ops_per_pass, SymmOps* ops) {
+  if (n_ops < 1 || !perm || ops_per_pass < 0) return fail(c, VMC_ERR_INVALID, "bad symmetry op arguments");
+  char msg[160];
+  if (plan_symm_check_ops(c->N, n_ops, perm, flip, msg, sizeof(msg)) != VMC_OK) return fail(c, VMC_ERR_INVALID, msg);
+  ops->perm.assign(perm, perm + (size_t)n_ops * (size_t)c->N);
+  ops->flip.assign((size_t)n_ops, 0);
+  if (flip) ops->flip.assign(flip, flip + n_ops);
+  return VMC_OK;
+}
+
+// the device half: the two buffers and the two uploads (ops: declared before the entry's guard)
+int symm_ops_upload(vmc_ctx* c, const SymmOps& ops) {
+  PROPAGATE(c->symm.perm.reserve(c, (long long)ops.perm.size(), "symm.perm"));
+  PROPAGATE(c->symm.flip.reserve(c, (long long)ops.flip.size(), "symm.flip"));
+  PROPAGATE(upload(c, c->symm.perm.p, ops.perm));
+  return upload(c, c->symm.flip.p, ops.flip);
+}
+
+// the rows and the forward of ops [k0, k0 + n), under the region names of the measurement
+int symm_row_pass(vmc_ctx* c, int which, const char* rows_region, const char* forward_region, long long k0, int n) {
+  const SymmBufs& m = c->symm;
+  return row_pass(c, which, rows_region, forward_region, (long long)n * c->B, c->tmp_out, c->tmp_sign, [&] {
+    return launch_symm_rows(c->stream, c->configs, m.perm + k0 * c->N, m.flip + k0, c->B, c->N, n, c->num_cus, c->tmp_cfg);
+  });
 }
 
 // ops [k0, k0 + n): rows, forward, fold
 int symm_pass(vmc_ctx* c, int which, long long k0, int n) {
-  const ParamSet& p = c->ps[which];
-  const SymmBufs& m = c->symm;
-  const long long rows = (long long)n * c->B;
-  {
-    Timer t(c, "symm_rows");
-    HIPCHK(c, launch_symm_rows(c->stream, c->configs, m.perm + k0 * c->N, m.flip + k0, c->B, c->N, n, c->num_cus,
-                               c->tmp_cfg));
-  }
-  {
-    Timer t(c, "symm_forward");
-    PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, rows, c->tmp_out, c->tmp_sign));
-  }
+  PROPAGATE(symm_row_pass(c, which, "symm_rows", "symm_forward", k0, n));
   Timer t(c, "symm_fold");
-  HIPCHK(c, launch_symm_fold(c->stream, p.logit, c->sgn ? p.sign : nullptr, c->tmp_out, c->sgn ? c->tmp_sign : nullptr,
-                             c->B, n, m.out + k0));
+  HIPCHK(c, launch_symm_fold(c->stream, own_amps(c, which), row_amps(c), c->B, n, c->symm.out + k0));
   return VMC_OK;
 }
 
-// ---- symmetry-projected energies (the ops are the symmetry expectation values': c->symm.perm / flip)
+// ---- symmetry-projected energies
 
 int proj_reserve(vmc_ctx* c, long long n_ops, long long n_sectors) {
-  PROPAGATE(c->symm.perm.reserve(c, n_ops * c->N, "symm.perm"));
-  PROPAGATE(c->symm.flip.reserve(c, n_ops, "symm.flip"));
   PROPAGATE(c->proj.chi.reserve(c, n_sectors * n_ops, "proj.chi"));
   PROPAGATE(c->proj.acc.reserve(c, n_sectors * c->B, "proj.acc"));
   return c->proj.out.reserve(c, 2 * n_sectors + 2, "proj.out");
@@ -271,25 +307,12 @@ int proj_reserve(vmc_ctx* c, long long n_ops, long long n_sectors) {
 
 // ops [k0, k0 + n): rows, forward, then their terms into the per-chain accumulator, PLAN_PROJ_LAUNCH_OPS ops a launch
 int proj_pass(vmc_ctx* c, int which, long long k0, int n, int n_ops, int n_sectors) {
-  const ParamSet& p = c->ps[which];
-  const SymmBufs& m = c->symm;
-  const long long rows = (long long)n * c->B;
-  {
-    Timer t(c, "proj_rows");
-    HIPCHK(c, launch_symm_rows(c->stream, c->configs, m.perm + k0 * c->N, m.flip + k0, c->B, c->N, n, c->num_cus,
-                               c->tmp_cfg));
-  }
-  {
-    Timer t(c, "proj_forward");
-    PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, rows, c->tmp_out, c->tmp_sign));
-  }
+  PROPAGATE(symm_row_pass(c, which, "proj_rows", "proj_forward", k0, n));
   Timer t(c, "proj_accum");
   for (int j0 = 0; j0 < n; j0 += PLAN_PROJ_LAUNCH_OPS) {
     const int nj = n - j0 < PLAN_PROJ_LAUNCH_OPS ? n - j0 : PLAN_PROJ_LAUNCH_OPS;
-    const long long at = (long long)j0 * c->B;
-    HIPCHK(c, launch_proj_accum(c->stream, p.logit, c->sgn ? p.sign : nullptr, c->tmp_out + at,
-                                c->sgn ? c->tmp_sign + at : nullptr, c->proj.chi, c->B, n_sectors, n_ops, (int)k0 + j0, nj,
-                                c->proj.acc));
+    HIPCHK(c, launch_proj_accum(c->stream, own_amps(c, which), row_amps(c, (long long)j0 * c->B), c->proj.chi, c->B,
+                                n_sectors, n_ops, (int)k0 + j0, nj, c->proj.acc));
   }
   return VMC_OK;
 }
@@ -309,28 +332,21 @@ int mom_reserve_list(vmc_ctx* c, long long n1) {
 
 // rows [q0, q0 + n) of the second-order list: descriptors, configurations, forward, into the chains' lanes
 int mom_pass(vmc_ctx* c, int which, long long q0, int n, int n1) {
-  const ParamSet& p = c->ps[which];
   const MomentBufs& m = c->mom;
   {
     Timer t(c, "mom_list");
     HIPCHK(c, launch_mom_fill(c->stream, c->configs, c->bonds, c->half_jx, c->quarter_jz, c->rowinfo, c->off + c->B, n1,
                               m.off2, c->N, c->n_bonds, q0, n, c->num_cus, m.desc, m.coef));
   }
-  {
-    Timer t(c, "mom_rows");
-    HIPCHK(c, launch_mom_rows(c->stream, c->configs, c->bonds, c->rowinfo, m.desc, c->N, n, c->num_cus, c->tmp_cfg));
-  }
-  {
-    Timer t(c, "mom_forward");
-    PROPAGATE(rows_forward_device(c, which, c->tmp_cfg, n, c->tmp_out, c->tmp_sign));
-  }
+  PROPAGATE(row_pass(c, which, "mom_rows", "mom_forward", n, c->tmp_out, c->tmp_sign, [&] {
+    return launch_mom_rows(c->stream, c->configs, c->bonds, c->rowinfo, m.desc, c->N, n, c->num_cus, c->tmp_cfg);
+  }));
   Timer t(c, "mom_fold");
-  HIPCHK(c, launch_mom_accum(c->stream, p.logit, c->sgn ? p.sign : nullptr, c->tmp_out, c->sgn ? c->tmp_sign : nullptr,
-                             m.coef, c->off, m.off2, c->B, q0, n, m.lanes));
+  HIPCHK(c, launch_mom_accum(c->stream, own_amps(c, which), row_amps(c), m.coef, c->off, m.off2, c->B, q0, n, m.lanes));
   return VMC_OK;
 }
 
-// an int the device holds, on the host (the stream is synchronised)
+// an int the device holds, on the host (host: declared before the entry's guard; the stream is synchronised)
 int read_int(vmc_ctx* c, const int* dev, int* host) {
   HIPCHK(c, hipMemcpyAsync(host, dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -345,8 +361,7 @@ namespace vmcapi {
 
 int overlap_refusals(vmc_ctx* c, const char* what) {
   if (c->prod) return fail(c, VMC_ERR_UNSUPPORTED, std::string(what) + " is not available on a product ctx ('prod')");
-  if (!c->sgn && c->oact != VMC_ACT_EXP_)
-    return fail(c, VMC_ERR_UNSUPPORTED, std::string(what) + " needs the exp output activation (the logit is ln psi only then)");
+  PROPAGATE(needs_ln_psi(c, what));
   if (!c->ps[1].has_params)
     return fail(c, VMC_ERR_STATE, std::string(what) + ": the frozen parameters are not set (vmc_set_params(VMC_OMEGA) / vmc_transfer_params)");
   return VMC_OK;
@@ -358,10 +373,9 @@ int overlap_sums_device(vmc_ctx* c) {
   PROPAGATE(m.code.reserve(c, c->B, "ovl.code"));
   PROPAGATE(m.bmax.reserve(c, plan_overlap_blocks(c->B), "ovl.bmax"));
   PROPAGATE(m.out.reserve(c, 4, "ovl.out"));
-  const ParamSet &p = c->ps[0], &w = c->ps[1];
   Timer t(c, "overlap_fold");
-  HIPCHK(c, launch_overlap_ratio(c->stream, p.logit, c->sgn ? p.sign.p : nullptr, (double)p.shift, w.logit,
-                                 c->sgn ? w.sign.p : nullptr, (double)w.shift, c->B, m.d, m.code, m.bmax));
+  HIPCHK(c, launch_overlap_ratio(c->stream, own_amps(c, 0), (double)c->ps[0].shift, own_amps(c, 1), (double)c->ps[1].shift,
+                                 c->B, m.d, m.code, m.bmax));
   HIPCHK(c, launch_overlap_fold(c->stream, m.d, m.code, m.bmax, c->B, m.out));
   return VMC_OK;
 }
@@ -383,22 +397,18 @@ int vmc_pair_correlations(vmc_ctx* c, int which, int32_t n_pairs, const int32_t*
   }
   const int per = plan_measure_per_pass(c->B, n_pairs, pairs_per_pass);
   if (per < 1) return fail(c, VMC_ERR_UNSUPPORTED, "batch_size does not leave room for one pair in the 32-bit row index");
-  PureMeasurement pure(c);
-  int rc = ensure_cache(c, which);           // (before the swap: it reads no bond set; gnn / ed_vector readiness, parameters)
-  if (rc == VMC_OK) rc = corr_reserve(c, per, n_pairs);
-  if (rc == VMC_OK) rc = upload(c, c->corr.pairs.p, pairs);
-  if (rc == VMC_OK) {
-    const CorrBufs& m = c->corr;
-    const BondSet hamiltonian = current_set(c);
-    rc = for_passes(n_pairs, per, rc, [&](long long k0, int n) {
-      install_set(c, BondSet{n, m.pairs + k0, m.hx, m.qz, m.rowinfo, m.val});
-      return corr_pass(c, which, k0, n, n_pairs);
-    });
-    install_set(c, hamiltonian);
-  }
   std::vector<double> out;
-  rc = read_back(c, rc, "vmc_pair_correlations", c->corr.out, 2 * (size_t)n_pairs, &out);
-  if (rc != VMC_OK) return rc;
+  PureMeasurement pure(c);
+  PROPAGATE(ensure_cache(c, which));         // (before the swap: it reads no bond set; gnn / ed_vector readiness, parameters)
+  PROPAGATE(corr_reserve(c, per, n_pairs));
+  PROPAGATE(upload(c, c->corr.pairs.p, pairs));
+  const CorrBufs& m = c->corr;
+  HamiltonianSet hamiltonian(c);
+  PROPAGATE(for_passes(n_pairs, per, [&](long long k0, int n) {
+    install_set(c, BondSet{n, m.pairs + k0, m.hx, m.qz, m.rowinfo, m.val});
+    return corr_pass(c, which, k0, n, n_pairs);
+  }));
+  PROPAGATE(read_back(pure, m.out, 2 * (size_t)n_pairs, &out));
   for (int k = 0; k < n_pairs; ++k) {
     if (zz_sum) zz_sum[k] = out[(size_t)k];
     if (ex_sum) ex_sum[k] = out[(size_t)n_pairs + (size_t)k];
@@ -411,8 +421,7 @@ int vmc_renyi2_swap(vmc_ctx* c, int which, int32_t n_regions, const uint8_t* reg
   MEASURE_GATE(c, which, "vmc_renyi2_swap");
   if (n_regions < 1 || !region_mask || regions_per_pass < 0) return fail(c, VMC_ERR_INVALID, "bad region arguments");
   if (c->B % 2 != 0) return fail(c, VMC_ERR_INVALID, "vmc_renyi2_swap pairs chain c with chain c + batch_size / 2: batch_size must be even");
-  if (!c->sgn && c->oact != VMC_ACT_EXP_)
-    return fail(c, VMC_ERR_UNSUPPORTED, "vmc_renyi2_swap needs the exp output activation (the logit is ln psi only then)");
+  PROPAGATE(needs_ln_psi(c, "vmc_renyi2_swap"));
   std::vector<unsigned char> mask((size_t)n_regions * (size_t)c->N);
   for (size_t k = 0; k < mask.size(); ++k) {
     if (region_mask[k] > 1) return fail(c, VMC_ERR_INVALID, "region mask entries are 0 or 1");
@@ -420,15 +429,14 @@ int vmc_renyi2_swap(vmc_ctx* c, int which, int32_t n_regions, const uint8_t* reg
   }
   const int per = plan_measure_per_pass(c->B, n_regions, regions_per_pass, plan_measure_row_limit(c->N, c->Hp));
   if (per < 1) return fail(c, VMC_ERR_UNSUPPORTED, "batch_size does not leave room for one region in the 32-bit row index");
-  PureMeasurement pure(c);
-  int rc = ensure_cache(c, which);           // l(x), l(y) and their signs, as the local energies take them
-  if (rc == VMC_OK) rc = renyi_reserve(c, n_regions);
-  if (rc == VMC_OK) rc = grow_tmp(c, (long long)per * c->B);
-  if (rc == VMC_OK) rc = upload(c, c->renyi.mask.p, mask);
-  rc = for_passes(n_regions, per, rc, [&](long long k0, int n) { return renyi_pass(c, which, k0, n, n_regions); });
   std::vector<double> out;
-  rc = read_back(c, rc, "vmc_renyi2_swap", c->renyi.out, 2 * (size_t)n_regions, &out);
-  if (rc != VMC_OK) return rc;
+  PureMeasurement pure(c);
+  PROPAGATE(ensure_cache(c, which));         // l(x), l(y) and their signs, as the local energies take them
+  PROPAGATE(renyi_reserve(c, n_regions));
+  PROPAGATE(grow_tmp(c, (long long)per * c->B));
+  PROPAGATE(upload(c, c->renyi.mask.p, mask));
+  PROPAGATE(for_passes(n_regions, per, [&](long long k0, int n) { return renyi_pass(c, which, k0, n, n_regions); }));
+  PROPAGATE(read_back(pure, c->renyi.out, 2 * (size_t)n_regions, &out));
   for (int k = 0; k < n_regions; ++k) {
     if (swap_sum) swap_sum[k] = out[(size_t)k];
     if (match_count) match_count[k] = out[(size_t)n_regions + (size_t)k];
@@ -460,32 +468,28 @@ int vmc_dimer_correlations(vmc_ctx* c, int which, int32_t n_bonds, const int32_t
     }
     hp[(size_t)p] = make_int2(a, b);
   }
-  if (!c->sgn && c->oact != VMC_ACT_EXP_)
-    return fail(c, VMC_ERR_UNSUPPORTED, "vmc_dimer_correlations needs the exp output activation (the logit is ln psi only then)");
+  PROPAGATE(needs_ln_psi(c, "vmc_dimer_correlations"));
   const long long row_limit = plan_measure_row_limit(c->N, c->Hp);
   const int per1 = plan_measure_per_pass(c->B, n_bonds, pairs_per_pass, row_limit);    // (a request splits both phases)
   const int per2 = n_pairs > 0 ? plan_measure_per_pass(c->B, n_pairs, pairs_per_pass, row_limit) : 0;
   if (per1 < 1 || (n_pairs > 0 && per2 < 1) || !plan_measure_rows_ok(c->B, n_bonds))
     return fail(c, VMC_ERR_UNSUPPORTED, "batch_size x bonds does not fit the 32-bit row index");
+  std::vector<double> out;
   PureMeasurement pure(c);
   const DimerBufs& m = c->dimer;
-  int rc = ensure_cache(c, which);           // ln|psi(x_c)| and the signs, as the local energies take them
-  if (rc == VMC_OK) rc = dimer_reserve(c, n_bonds, n_pairs);
-  if (rc == VMC_OK) rc = grow_tmp(c, (long long)(per1 > per2 ? per1 : per2) * c->B);
-  if (rc == VMC_OK) rc = upload(c, m.bonds.p, hb);
-  if (rc == VMC_OK && n_pairs > 0) rc = upload(c, m.pairs.p, hp);
-  rc = for_passes(n_bonds, per1, rc, [&](long long a0, int n) { return dimer_single_pass(c, which, a0, n); });
-  if (rc == VMC_OK) {
-    const ParamSet& p = c->ps[which];
+  PROPAGATE(ensure_cache(c, which));         // ln|psi(x_c)| and the signs, as the local energies take them
+  PROPAGATE(dimer_reserve(c, n_bonds, n_pairs));
+  PROPAGATE(grow_tmp(c, (long long)(per1 > per2 ? per1 : per2) * c->B));
+  PROPAGATE(upload(c, m.bonds.p, hb));
+  if (n_pairs > 0) PROPAGATE(upload(c, m.pairs.p, hp));
+  PROPAGATE(for_passes(n_bonds, per1, [&](long long a0, int n) { return dimer_single_pass(c, which, a0, n); }));
+  {
     Timer t(c, "dimer_fold");
-    hipError_t e = launch_dimer_bond_fold(c->stream, c->configs, m.bonds, p.logit, c->sgn ? p.sign : nullptr, m.logit,
-                                          c->sgn ? m.sign : nullptr, c->B, c->N, n_bonds, m.out);
-    if (e != hipSuccess) rc = fail(c, VMC_ERR_HIP, std::string("k_dimer_bond_fold: ") + hipGetErrorString(e));
+    HIPCHK(c, launch_dimer_bond_fold(c->stream, c->configs, m.bonds, own_amps(c, which), dimer_single_amps(c), c->B, c->N,
+                                     n_bonds, m.out));
   }
-  rc = for_passes(n_pairs, per2, rc, [&](long long p0, int n) { return dimer_double_pass(c, which, p0, n, m.out + n_bonds); });
-  std::vector<double> out;
-  rc = read_back(c, rc, "vmc_dimer_correlations", m.out, (size_t)n_bonds + (size_t)n_pairs, &out);
-  if (rc != VMC_OK) return rc;
+  PROPAGATE(for_passes(n_pairs, per2, [&](long long p0, int n) { return dimer_double_pass(c, which, p0, n, m.out + n_bonds); }));
+  PROPAGATE(read_back(pure, m.out, (size_t)n_bonds + (size_t)n_pairs, &out));
   for (int a = 0; a < n_bonds && bond_sum; ++a) bond_sum[a] = out[(size_t)a];
   for (int p = 0; p < n_pairs && dd_sum; ++p) dd_sum[p] = out[(size_t)n_bonds + (size_t)p];
   return VMC_OK;
@@ -494,26 +498,19 @@ int vmc_dimer_correlations(vmc_ctx* c, int which, int32_t n_bonds, const int32_t
 int vmc_symmetry_expectations(vmc_ctx* c, int which, int32_t n_ops, const int32_t* perm, const uint8_t* flip,
                               int32_t ops_per_pass, double* ratio_sum) {
   MEASURE_GATE(c, which, "vmc_symmetry_expectations");
-  if (n_ops < 1 || !perm || ops_per_pass < 0) return fail(c, VMC_ERR_INVALID, "bad symmetry op arguments");
-  char msg[160];
-  if (plan_symm_check_ops(c->N, n_ops, perm, flip, msg, sizeof(msg)) != VMC_OK) return fail(c, VMC_ERR_INVALID, msg);
-  if (!c->sgn && c->oact != VMC_ACT_EXP_)
-    return fail(c, VMC_ERR_UNSUPPORTED, "vmc_symmetry_expectations needs the exp output activation (the logit is ln psi only then)");
-  const std::vector<int> hperm(perm, perm + (size_t)n_ops * (size_t)c->N);
-  std::vector<unsigned char> hflip((size_t)n_ops, 0);
-  if (flip) hflip.assign(flip, flip + n_ops);
+  SymmOps ops;
+  PROPAGATE(symm_ops_check(c, n_ops, perm, flip, ops_per_pass, &ops));
+  PROPAGATE(needs_ln_psi(c, "vmc_symmetry_expectations"));
   const int per = plan_measure_per_pass(c->B, n_ops, ops_per_pass, plan_measure_row_limit(c->N, c->Hp));
   if (per < 1) return fail(c, VMC_ERR_UNSUPPORTED, "batch_size does not leave room for one op in the 32-bit row index");
-  PureMeasurement pure(c);
-  int rc = ensure_cache(c, which);           // ln|psi(x_c)| and the signs, as the local energies take them
-  if (rc == VMC_OK) rc = symm_reserve(c, n_ops);
-  if (rc == VMC_OK) rc = grow_tmp(c, (long long)per * c->B);
-  if (rc == VMC_OK) rc = upload(c, c->symm.perm.p, hperm);
-  if (rc == VMC_OK) rc = upload(c, c->symm.flip.p, hflip);
-  rc = for_passes(n_ops, per, rc, [&](long long k0, int n) { return symm_pass(c, which, k0, n); });
   std::vector<double> out;
-  rc = read_back(c, rc, "vmc_symmetry_expectations", c->symm.out, (size_t)n_ops, &out);
-  if (rc != VMC_OK) return rc;
+  PureMeasurement pure(c);
+  PROPAGATE(ensure_cache(c, which));         // ln|psi(x_c)| and the signs, as the local energies take them
+  PROPAGATE(symm_ops_upload(c, ops));
+  PROPAGATE(c->symm.out.reserve(c, n_ops, "symm.out"));
+  PROPAGATE(grow_tmp(c, (long long)per * c->B));
+  PROPAGATE(for_passes(n_ops, per, [&](long long k0, int n) { return symm_pass(c, which, k0, n); }));
+  PROPAGATE(read_back(pure, c->symm.out, (size_t)n_ops, &out));
   for (int k = 0; k < n_ops && ratio_sum; ++k) ratio_sum[k] = out[(size_t)k];
   return VMC_OK;
 }
@@ -522,9 +519,9 @@ int vmc_projected_energy(vmc_ctx* c, int which, int32_t n_ops, const int32_t* pe
                          int32_t n_sectors, const double* chi, int32_t ops_per_pass, double* w_sum, double* we_sum,
                          double* e_sum, int64_t* n_alive) {
   MEASURE_GATE(c, which, "vmc_projected_energy");
-  if (n_ops < 1 || !perm || ops_per_pass < 0) return fail(c, VMC_ERR_INVALID, "bad symmetry op arguments");
+  SymmOps ops;
+  PROPAGATE(symm_ops_check(c, n_ops, perm, flip, ops_per_pass, &ops));
   char msg[256];
-  if (plan_symm_check_ops(c->N, n_ops, perm, flip, msg, sizeof(msg)) != VMC_OK) return fail(c, VMC_ERR_INVALID, msg);
   if (n_sectors < 1 || !chi) return fail(c, VMC_ERR_INVALID, "bad sector arguments: n_sectors >= 1 and the characters chi [n_sectors][n_ops] required");
   if (!plan_proj_acc_ok(c->B, n_sectors)) {
     snprintf(msg, sizeof(msg), "n_sectors x batch_size = %lld beyond the accumulator budget of 2^26 doubles", (long long)n_sectors * c->B);
@@ -535,46 +532,35 @@ int vmc_projected_energy(vmc_ctx* c, int which, int32_t n_ops, const int32_t* pe
       snprintf(msg, sizeof(msg), "sector %d: the character of op %d is not finite", (int)(e / (size_t)n_ops), (int)(e % (size_t)n_ops));
       return fail(c, VMC_ERR_INVALID, msg);
     }
-  if (!c->sgn && c->oact != VMC_ACT_EXP_)
-    return fail(c, VMC_ERR_UNSUPPORTED, "vmc_projected_energy needs the exp output activation (the logit is ln psi only then)");
+  PROPAGATE(needs_ln_psi(c, "vmc_projected_energy"));
   const int per = plan_measure_per_pass(c->B, n_ops, ops_per_pass, plan_measure_row_limit(c->N, c->Hp));
   if (per < 1) return fail(c, VMC_ERR_UNSUPPORTED, "batch_size does not leave room for one op in the 32-bit row index");
   if (c->n_bonds <= 0) return fail(c, VMC_ERR_STATE, "bonds not set (vmc_set_bonds)");
   if (plan_symm_check_hamiltonian(c->N, c->n_bonds, c->ham_ij.data(), c->ham_jx.data(), c->ham_jz.data(), n_ops, perm, msg,
                                   sizeof(msg)) != VMC_OK)
     return fail(c, VMC_ERR_INVALID, msg);
-  const std::vector<int> hperm(perm, perm + (size_t)n_ops * (size_t)c->N);
-  std::vector<unsigned char> hflip((size_t)n_ops, 0);
-  if (flip) hflip.assign(flip, flip + n_ops);
   const std::vector<double> hchi(chi, chi + (size_t)n_sectors * (size_t)n_ops);
+  int cnt_total = 0;
+  std::vector<double> out;
   PureMeasurement pure(c);
   ProjBufs& m = c->proj;
-  int rc = ensure_cache(c, which);           // ln|psi(x_c)| and the signs, as the local energies take them
-  if (rc == VMC_OK) {
+  PROPAGATE(ensure_cache(c, which));         // ln|psi(x_c)| and the signs, as the local energies take them
+  {
     Timer t(c, "proj_eloc");                 // first: its rows go through the buffers the passes then take
-    rc = local_energy_device(c, which);
+    PROPAGATE(local_energy_device(c, which));
   }
-  if (rc == VMC_OK) rc = proj_reserve(c, n_ops, n_sectors);
-  if (rc == VMC_OK) rc = grow_tmp(c, (long long)per * c->B);
-  if (rc == VMC_OK) rc = upload(c, c->symm.perm.p, hperm);
-  if (rc == VMC_OK) rc = upload(c, c->symm.flip.p, hflip);
-  if (rc == VMC_OK) rc = upload(c, m.chi.p, hchi);
-  if (rc == VMC_OK) {
-    hipError_t e = hipMemsetAsync(m.acc, 0, (size_t)n_sectors * (size_t)c->B * sizeof(double), c->stream);
-    if (e != hipSuccess) rc = fail(c, VMC_ERR_HIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
-  }
-  rc = for_passes(n_ops, per, rc, [&](long long k0, int n) { return proj_pass(c, which, k0, n, n_ops, n_sectors); });
-  int cnt_total = 0;
-  if (rc == VMC_OK) {
-    const ParamSet& p = c->ps[which];
+  PROPAGATE(symm_ops_upload(c, ops));
+  PROPAGATE(proj_reserve(c, n_ops, n_sectors));
+  PROPAGATE(grow_tmp(c, (long long)per * c->B));
+  PROPAGATE(upload(c, m.chi.p, hchi));
+  HIPCHK(c, hipMemsetAsync(m.acc, 0, (size_t)n_sectors * (size_t)c->B * sizeof(double), c->stream));
+  PROPAGATE(for_passes(n_ops, per, [&](long long k0, int n) { return proj_pass(c, which, k0, n, n_ops, n_sectors); }));
+  {
     Timer t(c, "proj_fold");
-    hipError_t e = launch_proj_fold(c->stream, c->sgn ? p.sign : nullptr, p.eloc, m.acc, c->B, n_sectors, m.out);
-    if (e == hipSuccess) e = hipMemcpyAsync(&cnt_total, c->off + c->B, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-    if (e != hipSuccess) rc = fail(c, VMC_ERR_HIP, std::string("k_proj_fold: ") + hipGetErrorString(e));
+    HIPCHK(c, launch_proj_fold(c->stream, own_amps(c, which).sign, c->ps[which].eloc, m.acc, c->B, n_sectors, m.out));
+    HIPCHK(c, hipMemcpyAsync(&cnt_total, c->off + c->B, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   }
-  std::vector<double> out;
-  rc = read_back(c, rc, "vmc_projected_energy", m.out, 2 * (size_t)n_sectors + 2, &out);
-  if (rc != VMC_OK) return rc;
+  PROPAGATE(read_back(pure, m.out, 2 * (size_t)n_sectors + 2, &out));
   c->last_rows = cnt_total;                  // (as vmc_local_energy leaves it)
   for (int s = 0; s < n_sectors; ++s) {
     if (w_sum) w_sum[s] = out[(size_t)s];
@@ -589,51 +575,45 @@ int vmc_energy_moments(vmc_ctx* c, int which, int64_t rows_per_pass, double sums
                        int64_t* n_rows2) {
   MEASURE_GATE(c, which, "vmc_energy_moments");
   if (rows_per_pass < 0) return fail(c, VMC_ERR_INVALID, "bad rows_per_pass (0: the library decides)");
-  if (!c->sgn && c->oact != VMC_ACT_EXP_)
-    return fail(c, VMC_ERR_UNSUPPORTED, "vmc_energy_moments needs the exp output activation (the logit is ln psi only then)");
+  PROPAGATE(needs_ln_psi(c, "vmc_energy_moments"));
   if (c->n_bonds <= 0) return fail(c, VMC_ERR_STATE, "bonds not set (vmc_set_bonds)");
   if (!plan_moment_index_ok(c->B, c->n_bonds))
     return fail(c, VMC_ERR_UNSUPPORTED, "batch_size x n_bonds^2 does not fit the 32-bit row index of the second-order list");
+  int n1 = 0, n2 = 0;
+  std::vector<double> chain, out;
   PureMeasurement pure(c);
   MomentBufs& m = c->mom;
-  const ParamSet& p = c->ps[which];
-  int rc = ensure_cache(c, which);           // ln|psi(x_c)| and the signs, as the local energies take them
-  if (rc == VMC_OK) {
+  PROPAGATE(ensure_cache(c, which));         // ln|psi(x_c)| and the signs, as the local energies take them
+  {
     Timer t(c, "mom_eloc");                  // first: its rows go through the buffers the passes then take
-    rc = local_energy_device(c, which);
+    PROPAGATE(local_energy_device(c, which));
   }
-  int n1 = 0, n2 = 0;
-  if (rc == VMC_OK) rc = read_int(c, c->off + c->B, &n1);
-  if (rc == VMC_OK) rc = mom_reserve_list(c, n1);
-  if (rc == VMC_OK) {
+  PROPAGATE(read_int(c, c->off + c->B, &n1));
+  PROPAGATE(mom_reserve_list(c, n1));
+  {
     Timer t(c, "mom_list");
-    hipError_t e = launch_mom_count(c->stream, c->configs, c->bonds, c->half_jx, c->quarter_jz, c->rowinfo, c->off + c->B, n1,
-                                    c->N, c->n_bonds, c->num_cus, m.cnt2, m.off2, m.diag1, m.self1);
-    if (e == hipSuccess) e = hipMemsetAsync(m.lanes, 0, 64 * (size_t)c->B * sizeof(double), c->stream);
-    if (e != hipSuccess) rc = fail(c, VMC_ERR_HIP, std::string("k_mom_count: ") + hipGetErrorString(e));
+    HIPCHK(c, launch_mom_count(c->stream, c->configs, c->bonds, c->half_jx, c->quarter_jz, c->rowinfo, c->off + c->B, n1,
+                               c->N, c->n_bonds, c->num_cus, m.cnt2, m.off2, m.diag1, m.self1));
+    HIPCHK(c, hipMemsetAsync(m.lanes, 0, 64 * (size_t)c->B * sizeof(double), c->stream));
   }
-  if (rc == VMC_OK) rc = read_int(c, m.off2 + n1, &n2);
+  PROPAGATE(read_int(c, m.off2 + n1, &n2));
   const long long per = plan_moment_per_pass(n2, rows_per_pass, plan_measure_row_limit(c->N, c->Hp));
-  if (rc == VMC_OK && per < 1) rc = fail(c, VMC_ERR_HIP, "the second-order list has a negative length");
-  if (rc == VMC_OK) rc = m.desc.reserve(c, per, "mom.desc");
-  if (rc == VMC_OK) rc = m.coef.reserve(c, per, "mom.coef");
-  if (rc == VMC_OK) rc = grow_tmp(c, per);
-  rc = for_passes(n2, (int)per, rc, [&](long long q0, int n) { return mom_pass(c, which, q0, n, n1); });
-  std::vector<double> chain;
-  if (rc == VMC_OK) {
+  if (per < 1) return fail(c, VMC_ERR_HIP, "the second-order list has a negative length");
+  PROPAGATE(m.desc.reserve(c, per, "mom.desc"));
+  PROPAGATE(m.coef.reserve(c, per, "mom.coef"));
+  PROPAGATE(grow_tmp(c, per));
+  PROPAGATE(for_passes(n2, (int)per, [&](long long q0, int n) { return mom_pass(c, which, q0, n, n1); }));
+  {
     Timer t(c, "mom_fold");
-    hipError_t e = launch_mom_fold(c->stream, c->configs, c->bonds, c->half_jx, c->quarter_jz, c->rowinfo, c->off, c->val,
-                                   p.eloc, c->sgn ? p.sign : nullptr, m.diag1, m.self1, m.lanes, c->B, c->N, c->n_bonds,
-                                   m.chain, m.out);
-    if (e == hipSuccess && (e_loc || h2_loc)) {
+    HIPCHK(c, launch_mom_fold(c->stream, c->configs, c->bonds, c->half_jx, c->quarter_jz, c->rowinfo, c->off, c->val,
+                              c->ps[which].eloc, own_amps(c, which).sign, m.diag1, m.self1, m.lanes, c->B, c->N, c->n_bonds,
+                              m.chain, m.out));
+    if (e_loc || h2_loc) {
       chain.resize(2 * (size_t)c->B);
-      e = hipMemcpyAsync(chain.data(), m.chain, chain.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+      HIPCHK(c, hipMemcpyAsync(chain.data(), m.chain, chain.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
-    if (e != hipSuccess) rc = fail(c, VMC_ERR_HIP, std::string("k_mom_chain: ") + hipGetErrorString(e));
   }
-  std::vector<double> out;
-  rc = read_back(c, rc, "vmc_energy_moments", m.out, 6, &out);
-  if (rc != VMC_OK) return rc;
+  PROPAGATE(read_back(pure, m.out, 6, &out));
   c->last_rows = n1;                         // (as vmc_local_energy leaves it)
   for (int k = 0; k < 6 && sums; ++k) sums[k] = out[(size_t)k];
   for (int k = 0; k < c->B && e_loc; ++k) e_loc[k] = chain[(size_t)k];
@@ -645,25 +625,19 @@ int vmc_energy_moments(vmc_ctx* c, int which, int64_t rows_per_pass, double sums
 int vmc_overlap(vmc_ctx* c, double sums[4], double* ratio) {
   MEASURE_GATE(c, 0, "vmc_overlap");
   PROPAGATE(overlap_refusals(c, "vmc_overlap"));
+  std::vector<double> chain, out;
   PureMeasurement pure(c);
   OverlapBufs& m = c->ovl;
-  int rc = ensure_cache(c, VMC_OMEGA);
-  if (rc == VMC_OK) rc = ensure_cache(c, VMC_PSI);
-  if (rc == VMC_OK) rc = overlap_sums_device(c);
-  std::vector<double> chain;
-  if (rc == VMC_OK && ratio) {
-    rc = m.ratio.reserve(c, c->B, "ovl.ratio");
-    if (rc == VMC_OK) {
-      chain.resize((size_t)c->B);
-      hipError_t e = launch_overlap_weights(c->stream, m.d, m.code, m.out, nullptr, 0.f, c->B, nullptr, m.ratio);
-      if (e == hipSuccess)
-        e = hipMemcpyAsync(chain.data(), m.ratio, chain.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-      if (e != hipSuccess) rc = fail(c, VMC_ERR_HIP, std::string("k_overlap_weights: ") + hipGetErrorString(e));
-    }
+  PROPAGATE(ensure_cache(c, VMC_OMEGA));
+  PROPAGATE(ensure_cache(c, VMC_PSI));
+  PROPAGATE(overlap_sums_device(c));
+  if (ratio) {
+    PROPAGATE(m.ratio.reserve(c, c->B, "ovl.ratio"));
+    chain.resize((size_t)c->B);
+    HIPCHK(c, launch_overlap_weights(c->stream, m.d, m.code, m.out, nullptr, 0.f, c->B, nullptr, m.ratio));
+    HIPCHK(c, hipMemcpyAsync(chain.data(), m.ratio, chain.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   }
-  std::vector<double> out;
-  rc = read_back(c, rc, "vmc_overlap", m.out, 4, &out);
-  if (rc != VMC_OK) return rc;
+  PROPAGATE(read_back(pure, m.out, 4, &out));
   for (int k = 0; k < 4 && sums; ++k) sums[k] = out[(size_t)k];
   for (int k = 0; k < c->B && ratio; ++k) ratio[k] = chain[(size_t)k];
   return VMC_OK;

@@ -565,6 +565,16 @@ inline void sampler_returned(vmc_ctx* c, bool psi_cache, bool census_stays) {
   if (!census_stays) c->cnt_valid = false;
 }
 
+// The two amplitude pairs of the measurements' folds, the one place that asks whether the ctx holds signs.  own_amps: the
+// chains' cache of ps[which] (ensure_cache has run); row_amps: the rows of vmc_amplitude's buffers from row `at` on
+inline AmpPair own_amps(const vmc_ctx* c, int which) {
+  const ParamSet& p = c->ps[which];
+  return AmpPair{p.logit, c->sgn ? p.sign.p : nullptr};
+}
+inline AmpPair row_amps(const vmc_ctx* c, long long at = 0) {
+  return AmpPair{c->tmp_out + at, c->sgn ? c->tmp_sign + at : nullptr};
+}
+
 inline long long off_w(const vmc_ctx* c, int l) { return plan_off_w(c->lay, c->H, l); }   // weight matrix of layer l (0 = first)
 inline long long off_b(const vmc_ctx* c, int l) { return plan_off_b(c->lay, c->H, l); }   // biases sit right behind their weights
 inline long long off_wout(const vmc_ctx* c) { return c->lay.off_wout; }
