@@ -537,6 +537,23 @@ hipError_t launch_sr_row_linear(hipStream_t s, const float* x, long long ldx, co
                                 long long pstride);
 hipError_t launch_sr_colsum(hipStream_t s, const float* x, long long ldx, const float* t, int R,
                             int K, float* ws, int slices, float* u, float* tsum);
+// the sample-space solve (srgram.hip).  T [n][n] = sum over the terms of (A A^T + 1) (.) (D D^T); a term without D
+// (the output / onsite layer, last) adds A A^T + 1.  A and D are row panels of the sample store, K contiguous
+struct SrGramArgs {
+  const float* a[SRG_MAX_TERMS]; const float* d[SRG_MAX_TERMS];
+  long long lda[SRG_MAX_TERMS], ldd[SRG_MAX_TERMS];
+  int ka[SRG_MAX_TERMS], kd[SRG_MAX_TERMS];
+  int n_terms, n, nt;                 // nt: tiles per side (plan_sr_gram)
+  float* T;
+};
+hipError_t launch_sr_gram(hipStream_t s, const SrGramArgs& g, long long grid);
+// w = T v; sc: the solve's scalars (an iteration behind the stop does nothing) or null
+hipError_t launch_sr_gram_matvec(hipStream_t s, const float* T, const float* v, int n, const double* sc, float* w);
+hipError_t launch_srg_rhs(hipStream_t s, const float* e, int n, float tol, float* y, float* r, float* p, float* pc,
+                          double* sc);
+hipError_t launch_srg_step(hipStream_t s, const float* w, int n, float nlambda, float tol, float* q, float* y, float* r,
+                           float* p, float* pc, double* sc);
+hipError_t launch_srg_centre(hipStream_t s, const float* y, int n, float* t);
 
 // fully_connected with fc_layer_size > 256: the general path through materialised rows (wide.hip)
 hipError_t launch_wide_rows_act(hipStream_t s, const float* z1, const float* w1p, const int2* rowinfo,

@@ -1177,3 +1177,44 @@ inline int plan_sr_wsum_slices(int R, int num_cus) {
   if (s > num_cus) s = num_cus;
   return s < 1 ? 1 : s;
 }
+
+// Sample-space solve (srgram.hip): T = O O^T of the n stored samples in SRG_TILE x SRG_TILE tiles, one workgroup of eight
+// waves per tile, only the tiles (i, j) with j >= i (the tile is mirrored from the same registers).  The workgroups
+// form a linear grid over the upper triangle row by row: row i holds the nt - i tiles (i, i) .. (i, nt - 1).  A
+// workgroup stages the row panels of both tile sides through LDS in chunks of SRG_KC columns, rows SRG_LD floats apart
+// (16-byte aligned rows for the four-float fragment reads).
+#define SRG_TILE 128
+#define SRG_KC 32
+#define SRG_LD (SRG_KC + 4)
+#define SRG_MAX_N 16384     // T is n^2 floats: 1 GiB here; beyond, the parameter-space solver (vmc_sr_solve)
+#define SRG_MAX_TERMS 32    // layer terms of one launch (kernel argument table)
+
+struct SrGramPlan {
+  int nt;                   // tiles per side
+  long long grid;           // workgroups: nt (nt + 1) / 2
+  size_t lds_bytes;         // per workgroup: the two row panels of a chunk
+};
+
+PLAN_HD inline size_t plan_sr_gram_lds_bytes() { return (size_t)2 * SRG_TILE * SRG_LD * sizeof(float); }
+
+// VMC_OK and the plan, or the refusal (n < 1; n > SRG_MAX_N) with its text
+inline int plan_sr_gram(long long n, SrGramPlan* p, char* msg, size_t msg_len) {
+  if (n < 1) { snprintf(msg, msg_len, "no stored samples"); return VMC_ERR_STATE; }
+  if (n > SRG_MAX_N) {
+    snprintf(msg, msg_len, "the sample-space solve holds the n x n Gram matrix of the stored samples: n = %lld > %d "
+                           "(use the parameter-space solver, vmc_sr_solve)", n, SRG_MAX_N);
+    return VMC_ERR_UNSUPPORTED;
+  }
+  p->nt = (int)((n + SRG_TILE - 1) / SRG_TILE);
+  p->grid = (long long)p->nt * (p->nt + 1) / 2;
+  p->lds_bytes = plan_sr_gram_lds_bytes();
+  if (p->lds_bytes > PLAN_LDS_PER_CU) { snprintf(msg, msg_len, "Gram tile panels exceed the LDS of a CU"); return VMC_ERR_UNSUPPORTED; }
+  return VMC_OK;
+}
+
+// workgroup idx of the linear grid -> its tile (i, j), j >= i
+PLAN_HD inline void plan_sr_gram_tile(long long idx, int nt, int* i, int* j) {
+  int r = 0;
+  while (idx >= nt - r) { idx -= nt - r; ++r; }
+  *i = r; *j = r + (int)idx;
+}

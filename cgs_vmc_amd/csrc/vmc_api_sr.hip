@@ -35,7 +35,7 @@ int vmc_sr_reserve(vmc_ctx* c, int32_t n_batches) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->sr_cap = 0; c->sr_n = 0; c->sr_begun = false;      // (sr_cap stays 0 until everything below is there)
   for (DevBuf<float>* q : {&c->sr_cfg, &c->sr_act, &c->sr_delta, &c->sr_ws, &c->sr_t, &c->sr_ones, &c->sr_ctape, &c->sr_cdelta,
-                           &c->sr_cws, &c->sr_tpart}) q->release();
+                           &c->sr_cws, &c->sr_tpart, &c->sr_eloc, &c->sr_gram, &c->sr_gvec}) q->release();
   if (n_batches == 0) return VMC_OK;
   const long long B = c->B, N = c->N, Hp = c->Hp, L = c->A, R = (long long)n_batches * B;
   switch (c->path) {
@@ -71,6 +71,7 @@ int vmc_sr_reserve(vmc_ctx* c, int32_t n_batches) {
     HIPCHK(c, launch_fill(c->stream, c->sr_ones, 1.f, R));
     break;
   }
+  PROPAGATE(c->sr_eloc.alloc(c, R, "sr_eloc"));
   PROPAGATE(sr_cg_vectors(c));
   c->sr_cap = n_batches;
   return VMC_OK;
@@ -99,6 +100,37 @@ int vmc_sr_begin(vmc_ctx* c, double* rr0) {
   HIPCHK(c, launch_sr_rhs(c->stream, c->acc, (int)c->P, c->sr_x, c->sr_r, c->sr_p, c->sr_partial, c->sr_sc));
   c->sr_iter = 0; c->sr_begun = true;
   return sr_read_rr(c, 0, rr0);
+}
+
+// u[0 .. P) = sum_b t_b O_b over the stored samples of the dense store, u[P] = sum_b t_b, for any per-sample weights t
+// (device, [rows]): the second half of the parameter-space matvec, and the last step of the sample-space solve
+static int sr_weighted_sum(vmc_ctx* c, const float* t) {
+  const int B = c->B, N = c->N, H = c->H, Hp = c->Hp, L = c->A;
+  const long long R = (long long)c->sr_cap * B;   // row stride between layers of the store
+  const int rows = c->sr_n * B;
+  // per layer [a_{l-1} | 1]^T (t (.) delta_l), written in the theta layout, in
+  // (<= 256 input rows) x (<= 256 output units) blocks; the bias row comes with the first row block
+  const int slices = sr_wsum_slices(rows, c->num_cus);
+  for (int l = 0; l < L; ++l) {
+    const float* a_in = l == 0 ? c->sr_cfg : c->sr_act + (long long)(l - 1) * R * Hp;
+    const int M = l == 0 ? N : H;
+    for (int m0 = 0; m0 < M; m0 += 256)
+      for (int n0 = 0; n0 < H; n0 += 256) {
+        const int mb = M - m0 < 256 ? M - m0 : 256, nb = H - n0 < 256 ? H - n0 : 256;
+        HIPCHK(c, launch_sr_wsum(c->stream, a_in + m0, l == 0 ? N : Hp, c->sr_delta + (long long)l * R * Hp + n0, Hp,
+                                 t, c->sr_ws, c->sr_u + off_w(c, l) + (long long)m0 * H + n0, H,
+                                 m0 == 0 ? c->sr_u + off_b(c, l) + n0 : nullptr, mb, nb, rows, slices));
+      }
+  }
+  // the N = 1 layer (w_out, b_out of fully_connected; w_on, b_on of rbm: weights then bias in
+  // theta) and sum_b t_b in one column-sum pass
+  if (c->rbm)
+    HIPCHK(c, launch_sr_colsum(c->stream, c->sr_cfg, N, t, rows, N, c->sr_ws, slices,
+                               c->sr_u + c->lay.off_won, c->sr_u + c->P));
+  else
+    HIPCHK(c, launch_sr_colsum(c->stream, c->sr_act + (long long)(L - 1) * R * Hp, Hp, t, rows, H,
+                               c->sr_ws, slices, c->sr_u + off_wout(c), c->sr_u + c->P));
+  return VMC_OK;
 }
 
 // u[0..P) = sum over this rank's stored samples of (O_b . p) O_b,  u[P] = sum (O_b . p): the body of
@@ -168,29 +200,7 @@ static int sr_matvec(vmc_ctx* c) {
       HIPCHK(c, launch_sr_row_linear(c->stream, c->sr_act + (long long)(L - 1) * R * Hp, Hp, v + off_wout(c),
                                      v + off_bout(c), rows, H, c->sr_t, c->sr_tpart, np, R));
   }
-  // u = sum_b t_b O_b: per layer [a_{l-1} | 1]^T (t (.) delta_l), written in the theta layout, in
-  // (<= 256 input rows) x (<= 256 output units) blocks; the bias row comes with the first row block
-  const int slices = sr_wsum_slices(rows, c->num_cus);
-  for (int l = 0; l < L; ++l) {
-    const float* a_in = l == 0 ? c->sr_cfg : c->sr_act + (long long)(l - 1) * R * Hp;
-    const int M = l == 0 ? N : H;
-    for (int m0 = 0; m0 < M; m0 += 256)
-      for (int n0 = 0; n0 < H; n0 += 256) {
-        const int mb = M - m0 < 256 ? M - m0 : 256, nb = H - n0 < 256 ? H - n0 : 256;
-        HIPCHK(c, launch_sr_wsum(c->stream, a_in + m0, l == 0 ? N : Hp, c->sr_delta + (long long)l * R * Hp + n0, Hp,
-                                 c->sr_t, c->sr_ws, c->sr_u + off_w(c, l) + (long long)m0 * H + n0, H,
-                                 m0 == 0 ? c->sr_u + off_b(c, l) + n0 : nullptr, mb, nb, rows, slices));
-      }
-  }
-  // the N = 1 layer (w_out, b_out of fully_connected; w_on, b_on of rbm: weights then bias in
-  // theta) and sum_b t_b in one column-sum pass
-  if (c->rbm)
-    HIPCHK(c, launch_sr_colsum(c->stream, c->sr_cfg, N, c->sr_t, rows, N, c->sr_ws, slices,
-                               c->sr_u + c->lay.off_won, c->sr_u + c->P));
-  else
-    HIPCHK(c, launch_sr_colsum(c->stream, c->sr_act + (long long)(L - 1) * R * Hp, Hp, c->sr_t, rows, H,
-                               c->sr_ws, slices, c->sr_u + off_wout(c), c->sr_u + c->P));
-  return VMC_OK;
+  return sr_weighted_sum(c, c->sr_t);
 }
 
 int vmc_sr_matvec_partial(vmc_ctx* c) {
@@ -318,6 +328,112 @@ int vmc_sr_solve_dist(vmc_ctx* c, void* nccl_comm, int32_t world_size, float dia
                       int32_t max_iter, int32_t* iters, double* rel_residual) {
   ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_solve_dist)");
   return sr_solve_impl(c, nccl_comm, world_size, diag_shift, tol, max_iter, iters, rel_residual);
+}
+
+// ------------------------------------------------------------------ the sample-space solve (srgram.hip)
+// What vmc_sr_solve_samples and vmc_sr_debug_gram refuse, before anything is launched; *plan: the Gram launch of the
+// stored samples
+static int sr_gram_refusals(vmc_ctx* c, SrGramPlan* plan) {
+  if (c->sr_cap <= 0) return fail(c, VMC_ERR_STATE, "vmc_sr_reserve first");
+  if (c->sr_n <= 0) return fail(c, VMC_ERR_STATE, "no samples recorded (vmc_accumulate in ENERGY_GRADIENT mode)");
+  switch (c->path) {
+    case PATH_CONV: case PATH_CONV_GENERAL:
+      return fail(c, VMC_ERR_UNSUPPORTED, "the sample-space solve covers the dense sample store (fully_connected, rbm): the store of a "
+                                          "convolutional type has no per-layer Gram form here (use the parameter-space solver, vmc_sr_solve)");
+    case PATH_PBDG: case PATH_NNB: case PATH_EDVEC: case PATH_PRODUCT:     // (vmc_sr_reserve gives them no store)
+      return fail(c, VMC_ERR_STATE, "vmc_sr_reserve first");
+    case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP: break;
+  }
+  if (c->A + 1 > SRG_MAX_TERMS) return fail(c, VMC_ERR_UNSUPPORTED, "the sample-space solve takes at most 31 layers (use vmc_sr_solve)");
+  char msg[256];
+  const int rc = plan_sr_gram((long long)c->sr_n * c->B, plan, msg, sizeof(msg));
+  return rc == VMC_OK ? VMC_OK : fail(c, rc, msg);
+}
+
+// T = O O^T of the stored samples into sr_gram: per layer (a_{l-1} a_{l-1}^T + 1) (.) (delta_l delta_l^T), layers in
+// ascending order, then the output (fully_connected: a_L) / onsite (rbm: the configuration) term
+static int sr_gram(vmc_ctx* c, const SrGramPlan& plan) {
+  const int B = c->B, N = c->N, H = c->H, Hp = c->Hp, L = c->A;
+  const long long R = (long long)c->sr_cap * B;   // row stride between layers of the store
+  const long long n = (long long)c->sr_n * B;
+  PROPAGATE(c->sr_gram.reserve(c, n * n, "sr_gram"));
+  Timer t(c, "sr_gram");
+  SrGramArgs g;
+  memset((void*)&g, 0, sizeof(g));
+  for (int l = 0; l < L; ++l) {
+    g.a[l] = l == 0 ? c->sr_cfg.p : c->sr_act + (long long)(l - 1) * R * Hp;
+    g.lda[l] = l == 0 ? N : Hp; g.ka[l] = l == 0 ? N : H;
+    g.d[l] = c->sr_delta + (long long)l * R * Hp; g.ldd[l] = Hp; g.kd[l] = H;
+  }
+  g.a[L] = c->rbm ? c->sr_cfg.p : c->sr_act + (long long)(L - 1) * R * Hp;
+  g.lda[L] = c->rbm ? N : Hp; g.ka[L] = c->rbm ? N : H;
+  g.n_terms = L + 1; g.n = (int)n; g.nt = plan.nt; g.T = c->sr_gram;
+  HIPCHK(c, launch_sr_gram(c->stream, g, plan.grid));
+  return VMC_OK;
+}
+
+int vmc_sr_solve_samples(vmc_ctx* c, float diag_shift, float tol, int32_t max_iter, int32_t* iters, double* rel_residual) {
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_solve_samples)");
+  if (!(diag_shift > 0.f) || !std::isfinite(diag_shift))
+    return fail(c, VMC_ERR_INVALID, "the sample-space solve needs a finite diag_shift > 0 (the centred Gram matrix alone is singular)");
+  if (max_iter < 0 || !(tol >= 0.f)) return fail(c, VMC_ERR_INVALID, "bad CG arguments (tol < 0 or max_iter < 0)");
+  SrGramPlan plan;
+  PROPAGATE(sr_gram_refusals(c, &plan));
+  const int n = c->sr_n * c->B;
+  PROPAGATE(c->sr_gvec.reserve(c, 6LL * n, "sr_gvec"));
+  PROPAGATE(c->sr_gsc.reserve(c, 4, "sr_gsc"));
+  PROPAGATE(sr_gram(c, plan));
+  float *y = c->sr_gvec, *r = y + n, *p = r + n, *pc = p + n, *w = pc + n, *q = w + n;
+  double sc[4] = {0.0, 0.0, 0.0, 1.0};
+  {
+    Timer t(c, "sr_gram_cg");
+    HIPCHK(c, launch_srg_rhs(c->stream, c->sr_eloc, n, tol, y, r, p, pc, c->sr_gsc));
+    // iterations in groups of 8 between two reads of the scalars: one behind the stop does nothing, so the count and
+    // the solution do not depend on the grouping
+    for (int it = 0; it < max_iter;) {
+      const int group = max_iter - it < 8 ? max_iter - it : 8;
+      for (int k = 0; k < group; ++k) {
+        {
+          Timer tm(c, "sr_gram_matvec");
+          HIPCHK(c, launch_sr_gram_matvec(c->stream, c->sr_gram, pc, n, c->sr_gsc, w));
+        }
+        HIPCHK(c, launch_srg_step(c->stream, w, n, (float)n * diag_shift, tol, q, y, r, p, pc, c->sr_gsc));
+      }
+      it += group;
+      HIPCHK(c, hipMemcpyAsync(sc, c->sr_gsc, sizeof(sc), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      if (sc[3] != 0.0) break;
+    }
+    if (max_iter == 0) {
+      HIPCHK(c, hipMemcpyAsync(sc, c->sr_gsc, sizeof(sc), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+  }
+  // x = sum_b t_b O_b with t = y - ybar, into sr_x
+  HIPCHK(c, launch_srg_centre(c->stream, y, n, c->sr_t));
+  HIPCHK(c, hipMemsetAsync(c->sr_u, 0, (c->P + 1) * sizeof(float), c->stream));
+  {
+    Timer t(c, "sr_gram_wsum");
+    PROPAGATE(sr_weighted_sum(c, c->sr_t));
+  }
+  HIPCHK(c, hipMemcpyAsync(c->sr_x, c->sr_u, c->P * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  c->sr_begun = true;      // vmc_sr_apply may follow
+  if (iters) *iters = (int32_t)sc[2];
+  if (rel_residual) *rel_residual = sc[1] > 0.0 ? sqrt(sc[0] / sc[1]) : 0.0;
+  return VMC_OK;
+}
+
+int vmc_sr_debug_gram(vmc_ctx* c, float* T_host, int32_t* n_out) {
+  ENTER(c); REFUSE_COMPOSED(c); REFUSE_PRODUCT(c, "stochastic reconfiguration (vmc_sr_debug_gram)");
+  SrGramPlan plan;
+  PROPAGATE(sr_gram_refusals(c, &plan));
+  const long long n = (long long)c->sr_n * c->B;
+  if (n_out) *n_out = (int32_t)n;
+  if (!T_host) return VMC_OK;              // (the size alone)
+  PROPAGATE(sr_gram(c, plan));
+  HIPCHK(c, hipMemcpyAsync(T_host, c->sr_gram, n * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VMC_OK;
 }
 
 int vmc_sr_get_solution(vmc_ctx* c, float* x) {

@@ -194,6 +194,9 @@ static int sr_record(vmc_ctx* c) {
     return fail(c, VMC_ERR_STATE, "SR sample store full: vmc_sr_reserve fewer batches than accumulate calls");
   const long long B = c->B, N = c->N, Hp = c->Hp, L = c->A, k = c->sr_n, R = (long long)c->sr_cap * B;
   HIPCHK(c, hipMemcpyAsync(c->sr_cfg + k * B * N, c->configs, B * N * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  // the batch's local energies (the right-hand side of the sample-space solve): final here on every path -- where the
+  // back-propagation launch folds them (fold_eloc), that launch is already ahead on this stream
+  HIPCHK(c, hipMemcpyAsync(c->sr_eloc + k * B, c->ps[0].eloc, B * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   switch (c->path) {
   case PATH_CONV_GENERAL: break;     // (its matvec re-derives everything from the chains)
   case PATH_CONV: {   // the taped inputs of every convolution and d logit / d (their outputs) of this batch

@@ -676,6 +676,24 @@ class VmcEngine:
                                        C.byref(it), C.byref(res)))
     return int(it.value), float(res.value)
 
+  def sr_solve_samples(self, diag_shift: float, tol: float, max_iter: int) -> Tuple[int, float]:
+    """The solution of sr_solve from the sample space (MinSR): CG on the centred n x n Gram matrix of the stored samples
+    + n diag_shift I, whose iterations do not depend on the number of parameters -> (iterations, |r|/|eps|).  One rank;
+    fully_connected and rbm; at most 16,384 stored samples.  sr_get_solution / sr_apply follow as after sr_solve."""
+    it = C.c_int32()
+    res = C.c_double()
+    self._check(self._lib.vmc_sr_solve_samples(self._ctx, float(diag_shift), float(tol), int(max_iter),
+                                               C.byref(it), C.byref(res)))
+    return int(it.value), float(res.value)
+
+  def sr_debug_gram(self) -> np.ndarray:
+    """Test hook: the uncentred Gram matrix T = O O^T [n][n] of the stored samples."""
+    n = C.c_int32()
+    self._check(self._lib.vmc_sr_debug_gram(self._ctx, None, C.byref(n)))
+    out = np.empty((n.value, n.value), np.float32)
+    self._check(self._lib.vmc_sr_debug_gram(self._ctx, _fptr(out), C.byref(n)))
+    return out
+
   def sr_get_solution(self) -> np.ndarray:
     x = np.empty(self.num_params, np.float32)
     self._check(self._lib.vmc_sr_get_solution(self._ctx, _fptr(x)))

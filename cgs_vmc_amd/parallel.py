@@ -395,13 +395,26 @@ def rccl_collective(device: int, world: int = None, rank_: int = None) -> Collec
   return Collective(comm.value, world, device=device)
 
 
-def sr_solve(engine, diag_shift: float, tol: float, max_iter: int):
+SR_SOLVERS = ('parameters', 'samples')
+
+
+def sr_solve(engine, diag_shift: float, tol: float, max_iter: int, solver: str = 'parameters'):
   """Matrix-free CG for (S + diag_shift I) x = f with the chains (and therefore the stored
   samples) sharded over ranks: one P+1-float SUM all-reduce per iteration; every rank runs the
   identical recurrence on the reduced vectors.  Returns (iterations, |r| / |f|).  The
   accumulators must already be all-reduced (vmc_sr_begin reads f and <O> from them).
   Engines with the device-resident entry (vmc_sr_solve_dist) run the whole loop in one call, the
-  all-reduce in stream; the op-by-op loop below remains for engines without it."""
+  all-reduce in stream; the op-by-op loop below remains for engines without it.
+  solver='samples': the same update from the n x n Gram matrix of the stored samples (engine.sr_solve_samples), whose
+  iterations do not depend on the number of parameters; one rank only -- the Gram matrix of sharded samples needs an
+  all-gather of the store."""
+  if solver not in SR_SOLVERS:
+    raise ValueError('sr_solve: solver must be one of {}, got {!r}'.format(SR_SOLVERS, solver))
+  if solver == 'samples':
+    if world_size() > 1:
+      raise NotImplementedError('sr_solve(solver=\'samples\') runs on one rank: the Gram matrix of samples sharded over '
+                                '{} ranks needs an all-gather of the sample store (use solver=\'parameters\')'.format(world_size()))
+    return engine.sr_solve_samples(diag_shift, tol, max_iter)
   if world_size() == 1:
     return engine.sr_solve(diag_shift, tol, max_iter)
   if hasattr(engine, 'sr_solve_dist') and os.environ.get('CGS_VMC_DIST_FUSED', '1') != '0':

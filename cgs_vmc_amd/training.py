@@ -265,16 +265,19 @@ class StochasticReconfigurationOptimizer(EnergyGradientOptimizer):
   conjugate gradients on the GPU (csrc/sr.hip; one P-vector all-reduce per iteration when the
   chains are sharded) and steps theta -= learning_rate x.  hparams: sr_diag_shift,
   sr_cg_tolerance, sr_cg_max_iterations (defaults 0.01, 1e-3, 100) and the usual
-  learning_rates schedule (SR wants a larger rate than Adam, e.g. 0.05)."""
+  learning_rates schedule (SR wants a larger rate than Adam, e.g. 0.05).  hparams.sr_solver, or the environment's
+  CGS_VMC_SR_SOLVER, picks the solver: 'parameters' (the default, above) or 'samples' -- the same update from the
+  n x n Gram matrix of the stored samples (csrc/srgram.hip; one rank, fully_connected and rbm)."""
 
   def _apply_fn(self, hparams):
     shift = float(getattr(hparams, 'sr_diag_shift', 0.01))
     tol = float(getattr(hparams, 'sr_cg_tolerance', 1e-3))
     max_iter = int(getattr(hparams, 'sr_cg_max_iterations', 100))
+    solver = str(getattr(hparams, 'sr_solver', os.environ.get('CGS_VMC_SR_SOLVER', 'parameters')))
     self.last_cg = (0, 0.0)
 
     def apply(engine, optimizer):
-      self.last_cg = parallel.sr_solve(engine, shift, tol, max_iter)
+      self.last_cg = parallel.sr_solve(engine, shift, tol, max_iter, solver=solver)
       engine.sr_apply(optimizer.learning_rate())
     return apply
 

@@ -574,6 +574,23 @@ int vmc_sr_solve(vmc_ctx* ctx, float diag_shift, float tol, int32_t max_iter, in
  * The accumulators must already be all-reduced. */
 int vmc_sr_solve_dist(vmc_ctx* ctx, void* nccl_comm, int32_t world_size, float diag_shift, float tol,
                       int32_t max_iter, int32_t* iters, double* rel_residual);
+/* The same update from the sample space (MinSR): with n stored samples, Obar = O - 1 obar^T and eps_b = E_b - Ebar,
+ *   x = Obar^T (Obar Obar^T + n diag_shift I)^-1 eps
+ * -- the solution of vmc_sr_solve, from an n x n system.  The Gram matrix T = O O^T is formed once from the dense sample
+ * store (per layer two MFMA Gram products joined by a Hadamard product, never O itself); conjugate gradients on
+ * C T C + n diag_shift I (C v = v - mean(v)) run until |r| <= tol |eps| or max_iter, each iteration one n x n
+ * matrix-vector product whatever the number of parameters; x = sum_b t_b O_b, t = y - ybar, goes where vmc_sr_solve
+ * leaves its solution: vmc_sr_get_solution and vmc_sr_apply follow as after vmc_sr_solve.  eps reads the local
+ * energies recorded with the store, not the accumulators.  One rank only.  eps = 0 gives *iters = 0 and x = 0.
+ * Refusals, before anything is launched: diag_shift <= 0 or not finite (the centred Gram matrix alone is singular),
+ * tol < 0 or max_iter < 0: VMC_ERR_INVALID; no store or nothing recorded: VMC_ERR_STATE; a convolutional type (its
+ * store has no per-layer Gram form) or more than 16,384 stored samples (T is n^2 floats): VMC_ERR_UNSUPPORTED -- use
+ * vmc_sr_solve; a product ctx or a factor of one: as every vmc_sr_* entry. */
+int vmc_sr_solve_samples(vmc_ctx* ctx, float diag_shift, float tol, int32_t max_iter, int32_t* iters,
+                         double* rel_residual);
+/* test hook: the uncentred Gram matrix T = O O^T of the stored samples, *n = their number (T_host NULL: *n alone);
+ * refuses what vmc_sr_solve_samples refuses of the store */
+int vmc_sr_debug_gram(vmc_ctx* ctx, float* T_host /*[n][n]*/, int32_t* n);
 int vmc_sr_get_solution(vmc_ctx* ctx, float* x /*[P]*/);
 int vmc_sr_apply(vmc_ctx* ctx, float lr, double* energy);
 /* test hook: out = (S + diag_shift I) v over the stored samples (single rank) */
