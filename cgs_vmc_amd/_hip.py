@@ -25,6 +25,8 @@ VMC_MODE_PENALIZED_ENERGY = 2     # extension: E + lambda F against the frozen s
 ANSATZ_IDS = {'fully_connected': 0, 'rbm': 1, 'conv_2d': 2, 'res_net_2d': 3, 'conv_1d': 4, 'res_net_1d': 5,
               'gnn': 6, 'pbdg': 7, 'fully_connected_nnb': 9, 'ed_vector': 10}
 ANSATZ_PRODUCT = 11     # VMC_ANSATZ_PRODUCT: made by vmc_create_product, never by vmc_create
+ANSATZ_SYMMETRIZED = 13     # VMC_ANSATZ_SYMMETRIZED: made by vmc_create_symmetrized, never by vmc_create (12 is unassigned)
+PATH_SYMMETRIZED = 11       # enum KernelPath (csrc/plan.hpp), what vmc_debug_kernel_path reports for a symmetrized ctx
 CONV_ANSATZ = ('conv_2d', 'res_net_2d', 'conv_1d', 'res_net_1d', 'gnn')
 # layers.NONLINEARITIES ids (cgsvmc.h)
 ACT_IDS = {'relu': 0, 'exp': 1, 'cos': 2, 'tan': 3, 'tanh': 4, 'sigmoid': 5, 'identity': 6}
@@ -68,6 +70,8 @@ SIGNATURES = {
     'vmc_num_params_conv': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'vmc_create': (C.c_int, [C.POINTER(VmcDesc), C.POINTER(_ctx)]),
     'vmc_create_product': (C.c_int, [_ctx, _ctx, C.POINTER(_ctx)]),
+    'vmc_create_symmetrized': (C.c_int, [_ctx, C.c_int32, C.c_int32, _ip, C.POINTER(C.c_uint8), C.POINTER(C.c_double),
+                                         C.POINTER(_ctx)]),
     'vmc_destroy': (None, [_ctx]),
     'vmc_last_error': (C.c_char_p, [_ctx]),
     'vmc_set_bonds': (C.c_int, [_ctx, C.c_int32, _ip, _fp, _fp]),
@@ -176,8 +180,8 @@ _lib = None
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 _STAMP_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libcgsvmc_hip.stamp')
 # the files the library is built from, in the order csrc/Makefile hashes them
-_SOURCES = ('vmc_api.hip', 'vmc_api_cgen.hip', 'vmc_api_sweep.hip', 'vmc_api_train.hip', 'vmc_api_coll.hip', 'vmc_api_sr.hip', 'vmc_api_prod.hip', 'prod.hip', 'mlp.hip', 'eloc.hip', 'grad.hip', 'sr.hip', 'srmm.hip', 'srgram.hip', 'conv.hip', 'conv32.hip', 'conv48.hip', 'conv64.hip', 'conv_general.hip', 'conv_band.hip', 'conv_patch.hip', 'wide.hip', 'tail_split.hip', 'sweep_split.hip', 'sweep8.hip', 'pbdg.hip', 'nnb.hip', 'edvec.hip', 'vmc_api_measure.hip', 'corr.hip', 'renyi.hip', 'dimer.hip', 'symm.hip', 'proj.hip', 'moments.hip', 'overlap.hip', 'act_tail.hip',
-            'act_sweep.hip', 'vmc_ctx.hpp', 'prod.hpp', 'plan.hpp', 'common.hpp', 'pb_det.hpp', 'tail16.hpp', 'tail_lds.hpp', 'sweep16.hpp', 'conv.hpp', 'conv_kernels.hpp',
+_SOURCES = ('vmc_api.hip', 'vmc_api_cgen.hip', 'vmc_api_sweep.hip', 'vmc_api_train.hip', 'vmc_api_coll.hip', 'vmc_api_sr.hip', 'vmc_api_prod.hip', 'prod.hip', 'vmc_api_symz.hip', 'symz.hip', 'mlp.hip', 'eloc.hip', 'grad.hip', 'sr.hip', 'srmm.hip', 'srgram.hip', 'conv.hip', 'conv32.hip', 'conv48.hip', 'conv64.hip', 'conv_general.hip', 'conv_band.hip', 'conv_patch.hip', 'wide.hip', 'tail_split.hip', 'sweep_split.hip', 'sweep8.hip', 'pbdg.hip', 'nnb.hip', 'edvec.hip', 'vmc_api_measure.hip', 'corr.hip', 'renyi.hip', 'dimer.hip', 'symm.hip', 'proj.hip', 'moments.hip', 'overlap.hip', 'act_tail.hip',
+            'act_sweep.hip', 'vmc_ctx.hpp', 'prod.hpp', 'symz.hpp', 'plan.hpp', 'common.hpp', 'pb_det.hpp', 'tail16.hpp', 'tail_lds.hpp', 'sweep16.hpp', 'conv.hpp', 'conv_kernels.hpp',
             'conv_wide.hpp',
             os.path.join('..', '..', 'include', 'cgsvmc.h'), 'Makefile')
 

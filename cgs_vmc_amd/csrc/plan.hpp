@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "../../include/cgsvmc.h"
@@ -803,6 +804,76 @@ inline int plan_symm_check_hamiltonian(int N, int n_bonds, const int32_t* ij, co
   return VMC_OK;
 }
 
+// ------------------------------------------------------------------------------- symmetrized ctx (vmc_api_symz.hip, symz.hip)
+// psi_s(x) = sum_k chi_k psi(g_k x) over one set of B chains: the base ctx holds the n_ops B permuted rows (row = k B + c)
+// as its chains and does all network arithmetic; theta is the base's, the accumulators are [g1 | g2 | 8 scalars] at P.
+//
+// The structural zero.  Per chain, with l_k = ln|psi(g_k x)|, s_k its sign and m = max_k l_k over the ops that count
+// (chi_k != 0, s_k != 0): S = sum_k chi_k s_k exp(l_k - m), A = sum_k |chi_k| exp(l_k - m), both in fp64, ops ascending.
+// A row is AT A ZERO of the sector where |S| <= 2^-40 A.  Why 2^-40: the fp64 sum of at most 1,024 terms of magnitude
+// <= A is off by at most 1,024 x 2^-53 A = 2^-43 A, so a sum that cancels exactly in real arithmetic lands below
+// 2^-40 A with a factor 8 to spare -- but only if the terms that cancel are bit-identical, i.e. the SAME row evaluated
+// twice (an op with character -1 that maps the configuration onto itself).  Two different rows of equal amplitude carry
+// the fp32 logits' noise, 2^-24 A, sixteen binary orders above the threshold: the rule never fires on a near miss.
+#define PLAN_SYMZ_MAX_OPS 1024
+#define PLAN_SYMZ_ZERO_LOG2 (-40)
+#define PLAN_SYMZ_THREADS 256            // chains per workgroup of the one-thread-per-chain folds
+#define PLAN_SYMZ_CHAINS_PER_WG 4        // one wave per chain (k_symz_accept: the arithmetic of k_wide_propose)
+#define PLAN_SYMZ_ZERO 0x1p-40           // 2^PLAN_SYMZ_ZERO_LOG2
+PLAN_HD inline bool plan_symz_is_zero(double S, double A) { return !(fabs(S) > PLAN_SYMZ_ZERO * A); }
+inline unsigned plan_symz_chain_blocks(long long B) { return (unsigned)((B + PLAN_SYMZ_THREADS - 1) / PLAN_SYMZ_THREADS); }
+inline unsigned plan_symz_wave_grid(long long B) { return (unsigned)((B + PLAN_SYMZ_CHAINS_PER_WG - 1) / PLAN_SYMZ_CHAINS_PER_WG); }
+inline long long plan_symz_acc_floats(long long P) { return 2 * P + 8; }
+// What vmc_create_symmetrized decides before anything is allocated.  The base may be what a product takes as a factor
+// (fully_connected / rbm with the exp output, pbdg, ed_vector: their gradient sums take an external weight vector);
+// base_composite: the base is a product or a symmetrized ctx; base_owned: it already belongs to one.  VMC_OK, or the
+// status with the reason in msg.
+inline int plan_symz_check(int base_ansatz, int base_output_activation, bool base_composite, bool base_owned,
+                           long long base_B, int N, long long batch_size, long long n_ops, const int32_t* perms,
+                           const uint8_t* flips, const double* characters, char* msg, size_t msg_len) {
+  if (msg_len) msg[0] = 0;
+  if (base_composite) {
+    snprintf(msg, msg_len, "symmetrized: a product or symmetrized ctx cannot be the base of a symmetrized ctx");
+    return VMC_ERR_UNSUPPORTED;
+  }
+  if (base_ansatz == VMC_ANSATZ_FULLY_CONNECTED || base_ansatz == VMC_ANSATZ_RBM) {
+    if (base_output_activation != 1 /* VMC_ACT_EXP */) {
+      snprintf(msg, msg_len, "symmetrized: a dense base needs the exp output activation (a positive amplitude with a shift)");
+      return VMC_ERR_UNSUPPORTED;
+    }
+  } else if (base_ansatz != VMC_ANSATZ_PBDG && base_ansatz != VMC_ANSATZ_ED_VECTOR) {
+    snprintf(msg, msg_len, "symmetrized: the base is a fully_connected, rbm, pbdg or ed_vector ctx (the convolutional types, gnn and fully_connected_nnb are not taken)");
+    return VMC_ERR_UNSUPPORTED;
+  }
+  if (base_owned) {
+    snprintf(msg, msg_len, "symmetrized: the base already belongs to a product or symmetrized ctx");
+    return VMC_ERR_STATE;
+  }
+  if (batch_size < 1) { snprintf(msg, msg_len, "symmetrized: batch_size >= 1 required"); return VMC_ERR_INVALID; }
+  if (n_ops < 1 || n_ops > PLAN_SYMZ_MAX_OPS) {
+    snprintf(msg, msg_len, "symmetrized: n_ops = %lld, 1 .. %d required", n_ops, PLAN_SYMZ_MAX_OPS);
+    return VMC_ERR_INVALID;
+  }
+  if (base_B != batch_size * n_ops) {
+    snprintf(msg, msg_len, "symmetrized: the base holds %lld rows, batch_size x n_ops = %lld x %lld = %lld required", base_B,
+             batch_size, n_ops, batch_size * n_ops);
+    return VMC_ERR_INVALID;
+  }
+  if (!perms || !characters) { snprintf(msg, msg_len, "symmetrized: null ops or characters"); return VMC_ERR_INVALID; }
+  const int rc = plan_symm_check_ops(N, (int)n_ops, perms, flips, msg, msg_len);
+  if (rc != VMC_OK) return rc;
+  bool any = false;
+  for (long long k = 0; k < n_ops; ++k) {
+    if (!std::isfinite(characters[k])) {
+      snprintf(msg, msg_len, "symmetrized: character %lld is not finite", k);
+      return VMC_ERR_INVALID;
+    }
+    any = any || characters[k] != 0.0;
+  }
+  if (!any) { snprintf(msg, msg_len, "symmetrized: every character is zero"); return VMC_ERR_INVALID; }
+  return VMC_OK;
+}
+
 // Lanczos-step energies (vmc_energy_moments; moments.hip).  The second-order list -- the rows x^{ab} over (chain,
 // antiparallel bond a, bond b antiparallel on x^a) -- is indexed with 32-bit integers like the first-order list; a chain
 // has at most n_bonds first-order rows of at most n_bonds second-order rows each, so B n_bonds^2 <= 2^31 - 1 keeps every
@@ -850,6 +921,7 @@ enum KernelPath {
   PATH_NNB = 8,            // FullyConnectedNNB (nnb.hip): the general dense trunk into determinant rows
   PATH_EDVEC = 9,          // FullVector (edvec.hip): theta is the state vector
   PATH_PRODUCT = 10,       // a product ctx (vmc_create_product): its factors run their own paths
+  PATH_SYMMETRIZED = 11,   // a symmetrized ctx (vmc_create_symmetrized): its base runs its own path over the permuted rows
 };
 // the fused dense kernels run here: rows, sampler (and its refresh pass) and k_backprop16 with its folds
 constexpr bool path_fused_dense(KernelPath p) {
@@ -866,7 +938,7 @@ constexpr bool path_split(KernelPath p) { return p == PATH_SPLIT_ROWS || p == PA
 
 // ------------------------------------------------------------------------------- vmc_create
 struct DescPlan {
-  KernelPath path;           // PATH_SPLIT_* and PATH_PRODUCT are never planned here (plan_split_path, vmc_create_product)
+  KernelPath path;           // PATH_SPLIT_*, PATH_PRODUCT and PATH_SYMMETRIZED are never planned here (plan_split_path, vmc_create_product / _symmetrized)
   int rbm, resnet, one_d;
   int Hp;                    // padded units of the dense kernels (conv: 64, unused)
   int n_hh;                  // H x H layers
@@ -885,6 +957,8 @@ inline int plan_desc(const vmc_desc* d, bool wide_fast_allowed, DescPlan* out, c
 #define PLAN_FAIL(code, text) do { snprintf(msg, msg_len, "%s", text); return code; } while (0)
   if (d->ansatz == VMC_ANSATZ_PRODUCT)
     PLAN_FAIL(VMC_ERR_INVALID, "a product ctx is made by vmc_create_product from two ctxs, not by vmc_create");
+  if (d->ansatz == VMC_ANSATZ_SYMMETRIZED)
+    PLAN_FAIL(VMC_ERR_INVALID, "a symmetrized ctx is made by vmc_create_symmetrized from a base ctx, not by vmc_create");
   if (d->ansatz < VMC_ANSATZ_FULLY_CONNECTED ||
       (d->ansatz > VMC_ANSATZ_PBDG && d->ansatz != VMC_ANSATZ_NNB && d->ansatz != VMC_ANSATZ_ED_VECTOR))
     PLAN_FAIL(VMC_ERR_UNSUPPORTED, "only the fully_connected, rbm, conv_1d/2d, res_net_1d/2d, gnn, pbdg, fully_connected_nnb and ed_vector ansatz types have HIP kernels");

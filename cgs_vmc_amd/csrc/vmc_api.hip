@@ -38,6 +38,7 @@ int ensure_packed(vmc_ctx* c, int which) {
       p.bdiff_valid = false;      // (differences of the image just replaced)
       break;
     case PATH_PRODUCT: return product_has_none(c, "parameter image");
+    case PATH_SYMMETRIZED: return symmetrized_has_none(c, "parameter image");
   }
   p.packed_valid = true;
   return VMC_OK;
@@ -284,6 +285,7 @@ static int full_forward(vmc_ctx* c, int which, const float* configs, int n_rows,
       return VMC_OK;
     }
     case PATH_PRODUCT: return product_has_none(c, "forward");
+    case PATH_SYMMETRIZED: return symmetrized_has_none(c, "forward");
   }
   return VMC_OK;
 }
@@ -306,6 +308,7 @@ void invalidate_configs(vmc_ctx* c) {
   c->list_valid = false;
   c->cnt_valid = false;
   if (c->prod) prod_chains_changed(c);
+  if (c->symz) symz_chains_changed(c);
 }
 
 int ensure_list(vmc_ctx* c) {
@@ -324,6 +327,7 @@ int ensure_list(vmc_ctx* c) {
 int local_energy_device(vmc_ctx* c, int which, bool defer_reduce, bool* deferred) {
   if (deferred) *deferred = false;
   if (c->prod) return prod_local_energy(c, which);
+  if (c->symz) return symz_local_energy(c, which);
   PROPAGATE(ensure_cache(c, which));
   PROPAGATE(ensure_list(c));
   PROPAGATE(connected_rows_device(c, which, true));
@@ -398,6 +402,7 @@ int connected_rows_device(vmc_ctx* c, int which, bool share_cus) {
     break;
   }
   case PATH_PRODUCT: return product_has_none(c, "row kernel");
+  case PATH_SYMMETRIZED: return symmetrized_has_none(c, "row kernel");
   }
   return VMC_OK;
 }
@@ -429,6 +434,7 @@ int rows_forward_device(vmc_ctx* c, int which, const float* configs, long long n
 const char* signed_family_name(KernelPath path) {
   switch (path) {
     case PATH_PRODUCT: return "prod (a signed factor)";
+    case PATH_SYMMETRIZED: return "symmetrized (spin flips or a signed base)";
     case PATH_EDVEC: return "ed_vector";
     case PATH_NNB: return "fully_connected_nnb";
     case PATH_PBDG: return "pbdg";
@@ -679,6 +685,7 @@ static int create_buffers(vmc_ctx* c) {
   switch (c->path) {
     case PATH_FUSED: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP:
     case PATH_PRODUCT:      // (vmc_create_product starts from a minimal PATH_FUSED ctx and adds its own)
+    case PATH_SYMMETRIZED:  // (vmc_create_symmetrized likewise)
       break;
     case PATH_FUSED_LDS: case PATH_DENSE_GENERAL:
       c->wrows = B > 131072 ? B : 131072;
@@ -803,6 +810,8 @@ void vmc_destroy(vmc_ctx* c) {
   if (c->sweep_stream) hipStreamSynchronize(c->sweep_stream);
   hipStreamSynchronize(c->stream);
   if (c->prod) prod_release(c);            // the factors are borrowed: they stay alive, free again
+  if (c->symz) symz_release(c);            // (the base of a symmetrized ctx likewise)
+  if (c->owner && c->owner->symz) symz_base_destroyed(c);
   if (c->owner) prod_child_destroyed(c);   // (a factor destroyed before its product: the product refuses from now on)
   drain_timings(c);
   if (c->sweep_stream) hipStreamDestroy(c->sweep_stream);
@@ -817,6 +826,17 @@ void vmc_destroy(vmc_ctx* c) {
 int vmc_set_bonds(vmc_ctx* c, int32_t n_bonds, const int32_t* ij, const float* j_x, const float* j_z) {
   ENTER(c);
   if (n_bonds < 1 || !ij || !j_x || !j_z) return fail(c, VMC_ERR_INVALID, "bad bond arguments");
+  // a symmetrized ctx, before anything changes: the ops must be symmetries, and the base -- whose batch_size x n_ops rows
+  // are the larger demand -- takes the set first, so that a refusal of either leaves both ctxs as they were
+  if (c->symz) {
+    PROPAGATE(symz_set_bonds_check(c, n_bonds, ij, j_x, j_z));
+    PROPAGATE(symz_set_bonds(c, n_bonds, ij, j_x, j_z));
+  }
+  // (the base of a symmetrized ctx called directly: the same question, asked of its owner's ops)
+  if (c->owner && c->owner->symz) {
+    const int rc = symz_set_bonds_check(c->owner, n_bonds, ij, j_x, j_z);
+    if (rc != VMC_OK) { c->err = c->owner->err; return rc; }
+  }
   // connected rows are indexed with 32-bit integers (at most one row per chain and bond)
   if ((long long)c->B * n_bonds > 0x7fffffffLL - c->B)
     return fail(c, VMC_ERR_UNSUPPORTED, "batch_size x n_bonds does not fit the 32-bit row index");
@@ -898,13 +918,14 @@ int vmc_set_lin_tables(vmc_ctx* c, int32_t n_half, const int32_t* top, const int
 int vmc_set_params(vmc_ctx* c, int which, const float* theta) {
   ENTER(c);
   if ((which != 0 && which != 1) || !theta) return fail(c, VMC_ERR_INVALID, "bad arguments");
+  if (c->symz) return symz_set_params(c, which, theta);      // theta is the base's
   HIPCHK(c, hipMemcpyAsync(c->ps[which].theta, theta, c->P * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->ps[which].has_params = true;
   c->ps[which].packed_valid = c->ps[which].cache_valid = false;
   if (which == VMC_PSI) c->acts_valid = false;
   if (c->prod) PROPAGATE(prod_scatter_params(c, which));      // theta = a's floats followed by b's
-  if (c->owner) prod_child_params_changed(c, which);
+  if (c->owner) { prod_child_params_changed(c, which); symz_base_params_changed(c, which); }
   return VMC_OK;
 }
 
@@ -912,6 +933,7 @@ int vmc_get_params(vmc_ctx* c, int which, float* theta) {
   ENTER(c);
   if ((which != 0 && which != 1) || !theta) return fail(c, VMC_ERR_INVALID, "bad arguments");
   if (c->prod) PROPAGATE(prod_gather_params(c, which));
+  if (c->symz) return symz_get_params(c, which, theta);
   if (!c->ps[which].has_params) return fail(c, VMC_ERR_STATE, "parameters not set");
   HIPCHK(c, hipMemcpyAsync(theta, c->ps[which].theta, c->P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -921,7 +943,8 @@ int vmc_get_params(vmc_ctx* c, int which, float* theta) {
 int vmc_transfer_params(vmc_ctx* c) {
   ENTER(c);
   if (c->prod) return prod_transfer_params(c);
-  if (c->owner) prod_child_params_changed(c, VMC_OMEGA);
+  if (c->symz) return symz_transfer_params(c);
+  if (c->owner) { prod_child_params_changed(c, VMC_OMEGA); symz_base_params_changed(c, VMC_OMEGA); }
   if (!c->ps[0].has_params) return fail(c, VMC_ERR_STATE, "parameters not set");
   HIPCHK(c, hipMemcpyAsync(c->ps[1].theta, c->ps[0].theta, c->P * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   c->ps[1].has_params = true;
@@ -934,6 +957,7 @@ int vmc_set_configs(vmc_ctx* c, const float* configs) {
   REFUSE_COMPOSED(c);
   if (!configs) return fail(c, VMC_ERR_INVALID, "null configs");
   PROPAGATE(check_sz0_rows(c, configs, c->B));
+  if (c->symz) PROPAGATE(symz_check_configs(c, configs));      // (no row at a structural zero of the sector)
   const long long n = (long long)c->B * c->N;
   // staged in the alternate chain buffer (free between sampler launches), validated on the
   // device, and only then made current: a rejected batch leaves the chains untouched
@@ -962,6 +986,7 @@ int vmc_set_shift(vmc_ctx* c, int which, float shift) {
   if (which != 0 && which != 1) return fail(c, VMC_ERR_INVALID, "bad which");
   switch (c->path) {
     case PATH_PRODUCT: return fail(c, VMC_ERR_INVALID, "prod: the product has no exponent shift of its own (set the factors')");
+    case PATH_SYMMETRIZED: return fail(c, VMC_ERR_INVALID, "symmetrized: the symmetrized ctx has no exponent shift of its own (set the base's)");
     case PATH_NNB: case PATH_EDVEC: break;     // (neural-network backflow, ed_vector: no exponent shift, it stays 0)
     case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_CONV: case PATH_SPLIT_ROWS:
     case PATH_SPLIT_SWEEP: case PATH_CONV_GENERAL: case PATH_PBDG:
@@ -981,6 +1006,7 @@ int vmc_get_shift(vmc_ctx* c, int which, float* shift) {
 int vmc_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, float* logit, float* psi) {
   ENTER(c);
   if (c->prod) return prod_amplitude(c, which, configs, n_rows, logit, psi);
+  if (c->symz) return symz_amplitude(c, which, configs, n_rows, logit, psi);
   if (!configs) REFUSE_COMPOSED(c);
   if (which != 0 && which != 1) return fail(c, VMC_ERR_INVALID, "bad which");
   if (n_rows < 0) return fail(c, VMC_ERR_INVALID, "n_rows < 0");
@@ -1014,7 +1040,7 @@ int vmc_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, f
         // wavefunctions.py:350-353: exp(x - shift) (232), or the output activation itself, no shift
         psi[i] = c->oact == VMC_ACT_EXP_ ? expf(host[i] - shift) : host_activation(c->oact, host[i]);
         break;
-      case PATH_PRODUCT: break;                                                    // (prod_amplitude, above)
+      case PATH_PRODUCT: case PATH_SYMMETRIZED: break;                             // (prod_amplitude / symz_amplitude, above)
     }
   }
   return VMC_OK;

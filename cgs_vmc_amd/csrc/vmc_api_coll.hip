@@ -133,6 +133,7 @@ int vmc_accumulators_devptr(vmc_ctx* c, void** dev_ptr, int64_t* n_floats) {
 int vmc_allreduce_accumulators(vmc_ctx* c, void* nccl_comm, int32_t world_size) {
   CHECK_CTX(c);
   if (c->prod && world_size > 1) return fail(c, VMC_ERR_UNSUPPORTED, "vmc_allreduce_accumulators with world_size > 1 is not available on a product ctx ('prod')");
+  if (c->symz && world_size > 1) return fail(c, VMC_ERR_UNSUPPORTED, "vmc_allreduce_accumulators with world_size > 1 is not available on a symmetrized ctx ('symmetrized')");
   PROPAGATE(acc_zeros(c));
   PROPAGATE(reduce_accumulators(c, nccl_comm, world_size));
   return VMC_OK;
@@ -228,6 +229,7 @@ int vmc_rccl_comm_destroy(void* nccl_comm) {
 int vmc_debug_allreduce(vmc_ctx* c, void* nccl_comm, int32_t world_size, float* host, int64_t n, int32_t op) {
   ENTER(c);
   if (c->prod && world_size > 1) return fail(c, VMC_ERR_UNSUPPORTED, "vmc_debug_allreduce with world_size > 1 is not available on a product ctx ('prod')");
+  if (c->symz && world_size > 1) return fail(c, VMC_ERR_UNSUPPORTED, "vmc_debug_allreduce with world_size > 1 is not available on a symmetrized ctx ('symmetrized')");
   if (!host || n < 1 || (op != VMC_REDUCE_SUM && op != VMC_REDUCE_MAX)) return fail(c, VMC_ERR_INVALID, "bad arguments");
   PROPAGATE(c->d_stage.reserve(c, n, "d_stage"));
   HIPCHK(c, hipMemcpyAsync(c->d_stage, host, n * sizeof(float), hipMemcpyHostToDevice, c->stream));

@@ -361,6 +361,7 @@ namespace vmcapi {
 
 int overlap_refusals(vmc_ctx* c, const char* what) {
   if (c->prod) return fail(c, VMC_ERR_UNSUPPORTED, std::string(what) + " is not available on a product ctx ('prod')");
+  if (c->symz) return fail(c, VMC_ERR_UNSUPPORTED, std::string(what) + " is not available on a symmetrized ctx ('symmetrized')");
   PROPAGATE(needs_ln_psi(c, what));
   if (!c->ps[1].has_params)
     return fail(c, VMC_ERR_STATE, std::string(what) + ": the frozen parameters are not set (vmc_set_params(VMC_OMEGA) / vmc_transfer_params)");

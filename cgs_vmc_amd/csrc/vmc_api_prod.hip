@@ -322,6 +322,7 @@ int vmc_create_product(vmc_ctx* a, vmc_ctx* b, vmc_ctx** out) {
   *out = nullptr;
   if (a == b) return fail(nullptr, VMC_ERR_INVALID, "prod: the two factors must be two ctxs");
   for (vmc_ctx* ch : {a, b}) {
+    if (ch->symz) return fail(nullptr, VMC_ERR_UNSUPPORTED, "prod: a symmetrized ctx ('symmetrized') cannot be a factor of a product");
     char msg[256];
     const int rc = plan_prod_child_check(ch->d.ansatz, ch->oact, ch->prod != nullptr, msg, sizeof(msg));
     if (rc != VMC_OK) return fail(nullptr, rc, msg);

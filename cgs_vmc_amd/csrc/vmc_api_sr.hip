@@ -28,7 +28,7 @@ int vmc_sr_reserve(vmc_ctx* c, int32_t n_batches) {
         return fail(c, VMC_ERR_UNSUPPORTED, std::string("stochastic reconfiguration is not implemented for the ") + signed_family_name(c->path) +
                                             " ansatz (use EnergyGradient or LogOverlapITSWO)");
       case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_CONV: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP:
-      case PATH_CONV_GENERAL: case PATH_PRODUCT: break;      // (a product: REFUSE_PRODUCT, above)
+      case PATH_CONV_GENERAL: case PATH_PRODUCT: case PATH_SYMMETRIZED: break;      // (a product: REFUSE_PRODUCT, above)
     }
   if (n_batches > 0 && c->oact != VMC_ACT_EXP_)
     return fail(c, VMC_ERR_UNSUPPORTED, "stochastic reconfiguration (an extension) covers the exp output activation (every hidden activation)");
@@ -60,7 +60,7 @@ int vmc_sr_reserve(vmc_ctx* c, int32_t n_batches) {
     break;
   }
   case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP:
-  case PATH_PBDG: case PATH_NNB: case PATH_EDVEC: case PATH_PRODUCT:     // (the last four were refused above)
+  case PATH_PBDG: case PATH_NNB: case PATH_EDVEC: case PATH_PRODUCT: case PATH_SYMMETRIZED:     // (the last four were refused above)
     if (R > 0x7fffffffLL / Hp) return fail(c, VMC_ERR_UNSUPPORTED, "SR sample store too large (rows * Hp >= 2^31)");
     PROPAGATE(c->sr_cfg.alloc(c, R * N, "sr_cfg"));
     PROPAGATE(c->sr_act.alloc(c, L * R * Hp, "sr_act"));
@@ -171,7 +171,7 @@ static int sr_matvec(vmc_ctx* c) {
     return VMC_OK;
   }
   case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP:
-  case PATH_PBDG: case PATH_NNB: case PATH_EDVEC: case PATH_PRODUCT:     // (the last four have no store: never begun)
+  case PATH_PBDG: case PATH_NNB: case PATH_EDVEC: case PATH_PRODUCT: case PATH_SYMMETRIZED:     // (the last four have no store: never begun)
     break;      // the dense store, below
   }
   // t_b = O_b . p = sum_l delta_l[b] . (a_{l-1}[b] V_l + v_l) + (output / onsite layer term);
@@ -340,7 +340,7 @@ static int sr_gram_refusals(vmc_ctx* c, SrGramPlan* plan) {
     case PATH_CONV: case PATH_CONV_GENERAL:
       return fail(c, VMC_ERR_UNSUPPORTED, "the sample-space solve covers the dense sample store (fully_connected, rbm): the store of a "
                                           "convolutional type has no per-layer Gram form here (use the parameter-space solver, vmc_sr_solve)");
-    case PATH_PBDG: case PATH_NNB: case PATH_EDVEC: case PATH_PRODUCT:     // (vmc_sr_reserve gives them no store)
+    case PATH_PBDG: case PATH_NNB: case PATH_EDVEC: case PATH_PRODUCT: case PATH_SYMMETRIZED:     // (vmc_sr_reserve gives them no store)
       return fail(c, VMC_ERR_STATE, "vmc_sr_reserve first");
     case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP: break;
   }

@@ -294,16 +294,18 @@ static int dump_proposals(vmc_ctx* c, const SweepCall& s) {
 static int run_sweep(vmc_ctx* c, const SweepCall& s) {
   const bool dbg = s.dump(), injected = s.injected;
   const bool fused_arm = path_fused_dense(c->path) || c->path == PATH_CONV;   // one persistent launch into the alternate set
-  if (c->path != PATH_PRODUCT) {      // (a product's factors pack their own parameters and keep their own census)
+  if (c->path != PATH_PRODUCT && c->path != PATH_SYMMETRIZED) {      // (a product's factors, a symmetrized ctx's base pack their own parameters and keep their own census)
     PROPAGATE(ensure_packed(c, 0));
     if (!dbg) c->cnt_valid = false;   // the chains change (set again below when this launch leaves their census)
   }
   if (dbg && !fused_arm) {
     if (c->path == PATH_PRODUCT) PROPAGATE(prod_alive(c));      // (a product whose factor is gone refuses every entry)
+    if (c->path == PATH_SYMMETRIZED) PROPAGATE(symz_alive(c));
     return dump_proposals(c, s);
   }
   switch (c->path) {
     case PATH_PRODUCT: return prod_run_sweep(c, s);
+    case PATH_SYMMETRIZED: return symz_run_sweep(c, s);
     case PATH_EDVEC: return run_sweep_edvec(c, s);
     case PATH_NNB: return run_sweep_nnb(c, s);
     case PATH_DENSE_GENERAL: return run_sweep_wide(c, s);
@@ -461,7 +463,7 @@ int vmc_debug_sweep_profile(vmc_ctx* c, int64_t n_steps, double* phase_cycles) {
   switch (c->path) {
     case PATH_FUSED: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP: stamped = !c->rbm; break;
     case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_CONV: case PATH_CONV_GENERAL: case PATH_PBDG: case PATH_NNB:
-    case PATH_EDVEC: case PATH_PRODUCT: break;
+    case PATH_EDVEC: case PATH_PRODUCT: case PATH_SYMMETRIZED: break;
   }
   if (!stamped) return fail(c, VMC_ERR_UNSUPPORTED, "the diagnostic sweep build exists for fully_connected (<= 256 units) only");
   PROPAGATE(ensure_packed(c, 0));

@@ -55,6 +55,7 @@ static int gradient_sums(vmc_ctx* c, const float* w, bool fresh, const float* e,
     return VMC_OK;
   }
   case PATH_PRODUCT: return product_has_none(c, "gradient path");
+  case PATH_SYMMETRIZED: return symmetrized_has_none(c, "gradient path");
   case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP: case PATH_NNB:
     break;      // the dense trunk, below
   }
@@ -175,7 +176,7 @@ namespace vmcapi {
 // `configs` (whose cache the caller has made valid), with the caller's weights and accumulators
 int child_gradient_sums(vmc_ctx* c, const float* w, float* g1, float* g2) {
   switch (c->path) {
-    case PATH_CONV: case PATH_CONV_GENERAL: case PATH_NNB: case PATH_PRODUCT:     // (plan_prod_child_check refuses them)
+    case PATH_CONV: case PATH_CONV_GENERAL: case PATH_NNB: case PATH_PRODUCT: case PATH_SYMMETRIZED:     // (plan_prod_child_check, plan_symz_check refuse them)
       return fail(c, VMC_ERR_UNSUPPORTED, "prod: this ansatz type cannot be a factor");
     case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP:
     case PATH_PBDG: case PATH_EDVEC: break;
@@ -209,7 +210,7 @@ static int sr_record(vmc_ctx* c) {
     break;
   }
   case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP:
-  case PATH_PBDG: case PATH_NNB: case PATH_EDVEC: case PATH_PRODUCT:     // (the last four: vmc_sr_reserve gives them no store)
+  case PATH_PBDG: case PATH_NNB: case PATH_EDVEC: case PATH_PRODUCT: case PATH_SYMMETRIZED:     // (the last five: vmc_sr_reserve gives them no store)
     // layer-major store [L][cap * B][Hp]: every layer's rows of ALL stored batches are contiguous,
     // so the CG matrix-vector product runs each GEMM once over all samples
     HIPCHK(c, hipMemcpy2DAsync(c->sr_act + k * B * Hp, R * Hp * sizeof(float), c->act_all, B * Hp * sizeof(float),
@@ -254,6 +255,7 @@ int vmc_accumulate(vmc_ctx* c, int mode, float beta) {
   const bool penalized = mode == VMC_MODE_PENALIZED_ENERGY;      // (beta carries lambda)
   if (penalized) PROPAGATE(penalized_refusals(c, beta, "vmc_accumulate(VMC_MODE_PENALIZED_ENERGY)"));
   if (c->prod) return prod_accumulate(c, mode, beta);
+  if (c->symz) return symz_accumulate(c, mode, beta);
   // the scalar tail of mode PENALIZED_ENERGY is filled as LOG_OVERLAP_ITSWO fills it: e_total, r_total = sum w, the counts
   const int sc_mode = penalized ? VMC_MODE_LOG_OVERLAP_ITSWO : mode;
   const float* w = nullptr;
@@ -295,7 +297,7 @@ int vmc_accumulate(vmc_ctx* c, int mode, float beta) {
           HIPCHK(c, launch_itswo_ratio(c->stream, c->ps[0].logit, c->ps[1].logit, c->ps[1].eloc,
                                        c->ps[0].shift - c->ps[1].shift, beta, c->B, c->ratio, c->oact));
         break;
-      case PATH_PRODUCT: break;            // (prod_accumulate, above)
+      case PATH_PRODUCT: case PATH_SYMMETRIZED: break;            // (prod_accumulate, symz_accumulate, above)
     }
     w = c->ratio; e = c->ps[1].eloc;
   }
@@ -305,7 +307,7 @@ int vmc_accumulate(vmc_ctx* c, int mode, float beta) {
   switch (c->path) {
     case PATH_CONV: case PATH_CONV_GENERAL: case PATH_PBDG: case PATH_EDVEC: PROPAGATE(acc_zeros(c)); break;
     case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_SPLIT_ROWS: case PATH_SPLIT_SWEEP: case PATH_NNB:
-    case PATH_PRODUCT: break;
+    case PATH_PRODUCT: case PATH_SYMMETRIZED: break;
   }
   const bool fresh = c->acc_fresh;
   bool scalars_done = false;
@@ -372,17 +374,20 @@ int vmc_apply_adam(vmc_ctx* c, int mode, float lr, float beta1, float beta2, flo
   REFUSE_COMPOSED(c);
   if (mode != 0 && mode != 1 && mode != VMC_MODE_PENALIZED_ENERGY) return fail(c, VMC_ERR_INVALID, "bad mode");
   if (c->prod) PROPAGATE(prod_gather_params(c, VMC_PSI));      // theta = [a | b] from the factors
-  if (!c->ps[0].has_params) return fail(c, VMC_ERR_STATE, "parameters not set");
+  float* theta = c->ps[0].theta;
+  if (c->symz) PROPAGATE(symz_adam_theta(c, &theta));          // a symmetrized ctx: the base's theta, no copy
+  else if (!c->ps[0].has_params) return fail(c, VMC_ERR_STATE, "parameters not set");
   PROPAGATE(acc_zeros(c));
   c->adam_t += 1;
   const float t = (float)c->adam_t;
   const float lr_t = lr * sqrtf(1.f - powf(beta2, t)) / (1.f - powf(beta1, t));
   {
     Timer tm(c, "adam");
-    HIPCHK(c, launch_adam(c->stream, c->ps[0].theta, c->adam_m, c->adam_v, c->acc, (int)c->P, mode, lr_t, beta1, beta2, eps, nullptr));
+    HIPCHK(c, launch_adam(c->stream, theta, c->adam_m, c->adam_v, c->acc, (int)c->P, mode, lr_t, beta1, beta2, eps, nullptr));
   }
   c->ps[0].packed_valid = c->ps[0].cache_valid = false;
   c->acts_valid = false;
+  if (c->symz) symz_adam_applied(c);
   if (c->prod) PROPAGATE(prod_scatter_params(c, VMC_PSI));     // ... and back
   if (energy) PROPAGATE(vmc_mean_energy(c, energy));
   return VMC_OK;
@@ -411,6 +416,7 @@ static int update_norm_impl(vmc_ctx* c, void* comm, int world, float max_value) 
   const bool pbdg = c->path == PATH_PBDG;
   switch (c->path) {
     case PATH_PRODUCT: return VMC_OK;      // the product has no shift of its own; the factors' stay where they are (log domain)
+    case PATH_SYMMETRIZED: return VMC_OK;  // nor has a symmetrized ctx: the base keeps its shift
     case PATH_NNB: case PATH_EDVEC: return VMC_OK;     // no exponent shift
     case PATH_FUSED: case PATH_FUSED_LDS: case PATH_DENSE_GENERAL: case PATH_CONV: case PATH_SPLIT_ROWS:
     case PATH_SPLIT_SWEEP: case PATH_CONV_GENERAL: case PATH_PBDG: break;
@@ -526,6 +532,7 @@ int vmc_epoch_log_overlap(vmc_ctx* c, float beta, int64_t n_eq_steps, int32_t n_
                           float eps, double* energy) {
   ENTER(c);
   REFUSE_COMPOSED(c);
+  REFUSE_SYMZ(c, "vmc_epoch_log_overlap");
   return epoch_log_overlap_impl(c, nullptr, 1, beta, n_eq_steps, n_batches, n_mc_steps, max_value, lr, beta1, beta2,
                                 eps, energy);
 }
@@ -548,6 +555,8 @@ int vmc_evaluate(vmc_ctx* c, void* nccl_comm, int32_t world_size, int64_t n_eq_s
   REFUSE_COMPOSED(c);
   if (c->prod && (nccl_comm || world_size > 1))
     return fail(c, VMC_ERR_UNSUPPORTED, "vmc_evaluate over sharded chains is not available on a product ctx ('prod')");
+  if (c->symz && (nccl_comm || world_size > 1))
+    return fail(c, VMC_ERR_UNSUPPORTED, "vmc_evaluate over sharded chains is not available on a symmetrized ctx ('symmetrized')");
   if (n_eq_steps < 0 || n_samples < 0 || n_mc_steps < 0) return fail(c, VMC_ERR_INVALID, "negative count");
   if (n_samples > 0 && !means) return fail(c, VMC_ERR_INVALID, "null means");
   if (c->n_bonds <= 0) return fail(c, VMC_ERR_STATE, "bonds not set (vmc_set_bonds)");

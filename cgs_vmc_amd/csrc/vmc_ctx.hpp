@@ -83,6 +83,7 @@ using vmcapi::ParamSet;
 using vmcapi::TimedRegion;
 
 struct ProdState;      // vmc_api_prod.hip: what a product ctx keeps beside the members below
+struct SymzState;      // vmc_api_symz.hip: what a symmetrized ctx keeps beside them
 
 // spin correlations: the bond set of a pass of pairs -- swapped with the five Hamiltonian members of the ctx for the
 // pass -- the scatter target, the sums
@@ -148,6 +149,10 @@ struct vmc_ctx {
   // the owner's caches.  The dense members of a product ctx keep minimal shapes (unused); P = P_a + P_b.
   ProdState* prod = nullptr;
   vmc_ctx* owner = nullptr;
+  // The symmetrized ansatz (vmc_api_symz.hip, symz.hip): a ctx made by vmc_create_symmetrized owns the chains, the
+  // accumulators and the Adam state of psi_s = sum_k chi_k psi(g_k .) and borrows its base, whose `owner` it is (symz: its
+  // state; null on every other ctx).  P and theta are the base's.
+  SymzState* symz = nullptr;
   KernelPath path = PATH_FUSED;   // the kernel family (plan.hpp); vmc_debug_kernel_path reports it
   int N = 0, B = 0, L = 0, H = 0, Hp = 0;
   bool rbm = false;        // RestrictedBoltzmannNetwork instead of FullyConnectedNetwork
@@ -395,11 +400,18 @@ struct DeviceGuard {
   do { int rc_ = (expr); if (rc_ != VMC_OK) return rc_; } while (0)
 
 // a factor of a product ctx: its chains, accumulators and sampler state belong to the product
+// (the base of a symmetrized ctx likewise: they belong to the symmetrized ctx)
 #define REFUSE_COMPOSED(c) \
-  do { if ((c)->owner) return fail((c), VMC_ERR_STATE, "the ctx is a factor of a product ctx (vmc_create_product): its chain-state entries are the product's"); } while (0)
-// entries a product ctx does not have
+  do { if ((c)->owner) return fail((c), VMC_ERR_STATE, (c)->owner->symz \
+      ? "the ctx is the base of a symmetrized ctx (vmc_create_symmetrized): its chain-state entries are the symmetrized ctx's" \
+      : "the ctx is a factor of a product ctx (vmc_create_product): its chain-state entries are the product's"); } while (0)
+// entries a symmetrized ctx does not have
+#define REFUSE_SYMZ(c, what) \
+  do { if ((c)->symz) return fail((c), VMC_ERR_UNSUPPORTED, what " is not available on a symmetrized ctx ('symmetrized')"); } while (0)
+// entries a product ctx does not have (a symmetrized ctx has none of them either)
 #define REFUSE_PRODUCT(c, what) \
-  do { if ((c)->prod) return fail((c), VMC_ERR_UNSUPPORTED, what " is not available on a product ctx ('prod')"); } while (0)
+  do { if ((c)->prod) return fail((c), VMC_ERR_UNSUPPORTED, what " is not available on a product ctx ('prod')"); \
+       REFUSE_SYMZ(c, what); } while (0)
 // the PATH_PRODUCT arm of a switch no product ctx reaches (its entries go to the factors, which run their own paths)
 inline int product_has_none(vmc_ctx* c, const char* what) {
   return fail(c, VMC_ERR_STATE, std::string("prod: a product ctx has no ") + what + " of its own (its factors run theirs)");
@@ -658,6 +670,29 @@ void prod_chains_changed(vmc_ctx* c);
 void prod_child_params_changed(vmc_ctx* child, int which);
 void prod_release(vmc_ctx* c);                       // vmc_destroy of a product: the factors are free again
 void prod_child_destroyed(vmc_ctx* child);           // vmc_destroy of a factor that is still composed
+// vmc_api_symz.hip (the symmetrized ctx; every function takes the COMPOSITE unless named base)
+int symz_alive(vmc_ctx* c);                         // VMC_ERR_STATE (with the message) once the base has been destroyed
+int symz_ensure_cache(vmc_ctx* c, int which);
+int symz_local_energy(vmc_ctx* c, int which);
+int symz_run_sweep(vmc_ctx* c, const SweepCall& s);
+int symz_accumulate(vmc_ctx* c, int mode, float beta);
+int symz_set_bonds_check(vmc_ctx* c, int32_t n_bonds, const int32_t* ij, const float* j_x, const float* j_z);
+int symz_set_bonds(vmc_ctx* c, int32_t n_bonds, const int32_t* ij, const float* j_x, const float* j_z);
+int symz_set_params(vmc_ctx* c, int which, const float* theta);     // theta is the base's: the three forward
+int symz_get_params(vmc_ctx* c, int which, float* theta);
+int symz_transfer_params(vmc_ctx* c);
+int symz_adam_theta(vmc_ctx* c, float** theta);      // the buffer Adam runs on (the base's psi set)
+void symz_adam_applied(vmc_ctx* c);
+int symz_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, float* logit, float* psi);
+int symz_check_configs(vmc_ctx* c, const float* configs);     // vmc_set_configs: no row at a structural zero
+void symz_chains_changed(vmc_ctx* c);
+void symz_base_params_changed(vmc_ctx* base, int which);
+void symz_release(vmc_ctx* c);                       // vmc_destroy of a symmetrized ctx: the base is free again
+void symz_base_destroyed(vmc_ctx* base);             // vmc_destroy of a base that is still composed
+// the PATH_SYMMETRIZED arm of a switch no symmetrized ctx reaches (its entries go to the base, which runs its own path)
+inline int symmetrized_has_none(vmc_ctx* c, const char* what) {
+  return fail(c, VMC_ERR_STATE, std::string("symmetrized: a symmetrized ctx has no ") + what + " of its own (its base runs its)");
+}
 // vmc_api_measure.hip: what vmc_overlap and mode PENALIZED_ENERGY share -- the front of their refusals, and the ratio pass
 // and the fold over the two amplitude caches (ensure_cache of both sets has run) into c->ovl.out
 int overlap_refusals(vmc_ctx* c, const char* what);

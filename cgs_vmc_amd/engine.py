@@ -52,7 +52,8 @@ class VmcEngine:
                nonlinearity: str = 'relu', output_activation: str = 'exp', device: int = 0,
                chain_offset: int = 0, seed: int = 2024, stream: int = 0,
                ansatz: str = 'fully_connected', kernel_size: int = 0, size_x: int = 0,
-               size_y: int = 0, adjacency=None, lin_tables=None, children=None):
+               size_y: int = 0, adjacency=None, lin_tables=None, children=None, base=None, ops=None,
+               ops_digest=None):
     """Dense ansatz types: num_layers / layer_size = num_fc_layers / fc_layer_size.  Convolutional
     ones ('conv_2d', 'res_net_2d'): num_layers = num_conv_layers or num_resnet_blocks, layer_size =
     num_conv_filters, plus kernel_size and the lattice size_x x size_y (= n_sites).  'gnn':
@@ -64,10 +65,26 @@ class VmcEngine:
     entry until set_lin_tables is called.  'prod': `children`, the two factors' own keyword arguments (dicts, or
     tuples of sorted items as ProductOfWavefunctions._engine_spec carries them); the engine creates both factors as
     ordinary engines (self.children) with this engine's shape, device, seed and stream and composes them with
-    vmc_create_product.  num_params = a's + b's."""
+    vmc_create_product.  num_params = a's + b's.  'symmetrized': `base`, the base's own keyword arguments (a dict or a
+    tuple of sorted items), and `ops` = (perms int32 bytes, flips uint8 bytes, characters float64 bytes) as
+    SymmetrizedWavefunction._engine_spec carries them (`ops_digest` names them in comparisons of specs); the engine creates
+    the base with batch_size x n_ops rows and composes it (create_symmetrized)."""
     self._lib = _hip.load()
     self._ctx = C.c_void_p()
     self.children = ()
+    if ansatz == 'symmetrized':
+      if base is None or ops is None:
+        raise ValueError("the 'symmetrized' ansatz needs the spec of its base and its ops")
+      perms = np.frombuffer(ops[0], dtype=np.int32).reshape(-1, n_sites)
+      made = VmcEngine(n_sites=n_sites, batch_size=batch_size * perms.shape[0], device=device, chain_offset=chain_offset,
+                       seed=seed, stream=stream, **dict(base))
+      try:
+        self._init_symmetrized(made, batch_size, perms, np.frombuffer(ops[1], dtype=np.uint8),
+                               np.frombuffer(ops[2], dtype=np.float64))
+      except Exception:
+        made.close()
+        raise
+      return
     if ansatz == 'prod':
       self._init_product(n_sites, batch_size, device, chain_offset, seed, stream, children)
       return
@@ -157,6 +174,56 @@ class VmcEngine:
     self.num_params = made[0].num_params + made[1].num_params
     self.n_bonds = 0
 
+  @classmethod
+  def create_symmetrized(cls, base_engine: 'VmcEngine', batch_size: int, perms, flips=None, characters=None):
+    """The symmetrized ansatz psi_s(x) = sum_k chi_k psi(g_k x) over `batch_size` chains (vmc_create_symmetrized).
+    `base_engine`: an ordinary engine of batch_size x n_ops rows; the new engine borrows it (self.children = (base,)) and
+    closes it after itself, as a 'prod' engine does its factors.  perms [n_ops][n_sites] int, flips [n_ops] 0 / 1 or None,
+    characters [n_ops] float64 (None: the trivial sector, all ones).  The parameters are the base's: set_params /
+    get_params on either engine reach the same floats."""
+    self = cls.__new__(cls)
+    self._init_symmetrized(base_engine, batch_size, perms, flips, characters)
+    return self
+
+  def _init_symmetrized(self, base_engine, batch_size, perms, flips, characters):
+    """Fills this (empty) engine as the composite over `base_engine`: what create_symmetrized and the 'symmetrized'
+    branch of __init__ share.  Raises before anything of `self` is registered when the library refuses."""
+    perms = np.ascontiguousarray(np.asarray(perms, dtype=np.int32))
+    if perms.ndim != 2 or perms.shape[1] != base_engine.n_sites:
+      raise ValueError('perms must have shape [n_ops, n_sites]')
+    n_ops = perms.shape[0]
+    fl = None
+    if flips is not None:
+      fl = np.ascontiguousarray(np.asarray(flips, dtype=np.uint8).ravel())
+      if fl.size != n_ops:
+        raise ValueError('flips must have one entry per op')
+    chi = np.ones(n_ops, np.float64) if characters is None else \
+        np.ascontiguousarray(np.asarray(characters, dtype=np.float64).ravel())
+    if chi.size != n_ops:
+      raise ValueError('characters must have one entry per op')
+    self._lib = base_engine._lib
+    self._ctx = C.c_void_p()
+    self.children = ()
+    rc = self._lib.vmc_create_symmetrized(
+        base_engine._ctx, int(batch_size), n_ops, _iptr(perms),
+        fl.ctypes.data_as(C.POINTER(C.c_uint8)) if fl is not None else None,
+        chi.ctypes.data_as(C.POINTER(C.c_double)), C.byref(self._ctx))
+    if rc != _hip.VMC_OK:
+      msg = self._lib.vmc_last_error(None).decode()
+      self._ctx = C.c_void_p()
+      self._raise(rc, msg)
+    self.children = (base_engine,)
+    _LIVE_ENGINES.add(self)
+    self.n_sites, self.batch_size = base_engine.n_sites, int(batch_size)
+    self.num_layers, self.layer_size = 0, 0
+    self.chain_offset, self.seed, self.device = base_engine.chain_offset, base_engine.seed, base_engine.device
+    self.stream = base_engine.stream
+    self.ansatz = 'symmetrized'
+    self.kernel_size, self.size_x, self.size_y = 0, 0, 0
+    self.num_params = base_engine.num_params
+    self.n_bonds = base_engine.n_bonds
+    self.n_ops = n_ops
+
   # ------------------------------------------------------------------ plumbing
   @staticmethod
   def _raise(rc, msg):
@@ -169,7 +236,8 @@ class VmcEngine:
   def _check(self, rc):
     if rc != _hip.VMC_OK:
       msg = self._lib.vmc_last_error(self._ctx).decode()
-      if rc == _hip.VMC_ERR_STATE and 'factor of a product ctx' in msg:     # (REFUSE_COMPOSED, csrc/vmc_ctx.hpp)
+      if rc == _hip.VMC_ERR_STATE and ('factor of a product ctx' in msg or
+                                       'base of a symmetrized ctx' in msg):     # (REFUSE_COMPOSED, csrc/vmc_ctx.hpp)
         raise _hip.ComposedFactorError('libcgsvmc_hip error {}: {}'.format(rc, msg))
       self._raise(rc, msg)
 

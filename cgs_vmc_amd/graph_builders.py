@@ -111,10 +111,39 @@ class ConfigsVariable:
           device=parallel.local_rank(), chain_offset=self.chain_offset, seed=seed,
           **wavefunction._engine_spec())
       self._engine_spec = wavefunction._engine_spec()
+      if self._engine_spec.get('ansatz') == 'symmetrized':
+        # (a symmetrized ctx evaluates the rows it is given: the base's parameters go first)
+        theta = wavefunction._base._theta
+        if theta is not None:
+          self._engine.set_params(theta, _hip.VMC_PSI)
+        self._redraw_structural_zeros()
       self._engine.set_configs(self._host_value)
     elif self._engine_spec != wavefunction._engine_spec():
       raise ValueError('a CONFIGS variable serves one ansatz shape (psi and its deep copy)')
     return self._engine
+
+  def _redraw_structural_zeros(self, max_rounds: int = 64):
+    """A symmetrized ctx refuses initial chains at a structural zero of its sector (psi_s = 0 whatever the parameters:
+    an op with character -1 maps the row onto itself).  The rows set_configs would refuse are drawn again -- host rows,
+    checked with the engine's own amplitude -- for at most `max_rounds` rounds; a state that has no weight in the sector
+    never gets there and is a ValueError.  (The base's parameters must be on the engine: initialised or restored.)"""
+    try:
+      psi = self._engine.amplitude(self._host_value)[1]
+    except _hip.HipLibraryError as e:
+      if 'parameters not set' not in str(e):
+        raise
+      return                          # no parameters yet: the first set_configs after they arrive names any zero
+    rng_seed = None if self._seed is None else self._seed + self.chain_offset + 7919
+    for round_ in range(max_rounds):
+      zero = np.flatnonzero(psi == 0)
+      if zero.size == 0:
+        return
+      fresh = utils.random_configurations(self.shape[1], zero.size, None if rng_seed is None else rng_seed + round_)
+      self._host_value[zero] = fresh
+      psi[zero] = self._engine.amplitude(fresh)[1]
+    if (psi == 0).any():
+      raise ValueError('symmetrized: after {} rounds of redrawing, {} of {} initial chains are still at a structural zero: '
+                       'the state has no weight in this sector'.format(max_rounds, int((psi == 0).sum()), psi.size))
 
   def _claim_slot(self, wavefunction) -> int:
     for which in (_hip.VMC_PSI, _hip.VMC_OMEGA):

@@ -1037,6 +1037,146 @@ class ProductOfWavefunctions(Wavefunction):
     raise ValueError('Hparams initialization is not supported for product.')
 
 
+class SymmetrizedWavefunction(Wavefunction):
+  """psi_s(x) = sum_k chi_k psi(g_k x) (extension): the base ansatz projected onto one symmetry sector, sampled from
+  |psi_s|^2 and trained with its own log-derivatives.  g_k: row[i] = f_k x[perms[k][i]] (lattice.translations,
+  lattice.point_group; f_k = -1 where flips[k]), chi: the real characters of the sector (one row of
+  lattice.sector_characters; None: all ones).  One engine serves it: the base is an ordinary ctx of batch_size x n_ops rows
+  composed by vmc_create_symmetrized (csrc/vmc_api_symz.hip), which owns the chains; the base stays bound to its own ctx
+  for its variables and its shift.  The variables ARE the base's, under the base's own scope: a checkpoint of a
+  symmetrized run loads into the plain base type and the other way round.  No exp_norm_shift of its own: normalize_batch
+  / update_norm return None (the library folds in the log domain, nothing overflows)."""
+  _ansatz = 'symmetrized'
+
+  def __init__(self, base: Wavefunction, perms, flips=None, characters=None, name: str = 'symmetrized_wavefunction'):
+    from . import lattice
+    if not isinstance(base, Wavefunction):
+      raise NotImplementedError('symmetrized: the base must be a wavefunction')
+    if isinstance(base, (ProductOfWavefunctions, SymmetrizedWavefunction)):
+      raise NotImplementedError('symmetrized: a product or a symmetrized wavefunction cannot be the base')
+    if not isinstance(base, FullyConnectedNetwork) or base._ansatz not in ('fully_connected', 'rbm', 'pbdg', 'ed_vector'):
+      raise NotImplementedError('symmetrized: a base of type %s has no HIP kernels (fully_connected, rbm, pbdg and '
+                                'ed_vector are taken)' % type(base).__name__)
+    p = np.asarray(perms)
+    if p.ndim == 1 and p.size:
+      p = p.reshape(1, -1)
+    if p.ndim != 2:
+      raise ValueError('symmetrized: perms must have shape [n_ops, n_sites]')
+    self._perms, flip = lattice.check_symmetry_ops(p, flips, p.shape[1])
+    if self._perms.shape[0] > 1024:
+      raise ValueError('symmetrized: at most 1024 ops')
+    self._flips = None if flips is None else flip
+    n_ops = self._perms.shape[0]
+    chi = np.ones(n_ops) if characters is None else np.asarray(characters, np.float64)
+    if chi.ndim != 1 or chi.size != n_ops:
+      raise ValueError('symmetrized: one character per op required ({} for {} ops)'.format(chi.size, n_ops))
+    chi = lattice.check_characters(chi, n_ops)[0]
+    if not chi.any():
+      raise ValueError('symmetrized: every character is zero')
+    self._characters = None if characters is None else chi
+    self._chi = chi
+    if not name.startswith('dc_'):      # (a deep copy keeps the dc_<name> its original's __deepcopy__ chose)
+      name = 'symmetrized_' + base._unique_name
+    super(SymmetrizedWavefunction, self).__init__(name=name)
+    self._base = base
+    self._sub_wavefunctions += [base]
+
+  # omega = copy.deepcopy(psi): Wavefunction.__deepcopy__ rebuilds it from a deep copy of _base and the same ops
+
+  @property
+  def n_ops(self) -> int:
+    return int(self._perms.shape[0])
+
+  @property
+  def _has_values(self):
+    return self._base._has_values
+
+  @_has_values.setter
+  def _has_values(self, value):
+    self._base._has_values = value
+
+  @property
+  def _theta(self):
+    return None
+
+  @_theta.setter
+  def _theta(self, value):
+    if value is not None:
+      raise ValueError('symmetrized: the parameters live in the base')
+    if self._base._engine is not None:
+      self._base._theta = None
+
+  def ops_digest(self) -> str:
+    import hashlib
+    h = hashlib.sha256()
+    for a in self._ops_bytes():
+      h.update(a)
+    return h.hexdigest()
+
+  def _ops_bytes(self):
+    flips = np.zeros(self.n_ops, np.uint8) if self._flips is None else self._flips
+    return (np.ascontiguousarray(self._perms, np.int32).tobytes(), np.ascontiguousarray(flips, np.uint8).tobytes(),
+            np.ascontiguousarray(self._chi, np.float64).tobytes())
+
+  def _engine_spec(self):
+    freeze = lambda spec: tuple(sorted(spec.items()))
+    return dict(ansatz='symmetrized', num_layers=0, layer_size=0, base=freeze(self._base._engine_spec()),
+                ops=self._ops_bytes(), ops_digest=self.ops_digest())
+
+  def _bind(self, configs_var):
+    from . import parallel
+    if parallel.is_distributed():
+      raise NotImplementedError("a symmetrized wavefunction runs on one rank: a symmetrized ctx has no sharded entries")
+    spec = self._base._engine_spec()
+    if spec.get('ansatz') in ('fully_connected', 'rbm') and spec.get('output_activation') != 'exp':
+      raise NotImplementedError("symmetrized: a dense base needs the exp output activation (%s has %r)"
+                                % (self._base._unique_name, spec.get('output_activation')))
+    n_sites = configs_var.shape[1]
+    if self._perms.shape[1] != n_sites:
+      raise ValueError('symmetrized: the ops permute {} sites, the configurations have {}'.format(self._perms.shape[1], n_sites))
+    base = self._base
+    if base._n_sites is not None and base._n_sites != n_sites:
+      raise ValueError('Input tensor has wrong shape.')
+    base._n_sites = n_sites
+    base._shapes()                       # (the base's own shape checks, before an engine is asked for)
+    if base._engine is None and base._theta is None and not base._has_values:
+      base._maybe_initialize()           # (the symmetrized ctx evaluates its initial chains: it needs parameters to do so)
+    engine = configs_var._get_engine(self)
+    if self._engine is engine:
+      return engine
+    if self._engine is not None:
+      raise ValueError('wavefunction %s is already bound to another CONFIGS variable' % self._unique_name)
+    which = configs_var._claim_slot(self)
+    self._engine, self._which = engine, which
+    child = engine.children[0]
+    if base._engine is not None and base._engine is not child:
+      raise ValueError('wavefunction %s is already bound to another CONFIGS variable' % base._unique_name)
+    host_theta = base._theta
+    base._engine, base._which = child, which
+    if host_theta is not None:
+      child.set_params(host_theta, which)
+      base._theta = None
+    if base._exp_norm_shift is not None:
+      child.set_shift(float(base._exp_norm_shift), which)
+    return engine
+
+  def _build(self, inputs) -> session_lib.Tensor:
+    from . import graph_builders
+    if isinstance(inputs, graph_builders.ConfigsVariable):
+      return AmplitudeTensor(self, self._bind(inputs), None)
+    arr = np.asarray(inputs, np.float32)
+    if arr.ndim != 2 or arr.shape[1] != self._perms.shape[1]:
+      raise ValueError('Input tensor has wrong shape.')
+    if self._engine is None:
+      raise ValueError('apply the wavefunction to the CONFIGS variable first '
+                       '(graph_builders.get_configs) so that it is bound to a GPU engine')
+    return AmplitudeTensor(self, self._engine, arr)
+
+  @classmethod
+  def from_hparams(cls, hparams, name: str = ''):
+    raise ValueError('Hparams initialization is not supported for a symmetrized wavefunction.')
+
+
 class AmplitudeTensor(session_lib.Tensor):
   """psi = wavefunction(inputs); evaluates to a float32 array [rows]."""
 

@@ -97,7 +97,8 @@ enum { VMC_MODE_ENERGY_GRADIENT = 0, VMC_MODE_LOG_OVERLAP_ITSWO = 1 };
 enum { VMC_ANSATZ_FULLY_CONNECTED = 0, VMC_ANSATZ_RBM = 1, VMC_ANSATZ_CONV_2D = 2,
        VMC_ANSATZ_RES_NET_2D = 3, VMC_ANSATZ_CONV_1D = 4, VMC_ANSATZ_RES_NET_1D = 5,
        VMC_ANSATZ_GNN = 6, VMC_ANSATZ_PBDG = 7, VMC_ANSATZ_NNB = 9 /* 8 is unassigned */, VMC_ANSATZ_ED_VECTOR = 10,
-       VMC_ANSATZ_PRODUCT = 11 /* vmc_create_product only: vmc_create refuses it (VMC_ERR_INVALID) */ };
+       VMC_ANSATZ_PRODUCT = 11 /* vmc_create_product only: vmc_create refuses it (VMC_ERR_INVALID) */,
+       VMC_ANSATZ_SYMMETRIZED = 13 /* vmc_create_symmetrized only: vmc_create refuses it (VMC_ERR_INVALID); 12 is unassigned */ };
 
 /* layers.NONLINEARITIES ids (layers.py:13-21).  Every id is accepted as hidden and as output
  * activation of every ansatz type with kernels. */
@@ -165,6 +166,34 @@ int vmc_create(const vmc_desc* desc, vmc_ctx** out);
  * entry with world_size > 1, the reduce hooks, vmc_debug_sweep_profile, vmc_debug_sweep_tile and vmc_debug_conv_patch
  * return VMC_ERR_UNSUPPORTED.  The vmc_timing_* entries report the product's own regions ("sweep", "eloc_reduce", "grad"). */
 int vmc_create_product(vmc_ctx* a, vmc_ctx* b, vmc_ctx** out);
+/* The symmetrized ansatz (extension): psi_s(x) = sum_k chi_k psi(g_k x) over ONE set of batch_size chains, sampled from
+ * |psi_s|^2 and trained with its own log-derivatives.  g_k: row_k[i] = f_k x[perms[k][i]], f_k = -1 where flips[k] (NULL: no
+ * flips), as in vmc_symmetry_expectations; characters [n_ops]: the real characters chi_k of one sector.  The base is an
+ * ordinary ctx of batch_size x n_ops rows (VMC_ERR_INVALID otherwise, both numbers named) that the symmetrized ctx borrows
+ * as a product borrows its factors: fully_connected and rbm (every width, exp output only), pbdg or ed_vector; everything
+ * else, a product and a symmetrized ctx are refused (VMC_ERR_UNSUPPORTED), a base that is already composed with
+ * VMC_ERR_STATE.  1 <= n_ops <= 1024, every perm a bijection, every character finite and not all zero (VMC_ERR_INVALID).
+ * With flips, or a signed base, every configuration needs Sz = 0.
+ * The base holds the permuted rows (row = k batch_size + chain) as its chains and does all network arithmetic; theta IS the
+ * base's (vmc_set_params / vmc_get_params / vmc_transfer_params on either ctx reach the same floats), P = the base's; the
+ * symmetrized ctx owns the chains, the step counter, the accumulators [2 P + 8] and the Adam state.  While composed the base's
+ * chain-state entries return VMC_ERR_STATE; vmc_destroy of the symmetrized ctx frees it again, vmc_destroy of the base first
+ * leaves a symmetrized ctx whose every entry returns VMC_ERR_STATE.
+ * vmc_amplitude: per row, in fp64 with the ops ascending, m = max_k ln|psi(g_k x)| over the ops with chi_k != 0 and a
+ * nonzero amplitude, S = sum_k chi_k s_k exp(l_k - m), A = sum_k |chi_k| exp(l_k - m); logit = (m + ln|S|) - shift_base,
+ * psi = sgn(S) exp(logit) (ed_vector base: psi = sum_k chi_k psi_k itself).  Where |S| <= 2^-40 A the row is at a structural
+ * zero of the sector: psi = 0, logit = -inf.  vmc_get_shift returns 0, vmc_set_shift VMC_ERR_INVALID, vmc_update_norm
+ * changes nothing.  vmc_set_configs refuses a batch with a row at a structural zero (VMC_ERR_INVALID, the row named; if every
+ * row is, the message says that the state has no weight in this sector) and leaves the chains untouched; the sampler rejects
+ * every candidate at a zero, so no chain is ever at one.  vmc_set_bonds forwards to the base and refuses a bond set the ops
+ * do not map onto itself (VMC_ERR_INVALID, op and bond named, as vmc_projected_energy).
+ * Local energies: E_s(x) = sum_k c_k E_loc^psi(g_k x) with c_k = chi_k psi(g_k x) / psi_s(x); gradient sums likewise over
+ * O(g_k x).  The connected-row count is the base's, over all ops.  Modes 1 and 2 of vmc_accumulate, vmc_epoch_log_overlap,
+ * the vmc_sr_* entries, the _dist entries, every entry with world_size > 1, the reduce hooks, the measurement entries,
+ * vmc_create_product with a symmetrized factor, vmc_debug_sweep_profile, vmc_debug_sweep_tile and vmc_debug_conv_patch
+ * return VMC_ERR_UNSUPPORTED.  vmc_timing_* regions: "sweep", "symz_rows", "symz_fold", "eloc_fold", "grad". */
+int vmc_create_symmetrized(vmc_ctx* base, int32_t batch_size, int32_t n_ops, const int32_t* perms /*[n_ops][N]*/,
+                           const uint8_t* flips /*[n_ops] or NULL*/, const double* characters /*[n_ops]*/, vmc_ctx** out);
 void vmc_destroy(vmc_ctx* ctx);
 const char* vmc_last_error(const vmc_ctx* ctx); /* ctx may be NULL: last create error */
 
