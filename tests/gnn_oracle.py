@@ -70,6 +70,51 @@ def honeycomb_adjacency(lx, ly):
   return np.asarray(adj, np.int32)
 
 
+def ring_adjacency(n):
+  """Self and the next site of a ring (k = 2, the smallest table the planner takes)."""
+  return np.stack([np.arange(n), (np.arange(n) + 1) % n], 1).astype(np.int32)
+
+
+def random_adjacency(n, k, rng, self_first=False):
+  """Entries uniform over the sites (repeats within a row, uneven in-degrees); self_first: column 0 is the site."""
+  adj = rng.integers(0, n, size=(n, k)).astype(np.int32)
+  if self_first:
+    adj[:, 0] = np.arange(n)
+  return adj
+
+
+def hub_adjacency(n, k):
+  """Column 0 is the site, every other tap of every row is site 0: one inverse list of n (k - 1) + 1 entries next to
+  n - 1 lists of one."""
+  adj = np.zeros((n, k), np.int32)
+  adj[:, 0] = np.arange(n)
+  return adj
+
+
+def empty_list_adjacency(n, k, n_read, rng):
+  """The last n - n_read sites appear in NO row (empty inverse lists: their input gradient is 0): rows of the first
+  n_read sites are the site and k - 1 uniform draws below n_read, the other rows k uniform draws below n_read."""
+  adj = rng.integers(0, n_read, size=(n, k)).astype(np.int32)
+  adj[:n_read, 0] = np.arange(n_read)
+  return adj
+
+
+def irregular_adjacency():
+  """12 sites, k = 5: repeated entries within a row, tap columns that are not permutations (site 0 is read by
+  many taps, sites 10 / 11 by few), a site nobody reads but itself (k_gnn_col2im's uneven inverse lists)."""
+  rng = np.random.default_rng(5)
+  adj = rng.integers(0, 10, size=(12, 5)).astype(np.int32)
+  adj[:, 0] = np.arange(12)
+  adj[::3, 2] = 0
+  adj[1, 3] = adj[1, 4] = 7
+  return adj
+
+
+def in_degree(adj):
+  """How many (position, tap) pairs read each site: the lengths of plan_gnn_inverse's lists."""
+  return np.bincount(np.asarray(adj).ravel(), minlength=np.asarray(adj).shape[0])
+
+
 def adjacency_bonds(adj):
   """The distinct undirected pairs (i, j), i != j, of a table."""
   bonds = set()
@@ -129,7 +174,7 @@ def gnn_forward(theta, configs, adj, f, num_layers, nonlinearity='relu', dtype=n
   act = vo.NONLINEARITIES[nonlinearity]
   tape = []
   for l, (w, b) in enumerate(layers_):
-    z = np.einsum('bntc,tco->bno', a[:, adj], w) + b
+    z = np.einsum('bntc,tco->bno', a[:, adj], w, optimize=True) + b
     tape.append((a, z))
     a = act(z) if l + 1 != num_layers else z
   logit = a.reshape(a.shape[0], -1).sum(1)
@@ -168,9 +213,9 @@ def gnn_weighted_grads(theta, configs, weights, adj, f, num_layers, nonlinearity
       a_in, _ = tape[l]
       xg = a_in[:, adj]                                          # [B, N, k, Cin]
       w, _ = layers_[l]
-      grads[l] = (np.einsum('bntc,bno->tco', xg, delta)[None], delta.sum((0, 1)))
+      grads[l] = (np.einsum('bntc,bno->tco', xg, delta, optimize=True)[None], delta.sum((0, 1)))
       if l > 0:
-        dxg = np.einsum('bno,tco->bntc', delta, w)
+        dxg = np.einsum('bno,tco->bntc', delta, w, optimize=True)
         dx = np.zeros_like(a_in)
         for t in range(adj.shape[1]):
           np.add.at(dx, (slice(None), adj[:, t]), dxg[:, :, t])

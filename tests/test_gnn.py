@@ -10,6 +10,7 @@ import pytest
 from cgs_vmc_amd import session, utils, wavefunctions
 from oracle import vmc_oracle as vo
 from tests import gnn_oracle as go
+from tests import gnn_shape_cases as gsc
 
 
 def _hparams(tmp_path, adj, **kw):
@@ -111,3 +112,112 @@ def test_gnn_oracle_on_the_stencil_is_the_conv_2d_oracle(sx, sy, k, L, f, nonlin
   w = np.random.default_rng(3).standard_normal((9, 2))
   ref_g = vo.ANSATZ['conv_2d'][2](theta, cfg, w, (f, k, sx, sy), L, nonlin, np.float64)
   np.testing.assert_allclose(go.gnn_weighted_grads(theta, cfg, w, adj, f, L, nonlin), ref_g, rtol=1e-10, atol=1e-10)
+
+
+# ---------------------------------------------------------------------------- the inputs of tests/test_gpu_gnn_shapes.py
+def _all_tables():
+  names = sorted({c['graph'] for c in list(gsc.EDGE_CASES.values()) + list(gsc.BLOCK_CASES.values()) + gsc.SAMPLER_CASES})
+  tables = [(name, gsc.graph(name)[0]) for name in names + [gsc.BIG_GRAPH]]
+  return tables + [('random-%d' % i, gsc.random_table(s[0], s[1], s[6])) for i, s in enumerate(gsc.RANDOM_GRAPHS)]
+
+
+def test_gnn_shape_tables_are_in_range_and_keep_their_properties():
+  for name, adj in _all_tables():
+    n, k = adj.shape
+    assert adj.dtype == np.int32 and 2 <= k <= 64 and n % 2 == 0, name
+    assert adj.min() >= 0 and adj.max() < n, name
+    wavefunctions.check_adjacency(adj, n)
+    deg = go.in_degree(adj)
+    assert deg.shape == (n,) and deg.sum() == n * k, name
+    # the inverse lists (plan_gnn_inverse: entries m k + t of site s, position-major) have these lengths
+    flat = adj.ravel()
+    for s in range(n):
+      assert deg[s] == np.flatnonzero(flat == s).size, (name, s)
+    assert len(gsc.graph(name)[1] if not name.startswith('random-') else go.adjacency_bonds(adj)) > 0, name
+  ring = gsc.graph('ring-10')[0]
+  assert ring.tolist() == [[i, (i + 1) % 10] for i in range(10)]
+  hub = gsc.graph('hub-16')[0]
+  assert hub.shape == (16, 5) and (hub[:, 0] == np.arange(16)).all() and (hub[:, 1:] == 0).all()
+  assert go.in_degree(hub).tolist() == [16 * 4 + 1] + [1] * 15          # a site read by almost every (position, tap)
+  empty = gsc.graph('empty-14')[0]
+  assert empty.shape == (14, 5) and (go.in_degree(empty)[12:] == 0).all() and (go.in_degree(empty)[:12] > 0).all()
+  assert (empty[:12, 0] == np.arange(12)).all() and empty[12:].max() < 12    # rows 12 / 13 omit the site itself
+  wide = gsc.graph('wide-20')[0]
+  assert wide.shape == (20, 64) and (wide[:, 0] == np.arange(20)).all()
+  deep = gsc.graph('random-30')[0]
+  assert deep.shape == (30, 6) and (deep != np.arange(30)[:, None]).all(1).any()      # rows that omit the site itself
+  assert gsc.graph('triangular-8x8')[0].shape == (64, 7)
+
+
+def test_gnn_random_graph_shapes_cover_the_ranges():
+  shapes = gsc.RANDOM_GRAPHS
+  assert len(shapes) == 12 and shapes == gsc.random_graph_shapes(12)
+  for i, (n, k, f, L, b, nonlin, _) in enumerate(shapes):
+    assert n % 2 == 0 and 4 <= n <= 60 and 2 <= k <= 12 and 1 <= L <= 3 and 1 <= b <= 24 and nonlin in gsc.ACTS
+    assert (64 <= f <= 100) if i % 2 else (1 <= f <= 13)
+  assert {s[3] for s in shapes} == {1, 2, 3}
+  for n, k, f, L, b, nonlin, table_seed in shapes:       # conditioning: logits and proposal ratios of moderate size
+    theta, cfg = gsc.random_graph_inputs(n, k, f, L, b)
+    adj = gsc.random_table(n, k, table_seed)
+    assert theta.size == go.gnn_num_params(k, f, L) and cfg.shape == (b, n)
+    assert np.abs(go.gnn_forward(theta, cfg, adj, f, L, nonlin)).max() < 60.0
+    u_sites, u_acc = vo.step_uniforms(5, np.arange(b), 0, n)
+    i_up, i_dn = vo.propose_exchange(cfg, u_sites)
+    ratios = vo.mc_step(lambda c: go.gnn_psi(theta, c, adj, f, L, -10.0, nonlin), cfg, i_up, i_dn, u_acc)[2]
+    assert 1e-8 < ratios.min() and ratios.max() < 1e8, (n, k, f, ratios.min(), ratios.max())
+  assert any(s[2] % 4 for s in shapes) and any(s[2] % 4 == 0 for s in shapes)         # both VEC forms
+
+
+@pytest.mark.parametrize('cid', gsc.EDGE_IDS + list(gsc.BLOCK_CASES))
+def test_gnn_edge_cases_keep_three_quarters_of_the_chains_outside_the_tie_band(cid):
+  """The GPU comparison of the 12 sampler steps leaves out chains within 1e-4 of a tie and asks that more than half
+  remain; on the oracle alone at least three quarters do, so that cap cannot hide a failure."""
+  case = gsc.EDGE_CASES.get(cid) or gsc.BLOCK_CASES[cid]
+  theta, cfg, adj, _ = gsc.inputs(case)
+  cur, ok = gsc.oracle_steps(theta, cfg, adj, case['f'], case['L'], case['nonlin'], case.get('oact', 'exp'))
+  assert 4 * ok.sum() >= 3 * case['b'], (int(ok.sum()), case['b'])
+  assert (cur.sum(1) == 0).all() and (cur != cfg).any()
+
+
+def test_gnn_big_launches_cross_their_caps():
+  """Item counts of the launches tests/test_gpu_gnn_shapes.py means to push past a grid cap, from the configurations and
+  bonds alone; each is one block (create_conv_general's rule at 256 CUs)."""
+  adj, bonds = gsc.graph(gsc.BIG_GRAPH)
+  n, k = adj.shape
+  for case in gsc.IM2COL_CASES:
+    _, cfg, _, _ = gsc.big_inputs(case['f'], case['b'])
+    assert cfg.shape == (case['b'], n) and (cfg.sum(1) == 0).all() and (np.abs(cfg) == 1).all()
+    rows = gsc.connected_rows(cfg, bonds)
+    assert gsc.im2col0_items(rows, n, k) > 16384 * 256
+    assert rows * n > gsc.im2col_positions_cap(k, case['f'])
+    assert rows <= gsc.cgen_block_rows(n, k, case['f'], gsc.BIG_L, case['b'])
+  assert gsc.im2col_positions_cap(7, 12) == 65536 * 25 and gsc.im2col_positions_cap(7, 6) == 65536 * 13
+  for case in gsc.COL2IM_CASES:
+    items = gsc.col2im_items(case['b'], n, case['f'])
+    assert (items > 16384 * 256) == case['crosses']
+    assert case['b'] <= gsc.cgen_block_rows(n, k, case['f'], gsc.BIG_L, case['b']) and case['b'] % gsc.SMALL == 0
+  assert gsc.col2im_items(11008, 64, 6) == 4227072 and gsc.col2im_items(8256, 64, 8) == 1056768 and gsc.col2im_items(32832, 64, 8) == 4202496
+  assert gsc.cgen_lda(7, 12, 2) == 84 and gsc.cgen_lda(7, 10, 1) == 8 and gsc.cgen_block_rows(64, 7, 12, 2, 320) == 37376
+
+
+def test_gnn_shape_case_constants_are_the_sources():
+  """tests/gnn_shape_cases.py restates grid caps and thresholds that no entry of the C ABI reports; the 'past the cap'
+  assertions of the GPU tests mean something only while the two agree, so each is read back out of the source line that
+  sets it: whoever changes a cap there is sent to the test inputs."""
+  csrc = os.path.join(os.path.dirname(os.path.abspath(wavefunctions.__file__)), 'csrc')
+  read = lambda name: open(os.path.join(csrc, name)).read()
+  general, grad, cgen, api = read('conv_general.hip'), read('grad.hip'), read('vmc_api_cgen.hip'), read('vmc_api.hip')
+  cap = str(gsc.CG_BLOCKS_CAP)
+  assert 'int cg_blocks(long long n) { const long long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b < %s ? b : %s)); }' % (cap, cap) in general
+  assert 'const dim3 grid((unsigned)(blocks < %d ? blocks : %d));' % (gsc.IM2COL_GRID_CAP, gsc.IM2COL_GRID_CAP) in general
+  assert 'const int ppb = (int)(items >= 512 ? 1 : (512 + items - 1) / items);' in general
+  assert '#define GEMM_RING_MIN %d\n' % gsc.GEMM_RING_MIN in grad and '#define G2_TM %d\n' % gsc.GEMM_TILE_ROWS in grad
+  assert 'm.splitk = M >= %d ? CGEN_SPLITK : 1;' % gsc.SPLITK_MIN in cgen
+  # cgen_block_rows: the lines of create_conv_general it follows
+  for line in ('long long block_mb = 768;',
+               'if (rows > (1LL << 30) / cg.N) rows = (1LL << 30) / cg.N;',
+               'if (rows > (B > 65536 ? B : 65536)) rows = B > 65536 ? B : 65536;',
+               'if (rows * cg.N / 128 >= 2LL * c->num_cus) {',
+               'rows = rounds * 128LL * c->num_cus / cg.N;'):
+    assert line in api, line
+  assert 'return (g.K * g.KW * (g.n_conv > 1 ? g.F : 1) + 3) & ~3; }' in read('plan.hpp')

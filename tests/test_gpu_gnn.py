@@ -10,20 +10,13 @@ import pytest
 from cgs_vmc_amd import _hip
 from oracle import vmc_oracle as vo
 from tests import gnn_oracle as go
+from tests import gnn_shape_cases as gsc
 from tests.test_gpu_conv import _close
 
 pytestmark = pytest.mark.gpu
 
 
-def _irregular_adjacency():
-  """12 sites, k = 5: repeated entries within a row, tap columns that are not permutations (site 0 is read by
-  many taps, sites 10 / 11 by few), a site nobody reads but itself (k_gnn_col2im's uneven inverse lists)."""
-  rng = np.random.default_rng(5)
-  adj = rng.integers(0, 10, size=(12, 5)).astype(np.int32)
-  adj[:, 0] = np.arange(12)
-  adj[::3, 2] = 0
-  adj[1, 3] = adj[1, 4] = 7
-  return adj
+_irregular_adjacency = go.irregular_adjacency
 
 
 GRAPHS = {
@@ -97,6 +90,60 @@ def test_gnn_on_the_periodic_stencil_is_conv_2d_bit_for_bit(monkeypatch):
   np.testing.assert_array_equal(a1[2 * p:], a0[2 * p:])
 
 
+def _check_forward(eng, theta, cfg, adj, f, L, nonlin, b2=13):
+  """Amplitudes of the chains (the cached path) and of a second batch of another size against fp64."""
+  _logits_close(eng.amplitude()[0], theta, cfg, adj, f, L, nonlin)
+  c2 = vo.random_configurations(adj.shape[0], b2, np.random.RandomState(9))
+  _logits_close(eng.amplitude(c2)[0], theta, c2, adj, f, L, nonlin)
+
+
+def _check_local_energy(eng, theta, cfg, adj, bonds, f, L, nonlin, oact, scaled=False):
+  """scaled: the bound of tests/test_gpu_conv_general.py::test_general_convolution_random_shapes, which follows the
+  logits' rounding where sum |last map| is large."""
+  amp = lambda c: go.gnn_psi(theta, c, adj, f, L, -10.0, nonlin, oact)
+  rel = 2e-4
+  if scaled:
+    rel = max(2e-4, 4e-6 * float(np.max(go.gnn_forward(theta, cfg, adj, f, L, nonlin, return_tape='scale')[1])))
+  _close(eng.local_energy()[0], vo.local_value(amp, cfg, bonds, -1.0, 1.0, dtype=np.float64), rel)
+
+
+def _check_sampler_steps(eng, theta, cfg, adj, f, L, nonlin, oact):
+  """12 steps against the oracle's sampler on the same Philox streams (chains within 1e-4 of a tie excluded); returns
+  the engine's chains."""
+  b = cfg.shape[0]
+  eng.step_counter = 0
+  cur, ok = gsc.oracle_steps(theta, cfg, adj, f, L, nonlin, oact)
+  eng.mc_steps(gsc.STEPS)
+  got = eng.get_configs()
+  np.testing.assert_array_equal(got[ok], cur[ok])
+  assert ok.sum() > b // 2 and (got.sum(1) == cfg.sum(1)).all()
+  return got
+
+
+def _check_energy_gradient(eng, theta, got, adj, bonds, f, L, nonlin, oact):
+  """EnergyGradient accumulators (training.py:539-558) of the chains `got`."""
+  acc = vo.Accumulators(theta.size, np.float64)
+  go.energy_gradient_accumulate(acc, theta, got, bonds, -1.0, 1.0, -10.0, adj, f, L, nonlin, oact)
+  eng.reset_accumulators()
+  eng.accumulate(_hip.VMC_MODE_ENERGY_GRADIENT)
+  res = eng.get_accumulators()
+  _acc_close(res, acc, theta.size)
+  assert abs(res[2 * theta.size] - acc.e_total) < 2e-4 * max(1, abs(acc.e_total))
+
+
+def _check_log_overlap(eng, theta, theta_w, got, adj, bonds, f, L, nonlin, oact):
+  """LogOverlapITSWO accumulators (training.py:661-695) against a different supervisor."""
+  eng.set_params(theta_w, _hip.VMC_OMEGA)
+  eng.set_shift(-10.0, _hip.VMC_OMEGA)
+  acc = vo.Accumulators(theta.size, np.float64)
+  go.log_overlap_accumulate(acc, theta, theta_w, got, bonds, -1.0, 1.0, -10.0, -10.0, 0.05, adj, f, L, nonlin, oact)
+  eng.reset_accumulators()
+  eng.accumulate(_hip.VMC_MODE_LOG_OVERLAP_ITSWO, 0.05)
+  res = eng.get_accumulators()
+  _acc_close(res, acc, theta.size)
+  assert abs(res[2 * theta.size + 2] - acc.r_total) < 2e-4 * max(1, abs(acc.r_total))
+
+
 @pytest.mark.parametrize('graph,L,f,b,nonlin,oact', CASES, ids=[c[0] for c in CASES])
 def test_gnn_fp64_parity(graph, L, f, b, nonlin, oact):
   adj, bonds = GRAPHS[graph]
@@ -107,49 +154,18 @@ def test_gnn_fp64_parity(graph, L, f, b, nonlin, oact):
   eng = _engine(adj, L, f, b, nonlin, oact)
   assert eng.kernel_path() == 6 and eng.num_params == theta.size == go.gnn_num_params(k, f, L)
   eng.set_params(theta); eng.set_configs(cfg); eng.set_bonds(bonds, -1.0, 1.0)
-  amp = lambda c: go.gnn_psi(theta, c, adj, f, L, -10.0, nonlin, oact)
-  _logits_close(eng.amplitude()[0], theta, cfg, adj, f, L, nonlin)
-  c2 = vo.random_configurations(n, 13, np.random.RandomState(9))
-  _logits_close(eng.amplitude(c2)[0], theta, c2, adj, f, L, nonlin)
-  _close(eng.local_energy()[0], vo.local_value(amp, cfg, bonds, -1.0, 1.0, dtype=np.float64), 2e-4)
-  # 12 steps against the oracle's sampler on the same Philox streams (chains within 1e-4 of a tie excluded)
-  eng.step_counter = 0
-  cur, ok = cfg, np.ones(b, bool)
-  for step in range(12):
-    u_sites, u_acc = vo.step_uniforms(2024, np.arange(b), step, n)
-    i_up, i_dn = vo.propose_exchange(cur, u_sites)
-    cur, _, ratios = vo.mc_step(amp, cur, i_up, i_dn, u_acc)
-    ok &= ~(np.abs(ratios - np.sqrt(u_acc.astype(np.float64))) < 1e-4 * np.maximum(ratios, 1e-30))
-  eng.mc_steps(12)
-  got = eng.get_configs()
-  np.testing.assert_array_equal(got[ok], cur[ok])
-  assert ok.sum() > b // 2 and (got.sum(1) == cfg.sum(1)).all()
-  # EnergyGradient accumulators (training.py:539-558)
-  acc = vo.Accumulators(theta.size, np.float64)
-  go.energy_gradient_accumulate(acc, theta, got, bonds, -1.0, 1.0, -10.0, adj, f, L, nonlin, oact)
-  eng.reset_accumulators()
-  eng.accumulate(_hip.VMC_MODE_ENERGY_GRADIENT)
-  res = eng.get_accumulators()
-  _acc_close(res, acc, theta.size)
-  assert abs(res[2 * theta.size] - acc.e_total) < 2e-4 * max(1, abs(acc.e_total))
-  # LogOverlapITSWO accumulators (training.py:661-695) against a different supervisor
+  _check_forward(eng, theta, cfg, adj, f, L, nonlin)
+  _check_local_energy(eng, theta, cfg, adj, bonds, f, L, nonlin, oact)
+  got = _check_sampler_steps(eng, theta, cfg, adj, f, L, nonlin, oact)
+  _check_energy_gradient(eng, theta, got, adj, bonds, f, L, nonlin, oact)
   theta_w = (theta + 0.02 * rng.standard_normal(theta.size)).astype(np.float32)
-  eng.set_params(theta_w, _hip.VMC_OMEGA)
-  eng.set_shift(-10.0, _hip.VMC_OMEGA)
-  acc = vo.Accumulators(theta.size, np.float64)
-  go.log_overlap_accumulate(acc, theta, theta_w, got, bonds, -1.0, 1.0, -10.0, -10.0, 0.05, adj, f, L, nonlin, oact)
-  eng.reset_accumulators()
-  eng.accumulate(_hip.VMC_MODE_LOG_OVERLAP_ITSWO, 0.05)
-  res = eng.get_accumulators()
-  _acc_close(res, acc, theta.size)
-  assert abs(res[2 * theta.size + 2] - acc.r_total) < 2e-4 * max(1, abs(acc.r_total))
+  _check_log_overlap(eng, theta, theta_w, got, adj, bonds, f, L, nonlin, oact)
   eng.close()
 
 
-def test_gnn_stochastic_reconfiguration():
-  """One SR solve on a gnn ctx (irregular graph: the col2im backward in every CG iteration) against the dense fp64
-  solve on the oracle's per-sample gradients, checked as tests/test_gpu_conv_general.py checks the periodic path."""
-  adj, bonds = GRAPHS['irregular-12']
+def _check_sr(adj, bonds):
+  """One SR solve on a gnn ctx against the dense fp64 solve on the oracle's per-sample gradients, checked as
+  tests/test_gpu_conv_general.py checks the periodic path."""
   n, k = adj.shape
   L, f, b, n_store = 2, 8, 16, 2
   rng = np.random.default_rng(8)
@@ -185,6 +201,12 @@ def test_gnn_stochastic_reconfiguration():
   x_ref = vo.sr_solve(o, e, lam)
   assert np.abs(oc @ x - oc @ x_ref).max() <= 1e-2 * np.abs(oc @ x_ref).max() + 1e-5
   eng.close()
+
+
+def test_gnn_stochastic_reconfiguration():
+  """One SR solve on a gnn ctx (irregular graph: the col2im backward in every CG iteration) against the dense fp64
+  solve on the oracle's per-sample gradients, checked as tests/test_gpu_conv_general.py checks the periodic path."""
+  _check_sr(*GRAPHS['irregular-12'])
 
 
 def test_gnn_sharded_chains_match_one_ctx():
