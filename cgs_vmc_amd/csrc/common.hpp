@@ -664,10 +664,11 @@ struct EdvecSweepArgs {
 };
 hipError_t launch_edvec_sweep(hipStream_t s, EdvecSweepArgs a, int num_cus);
 hipError_t edvec_sweep_reserve_lds(int N);          // before the first launch with tables_lds set
-// val[row] = 0.5 jx psi(x')/psi(x) of every row of the antiparallel-bond list (launch_bond_list); psi [B]: the chains' amplitudes
+// val[row] = 0.5 jx psi(x')/psi(x) of every row of the antiparallel-bond list (launch_bond_list); psi [B]: the chains' amplitudes;
+// undivided_at_zero: 0.5 jx psi(x') on the chains whose psi(x) = 0 (the base of a symmetrized ctx)
 hipError_t launch_edvec_eloc(hipStream_t s, const float* vec, int len, const int* top, const int* bot, int N,
                              const float* configs, const float* psi, int B, const int* off, const int2* rowinfo,
-                             const int2* bonds, const float* half_jx, float* val);
+                             const int2* bonds, const float* half_jx, int undivided_at_zero, float* val);
 hipError_t launch_edvec_itswo_ratio(hipStream_t s, const float* psi, const float* psi_omega, const float* eloc_omega,
                                     float beta, int B, float* ratio);
 // g1[idx_b] += 1 / psi_b, g2[idx_b] += w_b / psi_b, every entry summed over its chains in chain order (no atomics);

@@ -139,13 +139,16 @@ __global__ __launch_bounds__(1024) void k_edvec_sweep(EdvecSweepArgs a) {
 }
 
 // val[q] = 0.5 jx psi(x')/psi(x) of every row {chain, +-(bond + 1)} of the antiparallel-bond list (k_bond_fill,
-// eloc.hip); k_eloc_reduce then folds each chain's rows in its fixed order
+// eloc.hip); k_eloc_reduce then folds each chain's rows in its fixed order.  undivided_at_zero (the base of a symmetrized
+// ctx): a chain with psi(x) = 0 gets 0.5 jx psi(x') itself, so that its off-diagonal sum is (H psi)(x) -- what the
+// composite's fold needs of an op whose row hits a zero entry
 __global__ __launch_bounds__(256) void k_edvec_eloc(const float* __restrict__ vec, int len, const int* __restrict__ top,
                                                     const int* __restrict__ bot, int N,
                                                     const float* __restrict__ configs, const float* __restrict__ psi,
                                                     int B, const int* __restrict__ off,
                                                     const int2* __restrict__ rowinfo, const int2* __restrict__ bonds,
-                                                    const float* __restrict__ half_jx, float* __restrict__ val) {
+                                                    const float* __restrict__ half_jx, int undivided_at_zero,
+                                                    float* __restrict__ val) {
   const int lane = threadIdx.x & 63;
   const int ch = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (ch >= B) return;
@@ -157,7 +160,7 @@ __global__ __launch_bounds__(256) void k_edvec_eloc(const float* __restrict__ ve
     const int kb = abs(rowinfo[q].y) - 1;
     const int2 ij = bonds[kb];
     const float pc = ed_gather(word ^ (1u << ij.x) ^ (1u << ij.y), N, top, bot, vec, len);
-    val[q] = __fmul_rn(half_jx[kb], __fdiv_rn(pc, p));        // operators.py:166-168; psi = 0: the reference's x / 0
+    val[q] = __fmul_rn(half_jx[kb], undivided_at_zero && p == 0.f ? pc : __fdiv_rn(pc, p));      // operators.py:166-168; psi = 0: the reference's x / 0
   }
 }
 
@@ -224,10 +227,10 @@ hipError_t launch_edvec_sweep(hipStream_t st, EdvecSweepArgs a, int num_cus) {
 
 hipError_t launch_edvec_eloc(hipStream_t st, const float* vec, int len, const int* top, const int* bot, int N,
                              const float* configs, const float* psi, int B, const int* off, const int2* rowinfo,
-                             const int2* bonds, const float* half_jx, float* val) {
+                             const int2* bonds, const float* half_jx, int undivided_at_zero, float* val) {
   if (B <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_edvec_eloc, dim3((B + 3) / 4), dim3(256), 0, st, vec, len, top, bot, N, configs, psi, B, off,
-                     rowinfo, bonds, half_jx, val);
+                     rowinfo, bonds, half_jx, undivided_at_zero, val);
   return hipGetLastError();
 }
 

@@ -155,9 +155,13 @@ __global__ __launch_bounds__(64 * PLAN_SYMZ_CHAINS_PER_WG) void k_symz_accept(Sy
 
 // One thread per chain: E_s = sum_k c_k E_k and the diagonal likewise, fp64, ops ascending, rounded once; an op that
 // does not count has c_k = 0 and its E_k (which may be anything: the base divided by a vanishing amplitude) is never read.
+// c_k E_k is chi_k (H psi)(g_k x) / psi_s, though, and (H psi)(g_k x) need not vanish where psi(g_k x) does: an ed_vector
+// base hands over that row's off-diagonal sum undivided (row_offdiag, k_edvec_eloc's undivided_at_zero), and the op adds
+// chi_k (H psi)(g_k x) / psi_s to E_s -- nothing to the diagonal, whose term carries psi(g_k x) = 0, and c_k stays 0.
 // A chain at a structural zero (none is, by the sampler's rule) gets NaN, not a number that looks like an energy.
 __global__ __launch_bounds__(PLAN_SYMZ_THREADS) void k_symz_eloc_fold(SymzRows r, const float* __restrict__ row_eloc,
                                                                       const float* __restrict__ row_diag,
+                                                                      const float* __restrict__ row_offdiag,
                                                                       float* __restrict__ eloc, float* __restrict__ diag,
                                                                       float* __restrict__ offdiag, float* __restrict__ ck,
                                                                       float* __restrict__ wk) {
@@ -173,6 +177,8 @@ __global__ __launch_bounds__(PLAN_SYMZ_THREADS) void k_symz_eloc_fold(SymzRows r
       w = r.chi[k] * sg * exp((double)r.logit[at] - s.m) / s.S;
       E += w * (double)row_eloc[at];
       D += w * (double)row_diag[at];
+    } else if (!s.zero && r.amp && r.chi[k] != 0.0 && r.sign[at] == 0.f) {
+      E += r.chi[k] * (double)row_offdiag[at] / s.amp;
     }
     ck[at] = (float)w;
   }
@@ -206,9 +212,9 @@ hipError_t launch_symz_accept(hipStream_t st, const SymzAcceptArgs& a) {
 }
 
 hipError_t launch_symz_eloc_fold(hipStream_t st, const SymzRows& r, const float* row_eloc, const float* row_diag,
-                                 float* eloc, float* diag, float* offdiag, float* ck, float* wk) {
+                                 const float* row_offdiag, float* eloc, float* diag, float* offdiag, float* ck, float* wk) {
   if (r.B <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_symz_eloc_fold, dim3(plan_symz_chain_blocks(r.B)), dim3(PLAN_SYMZ_THREADS), 0, st, r, row_eloc,
-                     row_diag, eloc, diag, offdiag, ck, wk);
+                     row_diag, row_offdiag, eloc, diag, offdiag, ck, wk);
   return hipGetLastError();
 }

@@ -29,6 +29,7 @@ struct SymzAcceptArgs {
   uint32_t seed_lo, seed_hi; int chain_offset;
 };
 hipError_t launch_symz_accept(hipStream_t st, const SymzAcceptArgs& a);
-// E_s(c) = sum_k c_k E_k, diag likewise, c_k = chi_k s_k exp(l_k - m) / S into ck [n_ops][B], wk = E_s c_k
+// E_s(c) = sum_k c_k E_k, diag likewise, c_k = chi_k s_k exp(l_k - m) / S into ck [n_ops][B], wk = E_s c_k.  r.amp: an op
+// whose amplitude is 0 adds chi_k row_offdiag / psi_s, row_offdiag [n_ops][B] the base's off-diagonal sums (undivided there)
 hipError_t launch_symz_eloc_fold(hipStream_t st, const SymzRows& r, const float* row_eloc, const float* row_diag,
-                                 float* eloc, float* diag, float* offdiag, float* ck, float* wk);
+                                 const float* row_offdiag, float* eloc, float* diag, float* offdiag, float* ck, float* wk);

@@ -350,7 +350,7 @@ int connected_rows_device(vmc_ctx* c, int which, bool share_cus) {
   switch (c->path) {
   case PATH_EDVEC:
     HIPCHK(c, launch_edvec_eloc(c->stream, p.theta, (int)c->P, c->ed_top, c->ed_bot, c->N, c->configs, p.sign, c->B, c->off,
-                                c->rowinfo, c->bonds, c->half_jx, c->val));
+                                c->rowinfo, c->bonds, c->half_jx, c->owner && c->owner->symz ? 1 : 0, c->val));
     break;
   case PATH_PBDG:      // (a fresh M^-1 per chain: never the sampler's incrementally updated one)
     HIPCHK(c, launch_pbdg_eloc(c->stream, p.theta, c->N, c->configs, c->B, c->off, c->rowinfo, c->bonds, c->half_jx,

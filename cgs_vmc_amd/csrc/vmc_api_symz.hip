@@ -120,8 +120,8 @@ int symz_local_energy(vmc_ctx* c, int which) {
   BASE(c, b, local_energy_device(b, which));
   {
     Timer t(c, "eloc_fold");
-    HIPCHK(c, launch_symz_eloc_fold(c->stream, base_rows(c, which), b->ps[which].eloc, b->diag, c->ps[which].eloc, c->diag,
-                                    c->offdiag, st->ck, st->wk));
+    HIPCHK(c, launch_symz_eloc_fold(c->stream, base_rows(c, which), b->ps[which].eloc, b->diag, b->offdiag,
+                                    c->ps[which].eloc, c->diag, c->offdiag, st->ck, st->wk));
   }
   // (vmc_local_energy / vmc_evaluate read the row count off the composite: the base's, over all ops)
   HIPCHK(c, hipMemcpyAsync(c->off + c->B, b->off + b->B, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
@@ -296,14 +296,16 @@ int symz_amplitude(vmc_ctx* c, int which, const float* configs, int64_t n_rows, 
   return VMC_OK;
 }
 
-// vmc_set_configs: a batch with a row at a structural zero is refused before the chains are touched
+// vmc_set_configs: a batch with a row at a structural zero is refused before the chains are touched.  The zero is read
+// off the logit (-inf there and nowhere else): psi = exp(logit - shift) also rounds to 0 below fp32's range, on rows the
+// sampler -- which compares logits -- may well hold
 int symz_check_configs(vmc_ctx* c, const float* configs) {
   const int B = c->B;
-  std::vector<float> psi((size_t)B);
-  PROPAGATE(symz_amplitude(c, VMC_PSI, configs, B, nullptr, psi.data()));
+  std::vector<float> logit((size_t)B);
+  PROPAGATE(symz_amplitude(c, VMC_PSI, configs, B, logit.data(), nullptr));
   int first = -1, zeros = 0;
   for (int r = 0; r < B; ++r)
-    if (psi[(size_t)r] == 0.f) { if (first < 0) first = r; ++zeros; }
+    if (logit[(size_t)r] == -INFINITY) { if (first < 0) first = r; ++zeros; }
   if (zeros == B)
     return fail(c, VMC_ERR_INVALID, "symmetrized: every row is at a structural zero of psi_s: the state has no weight in this sector");
   if (zeros > 0) {

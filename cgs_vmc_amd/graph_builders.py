@@ -128,22 +128,22 @@ class ConfigsVariable:
     checked with the engine's own amplitude -- for at most `max_rounds` rounds; a state that has no weight in the sector
     never gets there and is a ValueError.  (The base's parameters must be on the engine: initialised or restored.)"""
     try:
-      psi = self._engine.amplitude(self._host_value)[1]
+      zero_at = np.isneginf(self._engine.amplitude(self._host_value)[0])      # (the logit: set_configs' own criterion)
     except _hip.HipLibraryError as e:
       if 'parameters not set' not in str(e):
         raise
       return                          # no parameters yet: the first set_configs after they arrive names any zero
     rng_seed = None if self._seed is None else self._seed + self.chain_offset + 7919
     for round_ in range(max_rounds):
-      zero = np.flatnonzero(psi == 0)
+      zero = np.flatnonzero(zero_at)
       if zero.size == 0:
         return
       fresh = utils.random_configurations(self.shape[1], zero.size, None if rng_seed is None else rng_seed + round_)
       self._host_value[zero] = fresh
-      psi[zero] = self._engine.amplitude(fresh)[1]
-    if (psi == 0).any():
+      zero_at[zero] = np.isneginf(self._engine.amplitude(fresh)[0])
+    if zero_at.any():
       raise ValueError('symmetrized: after {} rounds of redrawing, {} of {} initial chains are still at a structural zero: '
-                       'the state has no weight in this sector'.format(max_rounds, int((psi == 0).sum()), psi.size))
+                       'the state has no weight in this sector'.format(max_rounds, int(zero_at.sum()), zero_at.size))
 
   def _claim_slot(self, wavefunction) -> int:
     for which in (_hip.VMC_PSI, _hip.VMC_OMEGA):

@@ -13,6 +13,7 @@ from cgs_vmc_amd import _hip, graph_builders, lattice, session, utils, wavefunct
 from oracle import vmc_oracle as vo
 from tests import prod_oracle as pro
 from tests import symmetrized_oracle as so
+from tests import symmetrized_shape_cases as sc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -98,6 +99,112 @@ def test_sector_levels_of_the_eight_site_chain():
   assert abs(e_pi[0] + 3.1284) < 1e-4 and abs(e_0[0] + 3.6511) < 1e-4
   total = sum(len(so.sector_hamiltonian_levels(8, bonds, 1.0, 1.0, t, None, c)) for c in chi)
   assert total == 70                                       # the sectors partition the Sz = 0 block
+
+
+# ---- the inputs of tests/test_gpu_symmetrized_shapes.py, on the oracle alone
+
+SHAPE_OP_SETS = sorted({(lat, sector) for _, lat, sector, _ in sc.AMPLITUDE_CASES} | {(lat, sector) for lat, sector, _ in sc.GRADIENT_CASES})
+
+
+@pytest.mark.parametrize('lat,sector', SHAPE_OP_SETS)
+def test_the_fold_identity_holds_on_every_shape_case(lat, sector):
+  """Direct sum against fold with the 2 x 16 oracle factor on every op set of the shape cases -- N up to 258, the spin flip,
+  a rectangle, the 128 ops of the space group, two couplings --, r-scaled as above: 1e-12 max(1, max|E|)."""
+  L = sc.LATTICES[lat]
+  perms, flips, chi = sc.ops(lat, sector)                  # (validated against the bonds and couplings there)
+  assert len(perms) == {'chain10': 10, 'chain12': 24, 'chain20': 20, 'chain68': 68, 'chain258': 6, 'torus6x4': 24,
+                        'torus4': 128, 'torus4-j1j2': 128}.get(lat, 140 if flips is not None else 70)
+  orc = sc.fc_oracle(lat, sector, sc.fc_theta(L['n'], 1))
+  cfg = sc.configs(L['n'], 5 if L['n'] > 64 else 8, 2, orc)
+  r = orc.cancellation(cfg)
+  for jx, jz in ((1.0, 1.0), (0.7, 1.3)):
+    bx, bz = sc.couplings(lat, jx, jz)
+    direct = orc.local_energy(cfg, L['bonds'], bx, bz)
+    fold = orc.local_energy_fold(cfg, L['bonds'], bx, bz)
+    assert (r * np.abs(direct - fold)).max() <= 1e-12 * max(1.0, np.abs(direct).max()), (lat, sector, jx, jz)
+  if lat == 'torus4-j1j2':                                 # the two couplings are what makes the ops symmetries: swap two and they are not
+    j = np.array(L['j']); j[0], j[40] = j[40], j[0]
+    with pytest.raises(ValueError, match='no symmetry of the Hamiltonian'):
+      lattice.check_hamiltonian_symmetry(L['bonds'], j, j, perms)
+
+
+@pytest.mark.parametrize('name', ['trivial', 'sign', 'A2'])
+def test_the_space_group_sectors_are_representations(name):
+  """chi(g) chi(h) = chi(g h) / |G| on the 128 x 128 table of the 4 x 4 torus' space group, and on the oracle
+  psi_s(g_k x) = chi_k / chi_0 psi_s(x) to 1e-12 A."""
+  perms, flips, chi = sc.ops('torus4', 'sg-' + name)
+  g = len(perms)
+  assert g == 128 and flips is None and (np.abs(chi) == 1.0 / g).all() and chi[0] > 0
+  assert (chi < 0).sum() == {'trivial': 0, 'sign': 64, 'A2': 64}[name]
+  index = {p.tobytes(): k for k, p in enumerate(perms)}
+  assert len(index) == g and index[np.arange(16, dtype=np.int32).tobytes()] == 0
+  # rows: x -> x[perm_a] -> (x[perm_a])[perm_b] = x[perm_a[perm_b]]
+  table = np.array([[index[perms[a][perms[b]].tobytes()] for b in range(g)] for a in range(g)])      # (a KeyError: not closed)
+  assert (np.sort(table, axis=1) == np.arange(g)).all()
+  assert (table != table.T).any()                          # the group does not commute
+  np.testing.assert_array_equal(chi[:, None] * chi[None, :], chi[table] / g)
+  orc = sc.fc_oracle('torus4', 'sg-' + name, sc.fc_theta(16, 1))
+  cfg = sc.configs(16, 8, 3)
+  psi, a = orc.psi(cfg), orc.A(cfg)
+  rows = orc.rows(cfg)
+  for k in range(g):
+    np.testing.assert_allclose(orc.psi(rows[k]), chi[k] / chi[0] * psi, rtol=0, atol=1e-12 * a.max())
+
+
+@pytest.mark.parametrize('lat,sector,b', sc.GRADIENT_CASES)
+def test_the_gradient_seed_table_keeps_r_min(lat, sector, b):
+  """Every (parameter seed, batch seed) of the GPU gradient tests: min_c r >= 0.01 on the unfiltered batch the seeds pick."""
+  theta_seed, seed = sc.GRADIENT_SEEDS[(lat, sector, b)]
+  n = sc.LATTICES[lat]['n']
+  orc = sc.fc_oracle(lat, sector, sc.fc_theta(n, theta_seed))
+  r = orc.cancellation(sc.configs(n, b, seed, orc))
+  assert r.min() >= sc.R_MIN, (lat, sector, r)
+
+
+def test_the_shape_cases_reach_what_they_are_named_for():
+  """What the GPU tests assert before they run, where it needs no GPU: the sizes, the logit spreads of the fold cases,
+  the rows of the zero-amplitude batches, the band share of the big injected step."""
+  n = lambda lat: sc.LATTICES[lat]['n']
+  assert n('chain10') % 4 == 2 and n('chain70') % 4 == 2 and n('chain68') % 4 == 0 and min(n('chain68'), n('chain70')) > 64
+  assert (n('chain258') + 3) // 4 == 65 and n('chain258') % 4 == 2
+  big = sc.BIG
+  assert len(sc.ops(big['lat'], big['sector'])[0]) * big['b'] > sc.ROW_ITEMS_PER_CU * 256      # (at the MI355X's 256 CUs)
+  assert sc.FOLD_THREADS < big['b'] < 2 * sc.FOLD_THREADS
+  plan = open(os.path.join(ROOT, 'cgs_vmc_amd', 'csrc', 'plan.hpp')).read()
+  common = open(os.path.join(ROOT, 'cgs_vmc_amd', 'csrc', 'common.hpp')).read()
+  assert re.search(r'#define\s+PLAN_SYMZ_THREADS\s+%d\b' % sc.FOLD_THREADS, plan)
+  assert 'long long blocks = (items + 3) / 4;' in common and 'const long long cap = 16LL * (num_cus > 0 ? num_cus : 1);' in common
+  # the fold cases: every row's orbit spreads past the range its factor is named for
+  for lat, sector in sc.FOLD_CASES:
+    for factor, spread in sc.FOLD_FACTORS.items():
+      theta = sc.fold_theta(n(lat), factor)
+      orc = sc.fc_oracle(lat, sector, theta)
+      l = sc.orbit_logits(theta, orc, sc.configs(n(lat), 5, sc.FOLD_SEED))
+      assert (l.max(0) - l.min(0) > 1.05 * spread).all(), (lat, factor, l.max(0) - l.min(0))
+  # zero characters: rows on which an odd translation's logit lies past fp64's exp range above every even one's
+  bare = sc.fold_theta(8, sc.ZERO_CHI_FACTOR)
+  l = sc.orbit_logits(bare, sc.fc_oracle('chain8', 'q0', bare), sc.configs(8, 13, sc.ZERO_CHI_SEED + 1))
+  assert (l[1::2].max(0) - l[0::2].max(0) > 1.05 * 745.0).sum() >= 2
+  # the zero-amplitude batches: a row with some but not all ops on a zero entry, every row with psi_s != 0
+  vec, top, bot = sc.zero_vector()
+  assert 0.25 * len(vec) < (vec == 0).sum() < 0.5 * len(vec)
+  for sector in sc.ZERO_AMP['sectors']:
+    perms, flips, chi = sc.ops('chain8', sector)
+    orc = so.Symmetrized(pro.edvec_factor(vec, top, bot), perms, flips, chi)
+    cfg, partial = sc.zero_amp_batch(orc)
+    assert len(cfg) == sc.ZERO_AMP['b'] and partial.any() and (orc.cancellation(cfg) > 1e-3).all()
+    assert (orc.terms(sc.DOMAIN_WALL[None]) == 0).all()
+  # the big injected step: the oracle alone keeps the band share
+  orc = sc.fc_oracle(big['lat'], big['sector'], sc.fc_theta(n(big['lat']), 0))
+  cfg = sc.configs(n(big['lat']), big['b'], big['seed'], orc)
+  i_up, i_dn, u = sc.big_step(cfg)
+  _, acc, ratio = pro.mc_step(orc, cfg, i_up, i_dn, u)
+  band = ~(np.abs(ratio ** 2 - u.astype(np.float64)) > 2e-4)
+  assert band.sum() <= sc.BAND_SHARE * big['b'] and 0.2 * big['b'] < acc.sum() < 0.9 * big['b']
+  # exact zeros where q2 of the 8-site chain should have them, and otherwise lattice.sector_characters' row
+  labels, table = lattice.sector_characters(8, 1)
+  assert (table[labels.index('q2')] != 0).all()
+  np.testing.assert_allclose(sc.CHI_Q2_EXACT, table[labels.index('q2')], rtol=0, atol=1e-16)
 
 
 def _base(n=8, **kw):
