@@ -106,6 +106,8 @@ SIGNATURES = {
                                        C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'vmc_energy_moments': (C.c_int, [_ctx, C.c_int, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    'vmc_set_four_spin_terms': (C.c_int, [_ctx, C.c_int32, _ip, _fp, C.c_int32, C.c_int64]),
+    'vmc_last_four_spin_rows': (C.c_int, [_ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'vmc_overlap': (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     'vmc_accumulate': (C.c_int, [_ctx, C.c_int, C.c_float]),
     'vmc_reset_accumulators': (C.c_int, [_ctx]),
@@ -180,7 +182,7 @@ _lib = None
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 _STAMP_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libcgsvmc_hip.stamp')
 # the files the library is built from, in the order csrc/Makefile hashes them
-_SOURCES = ('vmc_api.hip', 'vmc_api_cgen.hip', 'vmc_api_sweep.hip', 'vmc_api_train.hip', 'vmc_api_coll.hip', 'vmc_api_sr.hip', 'vmc_api_prod.hip', 'prod.hip', 'vmc_api_symz.hip', 'symz.hip', 'mlp.hip', 'eloc.hip', 'grad.hip', 'sr.hip', 'srmm.hip', 'srgram.hip', 'conv.hip', 'conv32.hip', 'conv48.hip', 'conv64.hip', 'conv_general.hip', 'conv_band.hip', 'conv_patch.hip', 'wide.hip', 'tail_split.hip', 'sweep_split.hip', 'sweep8.hip', 'pbdg.hip', 'nnb.hip', 'edvec.hip', 'vmc_api_measure.hip', 'corr.hip', 'renyi.hip', 'dimer.hip', 'symm.hip', 'proj.hip', 'moments.hip', 'overlap.hip', 'act_tail.hip',
+_SOURCES = ('vmc_api.hip', 'vmc_api_cgen.hip', 'vmc_api_sweep.hip', 'vmc_api_train.hip', 'vmc_api_coll.hip', 'vmc_api_sr.hip', 'vmc_api_prod.hip', 'prod.hip', 'vmc_api_symz.hip', 'symz.hip', 'mlp.hip', 'eloc.hip', 'grad.hip', 'sr.hip', 'srmm.hip', 'srgram.hip', 'conv.hip', 'conv32.hip', 'conv48.hip', 'conv64.hip', 'conv_general.hip', 'conv_band.hip', 'conv_patch.hip', 'wide.hip', 'tail_split.hip', 'sweep_split.hip', 'sweep8.hip', 'pbdg.hip', 'nnb.hip', 'edvec.hip', 'vmc_api_measure.hip', 'corr.hip', 'renyi.hip', 'dimer.hip', 'symm.hip', 'proj.hip', 'moments.hip', 'overlap.hip', 'fourspin.hip', 'act_tail.hip',
             'act_sweep.hip', 'vmc_ctx.hpp', 'prod.hpp', 'symz.hpp', 'plan.hpp', 'common.hpp', 'pb_det.hpp', 'tail16.hpp', 'tail_lds.hpp', 'sweep16.hpp', 'conv.hpp', 'conv_kernels.hpp',
             'conv_wide.hpp',
             os.path.join('..', '..', 'include', 'cgsvmc.h'), 'Makefile')

@@ -20,6 +20,14 @@ def _flag_bool(text) -> bool:
   return str(text).strip().lower() in ('1', 'true', 't', 'yes', 'y')
 
 
+# The flag of the drivers that train or evaluate the Hamiltonian of a run directory (run_training, run_energy_evaluation,
+# run_excited_state_training): their parsers take it beside their FLAG_TABLE, which keeps the reference's command-line
+# contract.  No other driver has it.
+FOUR_SPIN_FLAGS = (
+    ('four_spin_q', float, 1.0, 'Coupling q of the rows of `Q.txt` (four-spin terms) that state none.'),
+)
+
+
 def parser_from_table(description: str, table: Sequence[Tuple[str, type, object, str]]
                       ) -> argparse.ArgumentParser:
   """Builds an absl-like parser: --name=value or --name value; booleans also bare."""
@@ -34,13 +42,24 @@ def parser_from_table(description: str, table: Sequence[Tuple[str, type, object,
   return ap
 
 
-def heisenberg_system(hparams, directory: str, j_x: float):
+def heisenberg_system(hparams, directory: str, j_x: float, four_spin_q: float = 1.0):
   """(ansatz, Hamiltonian) for a run directory: the bond list comes from `J.txt` when the
   directory has one, otherwise the periodic chain of hparams.num_sites sites; j_z is fixed to 1
-  as in the reference (run_training.py:112-113)."""
+  as in the reference (run_training.py:112-113).  A directory that holds `Q.txt` (rows `i j k l [q]`,
+  lattice.read_four_spin_terms) gets the operators.JQHamiltonian of the bonds and those four-spin terms -- rows without a
+  fifth column take four_spin_q (--four_spin_q), the exchange sign is the sign of j_x; without the file nothing changes."""
   bonds = lattice.load_bonds(directory, hparams.num_sites)
   ansatz = wavefunctions.build_wavefunction(hparams)
+  four_spin = lattice.load_four_spin_terms(directory, four_spin_q)
+  if four_spin is not None:
+    return ansatz, operators.JQHamiltonian(bonds, j_x, 1., four_spin[0], four_spin[1])
   return ansatz, operators.HeisenbergHamiltonian(bonds, j_x, 1.)
+
+
+def refuse_four_spin_terms(directory: str, driver: str, why: str):
+  """NotImplementedError when the run directory holds `Q.txt`: `driver` would silently leave the four-spin terms out."""
+  if os.path.exists(os.path.join(directory, 'Q.txt')):
+    raise NotImplementedError('{}: {} holds Q.txt (four-spin terms), and {}'.format(driver, directory, why))
 
 
 def broadcast_parameters(ansatz):
@@ -76,6 +95,9 @@ def measurement_flag_table(own_rows, outputs: str):
 def evaluate_measurement(flags, evaluator, load_operator):
   """A measurement driver's evaluation: `hparams.pbtxt` with the --hparams overrides, the Heisenberg system of the
   checkpoint directory, operator = load_operator(hparams, the Hamiltonian's bonds), the latest checkpoint restored.
+  (Of the Hamiltonian the measurements of the state take the bond list alone: a `Q.txt` in the directory changes none of
+  them.  The two that measure the Hamiltonian itself, run_lanczos_evaluation and run_projected_energy_evaluation, refuse
+  such a directory: refuse_four_spin_terms.)
   -> (hparams, the Hamiltonian's bonds, the result of evaluator.run_evaluation)."""
   hp = utils.load_hparams(os.path.join(flags.checkpoint_dir, 'hparams.pbtxt'))
   hp.parse(flags.hparams)

@@ -395,6 +395,22 @@ hipError_t launch_mom_fold(hipStream_t s, const float* configs, const int2* bond
                            const float* sign, const double* diag1, const double* self1, const double* lanes, int B, int N,
                            int n_bonds, double* chain, double* out);
 
+// four-spin (J-Q) terms (fourspin.hip; its header states the list rules and the summation order).  pairs [n_pairs] the
+// distinct site pairs, term_pairs [n_terms] two pair indices per term, wq [n_terms] = -q / 4.  count: n_single / cnt [B]
+// and the exclusive prefix off [B + 1] with the single rows of all chains behind it (off [B + 2] in all); fill: the
+// descriptors {chain, code} of the rows [q0, q0 + n) of a pass; rows: their configurations; fold: own [B] the chains',
+// rows [off[B]] the whole list's -- eloc [B] += the term sums (one rounding), dsum / osum [B] their constant and ratio
+// parts in fp64 (both null: not wanted, the fold keeps the one sum)
+hipError_t launch_fs_count(hipStream_t s, const float* configs, const int2* pairs, const int2* term_pairs, int B, int N,
+                           int n_pairs, int n_terms, int num_cus, int* n_single, int* cnt, int* off);
+hipError_t launch_fs_fill(hipStream_t s, const float* configs, const int2* pairs, const int2* term_pairs, const int* off,
+                          int B, int N, int n_pairs, int n_terms, long long q0, int n, int num_cus, int2* desc);
+hipError_t launch_fs_rows(hipStream_t s, const float* configs, const int2* pairs, const int2* term_pairs, const int2* desc,
+                          int N, int n_pairs, int n, int num_cus, float* rows);
+hipError_t launch_fs_fold(hipStream_t s, const float* configs, const int2* pairs, const int2* term_pairs, const double* wq,
+                          const int* off, AmpPair own, AmpPair rows, int B, int N, int n_pairs, int n_terms,
+                          int exchange_sign, float* eloc, double* dsum, double* osum);
+
 // device helpers and the grid rule the Renyi-2, dimer, symmetry, projection and moment kernels share
 // sign of a stored sign / amplitude: +-1, 0 for a vanishing amplitude
 __device__ inline int sgn_of(float v) { return (v > 0.f) - (v < 0.f); }

@@ -903,6 +903,105 @@ inline long long plan_moment_rows_of_lane(long long s, long long lo, long long h
   return q >= hi ? 0 : (hi - q + 63) / 64;
 }
 
+// Four-spin (J-Q) terms (vmc_set_four_spin_terms; fourspin.hip).  A term is (i, j, k, l; q) with four distinct sites; the
+// host reduces the terms to the table of their distinct unordered site pairs -- pairs[p] = (min, max), ascending by
+// (min, max), n_pairs <= 2 n_terms -- and term_pairs[t] = the two indices of (i, j) and (k, l) into it (a term whose two
+// pairs are the same unordered pair cannot occur: the sites are distinct).  Per chain the list holds one single row per
+// antiparallel pair and one double row per term with both pairs antiparallel, so B (n_pairs + n_terms) <= 2^31 - 1 keeps
+// every row index and the prefix over the chains within 32 bits whatever the configurations are.  The fold keeps a chain's
+// single ratios in LDS by pair index (fp64): at most PLAN_FOURSPIN_MAX_PAIRS pairs; PLAN_FOURSPIN_MAX_TERMS bounds the
+// term table.  plan_fourspin_check validates everything before anything is stored; VMC_OK, or the error with the term
+// (or the cap) named in msg.  The list goes through the forward in passes of ROWS: plan_fourspin_per_pass is the rule of
+// plan_moment_per_pass (the budget of 2^24 rows, row_limit, the request; at least one row; -1: an argument out of range).
+#define PLAN_FOURSPIN_MAX_TERMS (1 << 16)
+#define PLAN_FOURSPIN_MAX_PAIRS 4096
+struct FourSpinTable {
+  std::vector<int32_t> pairs;        // [n_pairs][2]
+  std::vector<int32_t> term_pairs;   // [n_terms][2]
+  int n_pairs() const { return (int)(pairs.size() / 2); }
+};
+inline FourSpinTable plan_fourspin_pairs(int n_terms, const int32_t* ijkl) {
+  FourSpinTable t;
+  std::vector<std::pair<int32_t, int32_t>> all;
+  all.reserve((size_t)n_terms * 2);
+  for (int k = 0; k < 2 * n_terms; ++k) {
+    const int32_t a = ijkl[2 * (size_t)k], b = ijkl[2 * (size_t)k + 1];
+    all.emplace_back(a < b ? a : b, a < b ? b : a);
+  }
+  std::vector<std::pair<int32_t, int32_t>> uniq(all);
+  std::sort(uniq.begin(), uniq.end());
+  uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+  for (const auto& p : uniq) { t.pairs.push_back(p.first); t.pairs.push_back(p.second); }
+  for (const auto& p : all)
+    t.term_pairs.push_back((int32_t)(std::lower_bound(uniq.begin(), uniq.end(), p) - uniq.begin()));
+  return t;
+}
+inline int plan_fourspin_check(int N, long long B, int n_terms, const int32_t* ijkl, const float* q, int exchange_sign,
+                               long long rows_per_pass, char* msg, size_t msg_len) {
+  if (msg_len) msg[0] = 0;
+  if (N < 1 || B < 1 || n_terms < 1 || !ijkl || !q) {
+    snprintf(msg, msg_len, "vmc_set_four_spin_terms: bad term arguments");
+    return VMC_ERR_INVALID;
+  }
+  if (exchange_sign != 1 && exchange_sign != -1) {
+    snprintf(msg, msg_len, "vmc_set_four_spin_terms: exchange_sign = %d, +1 or -1 required", exchange_sign);
+    return VMC_ERR_INVALID;
+  }
+  if (rows_per_pass < 0) {
+    snprintf(msg, msg_len, "vmc_set_four_spin_terms: bad rows_per_pass (0: the library decides)");
+    return VMC_ERR_INVALID;
+  }
+  if (n_terms > PLAN_FOURSPIN_MAX_TERMS) {
+    snprintf(msg, msg_len, "vmc_set_four_spin_terms: %d terms beyond the cap of %d terms", n_terms, PLAN_FOURSPIN_MAX_TERMS);
+    return VMC_ERR_UNSUPPORTED;
+  }
+  for (int t = 0; t < n_terms; ++t) {
+    const int32_t* s = ijkl + 4 * (size_t)t;
+    bool ok = true;
+    for (int a = 0; a < 4; ++a) {
+      ok = ok && s[a] >= 0 && s[a] < N;
+      for (int b = 0; b < a; ++b) ok = ok && s[a] != s[b];
+    }
+    if (!ok) {
+      snprintf(msg, msg_len, "vmc_set_four_spin_terms: term %d = (%d, %d, %d, %d): four distinct sites in 0 .. %d required", t,
+               (int)s[0], (int)s[1], (int)s[2], (int)s[3], N - 1);
+      return VMC_ERR_INVALID;
+    }
+    if (!std::isfinite(q[t])) {
+      snprintf(msg, msg_len, "vmc_set_four_spin_terms: the coupling q of term %d is not finite", t);
+      return VMC_ERR_INVALID;
+    }
+  }
+  const int n_pairs = plan_fourspin_pairs(n_terms, ijkl).n_pairs();
+  if (n_pairs > PLAN_FOURSPIN_MAX_PAIRS) {
+    snprintf(msg, msg_len, "vmc_set_four_spin_terms: %d distinct site pairs beyond the cap of %d pairs (the fold's LDS table)",
+             n_pairs, PLAN_FOURSPIN_MAX_PAIRS);
+    return VMC_ERR_UNSUPPORTED;
+  }
+  if ((long long)n_pairs + n_terms > 0x7fffffffLL / B) {
+    snprintf(msg, msg_len, "vmc_set_four_spin_terms: batch_size x (pairs + terms) = %lld x %lld does not fit the 32-bit row index",
+             B, (long long)n_pairs + n_terms);
+    return VMC_ERR_UNSUPPORTED;
+  }
+  return VMC_OK;
+}
+inline long long plan_fourspin_per_pass(long long n_rows, long long requested, long long row_limit) {
+  return plan_moment_per_pass(n_rows, requested, row_limit);
+}
+// The result buffers span the whole list, whose length changes with the chains: they are reserved once for the a-priori
+// maximum B (n_pairs + n_terms) rows where that stays within PLAN_FOURSPIN_RESULT_ROWS (2^26 rows, 256 MiB a buffer), so
+// that training never reallocates; beyond it geometrically -- at least twice what is held, never past the maximum.
+#define PLAN_FOURSPIN_RESULT_ROWS (1LL << 26)
+inline long long plan_fourspin_result_rows(long long B, long long n_pairs, long long n_terms, long long total, long long held) {
+  const long long most = B * (n_pairs + n_terms);
+  if (total <= held) return held;
+  if (most <= PLAN_FOURSPIN_RESULT_ROWS) return most;
+  long long rows = held * 2 > total ? held * 2 : total;
+  if (rows < PLAN_FOURSPIN_RESULT_ROWS) rows = PLAN_FOURSPIN_RESULT_ROWS;
+  return rows > most ? most : rows;
+}
+inline size_t plan_fourspin_fold_lds(int n_pairs) { return (size_t)(n_pairs > 0 ? n_pairs : 1) * sizeof(double); }
+
 // ------------------------------------------------------------------------------- the kernel path of a ctx
 // Which family of kernels a ctx runs: decided once (plan_desc, plan_split_path; vmc_create_product sets PATH_PRODUCT),
 // kept in vmc_ctx::path, reported by vmc_debug_kernel_path -- the numbers are part of the test suite and of bench.py.

@@ -332,7 +332,7 @@ int local_energy_device(vmc_ctx* c, int which, bool defer_reduce, bool* deferred
   PROPAGATE(ensure_list(c));
   PROPAGATE(connected_rows_device(c, which, true));
   ParamSet& p = c->ps[which];
-  if (defer_reduce && deferred && path_fused_dense(c->path)) {
+  if (c->fs.n_terms == 0 && defer_reduce && deferred && path_fused_dense(c->path)) {
     *deferred = true;              // the fused back-propagation launch folds val into eloc
     return VMC_OK;
   }
@@ -340,6 +340,7 @@ int local_energy_device(vmc_ctx* c, int which, bool defer_reduce, bool* deferred
     Timer t(c, "eloc_reduce");
     HIPCHK(c, launch_eloc_reduce(c->stream, c->off, c->diag, c->val, c->B, c->offdiag, p.eloc));
   }
+  if (c->fs.n_terms > 0) PROPAGATE(four_spin_device(c, which));     // the four-spin terms on top, never deferred
   return VMC_OK;
 }
 
@@ -1067,10 +1068,23 @@ int vmc_local_energy_terms(vmc_ctx* c, int which, float* diag, float* offdiag_ov
   ENTER(c);
   REFUSE_COMPOSED(c);
   if (which != 0 && which != 1) return fail(c, VMC_ERR_INVALID, "bad which");
-  PROPAGATE(local_energy_device(c, which));
+  c->fs.want_parts = true;           // (the four-spin fold keeps its two parts for this entry alone)
+  const int rc_eloc = local_energy_device(c, which);
+  c->fs.want_parts = false;
+  PROPAGATE(rc_eloc);
   if (diag) HIPCHK(c, hipMemcpyAsync(diag, c->diag, c->B * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   if (offdiag_over_psi) HIPCHK(c, hipMemcpyAsync(offdiag_over_psi, c->offdiag, c->B * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  // four-spin terms: the 1 of every active term's bracket belongs to diag, its three ratio terms to offdiag_over_psi
+  std::vector<double> fs_parts(c->fs.n_terms > 0 ? 2 * (size_t)c->B : 0);
+  if (c->fs.n_terms > 0) {
+    HIPCHK(c, hipMemcpyAsync(fs_parts.data(), c->fs.dsum, c->B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(fs_parts.data() + c->B, c->fs.osum, c->B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  }
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (size_t k = 0; k < fs_parts.size() / 2; ++k) {
+    if (diag) diag[k] = (float)((double)diag[k] + fs_parts[k]);
+    if (offdiag_over_psi) offdiag_over_psi[k] = (float)((double)offdiag_over_psi[k] + fs_parts[(size_t)c->B + k]);
+  }
   return VMC_OK;
 }
 

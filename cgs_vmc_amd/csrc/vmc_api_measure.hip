@@ -60,6 +60,10 @@
 //
 // Overlap with the frozen set.  No rows: one ratio pass and one fold over the two amplitude caches (overlap.hip), shared
 // with the penalised-energy mode of the training entries (overlap_refusals, overlap_sums_device).
+//
+// Beside the measurements, on the same scaffold: the four-spin (J-Q) terms of the Hamiltonian (four_spin_device,
+// vmc_set_four_spin_terms; fourspin.hip) -- no measurement but a part of every local energy while terms are set; its
+// section below states it.
 #include "vmc_ctx.hpp"
 
 using namespace vmcapi;
@@ -381,9 +385,115 @@ int overlap_sums_device(vmc_ctx* c) {
   return VMC_OK;
 }
 
+// ---- four-spin (J-Q) terms of the Hamiltonian (fourspin.hip)
+//
+// Not a measurement: local_energy_device calls it behind the Heisenberg fold whenever the ctx holds terms, so every
+// reader of eloc (the modes of vmc_accumulate, the fused epochs, vmc_evaluate, the SR store) sees H_J + H_Q.  It uses the
+// measurements' scaffold: the list (count, prefix, its two lengths read back once), passes of ROWS through row_pass --
+// k_fs_fill and k_fs_rows into tmp_cfg, the family's own full forward into the result buffers that span the list -- and
+// ONE fold after the last pass.  The caches it reads (ensure_cache(which)) are the ones the Heisenberg part has filled.
+
+// rows [q0, q0 + n) of the list: descriptors, configurations, forward into the list's result buffers
+static int four_spin_pass(vmc_ctx* c, int which, long long q0, int n) {
+  FourSpinBufs& m = c->fs;
+  {
+    Timer t(c, "fs_list");
+    HIPCHK(c, launch_fs_fill(c->stream, c->configs, m.pairs, m.term_pairs, m.off, c->B, c->N, m.n_pairs, m.n_terms, q0, n,
+                             c->num_cus, m.desc));
+  }
+  float* sign = c->tmp_sign;                 // (an unsigned ctx keeps no sign per row: the forward's goes to the scratch rows)
+  if (c->sgn) sign = m.sign + q0;
+  return row_pass(c, which, "fs_rows", "fs_forward", n, m.logit + q0, sign, [&] {
+    return launch_fs_rows(c->stream, c->configs, m.pairs, m.term_pairs, m.desc, c->N, m.n_pairs, n, c->num_cus, c->tmp_cfg);
+  });
+}
+
+int four_spin_device(vmc_ctx* c, int which) {
+  FourSpinBufs& m = c->fs;
+  PROPAGATE(ensure_cache(c, which));         // ln|psi(x_c)| and the signs, as the Heisenberg part took them
+  PROPAGATE(m.n_single.reserve(c, c->B, "fs.n_single"));
+  PROPAGATE(m.cnt.reserve(c, c->B, "fs.cnt"));
+  PROPAGATE(m.off.reserve(c, (long long)c->B + 2, "fs.off"));
+  if (m.want_parts) {
+    PROPAGATE(m.dsum.reserve(c, c->B, "fs.dsum"));
+    PROPAGATE(m.osum.reserve(c, c->B, "fs.osum"));
+  }
+  int lengths[2] = {0, 0};                   // the rows of the list, its single rows
+  {
+    Timer t(c, "fs_list");
+    HIPCHK(c, launch_fs_count(c->stream, c->configs, m.pairs, m.term_pairs, c->B, c->N, m.n_pairs, m.n_terms, c->num_cus,
+                              m.n_single, m.cnt, m.off));
+    HIPCHK(c, hipMemcpyAsync(lengths, m.off + c->B, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  const long long total = lengths[0];
+  const long long per = plan_fourspin_per_pass(total, m.rows_per_pass, plan_measure_row_limit(c->N, c->Hp));
+  if (per < 1 || lengths[1] < 0 || lengths[1] > total) return fail(c, VMC_ERR_HIP, "the four-spin list has a negative length");
+  PROPAGATE(m.desc.reserve(c, per, "fs.desc"));
+  // (for the a-priori maximum where that fits, so that the list growing with the chains reallocates nothing: plan.hpp)
+  PROPAGATE(m.logit.reserve(c, plan_fourspin_result_rows(c->B, m.n_pairs, m.n_terms, total, m.logit.cap), "fs.logit"));
+  if (c->sgn) PROPAGATE(m.sign.reserve(c, plan_fourspin_result_rows(c->B, m.n_pairs, m.n_terms, total, m.sign.cap), "fs.sign"));
+  PROPAGATE(grow_tmp(c, per));
+  PROPAGATE(for_passes(total, (int)per, [&](long long q0, int n) { return four_spin_pass(c, which, q0, n); }));
+  {
+    Timer t(c, "fs_fold");
+    HIPCHK(c, launch_fs_fold(c->stream, c->configs, m.pairs, m.term_pairs, m.wq, m.off, own_amps(c, which),
+                             AmpPair{m.logit, c->sgn ? m.sign.p : nullptr}, c->B, c->N, m.n_pairs, m.n_terms,
+                             m.exchange_sign, c->ps[which].eloc, m.want_parts ? m.dsum.p : nullptr,
+                             m.want_parts ? m.osum.p : nullptr));
+  }
+  m.last_single = lengths[1];
+  m.last_double = total - lengths[1];
+  return VMC_OK;
+}
+
 }  // namespace vmcapi
 
 extern "C" {
+
+int vmc_set_four_spin_terms(vmc_ctx* c, int32_t n_terms, const int32_t* ijkl, const float* q, int32_t exchange_sign,
+                            int64_t rows_per_pass) {
+  ENTER(c);
+  if (n_terms < 0) return fail(c, VMC_ERR_INVALID, "vmc_set_four_spin_terms: n_terms < 0");
+  if (n_terms == 0) {                        // the ctx is what it was before it took terms
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->fs = FourSpinBufs();
+    return VMC_OK;
+  }
+  REFUSE_PRODUCT(c, "vmc_set_four_spin_terms");
+  if (c->owner)
+    return fail(c, VMC_ERR_STATE, c->owner->symz
+        ? "vmc_set_four_spin_terms is not available on the base of a symmetrized ctx (vmc_create_symmetrized)"
+        : "vmc_set_four_spin_terms is not available on a factor of a product ctx (vmc_create_product)");
+  PROPAGATE(needs_ln_psi(c, "vmc_set_four_spin_terms"));
+  char msg[256];
+  const int rc = plan_fourspin_check(c->N, c->B, n_terms, ijkl, q, exchange_sign, rows_per_pass, msg, sizeof(msg));
+  if (rc != VMC_OK) return fail(c, rc, msg);
+  const FourSpinTable table = plan_fourspin_pairs(n_terms, ijkl);
+  std::vector<double> wq((size_t)n_terms);
+  for (int t = 0; t < n_terms; ++t) wq[(size_t)t] = -0.25 * (double)q[t];
+  // the new set in buffers of its own: a failure below leaves the previous set in place
+  FourSpinBufs next;
+  next.n_terms = n_terms; next.n_pairs = table.n_pairs();
+  next.exchange_sign = exchange_sign; next.rows_per_pass = rows_per_pass;
+  PROPAGATE(next.pairs.alloc(c, next.n_pairs, "fs.pairs"));
+  PROPAGATE(next.term_pairs.alloc(c, n_terms, "fs.term_pairs"));
+  PROPAGATE(next.wq.alloc(c, n_terms, "fs.wq"));
+  HIPCHK(c, hipMemcpy(next.pairs, table.pairs.data(), table.pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(next.term_pairs, table.term_pairs.data(), table.term_pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(next.wq, wq.data(), wq.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (work in flight may read the previous set)
+  c->fs = std::move(next);
+  return VMC_OK;
+}
+
+int vmc_last_four_spin_rows(vmc_ctx* c, int64_t* single_rows, int64_t* double_rows) {
+  CHECK_CTX(c);
+  if (!single_rows || !double_rows) return fail(c, VMC_ERR_INVALID, "null");
+  *single_rows = c->fs.last_single;
+  *double_rows = c->fs.last_double;
+  return VMC_OK;
+}
 
 int vmc_pair_correlations(vmc_ctx* c, int which, int32_t n_pairs, const int32_t* ij, int32_t pairs_per_pass,
                           double* zz_sum, double* ex_sum) {
@@ -520,6 +630,8 @@ int vmc_projected_energy(vmc_ctx* c, int which, int32_t n_ops, const int32_t* pe
                          int32_t n_sectors, const double* chi, int32_t ops_per_pass, double* w_sum, double* we_sum,
                          double* e_sum, int64_t* n_alive) {
   MEASURE_GATE(c, which, "vmc_projected_energy");
+  if (c->fs.n_terms > 0)
+    return fail(c, VMC_ERR_UNSUPPORTED, "vmc_projected_energy is not available while four-spin terms are set (vmc_set_four_spin_terms): the symmetry check does not cover them");
   SymmOps ops;
   PROPAGATE(symm_ops_check(c, n_ops, perm, flip, ops_per_pass, &ops));
   char msg[256];
@@ -575,6 +687,8 @@ int vmc_projected_energy(vmc_ctx* c, int which, int32_t n_ops, const int32_t* pe
 int vmc_energy_moments(vmc_ctx* c, int which, int64_t rows_per_pass, double sums[6], double* e_loc, double* h2_loc,
                        int64_t* n_rows2) {
   MEASURE_GATE(c, which, "vmc_energy_moments");
+  if (c->fs.n_terms > 0)
+    return fail(c, VMC_ERR_UNSUPPORTED, "vmc_energy_moments is not available while four-spin terms are set (vmc_set_four_spin_terms): the rows of H^2 do not cover them");
   if (rows_per_pass < 0) return fail(c, VMC_ERR_INVALID, "bad rows_per_pass (0: the library decides)");
   PROPAGATE(needs_ln_psi(c, "vmc_energy_moments"));
   if (c->n_bonds <= 0) return fail(c, VMC_ERR_STATE, "bonds not set (vmc_set_bonds)");

@@ -327,6 +327,8 @@ int vmc_create_product(vmc_ctx* a, vmc_ctx* b, vmc_ctx** out) {
     const int rc = plan_prod_child_check(ch->d.ansatz, ch->oact, ch->prod != nullptr, msg, sizeof(msg));
     if (rc != VMC_OK) return fail(nullptr, rc, msg);
     if (ch->owner) return fail(nullptr, VMC_ERR_STATE, "prod: a factor already belongs to a product ctx");
+    if (ch->fs.n_terms > 0)
+      return fail(nullptr, VMC_ERR_UNSUPPORTED, "vmc_create_product: a factor holds four-spin terms (vmc_set_four_spin_terms); a product ctx has none -- remove them first (n_terms = 0)");
   }
   if (a->N != b->N || a->B != b->B || a->d.device != b->d.device || a->d.chain_offset != b->d.chain_offset ||
       a->stream != b->stream)

@@ -332,6 +332,8 @@ int vmc_create_symmetrized(vmc_ctx* base, int32_t batch_size, int32_t n_ops, con
                                    sizeof(msg));
     if (rc != VMC_OK) return fail(nullptr, rc, msg);
   }
+  if (base->fs.n_terms > 0)
+    return fail(nullptr, VMC_ERR_UNSUPPORTED, "vmc_create_symmetrized: the base holds four-spin terms (vmc_set_four_spin_terms); a symmetrized ctx has none -- remove them first (n_terms = 0)");
   bool any_flip = false;
   for (int k = 0; flips && k < n_ops; ++k) any_flip = any_flip || flips[k] != 0;
   // the composite's own ctx: chains, bond tables, accumulators, scratch -- a minimal dense shape whose network stays unused

@@ -319,7 +319,8 @@ int vmc_accumulate(vmc_ctx* c, int mode, float beta) {
   if (c->sr_cap > 0 && mode == VMC_MODE_ENERGY_GRADIENT) PROPAGATE(sr_record(c));
   c->acc_since_sweep = true;
   // a sampler launch behind a penalised accumulate waits for all of it: the call reads both amplitude caches to its end
-  c->token = cache_was_valid && !refresh_ran && !penalized;
+  // (so does one with four-spin terms: their pass reads the chains and the caches to its end)
+  c->token = cache_was_valid && !refresh_ran && !penalized && c->fs.n_terms == 0;
   return VMC_OK;
 }
 

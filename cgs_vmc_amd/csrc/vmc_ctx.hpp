@@ -141,6 +141,22 @@ struct DimerBufs {
   DevBuf<double> out;            // [n_bonds + n_pairs] bond sums, then dd sums
 };
 
+// four-spin (J-Q) terms of the Hamiltonian (fourspin.hip): the term set as vmc_set_four_spin_terms reduced it, the list
+// of an evaluation, and the result buffers that span it
+struct FourSpinBufs {
+  int n_terms = 0, n_pairs = 0;     // n_terms 0: no terms set -- the ctx is what it is without this struct
+  int exchange_sign = 1;
+  long long rows_per_pass = 0;      // the caller's request (0: the library decides)
+  DevBuf<int2> pairs, term_pairs;   // [n_pairs] sites (min, max); [n_terms] indices into pairs
+  DevBuf<double> wq;                // [n_terms] -q / 4
+  DevBuf<int> n_single, cnt, off;   // [B], [B], [B + 2] (the prefix, then the single rows of all chains)
+  DevBuf<int2> desc;                // [rows per pass] {chain, code}
+  DevBuf<float> logit, sign;        // [rows of the list]; sign: signed types only
+  DevBuf<double> dsum, osum;        // [B] the constant and the ratio part of the chains' term sums (vmc_local_energy_terms)
+  bool want_parts = false;          // the evaluation in flight is vmc_local_energy_terms': the fold keeps dsum / osum too
+  long long last_single = 0, last_double = 0;   // the list lengths of the last evaluation
+};
+
 struct vmc_ctx {
   vmc_desc d;
   // ProductOfWavefunctions (vmc_api_prod.hip, prod.hip): a ctx made by vmc_create_product owns the chains, the accumulators
@@ -280,6 +296,7 @@ struct vmc_ctx {
   ProjBufs proj;
   MomentBufs mom;
   OverlapBufs ovl;
+  FourSpinBufs fs;
   // the Hamiltonian as vmc_set_bonds was given it (vmc_projected_energy asks whether its ops are symmetries of it)
   std::vector<int32_t> ham_ij;
   std::vector<float> ham_jx, ham_jz;
@@ -697,6 +714,9 @@ inline int symmetrized_has_none(vmc_ctx* c, const char* what) {
 // and the fold over the two amplitude caches (ensure_cache of both sets has run) into c->ovl.out
 int overlap_refusals(vmc_ctx* c, const char* what);
 int overlap_sums_device(vmc_ctx* c);
+// vmc_api_measure.hip: the four-spin terms of the Hamiltonian on top of the Heisenberg local energies in ps[which].eloc
+// (local_energy_device calls it while c->fs.n_terms > 0)
+int four_spin_device(vmc_ctx* c, int which);
 // vmc_api_sweep.hip
 bool sampler_refresh_ok(const vmc_ctx* c);
 int refresh_cache_by_sampler(vmc_ctx* c, int which);

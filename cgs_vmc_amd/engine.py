@@ -48,6 +48,8 @@ atexit.register(_close_live_engines)
 class VmcEngine:
   """Owns the device state of one shard of Markov chains and one ansatz."""
 
+  n_four_spin_terms = 0      # four-spin terms the ctx holds (set_four_spin_terms)
+
   def __init__(self, n_sites: int, batch_size: int, num_layers: int, layer_size: int,
                nonlinearity: str = 'relu', output_activation: str = 'exp', device: int = 0,
                chain_offset: int = 0, seed: int = 2024, stream: int = 0,
@@ -273,6 +275,25 @@ class VmcEngine:
     self.n_bonds = nb
     for child in self.children:       # (vmc_set_bonds on a product ctx forwards the table to both factors)
       child.n_bonds = nb
+
+  def set_four_spin_terms(self, terms, q, exchange_sign, rows_per_pass: int = 0):
+    """Four-spin (J-Q) terms on top of the bonds (extension, vmc_set_four_spin_terms): `terms` [n][4] site indices
+    (i, j, k, l), each adding -q (1/4 - S_i.S_j)(1/4 - S_k.S_l); `q` a scalar or one value per term; exchange_sign +1
+    (physical frame) or -1 (sublattice-rotated frame, j_x < 0).  Every local energy of the engine is then that of the
+    whole Hamiltonian.  An empty `terms` removes them.  The term rows go through the ansatz type's full forward in passes
+    of at most rows_per_pass rows (0: the library decides); the results do not depend on it."""
+    ijkl = np.ascontiguousarray(np.asarray(terms, dtype=np.int32).reshape(-1, 4))
+    n = ijkl.shape[0]
+    qs = np.ascontiguousarray(np.broadcast_to(np.asarray(q, np.float32), (n,))) if n else np.zeros(1, np.float32)
+    self._check(self._lib.vmc_set_four_spin_terms(self._ctx, n, _iptr(ijkl) if n else None, _fptr(qs), int(exchange_sign),
+                                                  int(rows_per_pass)))
+    self.n_four_spin_terms = n
+
+  def last_four_spin_rows(self) -> Tuple[int, int]:
+    """(single rows, double rows) of the term list of the last local-energy evaluation with four-spin terms set."""
+    one, two = C.c_int64(), C.c_int64()
+    self._check(self._lib.vmc_last_four_spin_rows(self._ctx, C.byref(one), C.byref(two)))
+    return int(one.value), int(two.value)
 
   def set_lin_tables(self, top, bot):
     """The Lin tables of an 'ed_vector' ctx (vmc_set_lin_tables validates them against the vector's length)."""

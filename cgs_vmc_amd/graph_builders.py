@@ -156,6 +156,11 @@ class ConfigsVariable:
   def _ensure_hamiltonian(self, hamiltonian):
     if self._hamiltonian is not hamiltonian:
       self._engine.set_bonds(hamiltonian._bonds_list, hamiltonian._j_x, hamiltonian._j_z)
+      terms = getattr(hamiltonian, '_four_spin_terms', None)      # (operators.JQHamiltonian)
+      if terms is not None:
+        self._engine.set_four_spin_terms(terms, hamiltonian._q, hamiltonian._exchange_sign)
+      elif getattr(self._engine, 'n_four_spin_terms', 0):
+        self._engine.set_four_spin_terms([], [], 1)                 # a plain Heisenberg Hamiltonian clears them
       self._hamiltonian = hamiltonian
 
   # -- value ----------------------------------------------------------------

@@ -455,3 +455,85 @@ def write_bonds(checkpoint_dir, bonds):
   with open(os.path.join(checkpoint_dir, 'J.txt'), 'w') as f:
     for i, j in bonds:
       f.write('{} {}\n'.format(i, j))
+
+
+def jq_chain_terms(n_sites):
+  """The four-spin terms of the periodic J-Q chain (operators.JQHamiltonian): (i, i + 1, i + 2, i + 3) for every i, the
+  singlet projectors on the bonds (i, i + 1) and (i + 2, i + 3); [n_sites][4] int32.  n_sites >= 4."""
+  if n_sites < 4:
+    raise ValueError('jq_chain_terms: a term names four distinct sites, n_sites >= 4 required, got {}'.format(n_sites))
+  i = np.arange(n_sites).reshape(n_sites, 1)
+  return np.ascontiguousarray(((i + np.arange(4).reshape(1, 4)) % n_sites).astype(np.int32))
+
+
+def jq_torus_terms(size_x, size_y):
+  """The four-spin terms of the J-Q model on the size_x x size_y torus (site numbering of torus_coords): per plaquette
+  with lower left corner s = (x, y) the two parallel horizontal bonds, (s, s + x^, s + y^, s + x^ + y^), then the two
+  parallel vertical ones, (s, s + y^, s + x^, s + x^ + y^); [2 N][4] int32.  Both sizes >= 3."""
+  if size_x < 3 or size_y < 3:
+    raise ValueError('jq_torus_terms: both sizes >= 3 required (a smaller torus folds a plaquette onto itself), got '
+                     '{} x {}'.format(size_x, size_y))
+  terms = []
+  for y in range(size_y):
+    for x in range(size_x):
+      s = x + size_x * y
+      sx = (x + 1) % size_x + size_x * y
+      sy = x + size_x * ((y + 1) % size_y)
+      sxy = (x + 1) % size_x + size_x * ((y + 1) % size_y)
+      terms.append((s, sx, sy, sxy))
+      terms.append((s, sy, sx, sxy))
+  return np.ascontiguousarray(np.asarray(terms, dtype=np.int32))
+
+
+def check_four_spin_terms(terms, n_sites=None):
+  """[n_terms][4] int32 of `terms`, or ValueError: every term names four distinct sites (in 0 .. n_sites - 1 where
+  n_sites is given)."""
+  t = np.asarray(terms)
+  if t.size == 0 or t.ndim != 2 or t.shape[1] != 4 or not np.issubdtype(t.dtype, np.integer):
+    raise ValueError('four-spin terms: a list of (i, j, k, l) integer site indices required, got shape {}'.format(t.shape))
+  for k, row in enumerate(t):
+    if len(set(int(s) for s in row)) != 4 or row.min() < 0 or (n_sites is not None and row.max() >= n_sites):
+      raise ValueError('four-spin term {} = {}: four distinct sites{} required'.format(
+          k, tuple(int(s) for s in row), '' if n_sites is None else ' in 0 .. {}'.format(n_sites - 1)))
+  return np.ascontiguousarray(t.astype(np.int32))
+
+
+def read_four_spin_terms(path, default_q=1.0):
+  """(terms [n][4] int32, q [n] float32) from a text file of rows `i j k l [q]`: blanks or commas separate, `#` starts a
+  comment, a line without any field is skipped; a row without a fifth column takes default_q."""
+  terms, q = [], []
+  with open(path) as f:
+    for number, line in enumerate(f, 1):
+      fields = line.split('#', 1)[0].replace(',', ' ').split()
+      if not fields:
+        continue
+      try:
+        sites = [int(x) for x in fields[:4]]
+        value = float(fields[4]) if len(fields) == 5 else float(default_q)
+      except ValueError:
+        sites = []
+      if len(sites) != 4 or len(fields) > 5 or not np.isfinite(value):
+        raise ValueError('{}:{}: a line is a four-spin term `i j k l [q]` of integer site indices and a finite coupling, '
+                         'got {!r}'.format(path, number, line.strip()))
+      terms.append(sites)
+      q.append(value)
+  if not terms:
+    raise ValueError('{}: no four-spin term'.format(path))
+  return check_four_spin_terms(np.asarray(terms, dtype=np.int64)), np.asarray(q, dtype=np.float32)
+
+
+def write_four_spin_terms(path, terms, q=None):
+  """Rows `i j k l` (q None) or `i j k l q` (a scalar or one value per term) for read_four_spin_terms."""
+  terms = check_four_spin_terms(terms)
+  values = None if q is None else np.broadcast_to(np.asarray(q, np.float64), (terms.shape[0],))
+  with open(path, 'w') as f:
+    for k, (a, b, c, d) in enumerate(terms):
+      f.write('{} {} {} {}'.format(a, b, c, d) + ('\n' if values is None else ' {!r}\n'.format(float(values[k]))))
+
+
+def load_four_spin_terms(checkpoint_dir, default_q=1.0):
+  """(terms, q) of `Q.txt` in a run directory, or None when the directory has none."""
+  path = os.path.join(checkpoint_dir, 'Q.txt')
+  if not os.path.exists(path):
+    return None
+  return read_four_spin_terms(path, default_q)

@@ -89,6 +89,39 @@ class HeisenbergHamiltonian(Operator):
                               'driver and is outside the MI355X hot path')
 
 
+class JQHamiltonian(HeisenbergHamiltonian):
+  """The Heisenberg Hamiltonian of `bonds` plus four-spin terms (extension, no reference counterpart):
+    H = sum_bonds S_i.S_j  -  sum_t q_t (1/4 - S_i.S_j)(1/4 - S_k.S_l),   t = (i, j, k, l) four distinct sites,
+  the J-Q model for the terms of lattice.jq_chain_terms / jq_torus_terms.  `q` is a scalar or one value per term.
+  `exchange_sign` is the sign the transverse part of the projectors carries: +1 in the physical frame, -1 in the
+  sublattice-rotated frame that goes with j_x < 0; it defaults to the common sign of `j_x` (ValueError where the bonds
+  disagree or every j_x is 0).  Installing it on the chains uploads the bonds and then the terms
+  (ConfigsVariable._ensure_hamiltonian); installing a plain HeisenbergHamiltonian afterwards clears them.  Every local
+  energy -- evaluation, the gradient modes, the SR right-hand side -- is then that of the whole Hamiltonian
+  (csrc/fourspin.hip)."""
+
+  def __init__(self, bonds, j_x, j_z, four_spin_terms, q, exchange_sign=None):
+    super(JQHamiltonian, self).__init__(bonds, j_x, j_z)
+    from . import lattice
+    self._four_spin_terms = lattice.check_four_spin_terms(four_spin_terms)
+    n_terms = self._four_spin_terms.shape[0]
+    q = np.asarray(q, np.float32)
+    if q.ndim > 1 or (q.ndim == 1 and q.shape[0] != n_terms):
+      raise ValueError('JQHamiltonian: q is a scalar or one value per term ({} terms), got shape {}'.format(n_terms, q.shape))
+    self._q = np.broadcast_to(q, (n_terms,)).copy()
+    if not np.all(np.isfinite(self._q)):
+      raise ValueError('JQHamiltonian: every q must be finite')
+    if exchange_sign is None:
+      signs = set(np.sign(self._j_x).astype(int).tolist())
+      if signs not in ({1}, {-1}):
+        raise ValueError('JQHamiltonian: the bonds do not share one sign of j_x ({}); state exchange_sign = +1 (physical '
+                         'frame) or -1 (sublattice-rotated frame)'.format(sorted(signs)))
+      exchange_sign = signs.pop()
+    if exchange_sign not in (1, -1):
+      raise ValueError('JQHamiltonian: exchange_sign is +1 or -1, got {!r}'.format(exchange_sign))
+    self._exchange_sign = int(exchange_sign)
+
+
 class HeisenbergBond(HeisenbergHamiltonian):
   """S_i . S_j on one bond (operators.py:128-169): `build` returns
   (0.25 j_z s_i s_j, 0.25 j_x 2 [s_i s_j < 0] psi(R with i and j exchanged)).  It is the

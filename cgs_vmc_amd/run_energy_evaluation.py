@@ -28,7 +28,8 @@ FLAG_TABLE = (
 def evaluate(flags):
   hp = utils.load_hparams(os.path.join(flags.checkpoint_dir, 'hparams.pbtxt'))
   hp.parse(flags.hparams)
-  ansatz, hamiltonian = cli_common.heisenberg_system(hp, flags.checkpoint_dir, flags.heisenberg_jx)
+  ansatz, hamiltonian = cli_common.heisenberg_system(hp, flags.checkpoint_dir, flags.heisenberg_jx,
+                                                     getattr(flags, 'four_spin_q', 1.0))
   evaluator = evaluation.MonteCarloOperatorEvaluator()
   eval_ops = evaluator.build_eval_ops(**cli_common.graph_kwargs(
       wavefunction=ansatz, operator=hamiltonian, hparams=hp))
@@ -40,7 +41,7 @@ def evaluate(flags):
 
 
 def main(argv=None):
-  flags = cli_common.parser_from_table(__doc__, FLAG_TABLE).parse_args(argv)
+  flags = cli_common.parser_from_table(__doc__, FLAG_TABLE + cli_common.FOUR_SPIN_FLAGS).parse_args(argv)
   parallel.init_from_env('nccl')
   samples = evaluate(flags)
   mean_energy = samples.mean()

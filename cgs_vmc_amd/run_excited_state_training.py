@@ -56,7 +56,8 @@ def read_overlap_metrics(run_dir: str):
 
 def train(flags, hp):
   run_dir = hp.checkpoint_dir
-  ansatz, hamiltonian = cli_common.heisenberg_system(hp, flags.checkpoint_dir, flags.heisenberg_jx)
+  ansatz, hamiltonian = cli_common.heisenberg_system(hp, flags.checkpoint_dir, flags.heisenberg_jx,
+                                                     getattr(flags, 'four_spin_q', 1.0))
   check_lower_state(ansatz, hp.num_sites, flags.lower_state_dir)     # before an engine is asked for
   optimizer = training.EXCITED_STATE_OPTIMIZERS[flags.optimizer]()
   train_ops = optimizer.build_opt_ops(**cli_common.graph_kwargs(
@@ -81,7 +82,7 @@ def train(flags, hp):
 
 
 def main(argv=None):
-  flags = cli_common.parser_from_table(__doc__, FLAG_TABLE).parse_args(argv)
+  flags = cli_common.parser_from_table(__doc__, FLAG_TABLE + cli_common.FOUR_SPIN_FLAGS).parse_args(argv)
   if flags.optimizer not in training.EXCITED_STATE_OPTIMIZERS:
     raise ValueError('--optimizer {!r} is no key of training.EXCITED_STATE_OPTIMIZERS {}'.format(
         flags.optimizer, sorted(training.EXCITED_STATE_OPTIMIZERS)))

@@ -44,6 +44,8 @@ def read_lanczos(path: str):
 
 def evaluate(flags):
   """-> (hparams, bonds, result dict of LanczosStepEvaluator.run_evaluation)."""
+  cli_common.refuse_four_spin_terms(flags.checkpoint_dir, 'run_lanczos_evaluation',
+                                    'the local values of H^2 do not cover them (vmc_energy_moments)')
   return cli_common.evaluate_measurement(
       flags, evaluation.LanczosStepEvaluator(), lambda hp, bonds: operators.HeisenbergHamiltonian(bonds, flags.j_x, 1.))
 

@@ -80,6 +80,8 @@ def evaluate(flags):
     names, perms, flips, chi = load_sectors(flags.ops_file, flags.characters_file, flags.spin_flip, hp, bonds)
     labels.extend(names)
     return operators.HeisenbergHamiltonian(bonds, 1.0, 1.), perms, flips, chi
+  cli_common.refuse_four_spin_terms(flags.checkpoint_dir, 'run_projected_energy_evaluation',
+                                    'the symmetry check of the sector estimator does not cover them (vmc_projected_energy)')
   hp, bonds, result = cli_common.evaluate_measurement(flags, evaluation.ProjectedEnergyEvaluator(), load_operator)
   return hp, bonds, labels, result
 

@@ -73,6 +73,7 @@ def read_sector(directory: str, num_sites: int):
 def symmetrized_system(hparams, directory: str, j_x: float, label, perms, flips, chi):
   """(symmetrized ansatz, Hamiltonian): cli_common.heisenberg_system with the base wrapped."""
   del label
+  cli_common.refuse_four_spin_terms(directory, 'the symmetrized drivers', 'a symmetrized ctx takes no four-spin terms')
   base, hamiltonian = cli_common.heisenberg_system(hparams, directory, j_x)
   lattice.check_hamiltonian_symmetry(hamiltonian._bonds_list, j_x, 1.0, perms)
   return wavefunctions.SymmetrizedWavefunction(base, perms, flips if np.any(flips) else None, chi), hamiltonian

@@ -52,7 +52,8 @@ def hparams_from_flags(flags):
 def train(flags, hp):
   chief = parallel.rank() == 0
   run_dir = hp.checkpoint_dir
-  ansatz, hamiltonian = cli_common.heisenberg_system(hp, flags.checkpoint_dir, flags.heisenberg_jx)
+  ansatz, hamiltonian = cli_common.heisenberg_system(hp, flags.checkpoint_dir, flags.heisenberg_jx,
+                                                     getattr(flags, 'four_spin_q', 1.0))
   optimizer = training.GROUND_STATE_OPTIMIZERS[flags.optimizer]()
   train_ops = optimizer.build_opt_ops(**cli_common.graph_kwargs(
       wavefunction=ansatz, hamiltonian=hamiltonian, hparams=hp))
@@ -78,7 +79,7 @@ def train(flags, hp):
 
 
 def main(argv=None):
-  flags = cli_common.parser_from_table(__doc__, FLAG_TABLE).parse_args(argv)
+  flags = cli_common.parser_from_table(__doc__, FLAG_TABLE + cli_common.FOUR_SPIN_FLAGS).parse_args(argv)
   parallel.init_from_env('nccl')
   hp = hparams_from_flags(flags)
   cli_common.ensure_directory(flags.checkpoint_dir)

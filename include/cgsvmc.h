@@ -547,6 +547,41 @@ int vmc_energy_moments(vmc_ctx* ctx, int which, int64_t rows_per_pass /*0: the l
                        double* e_loc /*[batch_size] or NULL*/, double* h2_loc /*[batch_size] or NULL*/,
                        int64_t* n_rows2 /*[1]*/);
 
+/* Four-spin (J-Q) terms of the Hamiltonian -- EXTENSION with no reference counterpart.  A term t = (i, j, k, l; q_t) with
+ * four distinct sites adds
+ *   -q_t (1/4 - S_i . S_j)(1/4 - S_k . S_l)
+ * to the Hamiltonian of vmc_set_bonds.  With spins +-1 and r(y) = psi(y) / psi(x) its local value on a configuration x is
+ *   e_t(x) = -(q_t / 4) [s_i != s_j][s_k != s_l] (1 - sigma r(swap_ij x) - sigma r(swap_kl x) + r(swap_kl swap_ij x))
+ * where sigma = exchange_sign (+-1) is the sign the transverse part carries: +1 in the physical frame, -1 in the
+ * sublattice-rotated frame that goes with j_x < 0 (the frame the positive exp-output states are trained in).
+ * While terms are set every local energy of the ctx is that of H_J + H_Q: vmc_local_energy, the three modes of
+ * vmc_accumulate, the fused epochs, vmc_evaluate (the _dist entries too) and the right-hand side of the SR store; the fold
+ * of the local energies is then never deferred into the back-propagation launch, and a sampler launch behind an
+ * accumulate waits for all of it.  vmc_local_energy_terms adds the 1 of every active bracket (times -q_t / 4) to diag and
+ * the three ratio terms to offdiag_over_psi.
+ * ijkl [n_terms][4], q [n_terms].  n_terms = 0 removes the terms: the ctx is then what it was before it took any.
+ * Per evaluation: a compacted chain-major list -- per chain one single row for every distinct site pair of the terms
+ * that is antiparallel on the chain (pairs ascending by (min, max) site), then one double row for every term with both
+ * pairs antiparallel (terms ascending) -- goes through the ansatz type's own full forward in passes of at most
+ * rows_per_pass rows (0: the library decides; a pass may end inside a chain's rows), and one fold per chain adds, in
+ * fp64, per active term w = -q_t / 4, then fma(-sigma w, r_ij, .), fma(-sigma w, r_kl, .), fma(w, r_ijkl, .) -- lane l the
+ * terms l, l + 64, ... ascending, then a fixed butterfly -- and rounds once to fp32 when the sum is added to the chain's
+ * local energy: the same bits for every rows_per_pass, batch size and grid (csrc/fourspin.hip states every order).  A
+ * chain whose own amplitude vanishes (ed_vector) keeps what the Heisenberg part gives it; a row at a vanishing amplitude
+ * gives r = 0.
+ * Everything is validated before anything is stored, and a failed call leaves the previous term set in place: a site out
+ * of range or named twice in a term, a q that is not finite, an exchange_sign other than +-1, rows_per_pass < 0:
+ * VMC_ERR_INVALID; more than 65,536 terms, more than 4,096 distinct site pairs, batch_size x (pairs + terms) beyond
+ * 2^31 - 1, an output activation other than exp on an unsigned type, a product ctx, a symmetrized ctx:
+ * VMC_ERR_UNSUPPORTED; a factor of a product ctx or the base of a symmetrized ctx: VMC_ERR_STATE.  vmc_create_product and
+ * vmc_create_symmetrized refuse a ctx that holds terms, vmc_energy_moments and vmc_projected_energy refuse while terms
+ * are set (VMC_ERR_UNSUPPORTED); the other measurements are measurements of the state and stay available. */
+int vmc_set_four_spin_terms(vmc_ctx* ctx, int32_t n_terms, const int32_t* ijkl /*[n_terms][4]*/,
+                            const float* q /*[n_terms]*/, int32_t exchange_sign /*+1 or -1*/,
+                            int64_t rows_per_pass /*0: the library decides*/);
+/* The lengths of the list of the last evaluation with terms set: its single rows and its double rows. */
+int vmc_last_four_spin_rows(vmc_ctx* ctx, int64_t* single_rows, int64_t* double_rows);
+
 /* Overlap with the frozen parameter set -- EXTENSION with no reference counterpart.  Over the ctx's current chains x_c,
  * drawn from |psi|^2, with r_c = omega(x_c) / psi(x_c):
  *   d_c = (logit_omega(c) - shift_omega) - (logit_psi(c) - shift_psi)      fp64, from the two fp32 amplitude caches

@@ -7,6 +7,11 @@ J.txt in a directory, plus hparams.pbtxt and a first checkpoint (model_prior_0_e
   python tools/make_ed_vector.py DIR --lattice square --size 4 4
   python tools/make_ed_vector.py DIR --lattice triangular --size 4 4
   python tools/make_ed_vector.py DIR --lattice chain --size 28 --random [--seed 0]
+  python tools/make_ed_vector.py DIR --lattice chain --size 8 --jx -1 --jq 1.0
+
+--jq Q (chain and square lattices) adds the four-spin terms of the J-Q model, -Q (1/4 - S_i.S_j)(1/4 - S_k.S_l) over
+lattice.jq_chain_terms / jq_torus_terms, writes them to Q.txt -- the drivers then run operators.JQHamiltonian -- and the
+vector is the ground state of the whole Hamiltonian; the transverse part of the projectors carries the sign of --jx.
 
 The vector is the ground state of sum_<ij> jz Sz_i Sz_j + jx/2 (S+_i S-_j + h.c.) in the Sz = 0 sector by scipy's
 eigsh (a few thousand to a few million entries: up to about 24 sites), or with --random a positive random vector of
@@ -66,7 +71,7 @@ def bonds_of(lattice, size):
   return sorted(bonds)
 
 
-def ground_state(n, bonds, jx, jz):
+def ground_state(n, bonds, jx, jz, terms=(), jq=0.0):
   import scipy.sparse as sp
   import scipy.sparse.linalg as spla
   top, bot, length = lin_tables(n)
@@ -81,8 +86,16 @@ def ground_state(n, bonds, jx, jz):
     anti = np.flatnonzero(si != sj)
     rows.append(anti)
     cols.append(lookup(words[anti] ^ (1 << i) ^ (1 << j)))
-  rows, cols = np.concatenate(rows), np.concatenate(cols)
-  hmat = sp.csr_matrix((np.full(len(rows), 0.5 * jx), (rows, cols)), shape=(length, length)) + sp.diags(diag)
+  vals = [np.full(len(r), 0.5 * jx) for r in rows]
+  sigma, w = (1.0 if jx >= 0 else -1.0), -0.25 * jq
+  for i, j, k, l in terms:      # -jq (1/4 - S_i.S_j)(1/4 - S_k.S_l) = w [anti_ij][anti_kl] (1 - sigma P_ij - sigma P_kl + P_ij P_kl)
+    act = np.flatnonzero((((words >> i) ^ (words >> j)) & ((words >> k) ^ (words >> l)) & 1) == 1)
+    diag[act] += w
+    for flip, value in (((1 << i) ^ (1 << j), -sigma * w), ((1 << k) ^ (1 << l), -sigma * w),
+                        ((1 << i) ^ (1 << j) ^ (1 << k) ^ (1 << l), w)):
+      rows.append(act); cols.append(lookup(words[act] ^ flip)); vals.append(np.full(len(act), value))
+  rows, cols, vals = np.concatenate(rows), np.concatenate(cols), np.concatenate(vals)
+  hmat = sp.csr_matrix((vals, (rows, cols)), shape=(length, length)) + sp.diags(diag)
   w, v = spla.eigsh(hmat, k=1, which='SA')
   vec = v[:, 0]
   return float(w[0]), vec * np.sign(vec[np.argmax(np.abs(vec))])
@@ -95,6 +108,7 @@ def main(argv=None):
   ap.add_argument('--size', type=int, nargs='+', required=True, help='sites of the chain, or the two sides of the torus')
   ap.add_argument('--jx', type=float, default=1.0)
   ap.add_argument('--jz', type=float, default=1.0)
+  ap.add_argument('--jq', type=float, default=None, help='coupling Q of the four-spin (J-Q) terms; writes Q.txt')
   ap.add_argument('--random', action='store_true', help='a positive random vector instead of the ground state')
   ap.add_argument('--seed', type=int, default=0)
   args = ap.parse_args(argv)
@@ -106,19 +120,29 @@ def main(argv=None):
   if args.jz != 1.0 and not args.random:
     print('note: the drivers run HeisenbergHamiltonian with jz = 1; this state belongs to jz = %g' % args.jz)
   bonds = bonds_of(args.lattice, args.size)
+  terms = []
+  if args.jq is not None:
+    from cgs_vmc_amd import lattice as lat
+    if args.lattice == 'triangular':
+      ap.error('--jq takes the chain and the square lattice')
+    if args.jx == 0:
+      ap.error('--jq needs a sign of --jx: the exchange sign of the four-spin terms')
+    terms = (lat.jq_chain_terms(n) if args.lattice == 'chain' else lat.jq_torus_terms(*args.size)).tolist()
   top, bot, length = lin_tables(n)
   if args.random:
     vec = np.random.default_rng(args.seed).uniform(0.5, 1.5, length)
     vec /= np.linalg.norm(vec)
     e0 = None
   else:
-    e0, vec = ground_state(n, bonds, args.jx, args.jz)
+    e0, vec = ground_state(n, bonds, args.jx, args.jz, terms, args.jq or 0.0)
   from cgs_vmc_amd import lattice as lat, utils
   os.makedirs(args.directory, exist_ok=True)
   np.savetxt(os.path.join(args.directory, 'top_lin_table.txt'), top, fmt='%d')
   np.savetxt(os.path.join(args.directory, 'bot_lin_table.txt'), bot, fmt='%d')
   np.savetxt(os.path.join(args.directory, 'ed_vector.txt'), vec.astype(np.float32), fmt='%.9g')
   lat.write_bonds(args.directory, bonds)
+  if terms:
+    lat.write_four_spin_terms(os.path.join(args.directory, 'Q.txt'), terms, args.jq)
   hp = utils.create_hparams()
   for field, value in (('checkpoint_dir', args.directory), ('num_sites', n), ('wavefunction_type', 'ed_vector'),
                        ('top_lin_table_file', 'top_lin_table.txt'), ('bot_lin_table_file', 'bot_lin_table.txt'),
