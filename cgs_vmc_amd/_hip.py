@@ -183,7 +183,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 _STAMP_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libcgsvmc_hip.stamp')
 # the files the library is built from, in the order csrc/Makefile hashes them
 _SOURCES = ('vmc_api.hip', 'vmc_api_cgen.hip', 'vmc_api_sweep.hip', 'vmc_api_train.hip', 'vmc_api_coll.hip', 'vmc_api_sr.hip', 'vmc_api_prod.hip', 'prod.hip', 'vmc_api_symz.hip', 'symz.hip', 'mlp.hip', 'eloc.hip', 'grad.hip', 'sr.hip', 'srmm.hip', 'srgram.hip', 'conv.hip', 'conv32.hip', 'conv48.hip', 'conv64.hip', 'conv_general.hip', 'conv_band.hip', 'conv_patch.hip', 'wide.hip', 'tail_split.hip', 'sweep_split.hip', 'sweep8.hip', 'pbdg.hip', 'nnb.hip', 'edvec.hip', 'vmc_api_measure.hip', 'corr.hip', 'renyi.hip', 'dimer.hip', 'symm.hip', 'proj.hip', 'moments.hip', 'overlap.hip', 'fourspin.hip', 'act_tail.hip',
-            'act_sweep.hip', 'vmc_ctx.hpp', 'prod.hpp', 'symz.hpp', 'plan.hpp', 'common.hpp', 'pb_det.hpp', 'tail16.hpp', 'tail_lds.hpp', 'sweep16.hpp', 'conv.hpp', 'conv_kernels.hpp',
+            'act_sweep.hip', 'vmc_ctx.hpp', 'prod.hpp', 'symz.hpp', 'plan.hpp', 'common.hpp', 'measure_dev.hpp', 'pb_det.hpp', 'tail16.hpp', 'tail_lds.hpp', 'sweep16.hpp', 'conv.hpp', 'conv_kernels.hpp',
             'conv_wide.hpp',
             os.path.join('..', '..', 'include', 'cgsvmc.h'), 'Makefile')
 

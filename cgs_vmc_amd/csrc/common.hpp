@@ -411,26 +411,8 @@ hipError_t launch_fs_fold(hipStream_t s, const float* configs, const int2* pairs
                           const int* off, AmpPair own, AmpPair rows, int B, int N, int n_pairs, int n_terms,
                           int exchange_sign, float* eloc, double* dsum, double* osum);
 
-// device helpers and the grid rule the Renyi-2, dimer, symmetry, projection and moment kernels share
-// sign of a stored sign / amplitude: +-1, 0 for a vanishing amplitude
-__device__ inline int sgn_of(float v) { return (v > 0.f) - (v < 0.f); }
-// psi(row) / psi(x) from ln|psi| and, signed types, the signs (own_sgn = +-1: the caller has dropped a chain whose own
-// amplitude vanishes).  A vanishing amplitude of the row gives 0 exactly: its logarithm is never read.
-__device__ inline double measure_ratio(const float* __restrict__ row_logit, const float* __restrict__ row_sign, long long at,
-                                       double own_logit, int own_sgn) {
-  int sg = own_sgn;
-  if (row_sign) sg *= sgn_of(row_sign[at]);
-  if (sg == 0) return 0.0;
-  return (double)sg * exp((double)row_logit[at] - own_logit);
-}
-// the row writers (k_swap_rows, k_dimer_rows1 / 2, k_symm_rows): blocks of 4 wavefronts, one item per wavefront, at most 16 blocks per CU
-inline unsigned measure_rows_grid(long long items, int num_cus) {
-  long long blocks = (items + 3) / 4;
-  const long long cap = 16LL * (num_cus > 0 ? num_cus : 1);
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (unsigned)blocks;
-}
+// (the device helpers these kernels share -- sgn_of, measure_ratio, the row writer, the tile scan -- and their grid rule
+// measure_rows_grid: measure_dev.hpp)
 
 // overlap with the frozen parameter set (overlap.hip; the estimator, the dead-chain rule and every summation order are
 // stated there).  ratio: d [B] = ln|omega / psi| per chain in fp64, code [B] = the combined sign (+-1, 0 where omega

@@ -6,13 +6,14 @@
 // i.e. <x| A B |psi> / psi(x): B acts on the intermediate configuration x', so bonds that share a site and a == b are
 // the same lines of code as disjoint ones.
 //
-// k_dimer_rows1 / k_dimer_rows2 write the rows the family's own forward evaluates: an exchanged configuration where the
+// k_dimer_rows1 / k_dimer_rows2 write the rows the family's own forward evaluates (each decodes its item and its
+// indicator, then calls write_exchanged_row; spin_after gives the spins on x': measure_dev.hpp): an exchanged configuration where the
 // exchange acts (the bond antiparallel) and the chain's own elsewhere -- an exchange of two opposite spins keeps
 // Sz = 0, which the kernels that index by up / down counts (pbdg, nnb, ed_vector) rely on; the forward of an unexchanged
 // row is wasted work, the price of no compaction and no atomics.  The folds give one thread per bond / pair, which walks
 // the chains in ascending order, re-derives the indicator bits from the spins it gathers and adds the terms in fp64: a
 // sum depends on the chains alone -- not on the pass the pair is in, not on the other entries of the lists, not on the grid.
-#include "common.hpp"
+#include "measure_dev.hpp"
 
 // One wavefront per (bond, chain): the lanes run along the site axis, so the loads of the chain and the stores of the
 // row are contiguous per wavefront.  Spins stay the fp32 +-1 the family kernels read.
@@ -25,14 +26,7 @@ __global__ __launch_bounds__(256) void k_dimer_rows1(const float* __restrict__ c
     const float* x = configs + (long long)c * N;
     const int2 ij = bonds[a];
     const float si = x[ij.x], sj = x[ij.y];
-    const bool ex = si != sj;
-    float* row = rows + it * N;
-    for (int q = lane; q < N; q += 64) {
-      float v = x[q];
-      if (ex && q == ij.x) v = sj;
-      if (ex && q == ij.y) v = si;
-      row[q] = v;
-    }
+    write_exchanged_row(rows + it * N, x, N, lane, ij, si, sj, si != sj, ij, si, sj, false);
   }
 }
 
@@ -48,22 +42,9 @@ __global__ __launch_bounds__(256) void k_dimer_rows2(const float* __restrict__ c
     const int2 ab = pairs[p];
     const int2 ij = bonds[ab.x], kl = bonds[ab.y];
     const float si = x[ij.x], sj = x[ij.y];
-    const bool ex1 = si != sj;
-    // the spins of k and l on x'
-    const float sk = kl.x == ij.x ? sj : (kl.x == ij.y ? si : x[kl.x]);
-    const float sl = kl.y == ij.x ? sj : (kl.y == ij.y ? si : x[kl.y]);
-    const bool both = ex1 && sk != sl;
-    float* row = rows + it * N;
-    for (int q = lane; q < N; q += 64) {
-      float v = x[q];
-      if (both) {
-        if (q == ij.x) v = sj;                       // x'
-        if (q == ij.y) v = si;
-        if (q == kl.x) v = sl;                       // swap_kl x' (k or l may be i or j: the later exchange decides)
-        if (q == kl.y) v = sk;
-      }
-      row[q] = v;
-    }
+    const float sk = spin_after(x, kl.x, ij, si, sj), sl = spin_after(x, kl.y, ij, si, sj);       // on x'
+    const bool both = si != sj && sk != sl;          // (the chain's own row unless BOTH exchanges act)
+    write_exchanged_row(rows + it * N, x, N, lane, ij, si, sj, both, kl, sk, sl, both);
   }
 }
 
@@ -117,8 +98,7 @@ __global__ __launch_bounds__(64) void k_dimer_fold(const float* __restrict__ con
       term = 0.25 * (double)(si * sj) * inner;
       if (si != sj) {
         // B on x' = swap_ij x
-        const float tk = kl.x == ij.x ? sj : (kl.x == ij.y ? si : sk);
-        const float tl = kl.y == ij.x ? sj : (kl.y == ij.y ? si : sl);
+        const float tk = spin_after(x, kl.x, ij, si, sj), tl = spin_after(x, kl.y, ij, si, sj);
         double outer = 0.25 * (double)(tk * tl) * measure_ratio(one_logit, one_sign, (long long)ab.x * B + c, l0, own);
         if (tk != tl) outer += 0.5 * measure_ratio(two_logit, two_sign, (long long)p * B + c, l0, own);
         term += 0.5 * outer;

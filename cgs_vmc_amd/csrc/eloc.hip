@@ -6,7 +6,7 @@
 // generated: k_bond_count / k_bond_fill build a compact, chain-ordered list of the
 // antiparallel bonds, k_tail16 (mlp.hip) evaluates exactly those rows, and k_eloc_reduce sums
 // each chain's segment in a fixed order (deterministic, no float atomics).
-#include "common.hpp"
+#include "measure_dev.hpp"
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(1024) void k_bond_fill(const float* __restrict__ co
     }
     const unsigned long long m = __ballot(anti);
     if (anti) {
-      const int p = __popcll(m & ((1ull << lane) - 1ull));
+      const int p = lanes_below(m, lane);
       rowinfo[base + p] = make_int2(c, si > 0.f ? (k + 1) : -(k + 1));
     }
     base += __popcll(m);

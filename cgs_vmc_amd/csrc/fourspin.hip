@@ -9,11 +9,13 @@
 //
 // The list.  Chain-major and compacted: per chain first one SINGLE row for every pair antiparallel on the chain, pairs
 // ascending, then one DOUBLE row for every term with both pairs antiparallel, terms ascending.  k_fs_count counts both
-// per chain, k_fs_scan is the exclusive prefix off [B + 1] over the chains, and k_fs_fill writes the descriptors
-// {chain, code} -- code = the pair index of a single row, n_pairs + the term index of a double row -- of the rows
-// [q0, q0 + n) of ONE pass.  The place of a row within its chain is a ballot and a popcount over the lanes, which run
-// along the pairs or terms.  No atomics: the list depends on the configurations alone.  k_fs_rows writes the exchanged
-// configurations of a pass's rows (one wavefront per row, the lanes along the site axis) for the family's own full
+// per chain, k_fs_scan is the exclusive prefix off [B + 1] over the chains (tile_scan_1024), and k_fs_fill writes the
+// descriptors {chain, code} -- code = the pair index of a single row, n_pairs + the term index of a double row -- of the
+// rows [q0, q0 + n) of ONE pass.  The place of a row within its chain is a ballot and a popcount over the lanes, which
+// run along the pairs or terms: fs_walk states this order once, for the fill and the fold.  No atomics: the list depends
+// on the configurations alone.  (The prefix, the row writer, lanes_below, measure_ratio and the fp64 butterfly
+// wave_sum_f64 are the shared pieces of measure_dev.hpp.)  k_fs_rows writes the exchanged configurations of a pass's
+// rows (one wavefront per row, the lanes along the site axis) for the family's own full
 // forward, which leaves ln|psi| and the sign of every row in a result buffer that spans the whole list.
 //
 // The fold (k_fs_fold), once, after the last pass; one wavefront per chain:
@@ -28,16 +30,10 @@
 // operations in both.  Every output is the same bits for every pass size, batch size and grid.
 // A chain whose own amplitude vanishes (ed_vector) keeps what the Heisenberg part gave it: nothing is added, its rows are
 // in the list but their values are never read.  A row at a vanishing amplitude gives r = 0.
-#include "common.hpp"
+#include "measure_dev.hpp"
 #include "plan.hpp"
 
 namespace {
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 __device__ __forceinline__ bool pair_anti(const float* __restrict__ x, const int2* __restrict__ pairs, int n_pairs, int p) {
   if (p >= n_pairs) return false;
@@ -53,13 +49,38 @@ __device__ __forceinline__ bool term_active(const float* __restrict__ x, const i
   return x[ij.x] != x[ij.y] && x[kl.x] != x[kl.y];
 }
 
-__device__ __forceinline__ int lanes_below(unsigned long long m, int lane) {
-  return __popcll(m & ((1ull << lane) - 1ull));
+// The order of a chain's part of the list, stated once: the pairs in groups of 64 (lane = place in the group), then the
+// terms.  Per group the lanes within the table call f(emit, code, at) -- emit: this lane's pair / term has a row; code: the
+// pair index, or n_pairs + the term index; at: the row's place in the list, q + the emitting lanes below.  between() runs
+// once, behind the pair groups.  Returns q behind the chain's rows.  The whole wavefront calls it.  (A callable may tell
+// a pair from a term by code < n_pairs: the term's code is formed as n_pairs + t with t >= 0 in sight, so that the
+// compiler drops the other half in each loop -- profiles/list_scaffold_resources.txt has what it costs otherwise.)
+template <class F, class G>
+__device__ __forceinline__ long long fs_walk(const float* __restrict__ x, const int2* __restrict__ pairs,
+                                             const int2* __restrict__ term_pairs, int n_pairs, int n_terms, int lane,
+                                             long long q, F f, G between) {
+  for (int p0 = 0; p0 < n_pairs; p0 += 64) {
+    const int p = p0 + lane;
+    const bool emit = pair_anti(x, pairs, n_pairs, p);
+    const unsigned long long m = __ballot(emit);
+    if (p < n_pairs) f(emit, p, q + lanes_below(m, lane));
+    q += __popcll(m);
+  }
+  between();
+  for (int t0 = 0; t0 < n_terms; t0 += 64) {
+    const int t = t0 + lane;
+    const bool emit = term_active(x, pairs, term_pairs, n_terms, t);
+    const unsigned long long m = __ballot(emit);
+    if (t < n_terms) f(emit, n_pairs + t, q + lanes_below(m, lane));
+    q += __popcll(m);
+  }
+  return q;
 }
 
 }  // namespace
 
-// One wavefront per chain (grid-stride): n_single[c] single rows, cnt[c] = single + double rows
+// One wavefront per chain (grid-stride): n_single[c] single rows, cnt[c] = single + double rows.  (Not over fs_walk: it
+// wants the two totals and no place -- the order of the list does not enter a count.)
 __global__ __launch_bounds__(256) void k_fs_count(const float* __restrict__ configs, const int2* __restrict__ pairs,
                                                   const int2* __restrict__ term_pairs, int B, int N, int n_pairs,
                                                   int n_terms, int* __restrict__ n_single, int* __restrict__ cnt) {
@@ -73,37 +94,16 @@ __global__ __launch_bounds__(256) void k_fs_count(const float* __restrict__ conf
   }
 }
 
-// One workgroup: off[c] = sum of cnt[0 .. c) for c <= B, tiles of 1024 entries with a running carry, and off[B + 1] = the
-// sum of n_single (integers: the order of the additions does not matter)
+// One workgroup: off[c] = sum of cnt[0 .. c) for c <= B (tile_scan_1024, measure_dev.hpp) and off[B + 1] = the sum of
+// n_single (integers: the order of the additions does not matter)
 __global__ __launch_bounds__(1024) void k_fs_scan(const int* __restrict__ cnt, const int* __restrict__ n_single, int B,
                                                   int* __restrict__ off) {
   __shared__ int s_wave[16];
   __shared__ int s_single[16];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  int carry = 0, singles = 0;
-  for (int base = 0; base < B; base += 1024) {
-    const int i = base + t;
-    const int v = i < B ? cnt[i] : 0;
-    singles += i < B ? n_single[i] : 0;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-      const int sw = s_wave[w];
-      if (w < wave) before += sw;
-      total += sw;
-    }
-    if (i < B) off[i] = carry + before + incl - v;
-    carry += total;
-    __syncthreads();
-  }
+  tile_scan_1024(cnt, B, off, s_wave);
+  int singles = 0;
+  for (int i = t; i < B; i += 1024) singles += n_single[i];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) singles += __shfl_xor(singles, o, 64);
   if (lane == 0) s_single[wave] = singles;
@@ -111,7 +111,6 @@ __global__ __launch_bounds__(1024) void k_fs_scan(const int* __restrict__ cnt, c
   if (t == 0) {
     int all = 0;
     for (int w = 0; w < 16; ++w) all += s_single[w];
-    off[B] = carry;
     off[B + 1] = all;
   }
 }
@@ -125,23 +124,12 @@ __global__ __launch_bounds__(256) void k_fs_fill(const float* __restrict__ confi
   const int lane = threadIdx.x & 63;
   const long long q1 = q0 + n;
   for (long long c = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); c < B; c += (long long)gridDim.x * 4) {
-    long long q = off[c];
-    if (off[c + 1] <= q0 || q >= q1) continue;
-    const float* x = configs + c * N;
-    for (int p0 = 0; p0 < n_pairs; p0 += 64) {
-      const bool emit = pair_anti(x, pairs, n_pairs, p0 + lane);
-      const unsigned long long m = __ballot(emit);
-      const long long at = q + lanes_below(m, lane);
-      if (emit && at >= q0 && at < q1) desc[at - q0] = make_int2((int)c, p0 + lane);
-      q += __popcll(m);
-    }
-    for (int t0 = 0; t0 < n_terms; t0 += 64) {
-      const bool emit = term_active(x, pairs, term_pairs, n_terms, t0 + lane);
-      const unsigned long long m = __ballot(emit);
-      const long long at = q + lanes_below(m, lane);
-      if (emit && at >= q0 && at < q1) desc[at - q0] = make_int2((int)c, n_pairs + t0 + lane);
-      q += __popcll(m);
-    }
+    if (off[c + 1] <= q0 || off[c] >= q1) continue;
+    fs_walk(configs + c * N, pairs, term_pairs, n_pairs, n_terms, lane, off[c],
+            [&](bool emit, int code, long long at) {
+              if (emit && at >= q0 && at < q1) desc[at - q0] = make_int2((int)c, code);
+            },
+            [] {});
   }
 }
 
@@ -154,26 +142,18 @@ __global__ __launch_bounds__(256) void k_fs_rows(const float* __restrict__ confi
   for (long long it = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); it < n; it += (long long)gridDim.x * 4) {
     const int2 cd = desc[it];
     const float* x = configs + (long long)cd.x * N;
-    int2 ij, kl;
-    if (cd.y < n_pairs) {
-      ij = pairs[cd.y];
-      kl = ij;                                       // (a single row: the second exchange names the same sites and is skipped)
-    } else {
+    const bool two = cd.y >= n_pairs;
+    int2 ij, kl = make_int2(0, 0);
+    float sk = 0.f, sl = 0.f;                        // (a single row has no second exchange: never read)
+    if (two) {
       const int2 ab = term_pairs[cd.y - n_pairs];
       ij = pairs[ab.x];
       kl = pairs[ab.y];
+      sk = x[kl.x]; sl = x[kl.y];
+    } else {
+      ij = pairs[cd.y];
     }
-    const bool two = cd.y >= n_pairs;
-    const float si = x[ij.x], sj = x[ij.y], sk = x[kl.x], sl = x[kl.y];
-    float* row = rows + it * N;
-    for (int q = lane; q < N; q += 64) {
-      float v = x[q];
-      if (q == ij.x) v = sj;
-      if (q == ij.y) v = si;
-      if (two && q == kl.x) v = sl;
-      if (two && q == kl.y) v = sk;
-      row[q] = v;
-    }
+    write_exchanged_row(rows + it * N, x, N, lane, ij, x[ij.x], x[ij.y], true, kl, sk, sl, two);
   }
 }
 
@@ -198,38 +178,30 @@ __global__ __launch_bounds__(64) void k_fs_fold(const float* __restrict__ config
   }
   const double l0 = (double)logit[c];
   const float* x = configs + (long long)c * N;
-  long long q = off[c];
-  for (int p0 = 0; p0 < n_pairs; p0 += 64) {
-    const int p = p0 + lane;
-    const bool anti = pair_anti(x, pairs, n_pairs, p);
-    const unsigned long long m = __ballot(anti);
-    if (p < n_pairs) s_r[p] = anti ? measure_ratio(row_logit, row_sign, q + lanes_below(m, lane), l0, own) : 0.0;
-    q += __popcll(m);
-  }
-  __syncthreads();
   double s = 0.0, d = 0.0, o = 0.0;
-  for (int t0 = 0; t0 < n_terms; t0 += 64) {
-    const int t = t0 + lane;
-    const bool act = term_active(x, pairs, term_pairs, n_terms, t);
-    const unsigned long long m = __ballot(act);
-    if (act) {
-      const int2 ab = term_pairs[t];
-      const double w = wq[t], ws = -sigma * w;
-      const double r1 = s_r[ab.x], r2 = s_r[ab.y];
-      const double r12 = measure_ratio(row_logit, row_sign, q + lanes_below(m, lane), l0, own);
-      s += w;
-      s = fma(ws, r1, s);
-      s = fma(ws, r2, s);
-      s = fma(w, r12, s);
-      if (PARTS) {
-        d += w;
-        o = fma(ws, r1, o);
-        o = fma(ws, r2, o);
-        o = fma(w, r12, o);
-      }
-    }
-    q += __popcll(m);
-  }
+  fs_walk(x, pairs, term_pairs, n_pairs, n_terms, lane, off[c],
+          [&](bool emit, int code, long long at) {
+            if (code < n_pairs) {                    // a pair: its ratio by pair index, 0 where it is parallel
+              s_r[code] = emit ? measure_ratio(row_logit, row_sign, at, l0, own) : 0.0;
+            } else if (emit) {                       // an active term
+              const int t = code - n_pairs;
+              const int2 ab = term_pairs[t];
+              const double w = wq[t], ws = -sigma * w;
+              const double r1 = s_r[ab.x], r2 = s_r[ab.y];
+              const double r12 = measure_ratio(row_logit, row_sign, at, l0, own);
+              s += w;
+              s = fma(ws, r1, s);
+              s = fma(ws, r2, s);
+              s = fma(w, r12, s);
+              if (PARTS) {
+                d += w;
+                o = fma(ws, r1, o);
+                o = fma(ws, r2, o);
+                o = fma(w, r12, o);
+              }
+            }
+          },
+          [] { __syncthreads(); });                  // the terms read every pair's ratio
   s = wave_sum_f64(s);
   if (PARTS) {
     d = wave_sum_f64(d);
@@ -241,11 +213,9 @@ __global__ __launch_bounds__(64) void k_fs_fold(const float* __restrict__ config
   }
 }
 
-static unsigned fs_chain_grid(int B, int num_cus) { return measure_rows_grid(B, num_cus); }
-
 hipError_t launch_fs_count(hipStream_t s, const float* configs, const int2* pairs, const int2* term_pairs, int B, int N,
                            int n_pairs, int n_terms, int num_cus, int* n_single, int* cnt, int* off) {
-  hipLaunchKernelGGL(k_fs_count, dim3(fs_chain_grid(B, num_cus)), dim3(256), 0, s, configs, pairs, term_pairs, B, N,
+  hipLaunchKernelGGL(k_fs_count, dim3(measure_rows_grid(B, num_cus)), dim3(256), 0, s, configs, pairs, term_pairs, B, N,
                      n_pairs, n_terms, n_single, cnt);
   hipLaunchKernelGGL(k_fs_scan, dim3(1), dim3(1024), 0, s, cnt, n_single, B, off);
   return hipGetLastError();
@@ -253,7 +223,7 @@ hipError_t launch_fs_count(hipStream_t s, const float* configs, const int2* pair
 
 hipError_t launch_fs_fill(hipStream_t s, const float* configs, const int2* pairs, const int2* term_pairs, const int* off,
                           int B, int N, int n_pairs, int n_terms, long long q0, int n, int num_cus, int2* desc) {
-  hipLaunchKernelGGL(k_fs_fill, dim3(fs_chain_grid(B, num_cus)), dim3(256), 0, s, configs, pairs, term_pairs, off, B, N,
+  hipLaunchKernelGGL(k_fs_fill, dim3(measure_rows_grid(B, num_cus)), dim3(256), 0, s, configs, pairs, term_pairs, off, B, N,
                      n_pairs, n_terms, q0, n, desc);
   return hipGetLastError();
 }

@@ -193,7 +193,7 @@ static void check_per_pass() {
   for (long long total : totals)
     for (long long req : reqs)
       for (long long lim : limits) {
-        const long long per = plan_fourspin_per_pass(total, req, lim);
+        const long long per = plan_list_per_pass(total, req, lim);
         CHECK(per >= 1 && per <= PLAN_MEASURE_ROW_BUDGET);
         if (lim > 0) CHECK(per <= lim);
         if (req > 0) CHECK(per <= req);
@@ -203,7 +203,7 @@ static void check_per_pass() {
         CHECK(passes * per >= total && (passes == 0 || (passes - 1) * per < total));
         ++g_cases;
       }
-  CHECK(plan_fourspin_per_pass(-1, 0, 0) == -1 && plan_fourspin_per_pass(5, -1, 0) == -1 && plan_fourspin_per_pass(5, 0, -1) == -1);
+  CHECK(plan_list_per_pass(-1, 0, 0) == -1 && plan_list_per_pass(5, -1, 0) == -1 && plan_list_per_pass(5, 0, -1) == -1);
 }
 
 // the rows reserved for the result buffers: never fewer than the list, never more than the a-priori maximum, the maximum
@@ -255,7 +255,7 @@ static void check_list(std::mt19937& rng, int N, int B, const std::vector<int32_
   const long long total = off[(size_t)B];
   CHECK(total <= (long long)B * (n_pairs + n_terms));
   for (long long req : {1LL, 7LL, 61LL, total + 5, 0LL}) {
-    const long long per = plan_fourspin_per_pass(total, req, 0);
+    const long long per = plan_list_per_pass(total, req, 0);
     std::vector<int> written((size_t)total, 0), code_of((size_t)total, -1), chain_of((size_t)total, -1);
     bool inside = false;
     for (long long q0 = 0; q0 < total; q0 += per) {

@@ -39,7 +39,7 @@ static void check_per_pass() {
   for (long long n2 : n2s)
     for (long long req : reqs)
       for (long long lim : limits) {
-        const long long per = plan_moment_per_pass(n2, req, lim);
+        const long long per = plan_list_per_pass(n2, req, lim);
         CHECK(per >= 1 && per <= PLAN_MEASURE_ROW_BUDGET);
         if (lim > 0) CHECK(per <= lim);
         if (req > 0) CHECK(per <= req);
@@ -48,7 +48,7 @@ static void check_per_pass() {
         const long long passes = plan_measure_passes(n2, (int)per);
         CHECK(passes * per >= n2 && (passes == 0 || (passes - 1) * per < n2));
       }
-  CHECK(plan_moment_per_pass(-1, 0, 0) == -1 && plan_moment_per_pass(5, -1, 0) == -1 && plan_moment_per_pass(5, 0, -1) == -1);
+  CHECK(plan_list_per_pass(-1, 0, 0) == -1 && plan_list_per_pass(5, -1, 0) == -1 && plan_list_per_pass(5, 0, -1) == -1);
 }
 
 // a list: B chains, first-order rows per chain, second-order rows per first-order row
@@ -61,7 +61,7 @@ static void check_list(std::mt19937& rng, int B, int max_first, int max_second, 
   const long long n2 = off2[(size_t)n1];
   std::vector<int> last_by_lane((size_t)B * 64);
   for (long long req : pass_sizes) {
-    const long long per = plan_moment_per_pass(n2, req, 0);
+    const long long per = plan_list_per_pass(n2, req, 0);
     std::vector<int> written((size_t)n2, 0), read((size_t)n2, 0);
     std::fill(last_by_lane.begin(), last_by_lane.end(), -1);
     bool inside = false;

@@ -13,7 +13,8 @@
 // the sum of rule 1's hx_b per first-order row), k_mom_scan is the exclusive prefix off2 over the first-order rows, and
 // k_mom_fill writes the descriptors {first-order row, b} and coefficients of the rows [q0, q0 + n) of ONE pass -- the list
 // itself never exists as a whole.  No atomics: the same list on every run.  k_mom_rows writes the configurations of a
-// pass's rows (lanes along the site axis) for the family's own full forward.
+// pass's rows (lanes along the site axis) for the family's own full forward.  The prefix, the row writer, spin_after,
+// lanes_below and the fp64 butterfly wave_sum_f64 are the shared pieces of measure_dev.hpp.
 //
 // Summation order (every output is the same bits for every pass size; a pass may end inside a chain's rows):
 //   * diag(y) of any configuration: lane l adds qz_b y_i y_j of the bonds b = l, l + 64, ... ascending by fused
@@ -28,21 +29,10 @@
 //     sum e, sum e^2, sum g, sum e g, sum g^2 (each product rounded to fp64, then added) and the chains alive.
 // A chain whose own amplitude vanishes (ed_vector) has e = g = 0, adds to no sum and is not alive; its rows are in the
 // list (the list depends on the configurations alone) but their values are never read.
-#include "common.hpp"
+#include "measure_dev.hpp"
 #include "plan.hpp"
 
 namespace {
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// the spin of site q on x^a: a = (i, j) antiparallel on x, so the exchange hands q = i the spin of j and the reverse
-__device__ __forceinline__ float spin_after(const float* __restrict__ x, int q, int2 ij, float si, float sj) {
-  return q == ij.x ? sj : (q == ij.y ? si : x[q]);
-}
 
 // bond b = kl against a = ij: 1 the same unordered pair, 2 no common site, 3 exactly one common site
 __device__ __forceinline__ int bond_rule(int2 ij, int2 kl) {
@@ -106,37 +96,11 @@ __global__ __launch_bounds__(256) void k_mom_count(const float* __restrict__ con
   }
 }
 
-// One workgroup: off2[r] = sum of cnt2[0 .. r) for r <= *n1_dev, tiles of 1024 entries with a running carry (integers:
-// the order of the additions does not matter)
+// One workgroup: off2[r] = sum of cnt2[0 .. r) for r <= *n1_dev (tile_scan_1024, measure_dev.hpp)
 __global__ __launch_bounds__(1024) void k_mom_scan(const int* __restrict__ cnt2, const int* __restrict__ n1_dev,
                                                    int* __restrict__ off2) {
   __shared__ int s_wave[16];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int n1 = *n1_dev;
-  int carry = 0;
-  for (int base = 0; base < n1; base += 1024) {
-    const int i = base + t;
-    const int v = i < n1 ? cnt2[i] : 0;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-      const int sw = s_wave[w];
-      if (w < wave) before += sw;
-      total += sw;
-    }
-    if (i < n1) off2[i] = carry + before + incl - v;
-    carry += total;
-    __syncthreads();
-  }
-  if (t == 0) off2[n1] = carry;
+  tile_scan_1024(cnt2, *n1_dev, off2, s_wave);
 }
 
 // One wavefront per first-order row (grid-stride); a row whose part of the list misses the pass [q0, q0 + n) leaves at
@@ -162,7 +126,7 @@ __global__ __launch_bounds__(256) void k_mom_fill(const float* __restrict__ conf
       const int b = b0 + lane;
       const SecondOrder s = second_order(x, bonds, half_jx, quarter_jz, n_bonds, a, ij, si, sj, b);
       const unsigned long long m = __ballot(s.emit);
-      const long long at = q + __popcll(m & ((1ull << lane) - 1ull));
+      const long long at = q + lanes_below(m, lane);
       if (s.emit && at >= q0 && at < q1) {
         desc[at - q0] = make_int2((int)r, b);
         coef[at - q0] = (s.rule == 2 ? 2.0 : 1.0) * hxa * (double)s.hx;
@@ -185,15 +149,7 @@ __global__ __launch_bounds__(256) void k_mom_rows(const float* __restrict__ conf
     const int2 ij = bonds[a], kl = bonds[rb.y];
     const float si = x[ij.x], sj = x[ij.y];
     const float sk = spin_after(x, kl.x, ij, si, sj), sl = spin_after(x, kl.y, ij, si, sj);
-    float* row = rows + it * N;
-    for (int q = lane; q < N; q += 64) {
-      float v = x[q];
-      if (q == ij.x) v = sj;                         // x^a
-      if (q == ij.y) v = si;
-      if (q == kl.x) v = sl;                         // then b on x^a (k or l may be i or j: the later exchange decides)
-      if (q == kl.y) v = sk;
-      row[q] = v;
-    }
+    write_exchanged_row(rows + it * N, x, N, lane, ij, si, sj, true, kl, sk, sl, true);      // x^a, then b on x^a
   }
 }
 

@@ -7,7 +7,7 @@
 //
 // Dead chains.  A chain whose own amplitude vanishes (the signed types: a stored sign / entry of 0) is dead: code
 // OVERLAP_DEAD, ratio 0, in no sum, not alive.  A vanishing omega(x_c) gives code 0 and a ratio of 0 exactly: its
-// logarithm is never read, it takes no part in the max, the chain stays alive.  (measure_ratio's rule, common.hpp.)
+// logarithm is never read, it takes no part in the max, the chain stays alive.  (measure_ratio's rule, measure_dev.hpp.)
 //
 // Summation order.  k_overlap_ratio is the only kernel whose grid touches the sums, and only through the blocks' maxima
 // of d, which are exact in any order.  k_overlap_fold is ONE workgroup of 256: thread t adds the chains t, t + 256, ...
@@ -17,7 +17,7 @@
 // Weights.  w_c = E_loc(c) + lambda (S1 / S2) s_c exp(d_c - m) in fp64, rounded once to fp32: by Cauchy-Schwarz
 // |S1 s_c exp(d_c - m) / S2| <= sqrt(B), and S1 / S2 has no 0 / 0 when the states are orthogonal on the batch.  A dead
 // chain keeps E_loc(c); S2 = 0 (every ratio vanishes) leaves w = E_loc.
-#include "common.hpp"
+#include "measure_dev.hpp"
 
 __global__ __launch_bounds__(256) void k_overlap_ratio(const float* __restrict__ lp, const float* __restrict__ sp,
                                                        double shift_p, const float* __restrict__ lw,

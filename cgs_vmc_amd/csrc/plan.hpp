@@ -877,21 +877,22 @@ inline int plan_symz_check(int base_ansatz, int base_output_activation, bool bas
 // Lanczos-step energies (vmc_energy_moments; moments.hip).  The second-order list -- the rows x^{ab} over (chain,
 // antiparallel bond a, bond b antiparallel on x^a) -- is indexed with 32-bit integers like the first-order list; a chain
 // has at most n_bonds first-order rows of at most n_bonds second-order rows each, so B n_bonds^2 <= 2^31 - 1 keeps every
-// index and the prefix off2 in range whatever the configurations are.  The list goes through the forward in passes of
-// ROWS (not of items x B as its siblings): the budget of 2^24 rows, never more than row_limit (plan_measure_row_limit; 0:
-// none), requested > 0: at most that many; at least one row.  0 passes for an empty list; -1: an argument out of range.
+// index and the prefix off2 in range whatever the configurations are.  A compacted list (this one, the four-spin terms')
+// goes through the forward in passes of ROWS (not of items x B as the dense measurements): plan_list_per_pass is the
+// budget of 2^24 rows, never more than row_limit (plan_measure_row_limit; 0: none), requested > 0: at most that many; at
+// least one row.  0 passes for an empty list; -1: an argument out of range.
 // Within a chain the row at place p = q - s (s: the chain's first row) belongs to lane p mod 64 of the chain's
 // accumulator: plan_moment_first_row is the first row >= lo that lane `lane` owns, plan_moment_rows_of_lane how many
 // of [lo, hi) it owns -- together they state that the lanes' walks partition every pass's slice of a chain.
 inline bool plan_moment_index_ok(long long B, long long n_bonds) {
   return B >= 1 && n_bonds >= 1 && n_bonds <= 0x7fffffffLL && n_bonds * n_bonds <= 0x7fffffffLL / B;
 }
-inline long long plan_moment_per_pass(long long n_rows2, long long requested, long long row_limit) {
-  if (n_rows2 < 0 || requested < 0 || row_limit < 0) return -1;
+inline long long plan_list_per_pass(long long n_rows, long long requested, long long row_limit) {
+  if (n_rows < 0 || requested < 0 || row_limit < 0) return -1;
   long long per = PLAN_MEASURE_ROW_BUDGET;
   if (row_limit > 0 && row_limit < per) per = row_limit;
   if (requested > 0 && requested < per) per = requested;
-  if (per > n_rows2) per = n_rows2;
+  if (per > n_rows) per = n_rows;
   if (per < 1) per = 1;
   return per;
 }
@@ -911,8 +912,7 @@ inline long long plan_moment_rows_of_lane(long long s, long long lo, long long h
 // every row index and the prefix over the chains within 32 bits whatever the configurations are.  The fold keeps a chain's
 // single ratios in LDS by pair index (fp64): at most PLAN_FOURSPIN_MAX_PAIRS pairs; PLAN_FOURSPIN_MAX_TERMS bounds the
 // term table.  plan_fourspin_check validates everything before anything is stored; VMC_OK, or the error with the term
-// (or the cap) named in msg.  The list goes through the forward in passes of ROWS: plan_fourspin_per_pass is the rule of
-// plan_moment_per_pass (the budget of 2^24 rows, row_limit, the request; at least one row; -1: an argument out of range).
+// (or the cap) named in msg.  The list goes through the forward in passes of ROWS (plan_list_per_pass).
 #define PLAN_FOURSPIN_MAX_TERMS (1 << 16)
 #define PLAN_FOURSPIN_MAX_PAIRS 4096
 struct FourSpinTable {
@@ -984,9 +984,6 @@ inline int plan_fourspin_check(int N, long long B, int n_terms, const int32_t* i
     return VMC_ERR_UNSUPPORTED;
   }
   return VMC_OK;
-}
-inline long long plan_fourspin_per_pass(long long n_rows, long long requested, long long row_limit) {
-  return plan_moment_per_pass(n_rows, requested, row_limit);
 }
 // The result buffers span the whole list, whose length changes with the chains: they are reserved once for the a-priori
 // maximum B (n_pairs + n_terms) rows where that stays within PLAN_FOURSPIN_RESULT_ROWS (2^26 rows, 256 MiB a buffer), so

@@ -15,7 +15,7 @@
 // ascending, then the fixed butterfly -- into w_sum[s] = sum_c w_s(c) and we_sum[s] = sum_c w_s(c) E_loc(c); one more
 // wavefront gives e_sum = sum_c E_loc(c) and the number of chains alive.  E_loc of a chain whose own amplitude vanishes is
 // never read (ed_vector: it is a division by zero).
-#include "common.hpp"
+#include "measure_dev.hpp"
 #include "plan.hpp"
 
 // grid chain blocks x sector tiles (block = chain block + chain blocks x tile), PLAN_PROJ_THREADS threads; LDS: chi of the tile [n][tile] doubles.

@@ -9,7 +9,7 @@
 // no compaction and no atomics.  k_swap_fold gives one thread per region, which walks the pairs in ascending order,
 // re-derives the match from the spins it gathers under the mask and adds the terms in fp64: a region's sums depend on
 // the chains alone -- not on the pass the region is in, not on the other regions, not on the grid.
-#include "common.hpp"
+#include "measure_dev.hpp"
 
 // One wavefront per (region, pair): the lanes run along the site axis, so the loads of the two chains and of the mask
 // and the stores of the two rows are contiguous per wavefront.  Spins stay the fp32 +-1 the family kernels read.

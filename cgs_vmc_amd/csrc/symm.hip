@@ -8,7 +8,7 @@
 // order in fp64 and the 64 partial sums meet in a fixed butterfly, so that an op's sum depends on the chains alone -- not
 // on the pass the op is in, not on the other ops, not on the grid -- and the B fp64 exponentials of an op are spread over
 // the wavefront instead of one serial lane.
-#include "common.hpp"
+#include "measure_dev.hpp"
 
 // One wavefront per (op, chain): the lanes run along the site axis, so the loads of perm_k and the stores of the row
 // are contiguous per wavefront; the gather reads the chain's own N floats, which stay in cache.  Spins stay the fp32

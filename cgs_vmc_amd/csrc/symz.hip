@@ -10,6 +10,7 @@
 // per chain the loads of an op coalesce over the chains.  No atomics; everything goes through global memory with
 // vector loads and stores.
 #include "symz.hpp"
+#include "measure_dev.hpp"
 #include "plan.hpp"
 
 struct SymzSum {

@@ -54,7 +54,7 @@
 // Lanczos-step energies.  Per chain e = (H psi)(x) / psi(x) and g = (H^2 psi)(x) / psi(x) (moments.hip states the estimator,
 // the list rules and every summation order).  One local-energy call first; its row list, val and eloc are the first
 // order.  Then the second-order list: counted per first-order row and prefixed (k_mom_count, k_mom_scan), its length read
-// back, and walked in passes of ROWS (plan_moment_per_pass): k_mom_fill writes the descriptors of the pass alone,
+// back, and walked in passes of ROWS (plan_list_per_pass): k_mom_fill writes the descriptors of the pass alone,
 // k_mom_rows the configurations, the family's full forward evaluates them and k_mom_accum adds coef r into the chains'
 // lanes.  k_mom_chain / k_mom_sums fold at the end.  Like the projected energies it leaves what vmc_local_energy leaves.
 //
@@ -350,9 +350,9 @@ int mom_pass(vmc_ctx* c, int which, long long q0, int n, int n1) {
   return VMC_OK;
 }
 
-// an int the device holds, on the host (host: declared before the entry's guard; the stream is synchronised)
-int read_int(vmc_ctx* c, const int* dev, int* host) {
-  HIPCHK(c, hipMemcpyAsync(host, dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+// n ints the device holds, on the host (host: declared before the entry's guard; the stream is synchronised)
+int read_ints(vmc_ctx* c, const int* dev, int* host, int n) {
+  HIPCHK(c, hipMemcpyAsync(host, dev, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return VMC_OK;
 }
@@ -423,11 +423,10 @@ int four_spin_device(vmc_ctx* c, int which) {
     Timer t(c, "fs_list");
     HIPCHK(c, launch_fs_count(c->stream, c->configs, m.pairs, m.term_pairs, c->B, c->N, m.n_pairs, m.n_terms, c->num_cus,
                               m.n_single, m.cnt, m.off));
-    HIPCHK(c, hipMemcpyAsync(lengths, m.off + c->B, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    PROPAGATE(read_ints(c, m.off + c->B, lengths, 2));
   }
   const long long total = lengths[0];
-  const long long per = plan_fourspin_per_pass(total, m.rows_per_pass, plan_measure_row_limit(c->N, c->Hp));
+  const long long per = plan_list_per_pass(total, m.rows_per_pass, plan_measure_row_limit(c->N, c->Hp));
   if (per < 1 || lengths[1] < 0 || lengths[1] > total) return fail(c, VMC_ERR_HIP, "the four-spin list has a negative length");
   PROPAGATE(m.desc.reserve(c, per, "fs.desc"));
   // (for the a-priori maximum where that fits, so that the list growing with the chains reallocates nothing: plan.hpp)
@@ -703,7 +702,7 @@ int vmc_energy_moments(vmc_ctx* c, int which, int64_t rows_per_pass, double sums
     Timer t(c, "mom_eloc");                  // first: its rows go through the buffers the passes then take
     PROPAGATE(local_energy_device(c, which));
   }
-  PROPAGATE(read_int(c, c->off + c->B, &n1));
+  PROPAGATE(read_ints(c, c->off + c->B, &n1, 1));
   PROPAGATE(mom_reserve_list(c, n1));
   {
     Timer t(c, "mom_list");
@@ -711,8 +710,8 @@ int vmc_energy_moments(vmc_ctx* c, int which, int64_t rows_per_pass, double sums
                                c->N, c->n_bonds, c->num_cus, m.cnt2, m.off2, m.diag1, m.self1));
     HIPCHK(c, hipMemsetAsync(m.lanes, 0, 64 * (size_t)c->B * sizeof(double), c->stream));
   }
-  PROPAGATE(read_int(c, m.off2 + n1, &n2));
-  const long long per = plan_moment_per_pass(n2, rows_per_pass, plan_measure_row_limit(c->N, c->Hp));
+  PROPAGATE(read_ints(c, m.off2 + n1, &n2, 1));
+  const long long per = plan_list_per_pass(n2, rows_per_pass, plan_measure_row_limit(c->N, c->Hp));
   if (per < 1) return fail(c, VMC_ERR_HIP, "the second-order list has a negative length");
   PROPAGATE(m.desc.reserve(c, per, "mom.desc"));
   PROPAGATE(m.coef.reserve(c, per, "mom.coef"));

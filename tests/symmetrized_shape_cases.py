@@ -122,7 +122,7 @@ AMPLITUDE_SEED, ELOC_SEED = 21, 26             # tests/test_gpu_symmetrized.py's
 
 # ---- 2. more than one fold workgroup, more than one trip of the row kernels
 BIG = dict(lat='chain68', sector='q34', b=260, seed=41, step_seed=42)
-ROW_ITEMS_PER_CU = 16 * 4                      # common.hpp measure_rows_grid: at most 16 blocks of 4 items per CU
+ROW_ITEMS_PER_CU = 16 * 4                      # measure_dev.hpp measure_rows_grid: at most 16 blocks of 4 items per CU
 FOLD_THREADS = 256                             # plan.hpp PLAN_SYMZ_THREADS
 BAND_SHARE = 0.02
 

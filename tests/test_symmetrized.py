@@ -171,7 +171,7 @@ def test_the_shape_cases_reach_what_they_are_named_for():
   assert len(sc.ops(big['lat'], big['sector'])[0]) * big['b'] > sc.ROW_ITEMS_PER_CU * 256      # (at the MI355X's 256 CUs)
   assert sc.FOLD_THREADS < big['b'] < 2 * sc.FOLD_THREADS
   plan = open(os.path.join(ROOT, 'cgs_vmc_amd', 'csrc', 'plan.hpp')).read()
-  common = open(os.path.join(ROOT, 'cgs_vmc_amd', 'csrc', 'common.hpp')).read()
+  common = open(os.path.join(ROOT, 'cgs_vmc_amd', 'csrc', 'measure_dev.hpp')).read()      # (where measure_rows_grid lives)
   assert re.search(r'#define\s+PLAN_SYMZ_THREADS\s+%d\b' % sc.FOLD_THREADS, plan)
   assert 'long long blocks = (items + 3) / 4;' in common and 'const long long cap = 16LL * (num_cus > 0 ? num_cus : 1);' in common
   # the fold cases: every row's orbit spreads past the range its factor is named for

@@ -32,11 +32,11 @@ while True:
 PY
 for co in "$TMP"/co_*.elf; do
   $LLVM/llvm-readelf --notes "$co" | awk '
-    /\.name:/ {name=$2}
-    /\.vgpr_count:/ {v=$2}
-    /\.agpr_count:/ {a=$2}
-    /\.vgpr_spill_count:/ {sp=$2}
-    /\.private_segment_fixed_size:/ {ps=$2}
-    /\.group_segment_fixed_size:/ {g=$2}
-    /\.symbol:/ {printf "%s vgpr=%s agpr=%s spill=%s scratch=%s lds=%s\n", name, v, a, sp, ps, g}'
+    /\.name:/ {name=$NF}
+    /\.vgpr_count:/ {v=$NF}
+    /\.agpr_count:/ {a=$NF}
+    /\.vgpr_spill_count:/ {sp=$NF}
+    /\.private_segment_fixed_size:/ {ps=$NF}
+    /\.group_segment_fixed_size:/ {g=$NF}
+    /\.wavefront_size:/ {printf "%s vgpr=%s agpr=%s spill=%s scratch=%s lds=%s\n", name, v, a, sp, ps, g}'
 done | c++filt | grep -E "$PAT" | sort -u
