@@ -545,13 +545,13 @@ struct SrGramArgs {
   float* T;
 };
 hipError_t launch_sr_gram(hipStream_t s, const SrGramArgs& g, long long grid);
-// w = T v; sc: the solve's scalars (an iteration behind the stop does nothing) or null
-hipError_t launch_sr_gram_matvec(hipStream_t s, const float* T, const float* v, int n, const double* sc, float* w);
-hipError_t launch_srg_rhs(hipStream_t s, const float* e, int n, float tol, float* y, float* r, float* p, float* pc,
+// w = T v (T fp32; v, the sum and w fp64); sc: the solve's scalars (an iteration behind the stop does nothing) or null
+hipError_t launch_sr_gram_matvec(hipStream_t s, const float* T, const double* v, int n, const double* sc, double* w);
+hipError_t launch_srg_rhs(hipStream_t s, const float* e, int n, float tol, double* y, double* r, double* p, double* pc,
                           double* sc);
-hipError_t launch_srg_step(hipStream_t s, const float* w, int n, float nlambda, float tol, float* q, float* y, float* r,
-                           float* p, float* pc, double* sc);
-hipError_t launch_srg_centre(hipStream_t s, const float* y, int n, float* t);
+hipError_t launch_srg_step(hipStream_t s, const double* w, int n, double nlambda, float tol, double* q, double* y, double* r,
+                           double* p, double* pc, double* sc);
+hipError_t launch_srg_centre(hipStream_t s, const double* y, int n, float* t);
 
 // fully_connected with fc_layer_size > 256: the general path through materialised rows (wide.hip)
 hipError_t launch_wide_rows_act(hipStream_t s, const float* z1, const float* w1p, const int2* rowinfo,

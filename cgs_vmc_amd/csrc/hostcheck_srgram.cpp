@@ -52,6 +52,7 @@ static void check_n(long long n) {
 int main() {
   int cases = 0;
   for (long long n = 1; n <= 300; ++n, ++cases) check_n(n);
+  for (long long n : {516LL, 1024LL, 1025LL, 1040LL, 1100LL}) { check_n(n); ++cases; }      // tests/sr_gram_shape_cases.py
   for (long long n : {4095LL, 4096LL, 4097LL, 16384LL, 16385LL}) { check_n(n); ++cases; }
   {
     SrGramPlan p{};

@@ -131,8 +131,14 @@ hipError_t launch_sr_gram(hipStream_t s, const SrGramArgs& g, long long grid) {
 // ---------------------------------------------------------------- the conjugate gradients on C T C + n lambda I
 // sc (double[4]) = [rr, rr of the first residual, iterations done, 1 once the solve has stopped].  The host enqueues
 // iterations in groups and reads sc between them; an iteration enqueued behind the stop does nothing.
+// The six vectors of the recurrence (y, r, p, C p, w, q) and every sum are fp64: T stays fp32 -- a fixed, symmetric
+// rounding of the operator, which the recurrence follows as it would the exact one -- but fp32 vectors round anew in
+// every iteration, and conjugate gradients answer that with delayed convergence: measured 17 .. 28 % more iterations
+// than the fp64 recurrence at 129 .. 1100 samples, 5 % off in x after 13 of them.  Rounding C p to fp32
+// for the matvec alone undoes all of it (restated on the CPU), so the matvec reads v and sums in fp64: the same time
+// per launch at n = 4,096, 6 % more at 8,192, 30 % more at 16,384.
 
-__device__ __forceinline__ float wave_sum_g(float v) {
+__device__ __forceinline__ double wave_sum_g(double v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
   return v;
@@ -151,38 +157,38 @@ __device__ __forceinline__ double block_sum_g(double v, double* s) {
   return r;
 }
 
-// w = T v: one wave per row, 16-byte loads where the rows are 16-byte aligned (n a multiple of 4), lane partials in
-// ascending column order folded by the xor butterfly
-__global__ __launch_bounds__(256) void k_sr_gram_matvec(const float* __restrict__ T, const float* __restrict__ v, int n,
-                                                        const double* __restrict__ sc, float* __restrict__ w) {
+// w = T v: one wave per row, 16-byte loads of T where the rows are 16-byte aligned (n a multiple of 4), lane partials
+// in ascending column order folded by the xor butterfly
+__global__ __launch_bounds__(256) void k_sr_gram_matvec(const float* __restrict__ T, const double* __restrict__ v, int n,
+                                                        const double* __restrict__ sc, double* __restrict__ w) {
   if (sc && sc[3] != 0.0) return;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n) return;
   const float* t = T + (long long)row * n;
-  float s = 0.f;
+  double s = 0.0;
   if ((n & 3) == 0) {
     const float4* t4 = reinterpret_cast<const float4*>(t);
-    const float4* v4 = reinterpret_cast<const float4*>(v);
     for (int k = lane; k < (n >> 2); k += 64) {
-      const float4 a = t4[k], b = v4[k];
-      s = fmaf(a.x, b.x, s); s = fmaf(a.y, b.y, s); s = fmaf(a.z, b.z, s); s = fmaf(a.w, b.w, s);
+      const float4 a = t4[k];
+      const double* b = v + 4 * k;
+      s = fma((double)a.x, b[0], s); s = fma((double)a.y, b[1], s); s = fma((double)a.z, b[2], s); s = fma((double)a.w, b[3], s);
     }
   } else {
-    for (int k = lane; k < n; k += 64) s = fmaf(t[k], v[k], s);
+    for (int k = lane; k < n; k += 64) s = fma((double)t[k], v[k], s);
   }
   s = wave_sum_g(s);
   if (lane == 0) w[row] = s;
 }
 
-hipError_t launch_sr_gram_matvec(hipStream_t s, const float* T, const float* v, int n, const double* sc, float* w) {
+hipError_t launch_sr_gram_matvec(hipStream_t s, const float* T, const double* v, int n, const double* sc, double* w) {
   hipLaunchKernelGGL(k_sr_gram_matvec, dim3((n + 3) / 4), dim3(256), 0, s, T, v, n, sc, w);
   return hipGetLastError();
 }
 
 // right-hand side: eps = E - Ebar; y = 0, r = p = eps, pc = C p; sc = [|eps|^2, |eps|^2, 0, stop]
-__global__ __launch_bounds__(1024) void k_srg_rhs(const float* __restrict__ e, int n, float tol, float* __restrict__ y,
-                                                  float* __restrict__ r, float* __restrict__ p, float* __restrict__ pc,
+__global__ __launch_bounds__(1024) void k_srg_rhs(const float* __restrict__ e, int n, float tol, double* __restrict__ y,
+                                                  double* __restrict__ r, double* __restrict__ p, double* __restrict__ pc,
                                                   double* __restrict__ sc) {
   __shared__ double s[1024];
   double a = 0.0;
@@ -190,12 +196,12 @@ __global__ __launch_bounds__(1024) void k_srg_rhs(const float* __restrict__ e, i
   const double ebar = block_sum_g(a, s) / n;
   double rr = 0.0, ps = 0.0;
   for (int i = threadIdx.x; i < n; i += 1024) {
-    const float f = (float)((double)e[i] - ebar);
-    y[i] = 0.f; r[i] = f; p[i] = f;
-    rr += (double)f * (double)f; ps += (double)f;
+    const double f = (double)e[i] - ebar;
+    y[i] = 0.0; r[i] = f; p[i] = f;
+    rr += f * f; ps += f;
   }
   rr = block_sum_g(rr, s);
-  const float pbar = (float)(block_sum_g(ps, s) / n);
+  const double pbar = block_sum_g(ps, s) / n;
   for (int i = threadIdx.x; i < n; i += 1024) pc[i] = p[i] - pbar;
   if (threadIdx.x == 0) {
     sc[0] = rr; sc[1] = rr; sc[2] = 0.0;
@@ -205,39 +211,39 @@ __global__ __launch_bounds__(1024) void k_srg_rhs(const float* __restrict__ e, i
 
 // one iteration behind w = T (C p): q = C w + n lambda p; alpha = rr / p.q; y += alpha p; r -= alpha q;
 // beta = rr' / rr; p = r + beta p; pc = C p
-__global__ __launch_bounds__(1024) void k_srg_step(const float* __restrict__ w, int n, float nlambda, float tol,
-                                                   float* __restrict__ q, float* __restrict__ y, float* __restrict__ r,
-                                                   float* __restrict__ p, float* __restrict__ pc, double* __restrict__ sc) {
+__global__ __launch_bounds__(1024) void k_srg_step(const double* __restrict__ w, int n, double nlambda, float tol,
+                                                   double* __restrict__ q, double* __restrict__ y, double* __restrict__ r,
+                                                   double* __restrict__ p, double* __restrict__ pc, double* __restrict__ sc) {
   __shared__ double s[1024];
   if (sc[3] != 0.0) return;
   const double rr = sc[0], rr0 = sc[1];
   double a = 0.0;
-  for (int i = threadIdx.x; i < n; i += 1024) a += (double)w[i];
-  const float wbar = (float)(block_sum_g(a, s) / n);
+  for (int i = threadIdx.x; i < n; i += 1024) a += w[i];
+  const double wbar = block_sum_g(a, s) / n;
   a = 0.0;
   for (int i = threadIdx.x; i < n; i += 1024) {
-    const float qi = (w[i] - wbar) + nlambda * p[i];
+    const double qi = (w[i] - wbar) + nlambda * p[i];
     q[i] = qi;
-    a += (double)p[i] * (double)qi;
+    a += p[i] * qi;
   }
   const double pq = block_sum_g(a, s);
-  const float alpha = pq > 0.0 ? (float)(rr / pq) : 0.f;
+  const double alpha = pq > 0.0 ? rr / pq : 0.0;
   a = 0.0;
   for (int i = threadIdx.x; i < n; i += 1024) {
     y[i] += alpha * p[i];
-    const float ri = r[i] - alpha * q[i];
+    const double ri = r[i] - alpha * q[i];
     r[i] = ri;
-    a += (double)ri * (double)ri;
+    a += ri * ri;
   }
   const double rr1 = block_sum_g(a, s);
-  const float beta = rr > 0.0 ? (float)(rr1 / rr) : 0.f;
+  const double beta = rr > 0.0 ? rr1 / rr : 0.0;
   a = 0.0;
   for (int i = threadIdx.x; i < n; i += 1024) {
-    const float pi = r[i] + beta * p[i];
+    const double pi = r[i] + beta * p[i];
     p[i] = pi;
-    a += (double)pi;
+    a += pi;
   }
-  const float pbar = (float)(block_sum_g(a, s) / n);
+  const double pbar = block_sum_g(a, s) / n;
   for (int i = threadIdx.x; i < n; i += 1024) pc[i] = p[i] - pbar;
   if (threadIdx.x == 0) {
     sc[0] = rr1; sc[2] += 1.0;
@@ -245,28 +251,28 @@ __global__ __launch_bounds__(1024) void k_srg_step(const float* __restrict__ w, 
   }
 }
 
-// t = y - ybar: the per-sample weights of x = sum_b t_b O_b
-__global__ __launch_bounds__(1024) void k_srg_centre(const float* __restrict__ y, int n, float* __restrict__ t) {
+// t = y - ybar: the per-sample weights of x = sum_b t_b O_b (fp32, as sr_weighted_sum takes them)
+__global__ __launch_bounds__(1024) void k_srg_centre(const double* __restrict__ y, int n, float* __restrict__ t) {
   __shared__ double s[1024];
   double a = 0.0;
-  for (int i = threadIdx.x; i < n; i += 1024) a += (double)y[i];
-  const float ybar = (float)(block_sum_g(a, s) / n);
-  for (int i = threadIdx.x; i < n; i += 1024) t[i] = y[i] - ybar;
+  for (int i = threadIdx.x; i < n; i += 1024) a += y[i];
+  const double ybar = block_sum_g(a, s) / n;
+  for (int i = threadIdx.x; i < n; i += 1024) t[i] = (float)(y[i] - ybar);
 }
 
-hipError_t launch_srg_rhs(hipStream_t s, const float* e, int n, float tol, float* y, float* r, float* p, float* pc,
+hipError_t launch_srg_rhs(hipStream_t s, const float* e, int n, float tol, double* y, double* r, double* p, double* pc,
                           double* sc) {
   hipLaunchKernelGGL(k_srg_rhs, dim3(1), dim3(1024), 0, s, e, n, tol, y, r, p, pc, sc);
   return hipGetLastError();
 }
 
-hipError_t launch_srg_step(hipStream_t s, const float* w, int n, float nlambda, float tol, float* q, float* y, float* r,
-                           float* p, float* pc, double* sc) {
+hipError_t launch_srg_step(hipStream_t s, const double* w, int n, double nlambda, float tol, double* q, double* y, double* r,
+                           double* p, double* pc, double* sc) {
   hipLaunchKernelGGL(k_srg_step, dim3(1), dim3(1024), 0, s, w, n, nlambda, tol, q, y, r, p, pc, sc);
   return hipGetLastError();
 }
 
-hipError_t launch_srg_centre(hipStream_t s, const float* y, int n, float* t) {
+hipError_t launch_srg_centre(hipStream_t s, const double* y, int n, float* t) {
   hipLaunchKernelGGL(k_srg_centre, dim3(1), dim3(1024), 0, s, y, n, t);
   return hipGetLastError();
 }

@@ -35,7 +35,8 @@ int vmc_sr_reserve(vmc_ctx* c, int32_t n_batches) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->sr_cap = 0; c->sr_n = 0; c->sr_begun = false;      // (sr_cap stays 0 until everything below is there)
   for (DevBuf<float>* q : {&c->sr_cfg, &c->sr_act, &c->sr_delta, &c->sr_ws, &c->sr_t, &c->sr_ones, &c->sr_ctape, &c->sr_cdelta,
-                           &c->sr_cws, &c->sr_tpart, &c->sr_eloc, &c->sr_gram, &c->sr_gvec}) q->release();
+                           &c->sr_cws, &c->sr_tpart, &c->sr_eloc, &c->sr_gram}) q->release();
+  c->sr_gvec.release();
   if (n_batches == 0) return VMC_OK;
   const long long B = c->B, N = c->N, Hp = c->Hp, L = c->A, R = (long long)n_batches * B;
   switch (c->path) {
@@ -383,7 +384,7 @@ int vmc_sr_solve_samples(vmc_ctx* c, float diag_shift, float tol, int32_t max_it
   PROPAGATE(c->sr_gvec.reserve(c, 6LL * n, "sr_gvec"));
   PROPAGATE(c->sr_gsc.reserve(c, 4, "sr_gsc"));
   PROPAGATE(sr_gram(c, plan));
-  float *y = c->sr_gvec, *r = y + n, *p = r + n, *pc = p + n, *w = pc + n, *q = w + n;
+  double *y = c->sr_gvec, *r = y + n, *p = r + n, *pc = p + n, *w = pc + n, *q = w + n;
   double sc[4] = {0.0, 0.0, 0.0, 1.0};
   {
     Timer t(c, "sr_gram_cg");
@@ -397,7 +398,7 @@ int vmc_sr_solve_samples(vmc_ctx* c, float diag_shift, float tol, int32_t max_it
           Timer tm(c, "sr_gram_matvec");
           HIPCHK(c, launch_sr_gram_matvec(c->stream, c->sr_gram, pc, n, c->sr_gsc, w));
         }
-        HIPCHK(c, launch_srg_step(c->stream, w, n, (float)n * diag_shift, tol, q, y, r, p, pc, c->sr_gsc));
+        HIPCHK(c, launch_srg_step(c->stream, w, n, (double)n * (double)diag_shift, tol, q, y, r, p, pc, c->sr_gsc));
       }
       it += group;
       HIPCHK(c, hipMemcpyAsync(sc, c->sr_gsc, sizeof(sc), hipMemcpyDeviceToHost, c->stream));

@@ -339,10 +339,10 @@ struct vmc_ctx {
   DevBuf<double> sr_partial, sr_sc;
   bool sr_begun = false;
   // the sample-space solve (srgram.hip): the stored samples' local energies [cap B] (recorded with the store), the Gram
-  // matrix [n][n] and the six CG vectors [n] (y, r, p, C p, w, q) -- both allocated by the first solve, released by
-  // vmc_sr_reserve -- and the solve's scalars [4]
-  DevBuf<float> sr_eloc, sr_gram, sr_gvec;
-  DevBuf<double> sr_gsc;
+  // matrix [n][n] and the six CG vectors [n] (y, r, p, C p, w, q; fp64) -- both allocated by the first solve, released
+  // by vmc_sr_reserve -- and the solve's scalars [4]
+  DevBuf<float> sr_eloc, sr_gram;
+  DevBuf<double> sr_gvec, sr_gsc;
   // collectives over sharded chains: host hook for non-RCCL transports + its staging
   vmc_host_allreduce_fn host_reduce = nullptr;
   void* host_reduce_user = nullptr;

@@ -2,7 +2,8 @@
 fp32 MFMA, conjugate gradients on the centred n x n system) against the fp64 references of tests/sr_gram_cases.py and the
 oracle's dense solve, and against the parameter-space solver it stands beside.
 
-Tolerances (those of tests/test_gpu_sr.py for the same class of sums: fp32 MFMA + fp32 CG vectors against fp64):
+Tolerances (those of tests/test_gpu_sr.py for the same class of sums: fp32 MFMA + a CG on the fp32 matrix against fp64;
+tests/test_gpu_sr_gram_shapes.py goes on from here: more than 300 samples, a bound per element, the iterates one by one):
   Gram matrix   |d| <= 2e-4 * max|T_ref|
   CG solution   |d| <= 2e-3 * ||x_ref||_inf    (cond(C T C + n lambda I) is 90 .. 200 at these shapes)
   both solvers  |d| <= 4e-3 * ||x||_inf        (the two added)
@@ -109,7 +110,7 @@ def test_solution_matches_direct_solve(shape):
   assert res <= 1e-4, (iters, res)
   assert np.all(np.isfinite(x))
   assert err <= 2e-3 * scale, (iters, res)
-  assert iters <= 2 * c.it64 + 10
+  assert abs(iters - c.it64) <= 2           # (2 it64 + 10 while the CG vectors were fp32; measured: 0 or 1 off)
   if c.theta.size <= 20000:
     ref = vo.sr_solve(c.o, c.e, LAM)       # dense fp64 solve of the explicit (S + lam I)
     assert np.abs(x - ref).max() <= 2e-3 * np.abs(ref).max()
